@@ -22,7 +22,7 @@ import numpy as np  # noqa: E402
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec
 PF_STRONG_WATCHDOG_S = 300
 
 
@@ -1277,6 +1277,35 @@ def secondary_workload(args):
         dist.destroy_process_group()
 
 
+def lk_inputs(res, B, CH=1, H=1024, W=1024):
+    """the lk workload's seeded inputs: frame0, frame1 (frame0 through a small homography) and the B initial target corners"""
+    from mtf_amd import synth
+    frame0 = synth.make_frame(H, W) if CH == 1 else synth.make_frame_mc(H, W)
+    rng = np.random.default_rng(synth.DEFAULT_SEED + 1)
+    p_true = synth.random_small_homography(rng, 0.5)
+    frame1 = synth.warp_frame(frame0, p_true, (W / 2.0, H / 2.0))
+    # B target regions of res x res pixels (1:1 sampling) spread over the frame
+    half = res / 2.0 + 12
+    cx = rng.uniform(half, W - half, size=B)
+    cy = rng.uniform(half, H - half, size=B)
+    corners = np.stack([synth.square_corners(cx[i], cy[i], float(res)) for i in range(B)])
+    return frame0, frame1, corners
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each (name, array) as path/<name>.npy in float64 (the inputs are seeded, so equal builds write equal files)"""
+    os.makedirs(path, exist_ok=True)
+    arrays = [(name, np.ascontiguousarray(a, dtype=np.float64)) for name, a in arrays]
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays:
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--pf-peer-child":
         return pf_peer_child(sys.argv[2:])
@@ -1318,7 +1347,13 @@ def main():
                     "processes) to the lk line: -1 = at --gpus 1 with the default workload shape (default), 0 = never, 1 = always")
     ap.add_argument("--pf-strong", type=int, default=-1, help="append the sharded-filter strong-scaling record (pf_strong) to the lk line: "
                     "-1 = when --gpus > 1 (default), 0 = never, 1 = always (on one GPU it exercises the code path with one rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (batch.track: corners, n_iters) as "
+                         "DIR/<name>.npy in float64, so that two builds can be compared output for output.  The lk workload (the timed "
+                         "headline path) only: it is refused for --workload grid / pf / mi / nn / dropin")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "lk" or stub_mode()):
+        ap.error("--dump-outputs writes the device results of the lk workload (not of --workload %s%s)" % (args.workload, " / the stub" if stub_mode() else ""))
     self_spawn_if_needed(args, sys.argv[1:])
     if stub_mode():
         return stub_main(args)
@@ -1350,15 +1385,7 @@ def main():
     res, B = args.res, args.targets
     H = W = 1024
     CH = args.channels
-    frame0 = synth.make_frame(H, W) if CH == 1 else synth.make_frame_mc(H, W)
-    rng = np.random.default_rng(synth.DEFAULT_SEED + 1)
-    p_true = synth.random_small_homography(rng, 0.5)
-    frame1 = synth.warp_frame(frame0, p_true, (W / 2.0, H / 2.0))
-    # B target regions of res x res pixels (1:1 sampling) spread over the frame
-    half = res / 2.0 + 12
-    cx = rng.uniform(half, W - half, size=B)
-    cy = rng.uniform(half, H - half, size=B)
-    corners = np.stack([synth.square_corners(cx[i], cy[i], float(res)) for i in range(B)])
+    frame0, frame1, corners = lk_inputs(res, B, CH, H, W)
 
     stream = torch.cuda.current_stream(dev).cuda_stream
     ctx = mtf_amd.Context(local_rank, stream)
@@ -1400,6 +1427,8 @@ def main():
     # warm-up steps + EXACTLY K timed steps between barrier + synchronize, MAX over ranks; value = the median region, min / max beside it
     # r05 verdict item 8: roofline.frac and value from the SAME execution -- HIP events around every --event-stride-th fused launch INSIDE the
     # timed region (mtfhip_timing_enable(ctx, n > 1): two event records per sampled launch, on the queue the launch goes to)
+    last_outputs = []     # what batch.track returned in the last timed region (--dump-outputs)
+
     def timed_region():
         run(max(1, args.warmup))
         batch.set_state(np.zeros((B, 8)))
@@ -1417,6 +1446,7 @@ def main():
             dist.barrier()
         d = time.perf_counter() - t0
         assert int(n_it.min()) == args.steps and int(n_it.max()) == args.steps
+        last_outputs[:] = [("n_iters", n_it), ("corners", final)]
         km_r, kn_r = (0.0, 0)
         if args.event_stride > 0:
             ctx.timing(False)
@@ -1619,6 +1649,8 @@ def main():
             out["configs"] = {"error": "%s: %s" % (type(e).__name__, e)}
     if out is not None:
         print(json.dumps(out), flush=True)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_outputs)
     ctx.close()    # handles released while the HIP runtime is whole (the library's atexit hook would do the same)
     if dist is not None:
         dist.destroy_process_group()

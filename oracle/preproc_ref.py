@@ -4,7 +4,7 @@
 TEST INFRASTRUCTURE ONLY (tests/ import it; the product never does).
 
 PARITY UNPINNED: OpenCV is a third-party dependency of the reference ("2.4.13, 3.3.0, 3.4.1 tested", ReadMe.md:112-116)
-that is absent from /root/reference and from this image, so this file restates its published float32 algorithms:
+that is absent from the reference and from the build environment, so this file restates its published float32 algorithms:
   * cvtColor(BGR2GRAY) on CV_32F: gray = B*0.114f + G*0.587f + R*0.299f
   * getGaussianKernel(n, sigma > 0, CV_32F): exp(-x^2 / (2 sigma^2)) cast to float, normalised by the double sum of the floats
   * sepFilter2D with a symmetric 5-tap kernel: rows S[0]*k0 + (S[-1]+S[1])*k1 + (S[-2]+S[2])*k2 (SymmRowSmallFilter), columns

@@ -1,9 +1,10 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # Ablation of k_mi_pass_hist (pass 1 of the MI recompute iteration): variants of libmtfhip.so with -DMTFHIP_MI1_ABL=n under build/variants/
 # (built HERE on the CPU; build/ travels to the GPU box, scratch/ does not).  On the box:  bash tools/mi1_ablation.sh run
 #   1 no histogram product | 2 staging but no block products | 3 windows but no staging | 4 sampling only
 if [ "$1" = run ]; then
-  cd "$GRAFT_REPO_ROOT" || exit 1
+  cd "$here/.." || exit 1
   for n in 0 1 2 3 4; do
     lib=mtf_amd/libmtfhip.so; [ $n != 0 ] && lib=build/variants/libmtfhip_mi1abl$n.so
     echo -n "MI1_ABL=$n: "

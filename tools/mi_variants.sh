@@ -1,6 +1,7 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # times the MI passes with every build/variants/libmtfhip_*.so (and the in-tree library first)
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 for lib in mtf_amd/libmtfhip.so build/variants/libmtfhip_*.so; do
   echo -n "$(basename $lib): "
   MTFHIP_LIB=$lib python bench.py --workload mi --steps 5 --warmup 5 --no-cpu 2>/dev/null | tail -1 | python -c "

@@ -1,6 +1,7 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # NN dataset quick loop on the GPU box: the nn tests, then the bench lines over AM x sample count (kernel time by events, roofline fraction)
-cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT" || exit 1
+cd /tmp && export TMPDIR=/tmp; cd "$here/.." || exit 1
 o=gpurun_out/nn_quick; mkdir -p $o
 python -m pytest tests/test_gpu_nn.py tests/test_gpu_golden3.py tests/test_gpu_parity.py -k "nn" -m gpu -x -q 2>&1 | tail -2
 : > $o/nn_lines.jsonl

@@ -1,8 +1,9 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # Collect PMC counters for the bench workload, one rocprofv3 --pmc pass per counter group
 # (no trace domains combined with --pmc).  Usage: tools/pmc_collect.sh <outdir> "<bench args>" "<group1>" "<group2>" ...
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 out=$1; shift
 args=$1; shift
 mkdir -p "$out"

@@ -1,9 +1,10 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # Round profile on the GPU box: kernel-trace stats of the default bench command, then separate PMC passes
 # (FETCH_SIZE, WRITE_SIZE and a small SQ/TCC set) of the same command.  Outputs go to gpurun_out/profile/
 # (copy the summaries into profiles/ afterwards).   usage: tools/profile_round.sh <tag> [bench args]
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 tag=$1; shift
 args="${*:---steps 50 --warmup 10}"
 out=gpurun_out/profile

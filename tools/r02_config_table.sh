@@ -1,6 +1,7 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # The configurations tabulated in DESIGN.md section 5, one bench.py line each (one gpurun call): gpurun_out/r02_config_table.jsonl
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 out=gpurun_out/r02_config_table.jsonl; : > $out
 run() { timeout 300 python bench.py "$@" --no-cpu 2>/dev/null | tail -1 >> $out; }
 run --steps 200 --warmup 20

@@ -1,6 +1,7 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # The bench.py lines of the round's final code, one gpurun call: gpurun_out/r02_final_bench_lines.jsonl
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 out=gpurun_out/r02_final_bench_lines.jsonl; : > $out
 timeout 600 python bench.py 2>/dev/null | tail -1 >> $out
 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu 2>/dev/null | tail -1 >> $out

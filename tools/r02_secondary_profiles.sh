@@ -1,8 +1,9 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # Kernel traces + PMC passes of the secondary workloads (grid, pf, mi) on the GPU box.  Outputs: gpurun_out/<tag>/
 # usage: tools/r02_secondary_profiles.sh <tag>     (copy the summaries into profiles/ afterwards)
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 tag=${1:-r02}
 out=gpurun_out/$tag
 mkdir -p $out

@@ -1,8 +1,9 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # r03: the loop-body ablation of the fused LK kernel (what staging image tiles in LDS could buy at most) and the streaming
 # ceiling of its traffic pattern, on the r03 code, in ONE call (boxes differ by 10-15 %).  -> gpurun_out/r03_fused_ablation.txt
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 out=gpurun_out/r03_fused_ablation.txt
 mkdir -p gpurun_out
 {

@@ -1,9 +1,10 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # r03: everything the round's figures come from, one gpurun call (boxes differ by 10-15 %): gpurun_out/r03/
 #   headline bench line + rocprofv3 kernel trace + PMC passes (traffic) | secondary workloads (grid, pf at three sizes, mi) with kernel
 #   traces and the MI / PF counters | the configuration table | the parity record of the -m gpu tests
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 tag=r03
 out=gpurun_out/$tag
 mkdir -p $out

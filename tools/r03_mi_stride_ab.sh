@@ -1,6 +1,7 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # r03 A/B: LDS slab row strides of the MI recompute passes (bank conflicts of the per-lane-row window stores vs the MFMA operand reads)
-cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT" || exit 1
+cd /tmp && export TMPDIR=/tmp; cd "$here/.." || exit 1
 mkdir -p gpurun_out
 for v in ${MI_AB_VARIANTS:-"68 100" "65 100" "66 100"}; do
   set -- ${v//:/ }

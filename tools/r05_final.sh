@@ -1,10 +1,11 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # r05: everything the round's figures come from, one gpurun call (boxes differ by 10-15 %): gpurun_out/r05/
 #   headline bench line + rocprofv3 kernel trace + PMC passes (traffic) | PMC passes of the secondary workloads (mi, pf, grid) ->
 #   pmc_secondary_latest.json, which their bench lines then quote | secondary bench lines with kernel traces | the grid / PF probes of
 #   the round | the configuration table | the parity record of the -m gpu tests
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 tag=r05
 out=gpurun_out/$tag
 mkdir -p $out

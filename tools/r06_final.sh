@@ -1,11 +1,12 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # r06: ONE evidence run on the final sources (r05 verdict item 8), one gpurun call: gpurun_out/r06/
 #   1 headline: bench line, rocprofv3 kernel trace, PMC traffic passes            2 PMC passes of the secondary workloads (mi, pf, grid, nn)
 #   3 the driver's own command (the line with the configs block)                   4 secondary bench lines + kernel traces (grid incl. the shipped
 #   forward-backward frame, pf, mi 8 / 10 bins, nn over AM x size)                  5 the parity record of the -m gpu tests
 # Every rocprofv3 call runs under `timeout` (a hung counter pass cost 15 GPU-minutes once).
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 tag=r06
 out=gpurun_out/$tag
 mkdir -p $out

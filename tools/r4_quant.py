@@ -1,5 +1,5 @@
-import numpy as np, sys
-sys.path.insert(0, '/root/repo')
+import numpy as np, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mtf_amd import synth
 from oracle import numpy_ref as R
 img = synth.make_frame(512, 512)

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, mtf_amd
 from mtf_amd import synth, _lib as L
 ctx = mtf_amd.Context(0)

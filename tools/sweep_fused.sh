@@ -1,7 +1,8 @@
 #!/bin/bash
+here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative path)
 # Build fused-kernel variants (MTFHIP_FUSED_WAVES / MTFHIP_MIN_ROWS / MTFHIP_SLOTS; extra -D flags through SWEEP_EXTRA) and bench each on the GPU box.
 # usage: tools/sweep_fused.sh "<pipe> <waves> <min_rows> [coop] [slots]" ...   (A/B only within ONE call: boxes differ by 10-15 %)
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$here/.." || exit 1
 mkdir -p gpurun_out/sweep
 for v in "$@"; do
   set -- $v

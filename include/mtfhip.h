@@ -557,6 +557,11 @@ int mtfhip_timing_get_busy(mtfhip_ctx *ctx, const char *kernel_family, double *b
  * runtime lays the kernel-argument segment out the way the kernels read it; MTFHIP_INLINE_WARP=0 or a failed probe: 0, and
  * the warp is uploaded in front of every launch instead -- same results, 4-6 us more per iteration of a single target) */
 int mtfhip_batch_inline_warp(const mtfhip_batch *b);
+/* 1 when the next per-iteration fused launch of `sm` (mtfhip_batch_iterate, the launch-per-pass loop of mtfhip_batch_track) rebuilds the
+ * template grid from the corners' map instead of reading INIT_PTS: a unit-z, single-channel grid laid out by set_corners / set_region and
+ * not written by the caller since, and the materialising SSD homography launch of a chained FCLK / ESM.  Same results either way; 0 on a
+ * bad argument. */
+int mtfhip_batch_grid_regen(mtfhip_batch *b, const mtfhip_sm_desc *sm);
 
 #ifdef __cplusplus
 }

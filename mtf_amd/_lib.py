@@ -119,6 +119,7 @@ SYMBOLS = [
     "mtfhip_comm_unique_id", "mtfhip_comm_create", "mtfhip_comm_destroy", "mtfhip_comm_rank", "mtfhip_comm_world",
     "mtfhip_allgather_scores", "mtfhip_pf_set_comm", "mtfhip_pf_set_exchange", "mtfhip_pf_exchange_export", "mtfhip_pf_exchange_connect", "mtfhip_comm_create_detached",
     "mtfhip_timing_enable", "mtfhip_timing_reset", "mtfhip_timing_get", "mtfhip_timing_get_busy", "mtfhip_ssm_estimate_state_sigma", "mtfhip_batch_track_queues", "mtfhip_batch_inline_warp",
+    "mtfhip_batch_grid_regen",
 ]
 
 
@@ -198,6 +199,7 @@ def lib():
         L.mtfhip_batch_write.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mtfhip_timing_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.mtfhip_batch_inline_warp.argtypes = [C.c_void_p]
+        L.mtfhip_batch_grid_regen.argtypes = [C.c_void_p, C.c_void_p]
         L.mtfhip_ssm_estimate_state_sigma.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.mtfhip_pf_set_distributions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mtfhip_pf_set_distr_draws.argtypes = [C.c_void_p, C.c_void_p]

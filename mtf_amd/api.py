@@ -485,6 +485,10 @@ class Batch:
         """True when single-target launches carry the warp in the kernel arguments (mtfhip_batch_inline_warp)"""
         return bool(L.lib().mtfhip_batch_inline_warp(self._h))
 
+    def grid_regen(self, sm):
+        """True when the next per-iteration fused launch of `sm` rebuilds the template grid instead of reading INIT_PTS (mtfhip_batch_grid_regen)"""
+        return bool(L.lib().mtfhip_batch_grid_regen(self._h, C.byref(sm)))
+
     def track_targets_per_launch(self, sm):
         return L.lib().mtfhip_batch_track_targets_per_launch(self._h, C.byref(sm))
 

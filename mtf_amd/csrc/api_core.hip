@@ -714,6 +714,11 @@ int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, boo
 	b->have_corners = true;
 	b->pts_stale = grid_done && for_track;   /* k_init_grid writes the current points too, except in front of a device loop */
 	++b->corners_epoch;
+	/* (only here: the deferred layouts and the fused template initialisation lay the grid out on the device and never match, so
+	 * grid_w0_epoch == corners_epoch means "the last set_corners laid the grid out with k_init_grid from the staged w0") */
+	b->grid_w0_epoch = b->corners_epoch;
+	b->grid_w0_affine = true;
+	for (int t = 0; t < b->B; ++t) b->grid_w0_affine = b->grid_w0_affine && s_w0[9 * t + 6] == 0 && s_w0[9 * t + 7] == 0;
 	return MTFHIP_OK;
 }
 

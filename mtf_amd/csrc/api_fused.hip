@@ -572,6 +572,20 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 	fa.inline_warp = 0;
 	fa.fast_math = (b->math_mode == MTFHIP_MATH_FAST && !fa.materialize) ? 1 : 0;
 	{ int nb; fused_decomposition(b->N, b->B, nb, fa.rows_per_block); }
+	/* the template grid rebuilt in the kernel (16 B per point less): the grid is still the one k_init_grid laid out from d_w0 for these
+	 * corners (grid_w0_epoch; a caller write to INIT_PTS / INIT_Z / INIT_HXY clears grid_from_corners), the maps divide by nothing, and
+	 * the launch is the materialising SSD one -- the only instantiation with the rebuild (fused_lk_body, GR_OK), whose lattice products
+	 * launch_fused_mat gives (resx + resy) double2 of LDS */
+	fa.grid_regen = (b->unit_z && b->grid_from_corners && b->grid_w0_epoch == b->corners_epoch && b->grid_w0_affine && b->C == 1 &&
+		b->d_w0 && b->desc.resx + b->desc.resy <= kGridTabMax) ? 1 : 0;
+	fa.w0 = b->d_w0;
+	{
+		const bool hom = b->desc.ssm == MTFHIP_SSM_HOMOGRAPHY;   /* (set_corners_core's extents) */
+		fa.g_resx = b->desc.resx; fa.g_resy = b->desc.resy;
+		fa.g_lo_x = hom ? -0.5 : 1 - b->desc.resx / 2.0; fa.g_lo_y = hom ? -0.5 : 1 - b->desc.resy / 2.0;
+		fa.g_hi_x = hom ? 0.5 : b->desc.resx / 2.0; fa.g_hi_y = hom ? 0.5 : b->desc.resy / 2.0;
+		fa.g_step_x = (fa.g_hi_x - fa.g_lo_x) / (b->desc.resx - 1); fa.g_step_y = (fa.g_hi_y - fa.g_lo_y) / (b->desc.resy - 1);
+	}
 	switch (sm->sm) {
 	case MTFHIP_SM_FCLK: fa.mode = 0; break;
 	case MTFHIP_SM_ESM: fa.mode = 1; fa.hess_mean = sm->hess_type == 3; break;
@@ -579,7 +593,15 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 		if (sm->hess_type == 1) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "fused ICLK with hess_type CurrentSelf: use the un-fused entry points");
 		fa.mode = 2;
 	}
+	if (!grid_regen_kernel(b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
+		fa.grid_regen = 0;
 	return MTFHIP_OK;
+}
+
+int mtfhip_batch_grid_regen(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
+	if (!b || !sm) return 0;
+	FusedArgs fa;
+	return fused_args(b, sm, fa) == MTFHIP_OK && fa.grid_regen ? 1 : 0;
 }
 
 /* The second-order term an SSD search method adds to its Hessian (k_second_order_ssd's `term`), -1 for none:
@@ -1338,7 +1360,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 	const bool one_launch = !mi && !sm->leven_marq && iclk_one_launch(b, sm) && so_term < 0;
 	FusedArgs fa;
 	if (!one_launch && !mi) TRY(fused_args(b, sm, fa));
-	else { fa.materialize = 0; fa.mode = 2; fa.active = nullptr; fa.rows_per_block = 1; fa.j0_recompute = 0; fa.inline_warp = 0; fa.fast_math = 0; }
+	else { fa.materialize = 0; fa.mode = 2; fa.active = nullptr; fa.rows_per_block = 1; fa.j0_recompute = 0; fa.inline_warp = 0; fa.fast_math = 0; fa.grid_regen = 0; fa.w0 = nullptr; }
 	/* active = 1, iters = 0, corners, warps, states, NCC scalars: one pinned async copy of the whole slab
 	 * (w0 is copied along; init_grid consumed it long ago) */
 	/* right behind a fused grid re-initialisation the one-launch kernels need nothing of the slab's warps / states / corners (identity, zero, the
@@ -1559,6 +1581,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 			bc.warps += 9 * (size_t)t0; bc.states += 8 * (size_t)t0;
 			FusedArgs fc = fa;
 			fc.active = fa.active + t0;
+			if (fc.w0) fc.w0 += 9 * (size_t)t0;
 			TrackState tc{ts.acc + (size_t)t0 * RL, ts.h0 + (size_t)t0 * 64, ts.corners + 8 * (size_t)t0,
 				ts.init_corners_hm + 12 * (size_t)t0, ts.active + t0, ts.n_iters + t0, ncc ? ts.ncc + 8 * (size_t)t0 : nullptr,
 				ncc ? ts.ncc_tm + 52 * (size_t)t0 : nullptr, 0, ts.lm ? ts.lm + (size_t)kLmStride * t0 : nullptr, nullptr,
@@ -1566,6 +1589,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 				ts.h_extra ? ts.h_extra + (size_t)t0 * b->S * b->S : nullptr, ts.h_extra_scale, ts.fast_finish};
 			int nblk_c; { int rows; fused_decomposition(b->N, nt, nblk_c, rows, MTFHIP_SLOTS / n_streams); fc.rows_per_block = rows; }
 			if (nblk_c > b->nblk_max) { int rows; fused_decomposition(b->N, nt, nblk_c, rows); fc.rows_per_block = rows; }
+			if (fc.rows_per_block < kGridRegenMinRows) fc.grid_regen = 0;   /* (fused_args' test, for the chunk's own cut) */
 			double *part = b->d_partials + (size_t)t0 * b->nblk_max * RL;
 			/* MTFHIP_TRACK_SERIALIZE=1: the same chunks and the same cut of the pixel pass, one queue -- for the PMC passes, whose
 			 * per-dispatch counters are device-wide and would include the launch in flight on the other queue */

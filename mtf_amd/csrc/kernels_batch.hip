@@ -238,11 +238,11 @@ __global__ __launch_bounds__(kBlock) void k_iclk_track(BatchView bv, ImgView im,
 			const int i = tid + k * kBlock;
 			const int ic = i < N ? i : N - 1;
 			const int col = ic % rg.resx, row = ic / rg.resx;
-			const double nx = (rg.resx == 1 || col == rg.resx - 1) ? rg.hi_x : rg.lo_x + col * ((rg.hi_x - rg.lo_x) / (rg.resx - 1));
-			const double ny = (rg.resy == 1 || row == rg.resy - 1) ? rg.hi_y : rg.lo_y + row * ((rg.hi_y - rg.lo_y) / (rg.resy - 1));
-			const double X = W0[0] * nx + W0[1] * ny + W0[2] * 1.0;
-			const double Y = W0[3] * nx + W0[4] * ny + W0[5] * 1.0;
-			const double Z = W0[6] * nx + W0[7] * ny + W0[8] * 1.0;
+			const double nx = lattice_coord(col, rg.resx, rg.lo_x, rg.hi_x, (rg.hi_x - rg.lo_x) / (rg.resx - 1));
+			const double ny = lattice_coord(row, rg.resy, rg.lo_y, rg.hi_y, (rg.hi_y - rg.lo_y) / (rg.resy - 1));
+			double X, Y;
+			grid_point_xy(W0, nx, ny, X, Y);
+			const double Z = grid_point_z(W0, nx, ny);
 			/* (a parallelogram's map has Z = 1.0 exactly and x / 1.0 == x: the two divisions per point are skipped, same bits) */
 			const double2 p = (W0[6] == 0 && W0[7] == 0 && W0[8] == 1.0) ? make_double2(X, Y) : make_double2(X / Z, Y / Z);
 			const double z = rg.force_unit_z ? 1.0 : Z;

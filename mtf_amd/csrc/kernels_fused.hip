@@ -85,8 +85,10 @@ static void launch_fused_mat(const BatchView &bv, const ImgView &im, const Fused
 			MTFHIP_LAUNCH((k_fused_ncc<SSM, CHAINED, MODE, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
 		return;
 	}
-	if (fa.materialize)
-		MTFHIP_LAUNCH((k_fused_ssd<SSM, CHAINED, MODE, true>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
+	if (fa.materialize) {   /* (grid_regen: the lattice products, fused_lk_body) */
+		const size_t tab = fa.grid_regen ? sizeof(double2) * (size_t)(fa.g_resx + fa.g_resy) : 0;
+		MTFHIP_LAUNCH((k_fused_ssd<SSM, CHAINED, MODE, true>), g, dim3(kBlock), tab, st, bv, im, fa, partials, nblk);
+	}
 	else
 		MTFHIP_LAUNCH((k_fused_ssd<SSM, CHAINED, MODE, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
 }

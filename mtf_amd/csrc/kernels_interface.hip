@@ -3,6 +3,7 @@
  * (one of the translation units of libmtfhip.so; conventions and the shared device helpers: mtfhip_device.h)
  */
 #include "mtfhip_device.h"
+#include "mtfhip_grid_device.h"
 
 namespace mtfhip {
 
@@ -15,10 +16,6 @@ namespace mtfhip {
  * (ProjectiveBase::getPtsFromCorners SSM/src/ProjectiveBase.cc:20-25), then the bookkeeping of
  * Homography::setCorners (Homography.cc:61-69: init_pts_hm keeps the un-normalised third row) or
  * Affine::setCorners (Affine.cc:74-87: init_pts_hm is re-homogenised, third row = 1). */
-__device__ __forceinline__ double lin_spaced(int i, int n, double lo, double hi) {
-	if (n == 1 || i == n - 1) return hi;
-	return lo + i * ((hi - lo) / (n - 1));
-}
 /* (ing: the staged state slab, read from pinned host memory by the first workgroups of the same launch -- w0_all then points into
  * the host copy too, so nothing in this kernel depends on the ingest having landed) */
 struct SlabIngest { const uint4 *src; uint4 *dst; unsigned n16; const unsigned *src_tail; unsigned *dst_tail; unsigned n_tail; };
@@ -42,10 +39,10 @@ __global__ __launch_bounds__(kBlock) void k_init_grid(BatchView bv, const double
 	double2 *ch = reinterpret_cast<double2 *>(bv.buf[MTFHIP_BUF_CURR_HXY]) + (size_t)t * bv.NP;
 	for (int i = blockIdx.x * kBlock + threadIdx.x; i < bv.NP; i += gridDim.x * kBlock) {
 		const int col = i % resx, row = i / resx;
-		const double nx = lin_spaced(col, resx, lo_x, hi_x), ny = lin_spaced(row, resy, lo_y, hi_y);
-		const double X = W.m[0] * nx + W.m[1] * ny + W.m[2] * 1.0;
-		const double Y = W.m[3] * nx + W.m[4] * ny + W.m[5] * 1.0;
-		const double Z = W.m[6] * nx + W.m[7] * ny + W.m[8] * 1.0;
+		const double nx = lattice_coord(col, resx, lo_x, hi_x, (hi_x - lo_x) / (resx - 1)), ny = lattice_coord(row, resy, lo_y, hi_y, (hi_y - lo_y) / (resy - 1));
+		double X, Y;
+		grid_point_xy(W.m, nx, ny, X, Y);
+		const double Z = grid_point_z(W.m, nx, ny);
 		const double2 p = make_double2(X / Z, Y / Z);
 		const double z = force_unit_z ? 1.0 : Z;
 		/* affine re-homogenises (x, y, 1); homography keeps (X, Y, Z) */

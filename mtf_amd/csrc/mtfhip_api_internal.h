@@ -230,6 +230,10 @@ struct mtfhip_batch {
 	unsigned int frame_count = 0;   /* ImageBase::frame_count: ++ in initializePixVals and updateModel (ImageBase.cc:74, SSD.cc:51) */
 	bool j0_is_template = false;
 	long corners_epoch = 0, j0_template_corners_epoch = -1;   /* set_corners moves the grid: J0 rows depend on init_pts */
+	/* the corners epoch whose grid k_init_grid laid out from the slab's w0 (what the staged slab keeps re-uploading), and whether every
+	 * target's map had W0[6] = W0[7] = 0 there: FusedArgs::grid_regen */
+	long grid_w0_epoch = -1;
+	bool grid_w0_affine = false;
 	int j0_variant = MTFHIP_JAC_WARPED;
 	std::vector<double> template_corners;   /* [B][8] corners the stored J0 was computed on */
 	bool j0_recompute_enabled = !(std::getenv("MTFHIP_J0_RECOMPUTE") && std::getenv("MTFHIP_J0_RECOMPUTE")[0] == '0');

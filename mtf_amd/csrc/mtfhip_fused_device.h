@@ -6,6 +6,7 @@
 #ifndef MTFHIP_FUSED_DEVICE_H
 #define MTFHIP_FUSED_DEVICE_H
 #include "mtfhip_device.h"
+#include "mtfhip_grid_device.h"
 
 namespace mtfhip {
 
@@ -200,14 +201,30 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 #pragma unroll
 	for (int k = 0; k < K; ++k) acc[k] = 0.0;
 
-	auto load_in = [&](unsigned i, auto uz, auto jr) {
+	/* grid_regen (GR): the template grid point is rebuilt instead of read back (16 B per row less).  Only the instantiations
+	 * grid_regen_kernel names carry it -- the materialising SSD kernel whose time is its byte stream; the lean (tolerance-mode) kernels
+	 * are FP64 bound and the NCC ones sit at the register limit.  k_init_grid's point is (W0[0] nx + W0[1] ny) + W0[2] 1.0
+	 * with every product rounded on its own (grid_point_xy, no contraction), so the products that depend on the column alone and on the
+	 * row alone are tabulated once per workgroup in LDS (launch_fused_mat sizes it: (resx + resy) double2): a row costs two LDS reads
+	 * and four additions, and the loop keeps two scalars of the map (W0[2] 1.0, W0[5] 1.0) instead of the map and the lattice. */
+	constexpr bool GR_OK = grid_regen_kernel(AM, SSM, CHAINED, MODE, MAT) && !FAST && !PERSIST && !MC && !COHROW;
+	extern __shared__ double2 grid_tab[];   /* [resx] (W0[0] nx, W0[3] nx) | [resy] (W0[1] ny, W0[4] ny) */
+	double gz_x = 0.0, gz_y = 0.0;
+	/* gc, gr: the lattice column and row of pixel i (GR only) */
+	auto load_in = [&](unsigned i, auto uz, auto jr, auto grg, unsigned gc, unsigned gr) {
 		PixIn<S, MODE> in;
 		constexpr bool JR = decltype(jr)::value;   /* J0 rows rebuilt from dI0_dx (2 loads) instead of read back (S loads) */
+		constexpr bool GR = decltype(grg)::value;
+		auto grid_pt = [&]() {
+			const double2 c = grid_tab[gc], r = grid_tab[(unsigned)fa.g_resx + gr];
+			return make_double2(grid_point_sum(c.x, r.x, gz_x), grid_point_sum(c.y, r.y, gz_y));
+		};
 		const unsigned pi = MC ? i / Cc : i;   /* the row's pixel */
 		if constexpr (MC) in.ch = (int)(i - pi * Cc);
 #if MTFHIP_NT_LOAD
 		typedef double d2v __attribute__((ext_vector_type(2)));
-		{ const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v *>(ip) + pi); in.p = make_double2(v.x, v.y); }
+		if constexpr (GR) in.p = grid_pt();
+		else { const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v *>(ip) + pi); in.p = make_double2(v.x, v.y); }
 		in.i0 = __builtin_nontemporal_load(&I0[i]);
 		if constexpr (MODE != 0) {
 #pragma unroll
@@ -218,7 +235,8 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 		const unsigned o16 = pi * 16u, oz = pi * 8u;
 #else
 		const unsigned o8 = i * 8u, o16 = pi * 16u, oz = pi * 8u;
-		in.p = ld_off<double2>(ip, o16);
+		if constexpr (GR) in.p = grid_pt();
+		else in.p = ld_off<double2>(ip, o16);
 		in.i0 = ld_off<double>(I0, o8);
 		if constexpr (MODE != 0 && JR) {
 			in.j0[0] = ld_off<double>(dI0, o8); in.j0[1] = ld_off<double>(dI0 + N, o8);
@@ -621,8 +639,30 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 	 * for the texels with `s_waitcnt vmcnt(<next-row loads>)` and for the next row with `vmcnt(<stores>)`.
 	 * With guarded loads it has to assume the shortest path and emits vmcnt(0), which silently serialises the
 	 * prefetch behind the current row (that is what the ISA of the first version did). */
-	auto run_rows = [&](auto uz, auto jr) {
+	auto run_rows = [&](auto uz, auto jr, auto grg) {
 		const unsigned blk_first = blockIdx.x * (unsigned)(kBlock * n_rows);
+		/* GR: the lattice position of the next row to load, moved by kBlock points per row without a division (the row index is
+		 * clamped: the prefetch behind a target's last row lies past the lattice, and its point is never used) */
+		unsigned gc = 0, gr = 0, dgc = 0, dgr = 0;
+		const unsigned gresx = (unsigned)fa.g_resx, gresy_m1 = (unsigned)fa.g_resy - 1u;
+		if constexpr (decltype(grg)::value) {
+			const double *w0 = fa.w0 + 9 * t;
+			const double g0 = w0[0], g1 = w0[1], g3 = w0[3], g4 = w0[4];
+			for (unsigned c = threadIdx.x; c < gresx; c += kBlock) {
+				const double nx = lattice_coord((int)c, fa.g_resx, fa.g_lo_x, fa.g_hi_x, fa.g_step_x);
+				grid_tab[c] = make_double2(g0 * nx, g3 * nx);
+			}
+			for (unsigned r = threadIdx.x; r <= gresy_m1; r += kBlock) {
+				const double ny = lattice_coord((int)r, fa.g_resy, fa.g_lo_y, fa.g_hi_y, fa.g_step_y);
+				grid_tab[gresx + r] = make_double2(g1 * ny, g4 * ny);
+			}
+			gz_x = w0[2] * 1.0; gz_y = w0[5] * 1.0;
+			gc = base % gresx; gr = min(base / gresx, gresy_m1); dgc = kBlock % gresx; dgr = kBlock / gresx;
+			__syncthreads();   /* (every thread of the workgroup gets here: nothing above returns) */
+		}
+		auto next_pos = [&]() {
+			if constexpr (decltype(grg)::value) { gc += dgc; gr += dgr; if (gc >= gresx) { gc -= gresx; ++gr; } gr = min(gr, gresy_m1); }
+		};
 		/* full 256-pixel rows of this workgroup: no lane is masked, so nothing in the loop body is conditional */
 		int full = 0;
 		if (blk_first < N) {
@@ -630,7 +670,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 			full = avail < (unsigned)n_rows ? (int)avail : n_rows;
 		}
 		if (full > 0) {
-			PixIn<S, MODE> cur = load_in(base, uz, jr);
+			PixIn<S, MODE> cur = load_in(base, uz, jr, grg, gc, gr);
 			asm volatile("" ::: "memory");
 			setup_target();
 			if (!live) return;
@@ -640,30 +680,34 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 				const Tex tcur = issue_tex(cur, uz);
 				asm volatile("" ::: "memory");      /* texel fetch first, then the next row's operands: keeps the order */
 				const unsigned inext = i + kBlock;
-				const PixIn<S, MODE> nxt = load_in(inext < N ? inext : N - 1, uz, jr);
+				next_pos();   /* (past the end of the target on the last row: a point nobody uses, no memory touched) */
+				const PixIn<S, MODE> nxt = load_in(inext < N ? inext : N - 1, uz, jr, grg, gc, gr);
 				asm volatile("" ::: "memory");
 				row_compute(i, cur, tcur, jr);
 				cur = nxt;
 			}
 		}
-		/* the partial last row of a target (only the workgroup that owns the end of the patch gets here) */
+		/* the partial last row of a target (only the workgroup that owns the end of the patch gets here; the lattice position is
+		 * already the row's: `full` steps from base) */
 		if (full < n_rows) {
 			const unsigned i = base + (unsigned)full * kBlock;
 			if (full == 0) { setup_target(); if (!live) return; }
 			if (i < N) {
-				const PixIn<S, MODE> c = load_in(i, uz, jr);
+				const PixIn<S, MODE> c = load_in(i, uz, jr, grg, gc, gr);
 				const Tex tc = issue_tex(c, uz);
 				row_compute(i, c, tc, jr);
 			}
 		}
 	};
-	if constexpr (MODE == 0) {      /* no template row in the FCLK accumulation */
-		if (unit_z) run_rows(std::true_type{}, std::false_type{}); else run_rows(std::false_type{}, std::false_type{});
-	} else if (fa.j0_recompute) {
-		if (unit_z) run_rows(std::true_type{}, std::true_type{}); else run_rows(std::false_type{}, std::true_type{});
-	} else {
-		if (unit_z) run_rows(std::true_type{}, std::false_type{}); else run_rows(std::false_type{}, std::false_type{});
-	}
+	auto run_grid = [&](auto jr) {
+		if constexpr (GR_OK) {
+			if (fa.grid_regen && unit_z) { run_rows(std::true_type{}, jr, std::true_type{}); return; }
+		}
+		if (unit_z) run_rows(std::true_type{}, jr, std::false_type{}); else run_rows(std::false_type{}, jr, std::false_type{});
+	};
+	if constexpr (MODE == 0) run_grid(std::false_type{});      /* no template row in the FCLK accumulation */
+	else if (fa.j0_recompute) run_grid(std::true_type{});
+	else run_grid(std::false_type{});
 	if (!live) return;
 	double *dst = partials + ((size_t)t * nblk + blockIdx.x) * ROW_LEN;
 	if constexpr (NPARK > 0) {   /* (a thread's LDS operations execute in order: its own sums are complete) */

@@ -1,12 +1,31 @@
 /*
  * mtfhip_grid_device.h -- device helpers shared by the grid kernels (k_iclk_track, kernels_batch.hip; k_template_init, kernels_init.hip;
  * k_grid_fb, kernels_grid_fb.hip): the workgroup reductions of the one-launch ICLK loop, the reductions and the in-LDS inversion of the
- * fused template initialisation, the hand-over of a patch's results to the host.
+ * fused template initialisation, the hand-over of a patch's results to the host; and the template grid point itself, which k_init_grid,
+ * k_iclk_track's region mode and the fused Lucas-Kanade body (grid_regen) all evaluate with these expressions.
  */
 #pragma once
 #include "mtfhip_device.h"
 
 namespace mtfhip {
+
+/* ===================================================================== */
+/* the template grid point (ProjectiveBase::getPtsFromCorners + setCorners) */
+/* ===================================================================== */
+/* lattice coordinate `i` of `n` in [lo, hi]: Eigen's LinSpaced (lin_spaced_hd) with its step (hi - lo) / (n - 1) passed in, so a loop
+ * can divide once -- the same value, the same bits */
+__device__ __forceinline__ double lattice_coord(int i, int n, double lo, double hi, double step) {
+	return (n == 1 || i == n - 1) ? hi : lo + i * step;
+}
+/* one row of W0 * (nx, ny, 1) from its three products, in the order k_init_grid adds them (the fused kernel tabulates the products) */
+__device__ __forceinline__ double grid_point_sum(double a_nx, double b_ny, double c_1) { return a_nx + b_ny + c_1; }
+/* the first two rows of W0 * (nx, ny, 1): the point itself when W0[6] = W0[7] = 0 (W0[8] = 1: rect_to_quad_hd), where Z = 1.0 and
+ * X / 1.0 == X */
+__device__ __forceinline__ void grid_point_xy(const double *W0, double nx, double ny, double &X, double &Y) {
+	X = grid_point_sum(W0[0] * nx, W0[1] * ny, W0[2] * 1.0);
+	Y = grid_point_sum(W0[3] * nx, W0[4] * ny, W0[5] * 1.0);
+}
+__device__ __forceinline__ double grid_point_z(const double *W0, double nx, double ny) { return W0[6] * nx + W0[7] * ny + W0[8] * 1.0; }
 
 /* ===================================================================== */
 /* one-launch inverse-compositional tracker for small patches (GridTracker) */

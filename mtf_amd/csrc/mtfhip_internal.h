@@ -54,6 +54,18 @@ void note_launch_error(hipError_t e, const char *file, int line);
 #define MTFHIP_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); const hipError_t _le = hipGetLastError(); \
 	if (_le != hipSuccess) ::mtfhip::note_launch_error(_le, __FILE__, __LINE__); } while (0)
 constexpr int kBlock = 256;       /* threads per workgroup: 4 wave64 */
+constexpr int kGridTabMax = 2048; /* FusedArgs::grid_regen: columns + rows of the lattice tabulated in LDS (32 KB) */
+/* FusedArgs::grid_regen only when a workgroup walks at least this many rows: the map load, the table and its barrier stand in front of the
+ * first row's loads, which pays off in a streaming launch (64 x 200 x 200: 20 rows, 54.4 -> 49.4 us) and not in a latency-bound one
+ * (one 200 x 200 target, 4 rows: 12.2 -> 12.8 us per iteration with it) */
+constexpr int kGridRegenMinRows = 8;
+/* the fused instantiations that carry the grid rebuild (FusedArgs::grid_regen): the materialising SSD launch, homography, chained
+ * warp, FCLK or ESM -- the headline's kernel and its FCLK sibling, which keep their occupancy and stay clear of scratch with it
+ * (-Rpass-analysis=kernel-resource-usage, profiles/r07_resource_usage.txt); the others (lean / NCC / affine / non-chained / ICLK)
+ * would lose a wave per SIMD or spill, and read INIT_PTS */
+constexpr bool grid_regen_kernel(int am, int ssm, bool chained, int mode, bool mat) {
+	return am == MTFHIP_AM_SSD && ssm == MTFHIP_SSM_HOMOGRAPHY && chained && mode != 2 && mat;
+}
 #ifndef MTFHIP_SLOTS
 #define MTFHIP_SLOTS 512          /* resident workgroups of the fused kernel: 256 CUs x 2 (2 waves/SIMD, 4-wave groups) */
 #endif
@@ -273,6 +285,15 @@ struct FusedArgs {
 	/* 1: tolerance-mode arithmetic (mtfhip_device.h, "tolerance-mode arithmetic"); only with materialize == 0 -- the
 	 * materialised arrays stay bit-identical to what the per-function kernels write */
 	int fast_math;
+	/* 1: the template grid point of a row is rebuilt from the target's map (w0 [B][9], the slab) and the lattice index instead of
+	 * being read from INIT_PTS -- planned by fused_args only for a unit-z grid that k_init_grid laid out from these very maps with
+	 * W0[6] = W0[7] = 0 (no division), single channel, no caller write to the grid since (grid_point_xy, mtfhip_grid_device.h) */
+	int grid_regen;
+	/* (planned for the materialising SSD launch only, lattices of at most kGridTabMax columns + rows: mtfhip_batch_grid_regen) */
+	int g_resx, g_resy;
+	double g_lo_x, g_lo_y, g_hi_x, g_hi_y;
+	double g_step_x, g_step_y;   /* (hi - lo) / (res - 1), the layout's own step */
+	const double *w0;
 };
 
 /* one-time probe: does the kernel-argument segment hold (BatchView, ImgView, FusedArgs) where fused_lk_body's inline-warp path reads them? */

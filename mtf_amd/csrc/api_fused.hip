@@ -792,7 +792,9 @@ static int mi_enqueue_fast(mtfhip_batch *b, const mtfhip_sm_desc *sm, const MiPl
 	 * at a third of the occupancy (1024 workgroups over 768 slots; r05 ablation: the pass is bound by its sampling, 105 of 120 us, not
 	 * by the block products).  Its own count: the largest multiple of the resident slots that the partial-row buffer holds. */
 	/* (r05 advisor: nblk1 follows the device's resident slots, so tolerance mode's summation grouping -- and with it the last bits of its sums --
-	 * depends on the CU count: results are reproducible run to run on one device, not bit for bit across devices; MTFHIP_MI_PASS1_BLOCKS pins it) */
+	 * depends on the CU count: results are reproducible run to run on one device, not bit for bit across devices; MTFHIP_MI_PASS1_BLOCKS pins it.
+	 * Run to run on one device holds at every bin count: pass 2 sums its moment tables per wave, in wave order, with no atomics across
+	 * waves -- tests/test_gpu_golden5.py::test_mi_fused_reproducible) */
 	int nblk1 = nblk;
 	{
 		static const char *e_b1 = std::getenv("MTFHIP_MI_PASS1_BLOCKS");

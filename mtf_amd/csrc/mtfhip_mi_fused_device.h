@@ -288,22 +288,27 @@ constexpr int kTRows = 12;   /* gradient-factor tables in LDS, indexed with (bin
  * the chained kernels keep their register budget */
 /* NB (r06): the bin count the class tables are laid out for.  8 = the reference's default (parameters.h:344), the r03-r05 kernels unchanged
  * (pa.nb == 8).  10 = the shipped configuration (Config/modules.cfg:115-117: mi_n_bins 10, partition of unity) and every other count up to
- * ten: pa.nb classes and bins at run time, ten-class sort, the moment table M[class][power][s] SHARED by the four waves (ds_add_f64
- * at class boundaries only) so that the workgroup stays under half a CU's LDS -- constant-Hessian and self-Hessian forms (HK 0 / 1). */
+ * ten: pa.nb classes and bins at run time, ten-class sort -- constant-Hessian and self-Hessian forms (HK 0 / 1).  Every wave has a moment
+ * table of its own at every bin count, and the four are summed in wave order, so the sums are reproducible run to run.  To keep ten
+ * tables per wave under half a CU's LDS (two workgroups per CU), the NB = 10 tables are packed to the six live powers (48 doubles per
+ * class instead of kQR = 64) and the staging rows of phi^4 and phi^5 are not kept: a lane rebuilds them as phi^2 phi^2 phi^li from
+ * rows 2 and li, the same products the staging stores made. */
 template <int SSM, int HK, int HROW, bool MC = false, bool NONCH = false, int NB = 8>
 __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, ImgView im, MiPassArgs pa, double *partials, int nblk) {
 	constexpr int S = SSM == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6;
 	static_assert(NB == 8 || (NB == 10 && HK <= 1), "pass 2: 8 bins in every form, up to 10 in the polynomial forms (HK 0 / 1)");
 	const int nb = NB == 8 ? 8 : pa.nb;   /* (NB == 8: folded as a constant) */
 	constexpr bool SORTED = HK == 1;
-	constexpr bool SHARED_M = NB != 8;
-	constexpr int kSRows = 15;   /* sorted staging rows: valid phi^0..5 | J[8] | hess_term */
+	constexpr bool HI_ROWS = NB == 8;   /* phi^4, phi^5 staged (8 bins) or rebuilt from phi^2 (NB = 10, see above) */
+	constexpr int kSRows = HI_ROWS ? 15 : 13;   /* sorted staging rows: valid phi^0..5 (phi^0..3 when !HI_ROWS) | J[8] | hess_term */
+	constexpr int kPw = HI_ROWS ? 6 : 4;         /* staged power rows */
+	constexpr int kMS = NB == 8 ? kQR : 48;      /* doubles per class of a wave's moment table: M[power 0..5][s], power 4 + lk at 32 + 8 lk */
 	constexpr int kRowF = mi_fast_row_nb(NB), kPolyI = mi_poly_i(NB), kPolyH = mi_poly_h(NB), kPolySz = mi_poly_size_nb(NB);
-	constexpr int SLAB = SORTED ? kSRows * kRS2 + (SHARED_M ? 0 : 8 * kQR) : (HK ? (2 * kWinRows + 9) * kRS : 0);   /* dense: gd[11] | wd[11] | rw[8] | ht ; sorted: valid | phi | rw[8] | ht | M[8 classes][8 powers][8] */
+	constexpr int SLAB = SORTED ? kSRows * kRS2 + NB * kMS : (HK ? (2 * kWinRows + 9) * kRS : 0);   /* dense: gd[11] | wd[11] | rw[8] | ht ; sorted: valid | phi | rw[8] | ht | M[NB classes][powers][8] */
 	constexpr bool POLY = HK == 0 || HK == 1;   /* the table sums as per-class polynomials (no window is needed: the bin mode of the self Hessian is in moment form) */
 	__shared__ __attribute__((aligned(16))) double Tc[POLY ? 2 : kTRows * MI_NB], Ti[POLY ? 2 : kTRows * MI_NB], Th[1];
 	__shared__ __attribute__((aligned(16))) double Pl[POLY ? kPolySz : 2];
-	__shared__ __attribute__((aligned(16))) double slabs[HK ? 4 * SLAB + (SORTED && SHARED_M ? NB * kQR : 0) : 4 * 16];
+	__shared__ __attribute__((aligned(16))) double slabs[HK ? 4 * SLAB : 4 * 16];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const int t = blockIdx.y;
 	if (pa.active && !pa.active[t]) return;
@@ -320,11 +325,10 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 	}
 	const double *Tq = HK == 1 ? Th : (HK == 2 ? Tc : Ti);
 	double *gd = slabs + (size_t)wave * SLAB, *wd = gd + kWinRows * kRS, *rw = wd + kWinRows * kRS, *hts = rw + 8 * kRS;
-	double *sd = slabs + (size_t)wave * SLAB, *srw = sd + 6 * kRS2, *sht = srw + 8 * kRS2;   /* sorted form: sd = the six power rows valid phi^k (r05: staged once per pixel instead of rebuilt by every lane of every step) */
-	double *qabs = SHARED_M ? slabs + 4 * SLAB : sht + kRS2;   /* this wave's moment table M[class][power][s] (NB != 8: the workgroup's) */
+	double *sd = slabs + (size_t)wave * SLAB, *srw = sd + kPw * kRS2, *sht = srw + 8 * kRS2;   /* sorted form: sd = the power rows valid phi^k (r05: staged once per pixel instead of rebuilt by every lane of every step) */
+	double *qabs = sht + kRS2;   /* this wave's moment table M[class][power][s]: no other wave writes it */
 	if constexpr (SORTED) {
 		for (int k2 = lane; k2 < SLAB; k2 += 64) sd[k2] = 0.0;
-		if constexpr (SHARED_M) { for (int k2 = threadIdx.x; k2 < NB * kQR; k2 += kBlock) qabs[k2] = 0.0; }
 	}
 	else if constexpr (HK != 0) { for (int k2 = 0; k2 < 2 * kWinRows + 9; ++k2) gd[k2 * kRS + lane] = 0.0; }
 	__syncthreads();
@@ -505,7 +509,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 			if (valid) {
 				const double ph = phi_it;   /* phi = It - fl: every tap of the window is a polynomial of it */
 				const double ph2 = ph * ph, ph3 = ph2 * ph, ph4 = ph2 * ph2, ph5 = ph4 * ph;
-				sd[mycol] = 1.0; sd[kRS2 + mycol] = ph; sd[2 * kRS2 + mycol] = ph2; sd[3 * kRS2 + mycol] = ph3; sd[4 * kRS2 + mycol] = ph4; sd[5 * kRS2 + mycol] = ph5;
+				sd[mycol] = 1.0; sd[kRS2 + mycol] = ph; sd[2 * kRS2 + mycol] = ph2; sd[3 * kRS2 + mycol] = ph3;
+				if constexpr (HI_ROWS) { sd[4 * kRS2 + mycol] = ph4; sd[5 * kRS2 + mycol] = ph5; }
 #pragma unroll
 				for (int s2 = 0; s2 < 8; ++s2) srw[s2 * kRS2 + mycol] = jt[s2];
 				sht[mycol] = hess_term;
@@ -520,7 +525,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 			 * go to the wave's moment table through ds_add_f64.  Slots behind a class's last pixel have valid = 0 and hess_term = 0. */
 			/* A operands: row li of the low tile = valid phi^li, row li of the high tile = valid phi^(4 + li) for li < 2; rows 2, 3 of the high
 			 * tile are padding -- their results (rows 2, 3 of q10 / q11) are never flushed, so those lanes may read any finite row */
-			const double *plo = sd + li * kRS2, *phi_ = sd + (4 + (li & 1)) * kRS2, *pja = srw + li * kRS2, *pjb = pja + 4 * kRS2, *pht = sht;   /* + this lane's column of the step */
+			/* (!HI_ROWS: phi_ is the phi^2 row, and the high operand is phi^2 phi^2 phi^li -- exactly ph4 = ph2 ph2 for li = 0 and
+			 * ph5 = ph4 ph for li = 1, zero in padding slots) */
+			const double *plo = sd + li * kRS2, *phi_ = sd + (HI_ROWS ? 4 + (li & 1) : 2) * kRS2, *pja = srw + li * kRS2, *pjb = pja + 4 * kRS2, *pht = sht;   /* + this lane's column of the step */
 			/* class of the quad that starts at slot s0 = number of classes that end at or before it (empty classes included: they end
 			 * where their predecessor does); byte-wise on the packed end slots, no borrow between bytes: (s0 | 0x80) - end >= 0x80 - 88 > 0 */
 			unsigned ends_lo, ends_hi, ends_x = 0xFFFFFFFFu;   /* (ends_x: the third word of the ten-class sort; 0xFF bytes are never "at or before") */
@@ -533,11 +540,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 				return c;
 			};
 			/* leave class `cls` for `to`: M[cls][4 T + lk][4 h + li] += q<T><h>.  Result layout of the block product: column = li, block = lb,
-			 * row = lk. */
+			 * row = lk.  Only this wave adds to its table; lanes of one ds_add_f64 that meet on an address (blocks of the same class)
+			 * are applied by the LDS in a fixed lane order, so the sums do not depend on scheduling. */
 			auto leave_class = [&](int to) {
 #if !(defined(MTFHIP_MI_ABL) && MTFHIP_MI_ABL == 5)   /* ablation 5: class boundaries without the table update */
 				if (cls < NB) {
-					double *qe = qabs + cls * 64 + lk * 8 + li;
+					double *qe = qabs + cls * kMS + lk * 8 + li;
 					lds_add_f64(qe, q00); lds_add_f64(qe + 4, q01);
 					if (lk < 2) { lds_add_f64(qe + 32, q10); lds_add_f64(qe + 36, q11); }   /* powers 4, 5 */
 				}
@@ -546,7 +554,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 				cls = to;
 			};
 			int o = window_col(0, lb, lk);
-			double c_lo = plo[o], c_hi = phi_[o], c_ja = pja[o], c_jb = pjb[o], c_ht = pht[o];
+			auto hi_op = [&](double lo, double p2) -> double { if constexpr (HI_ROWS) return p2; else return p2 * p2 * lo; };
+			double c_lo = plo[o], c_hi = hi_op(c_lo, phi_[o]), c_ja = pja[o], c_jb = pjb[o], c_ht = pht[o];
 			const int s_first = 4 * lb * steps;   /* first slot of this block's range */
 			{
 				const int c_first = class_of(s_first);
@@ -561,7 +570,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 #endif
 				/* operands of the next step first (one step past the end reads the columns behind the window: discarded) */
 				o = window_col(j + 1, lb, lk);
-				const double n_lo = plo[o], n_hi = phi_[o], n_ja = pja[o], n_jb = pjb[o], n_ht = pht[o];
+				const double n_lo = plo[o], n_hi = hi_op(n_lo, phi_[o]), n_ja = pja[o], n_jb = pjb[o], n_ht = pht[o];
 				{
 					const double a_lo = c_lo, a_hi = c_hi;
 					q00 = __builtin_amdgcn_mfma_f64_4x4x4f64(a_lo, c_ja, q00, 0, 0, 0); q01 = __builtin_amdgcn_mfma_f64_4x4x4f64(a_lo, c_jb, q01, 0, 0, 0);
@@ -579,7 +588,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 			__builtin_amdgcn_wave_barrier();
 			if (valid) {   /* padding slots must keep zero power rows (valid = 0) and a zero hess_term */
 #pragma unroll
-				for (int k2 = 0; k2 < 6; ++k2) sd[k2 * kRS2 + mycol] = 0.0;
+				for (int k2 = 0; k2 < kPw; ++k2) sd[k2 * kRS2 + mycol] = 0.0;
 				sht[mycol] = 0.0;
 			}
 		} else if constexpr (HK != 0) {
@@ -631,7 +640,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 	}
 	if constexpr (SORTED) {   /* what the blocks still hold goes to the wave's table */
 		if (cls < NB) {
-			double *qe = qabs + cls * 64 + lk * 8 + li;
+			double *qe = qabs + cls * kMS + lk * 8 + li;
 			lds_add_f64(qe, q00); lds_add_f64(qe + 4, q01);
 			if (lk < 2) { lds_add_f64(qe + 32, q10); lds_add_f64(qe + 36, q11); }
 		}
@@ -663,8 +672,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 			/* (block_reduce_store above used the first 64 doubles as its scratch) */
 			for (int k2 = threadIdx.x; k2 < 4 * 64; k2 += kBlock) qred[k2] = 0.0;
 			__syncthreads();
-			/* tile (X, Y) of every block: row 4 X + lk, column 4 Y + li.  The four blocks of a wave meet through ds_add_f64; the target --
-			 * the first 256 doubles of the slabs, nobody's staging rows any more */
+			/* tile (X, Y) of every block: row 4 X + lk, column 4 Y + li.  The four blocks of a wave meet through ds_add_f64 -- in one
+			 * instruction per tile, so in the LDS's fixed lane order -- in the wave's own 64 doubles; the target is the first 256 doubles
+			 * of the slabs, nobody's staging rows any more */
 #pragma unroll
 			for (int xy = 0; xy < 4; ++xy) if (xy != 2) lds_add_f64(qred + wave * hl + (4 * (xy >> 1) + lk) * 8 + 4 * (xy & 1) + li, chs4[xy]);
 		} else {
@@ -676,10 +686,14 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 				const int r = k2 >> 3, c = k2 & 7, src = (r >= 4 && c < 4) ? c * 8 + r : k2;   /* the lower-left tile from the upper-right one */
 				dst[16 + k2] = (qred[src] + qred[64 + src]) + (qred[128 + src] + qred[192 + src]);
 			}
-			/* the four waves' moment tables -> one (in the first wave's, in place), then Q[(r, c)][s] = hist_norm sum_fl sum_j C[k][m][j] M[fl][j][s]
-			 * over the classes whose window holds both bins: k = r - (fl - 1), m = c - (fl - 1) in 0..3 */
-			double *m0 = SHARED_M ? slabs + 4 * SLAB : slabs + kSRows * kRS2;
-			if constexpr (!SHARED_M) {
+			/* the four waves' moment tables -> one (in the first wave's, in place, summed in wave order), then
+			 * Q[(r, c)][s] = hist_norm sum_fl sum_j C[k][m][j] M[fl][j][s] over the classes whose window holds both bins:
+			 * k = r - (fl - 1), m = c - (fl - 1) in 0..3 */
+			double *m0 = slabs + kSRows * kRS2;
+			if constexpr (NB != 8) {   /* (each entry is read and written by one thread only) */
+				for (int k2 = threadIdx.x; k2 < NB * kMS; k2 += kBlock) m0[k2] = (m0[k2] + m0[SLAB + k2]) + (m0[2 * SLAB + k2] + m0[3 * SLAB + k2]);
+				__syncthreads();
+			} else {
 				double msum[2];
 #pragma unroll
 				for (int u = 0; u < 2; ++u) { const int k2 = threadIdx.x + u * kBlock; msum[u] = (m0[k2] + m0[SLAB + k2]) + (m0[2 * SLAB + k2] + m0[3 * SLAB + k2]); }
@@ -696,7 +710,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_mi_pass_grad_hess(BatchView bv, I
 				for (int k = 0; k < 4; ++k) {
 					const int fl = r + 1 - k, m = c - (fl - 1);
 					if (fl >= 0 && fl < nb && m >= 0 && m < 4) {
-						const double *mm = m0 + fl * 64 + sx;
+						const double *mm = m0 + fl * kMS + sx;
 						double acc6 = 0.0;
 #pragma unroll
 						for (int j = 0; j < 6; ++j) {

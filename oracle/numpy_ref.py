@@ -457,13 +457,46 @@ def nn_dataset_rows(img, init_hm, perts, ncc=False):
     return np.stack(rows)
 
 
+def mi_pix_norm(n_bins, pou):
+    """The MI AM's pixel normalisation (AM/src/MI.cc:79-94) -> (pix_norm_mult, pix_norm_add): raw values over PIX_MAX - PIX_MIN + 1 = 256
+    levels are mapped to [0, n_bins - 1], or with partition of unity to [1, n_bins - 2]; the stored value is mult * v + add."""
+    lo, hi = (1.0, n_bins - 2.0) if pou else (0.0, n_bins - 1.0)
+    return (hi - lo) / 256.0, lo
+
+
+def mi_init_hessian(I0n, Itn, J0, n_bins=8, pre_seed=10.0):
+    """MI::cmptInitHessian (AM/src/MI.cc:461-513, after updateInitGrad :389-416), written densely: the roles of the two patches swapped
+    against mi_curr_hessian -- the template's B-spline derivatives, the template's marginal h_i, the template Jacobian J0:
+    H = J0^T diag(t) J0 + sum_{r,c} (1/h(r,c) - 1/h_i(c)) Q(r,c)^T Q(r,c),
+    t_p = sum_c d2/dI02 b3(c - I0_p) norm * sum_r b3(r - It_p) (1 + log h(r,c) - log h_i(c)),
+    Q(r,c) = sum_p d/dI0 b3(c - I0_p) norm * b3(r - It_p) * J0[p, :],
+    with r the bin of the current patch and c that of the template, h(r, c) the joint histogram as in mi_similarity."""
+    I0n = np.asarray(I0n, dtype=np.float64); Itn = np.asarray(Itn, dtype=np.float64)
+    N = I0n.size
+    bins = np.arange(n_bins, dtype=np.float64)
+    X0 = bins[:, None] - I0n[None, :]
+    Bt, B0 = bspline3(bins[:, None] - Itn[None, :]), bspline3(X0)
+    seed_h = n_bins * pre_seed
+    norm = 1.0 / (N + seed_h * n_bins)
+    hi = (seed_h + B0.sum(axis=1)) * norm
+    hj = (pre_seed + Bt @ B0.T) * norm                  # [r (current), c (template)]
+    G = 1.0 + np.log(hj) - np.log(hi)[None, :]
+    dB0 = -bspline3_d1(X0) * norm
+    d2B0 = bspline3_d2(X0) * norm
+    t = np.einsum("cp,rc,rp->p", d2B0, G, Bt)
+    H = J0.T @ (t[:, None] * J0)
+    Q = np.einsum("cp,rp,ps->rcs", dB0, Bt, J0)
+    fac = 1.0 / hj - 1.0 / hi[None, :]
+    return H + np.einsum("rc,rcs,rcu->su", fac, Q, Q)
+
+
 def nn_mi_dist_feat(It, n_bins, pou):
     """MI::updateDistFeat (AM/src/MI.cc:736-747) of raw pixel values It (N,): the AM's pixel normalisation first (MI.cc:80-94: [0, 255] ->
     [0, n_bins - 1], with partition of unity [1, n_bins - 2], over PIX_MAX - PIX_MIN + 1 = 256), then per pixel the 5 x N matrix, row-major:
     floor(v) | bSpl3(d), bSpl3(d + 1), bSpl3(d + 2), bSpl3(d + 3) with d = first id of the floor's B-spline window (max(floor - 1, 0), the
     standard ids of histUtils) - v.  -> (5 N,)"""
-    lo, hi = (1.0, n_bins - 2.0) if pou else (0.0, n_bins - 1.0)
-    v = (hi - lo) / 256.0 * np.asarray(It, dtype=np.float64) + lo
+    mult, add = mi_pix_norm(n_bins, pou)
+    v = mult * np.asarray(It, dtype=np.float64) + add
     fl = np.floor(v)
     d = np.maximum(fl - 1.0, 0.0) - v
     return np.concatenate([fl, bspline3(d), bspline3(d + 1.0), bspline3(d + 2.0), bspline3(d + 3.0)])

@@ -237,15 +237,43 @@ def test_fused_mi_partition_of_unity(oracle, gpu_ctx, frame, case, materialize, 
 def test_fused_mi_other_bin_counts(oracle, gpu_ctx, frame, case, n_bins, pou):
     """r06: the recompute passes with other bin counts than 8 -- the shipped configuration is mi_n_bins 10 with the partition of unity
     (Config/modules.cfg:115-117) -- for the constant and the self Hessian forms of the three search methods: ten-class sort, 3 x 3 tiles of
-    the histograms' block products, the workgroup's shared moment table (k_mi_pass_hist / k_mi_pass_grad_hess <.., NB = 10>).  Held to the
+    the histograms' block products, the waves' moment tables (k_mi_pass_hist / k_mi_pass_grad_hess <.., NB = 10>).  Held to the
     oracle exactly as the 8-bin cases are (_fused_follow: both arithmetic modes, every iteration).  9 and 5 bins: ragged last tiles."""
     if pou and n_bins < 4:
         pytest.skip("MI::Too few bins to enforce the partition of unity constraint (MI.cc:83-87)")
+    dp_tol = 1e-5
     if n_bins != 10 and case[3].get("chained_warp") == 0:
-        # (measured: dp 1.1e-5 / 1.25e-5 of the 1e-5 budget at 9 bins + pou and 5 bins -- MI's update is ill-conditioned, the two oracles themselves
-        # differ by 1.5e-5 .. 2.8e-5 there (test_mi_update_noise_floor); the non-chained route is held at the shipped count)
-        pytest.skip("the non-chained route is held to the 1e-5 budget at the shipped bin count")
-    _fused_follow(oracle, gpu_ctx, frame, L.AM_MI, case, 0, "device_grid", am_kw=dict(mi_n_bins=n_bins, mi_pou=pou))
+        # (measured before: dp 1.1e-5 / 1.25e-5 at 9 bins + pou and 5 bins -- MI's update is ill-conditioned there and the reference's own
+        # update moves by as much when its finite-difference step or its gradient route changes.)  The bound is that floor, measured here
+        # for this case: 4 x the floor, never above 1e-4 absolute -- and never below the 1e-5 budget the other cases are held to
+        floor = _mi_dp_noise_floor(oracle, frame, case, n_bins, pou)
+        dp_tol = min(max(4.0 * floor, 1e-5), 1e-4)
+    _fused_follow(oracle, gpu_ctx, frame, L.AM_MI, case, 0, "device_grid", am_kw=dict(mi_n_bins=n_bins, mi_pou=pou), dp_tol=dp_tol)
+
+
+def _mi_dp_noise_floor(oracle, frame, case, n_bins, pou):
+    """How far the oracle's own MI parameter update moves for this case's search method, bin count and pou (as test_oracle_relations.py::test_mi_update_noise_floor does for 8 bins): the relative dp between the oracle at
+    grad_eps 1e-8 and at 2e-8, and between the non-chained and the chained route, over the first two iterations (where dp is held
+    plain relative; later ones go to zero); each run follows its own trajectory from _fused_follow's start."""
+    sm_kind, ssm, res, extra = case
+    rng = np.random.default_rng(17)
+    centre = (250.0, 262.0)
+    corners = synth.square_corners(centre[0], centre[1], 2.0 * res if res <= 60 else float(res))
+    frame2 = synth.warp_frame(frame, synth.random_small_homography(rng, 0.6), centre)
+
+    def run(eps, chained):
+        o_ssm = oracle.SSM(ssm, res, res)
+        o_am = oracle.AM(L.AM_MI, res, res, grad_eps=eps, n_bins=n_bins, pou=pou)
+        o_am.set_curr_img(frame)
+        params = dict(leven_marq=0, max_iters=8)
+        params.update(extra)
+        params["chained_warp"] = chained
+        trk = oracle.Tracker(sm_kind, o_am, o_ssm, **params)
+        trk.initialize(corners); o_am.set_curr_img(frame2); trk.update()
+        return trk.trace()
+
+    a, b, c = run(1e-8, 0), run(2e-8, 0), run(1e-8, 1)
+    return max(max(rel(a[k]["dp"], b[k]["dp"]), rel(a[k]["dp"], c[k]["dp"])) for k in range(2))
 
 
 @pytest.mark.parametrize("grid", ["oracle_grid", "device_grid"])
@@ -255,7 +283,7 @@ def test_fused_iterations_follow_oracle(oracle, gpu_ctx, frame, case, materializ
     _fused_follow(oracle, gpu_ctx, frame, L.AM_SSD, case, materialize, grid)
 
 
-def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=None):
+def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=None, dp_tol=1e-5):
     """Drive the SM loop on the host exactly as the reference does (solve + compositional update on the
     CPU), with the device producing f, g, H per iteration; compare every iteration with the oracle's
     trace of nt::ESM / nt::FCLK / nt::ICLK::update.
@@ -266,7 +294,9 @@ def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=Non
       oracle's by ~1e-13 px).  The reference's grad_eps = 1e-8 finite difference turns that jitter into
       ~5e-6 absolute noise on every image-gradient component (the reference's own noise floor), so H and
       the parameter update are held to the north-star 1e-5, and g to 1e-5 of its Cauchy-Schwarz scale
-      ||J||_F ||r|| (g itself cancels to ~0 at convergence)."""
+      ||J||_F ||r|| (g itself cancels to ~0 at convergence).
+    dp_tol: the relative bound on the parameter update where north_star's 1e-5 holds it (a caller passes a measured noise floor
+      where the reference's own update moves by more; H, g and f keep their bounds)."""
     sm_kind, ssm, res, extra = case
     rng = np.random.default_rng(17)
     centre = (250.0, 262.0)
@@ -333,7 +363,7 @@ def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=Non
                 # ESM + MI chained_warp = 0; now 1.6e-7 / 1.9e-6, profiles/r05_parity_record.jsonl)
                 if am != L.AM_MI:   # (MI's update moves by 1.5e-5 .. 2.8e-5 between the 1e-8 and the 1e-6 oracle: test_mi_update_noise_floor)
                     assert rel(gf[0], r6["g"]) < 2e-5 and rel(dpf, r6["dp"]) < 2e-5, it
-                assert rel(gf[0], rec["g"]) < 1e-5 and rel(dpf, rec["dp"]) < 1e-5, it
+                assert rel(gf[0], rec["g"]) < 1e-5 and rel(dpf, rec["dp"]) < dp_tol, it
             # (ii) against the reference's own arithmetic: one set of bounds for SSD, NCC and MI
             assert rel(ff[0], rec["f"]) < 1e-8, it
             assert rel(Hf[0], rec["H"]) < 2e-6, it
@@ -341,12 +371,12 @@ def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=Non
             cf = b.apply_warp_to_corners(corners[None], dpf[None])[0]
             cr = b.apply_warp_to_corners(corners[None], rec["dp"][None])[0]
             # (later passes: dp itself goes to zero, so either its relative error or what it does to the corners)
-            assert rel(dpf, rec["dp"]) < 1e-5 or np.abs(cf - cr).max() < 1e-6, it
+            assert rel(dpf, rec["dp"]) < dp_tol or np.abs(cf - cr).max() < 1e-6, it
         f, g, H = b.iterate(sm)
         dp = -oracle.colpiv_qr_solve(H[0], g[0])
         if it <= 1 and not tight:    # plain relative errors while g and dp are far from zero (north_star's literal wording)
             assert rel(g[0], rec["g"]) < 1e-5, it
-            assert rel(dp, rec["dp"]) < 1e-5, it
+            assert rel(dp, rec["dp"]) < dp_tol, it
         # scale of g: Cauchy-Schwarz ||J|| ||r|| for SSD; for NCC the gradient vectors have norm <= 2 / b, so ||Jc|| ~ sqrt(|tr H|)
         g_scale = np.sqrt(abs(np.trace(rec["H"]))) * (np.sqrt(abs(2 * rec["f"])) if am == L.AM_SSD else 1.0)
         if tight:
@@ -360,7 +390,7 @@ def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=Non
             assert np.linalg.norm(g[0] - rec["g"]) < 1e-5 * max(np.linalg.norm(rec["g"]), g_scale), it
             c_gpu = b.apply_warp_to_corners(corners[None], dp[None])[0]
             c_ref = b.apply_warp_to_corners(corners[None], rec["dp"][None])[0]
-            assert rel(dp, rec["dp"]) < 1e-5 or np.abs(c_gpu - c_ref).max() < 1e-6, it
+            assert rel(dp, rec["dp"]) < dp_tol or np.abs(c_gpu - c_ref).max() < 1e-6, it
         # follow the oracle's trajectory so that every iteration is compared on identical inputs
         dp = rec["dp"]
         if sm_kind == L.SM_ICLK:

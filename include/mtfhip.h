@@ -43,7 +43,10 @@ typedef enum mtfhip_status {
 	MTFHIP_ERR_NO_DEVICE = -5
 } mtfhip_status;
 
-enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2 };
+/* MTFHIP_AM_SCV: Sum of Conditional Variance (AM/src/SCV.cc), an SSD whose template is re-mapped through the conditional expectation
+ * E[It | I0] before every similarity update; single channel, first-order Hessians, the per-function entry points and the fused
+ * init_template / iterate / track / track_region (mtfhip_batch_set_scv below) */
+enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3 };
 enum { MTFHIP_SSM_HOMOGRAPHY = 0, MTFHIP_SSM_AFFINE = 1 };
 enum { MTFHIP_SM_ESM = 0, MTFHIP_SM_FCLK = 1, MTFHIP_SM_ICLK = 2 };
 /* pixel-Jacobian variants of StateSpaceModel.h:170-181 */
@@ -83,7 +86,7 @@ typedef struct mtfhip_patch_desc {
 	int resx, resy;         /* ImgParams / SSMParams resx, resy */
 	double grad_eps;        /* ImgParams::grad_eps (1e-8, AM/include/mtf/AM/ImageBase.h:7-8) */
 	double likelihood_alpha;/* AMParams::likelihood_alpha */
-	int mi_n_bins;          /* MIParams::n_bins */
+	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV: SCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as SCVParams does */
 	double mi_pre_seed;     /* MIParams::pre_seed */
 	int mi_partition_of_unity;
 	double hess_eps;        /* ImgParams::hess_eps (1, AM/include/mtf/AM/ImageBase.h:9); <= 0 selects that default */
@@ -562,6 +565,15 @@ int mtfhip_batch_inline_warp(const mtfhip_batch *b);
  * not written by the caller since, and the materialising SSD homography launch of a chained FCLK / ESM.  Same results either way; 0 on a
  * bad argument. */
 int mtfhip_batch_grid_regen(mtfhip_batch *b, const mtfhip_sm_desc *sm);
+
+/* ---- SCV (MTFHIP_AM_SCV) ---- */
+enum { MTFHIP_SCV_HIST_DIRAC = 0, MTFHIP_SCV_HIST_BILINEAR = 1, MTFHIP_SCV_HIST_BSPLINE = 2 };   /* SCVParams::hist_type */
+/* SCVParams hist_type, weighted_mapping, mapped_gradient; call before init_template.  Defaults: the shipped modules.cfg values (Dirac,
+ * nearest mapping, no mapped gradient).  BSpline histograms and mapped_gradient = 1 return MTFHIP_ERR_NOT_IMPLEMENTED. */
+int mtfhip_batch_set_scv(mtfhip_batch *b, int hist_type, int weighted_mapping, int mapped_gradient);
+/* SCV::intensity_map of every target after its last similarity update: B x n_bins (all n_bins = the template's bin value before
+ * the first update) */
+int mtfhip_batch_scv_intensity_map(mtfhip_batch *b, double *dst);
 
 #ifdef __cplusplus
 }

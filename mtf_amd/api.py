@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._lib import (AM_MI, AM_NCC, AM_SSD, BUF_CURR_PTS, BUF_D2I0_DP2, BUF_D2I0_DX2, BUF_D2IM_DP2, BUF_D2IT_DP2, BUF_D2IT_DX2,
+from ._lib import (AM_MI, AM_NCC, AM_SCV, AM_SSD, BUF_CURR_PTS, BUF_D2I0_DP2, BUF_D2I0_DX2, BUF_D2IM_DP2, BUF_D2IT_DP2, BUF_D2IT_DX2,
                    BUF_DF_DI0, BUF_DF_DIT, BUF_DI0_DX, BUF_DIT_DX, BUF_HESS_PTS,
                    BUF_GRAD_PTS, BUF_I0, BUF_INIT_PTS, BUF_IT, BUF_J0, BUF_JM, BUF_JT, JAC_APPROX, JAC_INIT,
                    JAC_PIX, JAC_WARPED, SM_ESM, SM_FCLK, SM_ICLK, SSM_AFFINE, SSM_HOMOGRAPHY, PatchDesc, SMDesc)
@@ -484,6 +484,18 @@ class Batch:
     def inline_warp(self):
         """True when single-target launches carry the warp in the kernel arguments (mtfhip_batch_inline_warp)"""
         return bool(L.lib().mtfhip_batch_inline_warp(self._h))
+
+    def set_scv(self, hist_type=0, weighted_mapping=0, mapped_gradient=0):
+        """SCVParams hist_type (SCV_HIST_DIRAC / SCV_HIST_BILINEAR), weighted_mapping, mapped_gradient of an AM_SCV batch, before
+        init_template; the defaults are the shipped modules.cfg values (mtfhip_batch_set_scv)"""
+        L.check(L.lib().mtfhip_batch_set_scv(self._h, int(hist_type), int(weighted_mapping), int(mapped_gradient)))
+
+    def scv_intensity_map(self):
+        """B x n_bins: each target's SCV intensity map after its last similarity update (mtfhip_batch_scv_intensity_map)"""
+        nb = self.desc.mi_n_bins if self.desc.mi_n_bins > 0 else 256
+        out = np.empty((self.B, nb))
+        L.check(L.lib().mtfhip_batch_scv_intensity_map(self._h, _p(out)))
+        return out
 
     def grid_regen(self, sm):
         """True when the next per-iteration fused launch of `sm` rebuilds the template grid instead of reading INIT_PTS (mtfhip_batch_grid_regen)"""

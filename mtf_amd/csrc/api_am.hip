@@ -25,6 +25,7 @@ int mtfhip_am_initialize_pix_vals(mtfhip_batch *b, const double *pts) {
 		b->init_pix_vals = true;
 		b->it_valid = true;
 	}
+	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_capture(b));   /* SCV::initializePixVals: I0_orig = I0 (SCV.cc:166) */
 	return MTFHIP_OK;
 }
 /* SSD::updateModel AM/src/SSD.cc:49-75, NCC::updateModel AM/src/NCC.cc:539-566 (the search methods call it at the end of update()
@@ -34,6 +35,7 @@ int mtfhip_am_update_model(mtfhip_batch *b, const double *pts, double learning_r
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "update_model: NULL batch");
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: MI has no online template update in the reference either");
+	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: SCV is not available on this entry point (the template update would have to refresh I0_orig)");
 	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: appearance model %d", b->desc.am);
 	TRY(single_channel(b, "update_model"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "update_model before initializePixVals");
@@ -325,7 +327,7 @@ static int mi_grad(mtfhip_batch *b, int curr) {
 
 /* ------------------------------------------------------------------ AppearanceModel */
 static int am_supported(mtfhip_batch *b, const char *fn) {
-	if (b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_NCC || b->desc.am == MTFHIP_AM_MI) return MTFHIP_OK;
+	if (ssd_like(b) || b->desc.am == MTFHIP_AM_NCC || b->desc.am == MTFHIP_AM_MI) return MTFHIP_OK;
 	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s :: appearance model %d is not available on the device path yet", fn, b->desc.am);
 }
 
@@ -407,6 +409,8 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 		if (!prereq_only) TRY(mi_read_f(b));
 		return MTFHIP_OK;
 	}
+	/* SCV::updateSimilarity (SCV.cc:194-230): the intensity map from It and I0_orig, I0 re-mapped, then SSDBase::updateSimilarity */
+	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 1, b->ctx->stream));
 	int nblk = simple_blocks_per_target(b->N);
 	{
 		TimedScope ts(b->ctx, "ssd_residual");
@@ -442,7 +446,7 @@ int mtfhip_am_update_curr_grad(mtfhip_batch *b) {
 int mtfhip_am_update_init_grad(mtfhip_batch *b) {
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "update_init_grad: NULL batch");
 	TRY(am_supported(b, "updateInitGrad"));
-	if (b->desc.am == MTFHIP_AM_SSD) return MTFHIP_OK;   /* SSD::updateInitGrad is empty: df_dI0 is updateSimilarity's residual */
+	if (ssd_like(b)) return MTFHIP_OK;   /* SSD::updateInitGrad is empty: df_dI0 is updateSimilarity's residual */
 	if (b->lz.enabled) {   /* NCC */
 		if (b->lz.ig) FLUSH(b);
 		b->lz.ig = ++b->lz.seq;
@@ -466,7 +470,7 @@ int mtfhip_am_get_likelihood(mtfhip_batch *b, double *l) {
 	FLUSH_AM(b);
 	for (int t = 0; t < b->B; ++t) {
 		double f = b->th[t].f;
-		if (b->desc.am == MTFHIP_AM_SSD) l[t] = std::exp(-b->desc.likelihood_alpha * std::sqrt(-f / (double)b->N));
+		if (ssd_like(b)) l[t] = std::exp(-b->desc.likelihood_alpha * std::sqrt(-f / (double)b->N));
 		else { double d = (1.0 / f) - 1; l[t] = std::exp(-b->desc.likelihood_alpha * d * d); }
 	}
 	return MTFHIP_OK;
@@ -807,7 +811,7 @@ int mtfhip_am_cmpt_difference_of_jacobians(mtfhip_batch *b, int j0_buf, int jt_b
 	{ int done; TRY(lazy_try_fused(b, LAZY_DIFF_JAC, j0_buf, jt_buf, g, &done)); if (done) return MTFHIP_OK; }
 	FLUSH_AM(b);
 	TRY(ensure_df(b));
-	if (b->desc.am != MTFHIP_AM_SSD) /* (df_dIt * dIt_dp) - (df_dI0 * dI0_dp), NCC.cc:268-280, AppearanceModel.h:161-164 */
+	if (!ssd_like(b)) /* (df_dIt * dIt_dp) - (df_dI0 * dI0_dp), NCC.cc:268-280, AppearanceModel.h:161-164 */
 		return gemv_to_host(b, b->buf[MTFHIP_BUF_DF_DIT], jt_buf, b->buf[MTFHIP_BUF_DF_DI0], j0_buf, 0, g, 1);
 	/* SSD: df_dIt * (dI0_dpssm + dIt_dpssm), SSDBase.cc:186 */
 	return gemv_to_host(b, b->buf[MTFHIP_BUF_DF_DIT], jt_buf, nullptr, j0_buf, 1, g, 0);
@@ -884,7 +888,7 @@ int mtfhip_am_cmpt_sum_of_hessians(mtfhip_batch *b, int j0_buf, int jt_buf, doub
 	TRY(am_supported(b, "cmptSumOfHessians"));
 	TRY(j_ready(b, j0_buf, "cmptSumOfHessians"));
 	TRY(j_ready(b, jt_buf, "cmptSumOfHessians"));
-	if (b->desc.am != MTFHIP_AM_SSD) {
+	if (!ssd_like(b)) {
 		/* generic AppearanceModel::cmptSumOfHessians AppearanceModel.h:196-208 */
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
 		if (b->desc.am == MTFHIP_AM_NCC) { TRY(ncc_hessian(b, j0_buf, 0, H0.data())); TRY(ncc_hessian(b, jt_buf, 1, H)); }
@@ -1031,6 +1035,7 @@ static int add_second_order(mtfhip_batch *b, int d2a, int d2b, const double *dev
 /* SSDBase.cc:313-343 ; NCC.cc:391-400 ; MI.cc:659-673 */
 int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
+	TRY(scv_refuse(b, "cmpt_init_hessian (second order)", 1));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_init_hessian(b, j0_buf, H));
 	return add_second_order(b, d2_buf, -1, b->buf[MTFHIP_BUF_DF_DI0], H);
@@ -1038,6 +1043,7 @@ int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double
 /* SSDBase.cc:345-375 ; NCC.cc:401-410 ; MI.cc:680-694 */
 int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
+	TRY(scv_refuse(b, "cmpt_curr_hessian (second order)", 1));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_curr_hessian(b, jt_buf, H));
 	return add_second_order(b, d2_buf, -1, b->buf[MTFHIP_BUF_DF_DIT], H);
@@ -1045,6 +1051,7 @@ int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 /* SSD: first order only (SSDBase.h:95-98) ; NCC: am_func_not_implemeted (AppearanceModel.h:188-191) ; MI.cc:696-733 */
 int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
+	TRY(scv_refuse(b, "cmpt_self_hessian (second order)", 1));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_self_hessian (second order): NULL argument");
 	if (b->desc.am == MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "ncc :: cmptSelfHessian(second order) :: function not implemented yet");
@@ -1060,6 +1067,7 @@ int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 /* SSDBase.cc:377-415 (both pixel Hessians weighted by df_dI0) ; NCC / MI: generic AppearanceModel.h:209-219 */
 int mtfhip_am_cmpt_sum_of_hessians2(mtfhip_batch *b, int j0_buf, int jt_buf, int d20_buf, int d2t_buf, double *H) {
 	FLUSH_AM(b);
+	TRY(scv_refuse(b, "cmpt_sum_of_hessians (second order)", 1));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_sum_of_hessians (second order): NULL argument");
 	if (b->desc.am == MTFHIP_AM_SSD) {

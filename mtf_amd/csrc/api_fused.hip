@@ -29,7 +29,8 @@ static int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char 
 		 * initialize / setRegion).  Eight bins (the weights are read from the 8-bin gradient-factor tables). */
 		return MTFHIP_OK;
 	}
-	if (b->desc.am != MTFHIP_AM_SSD) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: unknown appearance model", fn);
+	TRY(scv_refuse(b, fn, sm->sec_ord_hess));   /* (SCV: SSD on the re-mapped template, first order) */
+	if (!ssd_like(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: unknown appearance model", fn);
 	return MTFHIP_OK;
 }
 
@@ -510,7 +511,8 @@ static int iclk_one_launch_max_pix() {
 	return v < kIclkTrackMaxPix ? v : kIclkTrackMaxPix;
 }
 static bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
-	return b->C == 1 && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
+	/* (SCV re-maps its template between the passes: it takes the fused launch + finish per pass) */
+	return b->C == 1 && b->desc.am != MTFHIP_AM_SCV && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
 		b->N <= iclk_one_launch_max_pix();
 }
 static bool region_refreshes(const mtfhip_sm_desc *sm) { return sm->sm == MTFHIP_SM_ESM || (sm->sm == MTFHIP_SM_FCLK && sm->hess_type == 0); }
@@ -593,7 +595,7 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 		if (sm->hess_type == 1) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "fused ICLK with hess_type CurrentSelf: use the un-fused entry points");
 		fa.mode = 2;
 	}
-	if (!grid_regen_kernel(b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
+	if (!grid_regen_kernel(ssd_like(b) ? MTFHIP_AM_SSD : b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
 		fa.grid_regen = 0;
 	return MTFHIP_OK;
 }
@@ -882,6 +884,8 @@ int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, d
 	TRY(need_image(b));
 	if (b->desc.am == MTFHIP_AM_MI) return mi_iterate(b, sm, f, g, H);
 	if (second_order_term(sm) >= 0) TRY(ensure_pts(b));   /* k_second_order_ssd reads the current points */
+	/* SCV::updateSimilarity: the intensity map at the current warp and the re-mapped template, then the SSD iteration on it */
+	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 0, b->ctx->stream));
 	FusedArgs fa;
 	TRY(fused_args(b, sm, fa));
 	int nblk = fused_blocks_per_target(b->N, b->B);
@@ -1031,6 +1035,7 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 	const char *e = std::getenv("MTFHIP_PERSIST");
 	if (!(e && e[0] == '1') || !b->persist_ok || fa.materialize || b->ctx->n_cus <= 0 || b->B > b->ctx->n_cus || !b->h_pub_dev) return false;
 	if (b->C != 1) return false;   /* (no multi-channel instantiation of the persistent kernel) */
+	if (b->desc.am == MTFHIP_AM_SCV) return false;   /* (the template re-map runs between the passes) */
 	if (b->B > 8) return false;   /* a batch is better served by its own decomposition (eight workgroups per target) */
 	if (sm->max_iters < 2) return false;
 	int nblk, rows;
@@ -1113,6 +1118,7 @@ int mtfhip_batch_track_region(mtfhip_batch *b, const mtfhip_sm_desc *sm, const d
  * robust estimator.  (The layout conversion and the centroids were ~9 of the ~14 us a frame spent in the Python layer.) */
 int mtfhip_grid_update(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *regions_2x4, int *n_iters, double *corners_2x4, double *centroids) {
 	if (!b || !sm || !regions_2x4) return fail(MTFHIP_ERR_INVALID_ARG, "grid_update: NULL argument");
+	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "grid_update: SCV is not available on the grid tracker");
 	const size_t B = (size_t)b->B;
 	static thread_local std::vector<double> in, out;
 	in.resize(8 * B); out.resize(8 * B);
@@ -1135,6 +1141,7 @@ static inline void centroid_f(float *dst, const double *c) {
 }
 static int grid_batch_ok(const mtfhip_batch *b, const mtfhip_grid_desc *g, const char *fn) {
 	if (!b || !g) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
+	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SCV is not available on the grid tracker", fn);
 	if (g->grid_size_x <= 0 || g->grid_size_y <= 0 || g->grid_size_x * g->grid_size_y != b->B)   /* GridTracker.cc:124-129 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "%s: mismatch between the grid dimensions (%d x %d) and the batch's %d patch trackers", fn, g->grid_size_x, g->grid_size_y, b->B);
 	return MTFHIP_OK;
@@ -1566,7 +1573,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 			const char *e_st = std::getenv("MTFHIP_STEP");   /* (read per call: the tests flip it) */
 			const char *e_mx = std::getenv("MTFHIP_STEP_MAX_TARGETS");
 			const int max_t = e_mx ? std::atoi(e_mx) : 8;
-			use_step = (e_st && e_st[0] == '1') && so_term < 0 && n_streams == 1 && b->B <= max_t && track_step_available(bv, fa);
+			use_step = (e_st && e_st[0] == '1') && so_term < 0 && b->desc.am != MTFHIP_AM_SCV && n_streams == 1 && b->B <= max_t && track_step_available(bv, fa);
 			if (use_step && !b->d_persist) {
 				HIP_TRY(hipMalloc(&b->d_persist, 2 * sizeof(int) * (size_t)b->B));
 				HIP_TRY(hipMemsetAsync(b->d_persist, 0, 2 * sizeof(int) * (size_t)b->B, st));
@@ -1624,6 +1631,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 						all_done = all_done && r.done;
 						continue;
 					}
+					if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, r.bc, r.t0, r.fc.active, 0, r.s));   /* (the chunk's template re-map) */
 					{
 						TimedScope tsc(b->ctx, "fused_lk", r.s);
 						launch_fused_ssd(r.bc, b->ctx->img, r.fc, r.part, r.nblk_c, r.s);
@@ -1789,6 +1797,7 @@ int mtfhip_score_candidates_dev(mtfhip_batch *b, const double *dev_states, int C
 	FLUSH_AM(b);   /* (every candidate warps the template grid itself: CURR_PTS are not read) */
 	if (!b || !dev_states) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: NULL argument");
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
+	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: SCV candidates are not available (SCVDist is a per-candidate intensity map)");
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "score_candidates before the template was initialised");
 	TRY(need_image(b));
 	TimedScope ts(b->ctx, "score_candidates");
@@ -1821,6 +1830,7 @@ int mtfhip_sample_candidates_dev(mtfhip_batch *b, const double *dev_states, int 
 	if (!b || !dev_states || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: NULL argument");
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: MI distance features (5 x N B-spline rows) are not available");
+	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: SCV distance features are not available (SCVDist is a per-candidate intensity map)");
 	TRY(single_channel(b, "sample_candidates"));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "sample_candidates before set_corners");
 	TRY(need_image(b));
@@ -1854,6 +1864,7 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 	int row_lo, int row_count) {
 	FLUSH(b);
 	if (!b || !d || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
+	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: SCV is not available on the NN dataset (SCVDist is a per-candidate intensity map)");
 	if (d->n_samples <= 0 || row_lo < 0 || row_count < 0 || row_lo + row_count > d->n_samples)
 		return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: rows [%d, %d) of %d samples", row_lo, row_lo + row_count, d->n_samples);
 	if (d->additive_update) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: additive_update (NNParams, NT/NN.cc:150-152): the compositional form only");

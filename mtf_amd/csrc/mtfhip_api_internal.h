@@ -240,6 +240,11 @@ struct mtfhip_batch {
 	int d0_variant = MTFHIP_JAC_WARPED; /* how the template's pixel Hessian was formed (fused second-order path) */
 	int mi_row_len = 0;
 	double mi_hist_norm = 0;
+	/* SCV (am = MTFHIP_AM_SCV): SCVParams hist_type / weighted_mapping / mapped_gradient, n_bins; the original template (I0_orig, the
+	 * normalised samples of initializePixVals) and its code plane, pass-1 rows and the intensity maps (kernels_scv.hip) */
+	int scv_hist = 0, scv_linear = 0, scv_mapped_grad = 0, scv_nb = 0;
+	double *d_scv_i0 = nullptr, *d_scv_part = nullptr, *d_scv_map = nullptr;
+	unsigned short *d_scv_code = nullptr;
 	size_t cand_capacity = 0;
 	double *d_cand_mi = nullptr; size_t cand_mi_capacity = 0;   /* MI candidate scoring: histogram rows per candidate */
 	int *d_active = nullptr, *d_iters = nullptr;
@@ -412,6 +417,13 @@ static int push_warps(mtfhip_batch *b) {
 }
 
 /* the BatchView of a fused launch: a stale single-target warp goes into the kernel arguments instead of being uploaded */
+/* SCV is SSD on its re-mapped template: every SSD branch of the entry points serves it */
+static inline bool ssd_like(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV; }
+/* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
+int scv_capture(mtfhip_batch *b);
+int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
+/* the configurations SCV refuses on the device path, for the entry point fn */
+int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess);
 static inline BatchView fused_view(mtfhip_batch *b, FusedArgs &fa) {
 	fa.inline_warp = 0;
 	if (b->warps_dirty && b->B == 1) {

@@ -550,5 +550,20 @@ struct PhaseCtl { unsigned long long *mine; const unsigned long long *other; dou
 void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials,
 	int nblk, hipStream_t st, PhaseCtl pc = PhaseCtl{nullptr, nullptr, 0.0});
 
+/* ---- SCV: the template re-map of SCV::updateSimilarity (kernels_scv.hip) ---- */
+constexpr int kScvMaxBins = 256;
+struct ScvArgs {
+	int nb, hist, linear;        /* n_bins, hist_type (0 Dirac, 1 Bilinear), weighted_mapping */
+	int from_it;                 /* 1: It from MTFHIP_BUF_IT (per-function path); 0: sampled at the current warp */
+	double norm_mult, norm_add;
+	const unsigned short *code;  /* [B][N] (int)I0_orig | (int)rint(I0_orig) << 8 */
+	const double *i0o;           /* [B][N] I0_orig */
+	const int *active;           /* optional [B] mask (device-side loop) */
+};
+int scv_hist_blocks(int N);
+void launch_scv_codes(int N, int B, int nb, const double *i0o, unsigned short *code, hipStream_t st);
+/* pass 1 + map + re-map; part: [B][scv_hist_blocks(N)][2 nb], map: [B][nb], I0: MTFHIP_BUF_I0 (all offset to bv's first target) */
+void launch_scv_update(const BatchView &bv, const ImgView &im, const ScvArgs &a, double *part, double *map, double *I0, hipStream_t st);
+
 } // namespace mtfhip
 #endif

@@ -45,6 +45,7 @@ struct HipPair {
 	~HipPair();
 	static void check(int rc);               /* rethrows C-ABI failures as mtf::utils::Exception */
 	int jacobianBuffer(const MatrixXd &J, bool may_register, int preferred = -1);
+	void setSCV(int hist_type, bool weighted_mapping, bool mapped_gradient);   /* mtfhip_batch_set_scv (am = MTFHIP_AM_SCV) */
 	int hessianBuffer(const MatrixXd &D, bool may_register);
 };
 
@@ -54,12 +55,25 @@ struct HipPair {
  * `SSD(const ParamType *ssd_params = nullptr, const int _n_channels = 1)`, SSM/include/mtf/SSM/Homography.h
  * `Homography(const ParamType *params_in = nullptr)`), so the two adapter objects cannot be handed a shared pair by the caller: both
  * parameter blocks point at one HipLink, and whichever model is constructed first creates the pair (context + one-target batch). */
+/* SCVParams (AM/include/mtf/AM/SCV.h), the reference's field names and class defaults (SCV.cc:5-13).  n_bins <= 0 selects 256.
+ * The device path serves hist_type Dirac (0) and Bilinear (1) with mapped_gradient off; pre_seed and partition_of_unity only act on the
+ * BSpline histograms it refuses. */
+struct HipSCVParams {
+	int hist_type = 0; int n_bins = 256; double pre_seed = 0; bool partition_of_unity = false;
+	bool weighted_mapping = false; bool mapped_gradient = false;
+};
 struct HipLink {
 	int am = MTFHIP_AM_SSD, ssm = MTFHIP_SSM_HOMOGRAPHY, resx = 50, resy = 50;   /* AMParams / SSMParams: resx, resy */
 	double grad_eps = 1e-8, likelihood_alpha = 1.0;                           /* AMParams::grad_eps; SSDParams / NCCParams / MIParams::likelihood_alpha */
 	int mi_n_bins = 8; double mi_pre_seed = 10; int mi_pou = 0;                /* MIParams */
+	HipSCVParams scv;                                                          /* am = MTFHIP_AM_SCV ("scv") */
 	int device = 0; void *stream = nullptr;
 	std::shared_ptr<HipPair> pair(int n_channels = 1) {
+		if (!p && am == MTFHIP_AM_SCV) {
+			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, scv.n_bins, scv.pre_seed, scv.partition_of_unity ? 1 : 0,
+				device, stream, n_channels);
+			p->setSCV(scv.hist_type, scv.weighted_mapping, scv.mapped_gradient);
+		}
 		if (!p) p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, device, stream, n_channels);
 		else if (n_channels > 1 && n_channels != p->n_channels)   /* (SearchMethod<AM, SSM> constructs the AM first: it fixes the channel count) */
 			throw utils::InvalidArgument("HipLink :: the pair exists with another channel count");

@@ -32,12 +32,11 @@ extern "C" {
 
 const char *mtfhost_last_error(void) { return g_err.c_str(); }
 
-mtfhost_tracker *mtfhost_create(int sm, int am, int ssm, int resx, int resy, int max_iters, double epsilon,
-	int jac_type, int hess_type, int chained_warp, int leven_marq, double lm_delta_init, double lm_delta_update,
-	int device, int sec_ord_hess, int n_channels) {
-	try {
+static mtfhost_tracker *create_on(std::shared_ptr<hip::HipPair> pair, int sm, int max_iters, double epsilon,
+	int jac_type, int hess_type, int chained_warp, int leven_marq, double lm_delta_init, double lm_delta_update, int sec_ord_hess) {
+	{
 		std::unique_ptr<mtfhost_tracker> t(new mtfhost_tracker());   /* (a constructor below may throw: nothing leaks) */
-		t->pair = std::make_shared<hip::HipPair>(am, ssm, resx, resy, 1e-8, 1.0, 8, 10.0, 0, device, nullptr, n_channels);
+		t->pair = pair;
 		t->am = std::make_shared<hip::HipAM>(t->pair);
 		t->ssm = std::make_shared<hip::HipSSM>(t->pair);
 		nt::SMParams p;
@@ -52,6 +51,25 @@ mtfhost_tracker *mtfhost_create(int sm, int am, int ssm, int resx, int resy, int
 		else if (sm == MTFHIP_SM_ICLK) t->sm.reset(new nt::ICLK(t->am, t->ssm, p));
 		else { g_err = "unknown search method"; return nullptr; }
 		return t.release();
+	}
+}
+mtfhost_tracker *mtfhost_create(int sm, int am, int ssm, int resx, int resy, int max_iters, double epsilon,
+	int jac_type, int hess_type, int chained_warp, int leven_marq, double lm_delta_init, double lm_delta_update,
+	int device, int sec_ord_hess, int n_channels) {
+	try {
+		return create_on(std::make_shared<hip::HipPair>(am, ssm, resx, resy, 1e-8, 1.0, 8, 10.0, 0, device, nullptr, n_channels), sm, max_iters,
+			epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, sec_ord_hess);
+	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+/* the same tracker with HipAM("scv"): its SCVParams through the HipLink the reference's model constructors take */
+mtfhost_tracker *mtfhost_create_scv(int sm, int ssm, int resx, int resy, int max_iters, double epsilon, int jac_type, int hess_type, int chained_warp,
+	int leven_marq, double lm_delta_init, double lm_delta_update, int device, int hist_type, int n_bins, int weighted_mapping, int mapped_gradient) {
+	try {
+		auto link = std::make_shared<hip::HipLink>();
+		link->am = MTFHIP_AM_SCV; link->ssm = ssm; link->resx = resx; link->resy = resy; link->device = device;
+		link->scv.hist_type = hist_type; link->scv.n_bins = n_bins; link->scv.weighted_mapping = weighted_mapping != 0;
+		link->scv.mapped_gradient = mapped_gradient != 0;
+		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
 	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
 void mtfhost_destroy(mtfhost_tracker *t) { delete t; }

@@ -46,7 +46,10 @@ typedef enum mtfhip_status {
 /* MTFHIP_AM_SCV: Sum of Conditional Variance (AM/src/SCV.cc), an SSD whose template is re-mapped through the conditional expectation
  * E[It | I0] before every similarity update; single channel, first-order Hessians, the per-function entry points and the fused
  * init_template / iterate / track / track_region (mtfhip_batch_set_scv below) */
-enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3 };
+/* MTFHIP_AM_RSCV: Reversed SCV (AM/src/RSCV.cc), an SSD whose current patch is re-mapped through E[I0 | It] after every sampling
+ * (RSCV::updatePixVals, RSCV.cc:170-238); single channel, Dirac histograms, first-order Hessians, the per-function entry points and
+ * the fused init_template / iterate / track / track_region (mtfhip_batch_set_rscv below) */
+enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4 };
 enum { MTFHIP_SSM_HOMOGRAPHY = 0, MTFHIP_SSM_AFFINE = 1 };
 enum { MTFHIP_SM_ESM = 0, MTFHIP_SM_FCLK = 1, MTFHIP_SM_ICLK = 2 };
 /* pixel-Jacobian variants of StateSpaceModel.h:170-181 */
@@ -86,7 +89,7 @@ typedef struct mtfhip_patch_desc {
 	int resx, resy;         /* ImgParams / SSMParams resx, resy */
 	double grad_eps;        /* ImgParams::grad_eps (1e-8, AM/include/mtf/AM/ImageBase.h:7-8) */
 	double likelihood_alpha;/* AMParams::likelihood_alpha */
-	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV: SCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as SCVParams does */
+	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV / MTFHIP_AM_RSCV: SCVParams / RSCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as they do */
 	double mi_pre_seed;     /* MIParams::pre_seed */
 	int mi_partition_of_unity;
 	double hess_eps;        /* ImgParams::hess_eps (1, AM/include/mtf/AM/ImageBase.h:9); <= 0 selects that default */
@@ -574,6 +577,13 @@ int mtfhip_batch_set_scv(mtfhip_batch *b, int hist_type, int weighted_mapping, i
 /* SCV::intensity_map of every target after its last similarity update: B x n_bins (all n_bins = the template's bin value before
  * the first update) */
 int mtfhip_batch_scv_intensity_map(mtfhip_batch *b, double *dst);
+
+/* ---- RSCV (MTFHIP_AM_RSCV) ---- */
+/* RSCVParams use_bspl, weighted_mapping, mapped_gradient (RSCV.cc:6-12); call before init_template.  Defaults: Dirac histograms,
+ * nearest mapping, no mapped gradient.  use_bspl = 1 (BSpline histograms) and mapped_gradient = 1 return MTFHIP_ERR_NOT_IMPLEMENTED. */
+int mtfhip_batch_set_rscv(mtfhip_batch *b, int use_bspl, int weighted_mapping, int mapped_gradient);
+/* RSCV::intensity_map of every target after its last updatePixVals (RSCV.cc:211-229): B x n_bins (map[b] = b before the first one) */
+int mtfhip_batch_rscv_intensity_map(mtfhip_batch *b, double *dst);
 
 #ifdef __cplusplus
 }

@@ -497,6 +497,18 @@ class Batch:
         L.check(L.lib().mtfhip_batch_scv_intensity_map(self._h, _p(out)))
         return out
 
+    def set_rscv(self, use_bspl=0, weighted_mapping=0, mapped_gradient=0):
+        """RSCVParams use_bspl, weighted_mapping, mapped_gradient of an AM_RSCV batch, before init_template; the defaults are the
+        reference's (Dirac histograms, nearest mapping) (mtfhip_batch_set_rscv)"""
+        L.check(L.lib().mtfhip_batch_set_rscv(self._h, int(use_bspl), int(weighted_mapping), int(mapped_gradient)))
+
+    def rscv_intensity_map(self):
+        """B x n_bins: each target's RSCV intensity map after its last updatePixVals (mtfhip_batch_rscv_intensity_map)"""
+        nb = self.desc.mi_n_bins if self.desc.mi_n_bins > 0 else 256
+        out = np.empty((self.B, nb))
+        L.check(L.lib().mtfhip_batch_rscv_intensity_map(self._h, _p(out)))
+        return out
+
     def grid_regen(self, sm):
         """True when the next per-iteration fused launch of `sm` rebuilds the template grid instead of reading INIT_PTS (mtfhip_batch_grid_regen)"""
         return bool(L.lib().mtfhip_batch_grid_regen(self._h, C.byref(sm)))

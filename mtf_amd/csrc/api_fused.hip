@@ -511,8 +511,8 @@ static int iclk_one_launch_max_pix() {
 	return v < kIclkTrackMaxPix ? v : kIclkTrackMaxPix;
 }
 static bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
-	/* (SCV re-maps its template between the passes: it takes the fused launch + finish per pass) */
-	return b->C == 1 && b->desc.am != MTFHIP_AM_SCV && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
+	/* (SCV re-maps its template, RSCV rebuilds its map between the passes: they take the fused launch + finish per pass) */
+	return b->C == 1 && !intensity_mapped(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
 		b->N <= iclk_one_launch_max_pix();
 }
 static bool region_refreshes(const mtfhip_sm_desc *sm) { return sm->sm == MTFHIP_SM_ESM || (sm->sm == MTFHIP_SM_FCLK && sm->hess_type == 0); }
@@ -595,7 +595,7 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 		if (sm->hess_type == 1) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "fused ICLK with hess_type CurrentSelf: use the un-fused entry points");
 		fa.mode = 2;
 	}
-	if (!grid_regen_kernel(ssd_like(b) ? MTFHIP_AM_SSD : b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
+	if (!grid_regen_kernel(b->desc.am == MTFHIP_AM_SCV ? MTFHIP_AM_SSD : b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
 		fa.grid_regen = 0;
 	return MTFHIP_OK;
 }
@@ -888,10 +888,13 @@ int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, d
 	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 0, b->ctx->stream));
 	FusedArgs fa;
 	TRY(fused_args(b, sm, fa));
+	/* RSCV::updatePixVals: the intensity map of the current patch at the current warp, applied by the fused pass to every sample */
+	RscvMap rm;
+	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_enqueue(b, b->view(), 0, nullptr, fa, b->ctx->stream, &rm));
 	int nblk = fused_blocks_per_target(b->N, b->B);
 	{
 		TimedScope ts(b->ctx, "fused_lk");
-		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream);
+		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream, &rm);
 	}
 	b->it_valid = fa.materialize;
 	b->dit_valid = fa.materialize && fa.mode != 2;
@@ -1035,7 +1038,7 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 	const char *e = std::getenv("MTFHIP_PERSIST");
 	if (!(e && e[0] == '1') || !b->persist_ok || fa.materialize || b->ctx->n_cus <= 0 || b->B > b->ctx->n_cus || !b->h_pub_dev) return false;
 	if (b->C != 1) return false;   /* (no multi-channel instantiation of the persistent kernel) */
-	if (b->desc.am == MTFHIP_AM_SCV) return false;   /* (the template re-map runs between the passes) */
+	if (intensity_mapped(b)) return false;   /* (the template re-map / the current map runs between the passes) */
 	if (b->B > 8) return false;   /* a batch is better served by its own decomposition (eight workgroups per target) */
 	if (sm->max_iters < 2) return false;
 	int nblk, rows;
@@ -1118,7 +1121,7 @@ int mtfhip_batch_track_region(mtfhip_batch *b, const mtfhip_sm_desc *sm, const d
  * robust estimator.  (The layout conversion and the centroids were ~9 of the ~14 us a frame spent in the Python layer.) */
 int mtfhip_grid_update(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *regions_2x4, int *n_iters, double *corners_2x4, double *centroids) {
 	if (!b || !sm || !regions_2x4) return fail(MTFHIP_ERR_INVALID_ARG, "grid_update: NULL argument");
-	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "grid_update: SCV is not available on the grid tracker");
+	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "grid_update: %s is not available on the grid tracker", b->desc.am == MTFHIP_AM_SCV ? "SCV" : "RSCV");
 	const size_t B = (size_t)b->B;
 	static thread_local std::vector<double> in, out;
 	in.resize(8 * B); out.resize(8 * B);
@@ -1141,7 +1144,7 @@ static inline void centroid_f(float *dst, const double *c) {
 }
 static int grid_batch_ok(const mtfhip_batch *b, const mtfhip_grid_desc *g, const char *fn) {
 	if (!b || !g) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
-	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SCV is not available on the grid tracker", fn);
+	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s is not available on the grid tracker", fn, b->desc.am == MTFHIP_AM_SCV ? "SCV" : "RSCV");
 	if (g->grid_size_x <= 0 || g->grid_size_y <= 0 || g->grid_size_x * g->grid_size_y != b->B)   /* GridTracker.cc:124-129 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "%s: mismatch between the grid dimensions (%d x %d) and the batch's %d patch trackers", fn, g->grid_size_x, g->grid_size_y, b->B);
 	return MTFHIP_OK;
@@ -1573,7 +1576,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 			const char *e_st = std::getenv("MTFHIP_STEP");   /* (read per call: the tests flip it) */
 			const char *e_mx = std::getenv("MTFHIP_STEP_MAX_TARGETS");
 			const int max_t = e_mx ? std::atoi(e_mx) : 8;
-			use_step = (e_st && e_st[0] == '1') && so_term < 0 && b->desc.am != MTFHIP_AM_SCV && n_streams == 1 && b->B <= max_t && track_step_available(bv, fa);
+			use_step = (e_st && e_st[0] == '1') && so_term < 0 && !intensity_mapped(b) && n_streams == 1 && b->B <= max_t && track_step_available(bv, fa);
 			if (use_step && !b->d_persist) {
 				HIP_TRY(hipMalloc(&b->d_persist, 2 * sizeof(int) * (size_t)b->B));
 				HIP_TRY(hipMemsetAsync(b->d_persist, 0, 2 * sizeof(int) * (size_t)b->B, st));
@@ -1632,9 +1635,11 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 						continue;
 					}
 					if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, r.bc, r.t0, r.fc.active, 0, r.s));   /* (the chunk's template re-map) */
+					RscvMap rm;
+					if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &rm));   /* (the chunk's current maps) */
 					{
 						TimedScope tsc(b->ctx, "fused_lk", r.s);
-						launch_fused_ssd(r.bc, b->ctx->img, r.fc, r.part, r.nblk_c, r.s);
+						launch_fused_ssd(r.bc, b->ctx->img, r.fc, r.part, r.nblk_c, r.s, &rm);
 					}
 					if (so_term >= 0) {
 						TimedScope tsc(b->ctx, "second_order", r.s);
@@ -1798,6 +1803,7 @@ int mtfhip_score_candidates_dev(mtfhip_batch *b, const double *dev_states, int C
 	if (!b || !dev_states) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: NULL argument");
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: SCV candidates are not available (SCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: RSCV candidates are not available (RSCVDist is a per-candidate intensity map)");
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "score_candidates before the template was initialised");
 	TRY(need_image(b));
 	TimedScope ts(b->ctx, "score_candidates");
@@ -1831,6 +1837,7 @@ int mtfhip_sample_candidates_dev(mtfhip_batch *b, const double *dev_states, int 
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: MI distance features (5 x N B-spline rows) are not available");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: SCV distance features are not available (SCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: RSCV distance features are not available (RSCVDist is a per-candidate intensity map)");
 	TRY(single_channel(b, "sample_candidates"));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "sample_candidates before set_corners");
 	TRY(need_image(b));
@@ -1865,6 +1872,7 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 	FLUSH(b);
 	if (!b || !d || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: SCV is not available on the NN dataset (SCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: RSCV is not available on the NN dataset (RSCVDist is a per-candidate intensity map)");
 	if (d->n_samples <= 0 || row_lo < 0 || row_count < 0 || row_lo + row_count > d->n_samples)
 		return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: rows [%d, %d) of %d samples", row_lo, row_lo + row_count, d->n_samples);
 	if (d->additive_update) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: additive_update (NNParams, NT/NN.cc:150-152): the compositional form only");

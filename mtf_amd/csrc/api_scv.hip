@@ -48,9 +48,10 @@ int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active,
 }
 
 int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess) {
-	if (!b || b->desc.am != MTFHIP_AM_SCV) return MTFHIP_OK;
+	if (!b || !intensity_mapped(b)) return MTFHIP_OK;
 	if (sec_ord_hess)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SCV with second-order Hessians is not available on the device path (first-order only)", fn);
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with second-order Hessians is not available on the device path (first-order only)", fn,
+			b->desc.am == MTFHIP_AM_SCV ? "SCV" : "RSCV");
 	return MTFHIP_OK;
 }
 

@@ -110,7 +110,11 @@ static void launch_fused_fast(const BatchView &bv, const ImgView &im, const Fuse
 	else MTFHIP_LAUNCH((k_fused_fast<AM, SSM, 1, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
 }
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	hipStream_t st) {
+	hipStream_t st, const RscvMap *rm) {
+	if (bv.am == MTFHIP_AM_RSCV) {   /* (the API enqueues RSCV's pass 1 in front and hands its maps over: no map, no launch) */
+		if (rm && rm->map) launch_fused_rscv(bv, im, fa, partials, nblk, *rm, st);
+		return;
+	}
 	const bool hom = bv.ssm == MTFHIP_SSM_HOMOGRAPHY;
 	if (bv.C > 1) { launch_fused_mc(bv, im, fa, partials, nblk, st); return; }   /* MCSSD / MCNCC */
 	if (fa.fast_math && !fa.materialize) {

@@ -245,6 +245,12 @@ struct mtfhip_batch {
 	int scv_hist = 0, scv_linear = 0, scv_mapped_grad = 0, scv_nb = 0;
 	double *d_scv_i0 = nullptr, *d_scv_part = nullptr, *d_scv_map = nullptr;
 	unsigned short *d_scv_code = nullptr;
+	/* RSCV (am = MTFHIP_AM_RSCV): RSCVParams weighted_mapping, n_bins; the template's code plane ((int)I0), pass-1 rows and arrival
+	 * counters, the intensity maps, and It_orig of the per-function route (kernels_rscv.hip) */
+	int rscv_linear = 0, rscv_nb = 0;
+	unsigned char *d_rscv_code = nullptr;
+	unsigned *d_rscv_part = nullptr, *d_rscv_arrive = nullptr;
+	double *d_rscv_map = nullptr, *d_rscv_it = nullptr;
 	size_t cand_capacity = 0;
 	double *d_cand_mi = nullptr; size_t cand_mi_capacity = 0;   /* MI candidate scoring: histogram rows per candidate */
 	int *d_active = nullptr, *d_iters = nullptr;
@@ -417,13 +423,20 @@ static int push_warps(mtfhip_batch *b) {
 }
 
 /* the BatchView of a fused launch: a stale single-target warp goes into the kernel arguments instead of being uploaded */
-/* SCV is SSD on its re-mapped template: every SSD branch of the entry points serves it */
-static inline bool ssd_like(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV; }
+/* SCV is SSD on its re-mapped template, RSCV SSD on its mapped current patch: every SSD branch of the entry points serves them */
+static inline bool ssd_like(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV; }
+/* SCV and RSCV: an intensity map is rebuilt between the fused passes -- the one-launch, persistent and step loops do not take them */
+static inline bool intensity_mapped(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV; }
 /* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
 int scv_capture(mtfhip_batch *b);
 int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
-/* the configurations SCV refuses on the device path, for the entry point fn */
+/* the configurations SCV and RSCV refuse on the device path, for the entry point fn */
 int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess);
+/* api_rscv.hip: the code plane and the identity map (initializePixVals); pass 1 + the map in front of the fused launch fa for the targets
+ * [t0, t0 + bv.B), and the map that launch applies (rm); the per-function updatePixVals (It_orig, the map, It = map(It_orig)) */
+int rscv_capture(mtfhip_batch *b);
+int rscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, const FusedArgs &fa, hipStream_t st, RscvMap *rm);
+int rscv_update_pix_vals(mtfhip_batch *b, const double *dp);
 static inline BatchView fused_view(mtfhip_batch *b, FusedArgs &fa) {
 	fa.inline_warp = 0;
 	if (b->warps_dirty && b->B == 1) {

@@ -104,10 +104,28 @@ __device__ __forceinline__ double bilin_mc(double t00, double t01, double t10, d
 	const double ly_lx = (1 - dx) * (1 - dy), ly_ux = dx * (1 - dy), uy_lx = (1 - dx) * dy, uy_ux = dx * dy;
 	return t00 * ly_lx + t01 * ly_ux + t10 * uy_lx + t11 * uy_ux;
 }
+/* utils::mapPixVal<Nearest / Linear> (imgUtils.h:682-695) through a map of nb entries: nearest map[(int)rint(x)], linear
+ * (1 - dx) map[lx] + dx map[lx + 1] (map[lx] when dx == 0).  Indices are clamped to [0, nb - 1]: a sample of a region saturated at 255
+ * can come out a few ulps above nb - 1, where the reference would read one past its map. */
+__device__ __forceinline__ double rscv_map_val(const double *m, int nb, int linear, double x) {
+	/* (one index and one table read for both forms: (double)(int)x is trunc(x)) */
+	const double xi = linear ? trunc(x) : rint(x);
+	int k = (int)xi;
+	k = k < 0 ? 0 : (k > nb - 1 ? nb - 1 : k);
+	const double m0 = m[k];
+	const double dx = x - xi;
+	if (!linear || dx == 0) return m0;
+	return (1 - dx) * m0 + dx * m[k + 1 < nb ? k + 1 : nb - 1];
+}
+/* AM = MTFHIP_AM_RSCV (kernels_fused_rscv.hip): SSD on the mapped current patch.  The prologue copies the target's map (rm, at most
+ * 2 KB) into the dynamic LDS the grid rebuild would use (RSCV does not take it); every sample It_orig is mapped right after it is taken,
+ * so the residual and the materialised It are the reference's It = map(It_orig) (RSCV.cc:230-234), while the gradients stay those of
+ * the unmapped image (mapped_gradient 0, ImageBase::updatePixGrad). */
 /* COHROW: the workgroup's partial row leaves as write-through stores (the persistent loop, and the one-launch-per-pass kernel of
  * kernels_step.hip whose last-arriving workgroup reads every row in the same launch) */
 template <int AM, int SSM, bool CHAINED, int MODE, bool MAT, bool FAST = false, bool PERSIST = false, bool MC = false, bool COHROW = PERSIST>
-__device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk) {
+__device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
+	const RscvMap &rm = RscvMap{}) {
 	constexpr int S = (SSM == MTFHIP_SSM_HOMOGRAPHY) ? 8 : 6;
 	constexpr bool NCC = AM == MTFHIP_AM_NCC;
 	constexpr int K = NCC ? NCC_ACC_COUNT : 48;
@@ -208,7 +226,18 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 	 * row alone are tabulated once per workgroup in LDS (launch_fused_mat sizes it: (resx + resy) double2): a row costs two LDS reads
 	 * and four additions, and the loop keeps two scalars of the map (W0[2] 1.0, W0[5] 1.0) instead of the map and the lattice. */
 	constexpr bool GR_OK = grid_regen_kernel(AM, SSM, CHAINED, MODE, MAT) && !FAST && !PERSIST && !MC && !COHROW;
-	extern __shared__ double2 grid_tab[];   /* [resx] (W0[0] nx, W0[3] nx) | [resy] (W0[1] ny, W0[4] ny) */
+	extern __shared__ double2 grid_tab[];   /* [resx] (W0[0] nx, W0[3] nx) | [resy] (W0[1] ny, W0[4] ny) -- RSCV: its map, [rm.nb] double */
+	constexpr bool RSCV = AM == MTFHIP_AM_RSCV;
+	static_assert(!(RSCV && (GR_OK || NCC || PERSIST || MC || COHROW)), "RSCV: single channel, one launch per pass, no grid rebuild");
+	/* (uniform per workgroup; every thread of the workgroup gets here, nothing before it returns) */
+	auto fill_map = [&]() {
+		if constexpr (RSCV) {
+			double *s_map = reinterpret_cast<double *>(grid_tab);
+			const double *src = rm.map + (size_t)t * (unsigned)rm.nb;
+			for (int k = threadIdx.x; k < rm.nb; k += kBlock) s_map[k] = src[k];
+			__syncthreads();
+		}
+	};
 	double gz_x = 0.0, gz_y = 0.0;
 	/* gc, gr: the lattice column and row of pixel i (GR only) */
 	auto load_in = [&](unsigned i, auto uz, auto jr, auto grg, unsigned gc, unsigned gr) {
@@ -428,6 +457,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 				gy = (inc - dec) * gmult;
 			}
 		}
+		if constexpr (RSCV) it = rscv_map_val(reinterpret_cast<const double *>(grid_tab), rm.nb, rm.linear, it);
 		const double r = it - cur.i0;
 		if constexpr (NCC) {
 			acc[NCC_IT] += it; acc[NCC_IT2] = fma(it, it, acc[NCC_IT2]); acc[NCC_I0IT] = fma(cur.i0, it, acc[NCC_I0IT]);
@@ -672,6 +702,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 		if (full > 0) {
 			PixIn<S, MODE> cur = load_in(base, uz, jr, grg, gc, gr);
 			asm volatile("" ::: "memory");
+			fill_map();   /* (behind the first row's loads) */
 			setup_target();
 			if (!live) return;
 #pragma unroll 1
@@ -691,7 +722,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 		 * already the row's: `full` steps from base) */
 		if (full < n_rows) {
 			const unsigned i = base + (unsigned)full * kBlock;
-			if (full == 0) { setup_target(); if (!live) return; }
+			if (full == 0) { fill_map(); setup_target(); if (!live) return; }
 			if (i < N) {
 				const PixIn<S, MODE> c = load_in(i, uz, jr, grg, gc, gr);
 				const Tex tc = issue_tex(c, uz);

@@ -296,6 +296,13 @@ struct FusedArgs {
 	const double *w0;
 };
 
+/* RSCV (am = MTFHIP_AM_RSCV): the intensity maps the fused pass applies to every sample (kernels_rscv.hip builds them), an extra
+ * argument behind the fused kernels' own -- map: [bv.B][nb], offset to bv's first target; linear: RSCVParams::weighted_mapping */
+struct RscvMap {
+	const double *map = nullptr;
+	int nb = 0, linear = 0;
+};
+
 /* one-time probe: does the kernel-argument segment hold (BatchView, ImgView, FusedArgs) where fused_lk_body's inline-warp path reads them? */
 bool kernarg_layout_verified(hipStream_t st);
 void launch_queue_delay(double microseconds, hipStream_t st);
@@ -472,9 +479,12 @@ void launch_finish_host(double *partials, int nblk, int row_len, double *out_hos
 	unsigned long long seq, int B, hipStream_t st);
 void launch_publish_host(const void *src, void *dst_host, size_t bytes, int *count, unsigned long long *flag_host,
 	unsigned long long seq, hipStream_t st);
-/* the fused LK iteration for SSD */
+/* the fused LK iteration for SSD (and RSCV: bv.am == MTFHIP_AM_RSCV takes the RSCV instantiations, which need rm) */
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials,
-	int nblk, hipStream_t st);
+	int nblk, hipStream_t st, const RscvMap *rm = nullptr);
+/* kernels_fused_rscv.hip: the RSCV instantiations of the fused body (replay and tolerance mode) */
+void launch_fused_rscv(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const RscvMap &rm,
+	hipStream_t st);
 /* second-order path: hess_pts, image Hessians ([N][4]), SSM pixel Hessians ([S*S][N] planes), sum_p w[p] d2[:, p] */
 void launch_hess_pts(const BatchView &bv, double eps, hipStream_t st);
 void launch_img_hess(const BatchView &bv, const ImgView &im, const double *pts, double *hess, double eps, double mult, hipStream_t st);
@@ -564,6 +574,29 @@ int scv_hist_blocks(int N);
 void launch_scv_codes(int N, int B, int nb, const double *i0o, unsigned short *code, hipStream_t st);
 /* pass 1 + map + re-map; part: [B][scv_hist_blocks(N)][2 nb], map: [B][nb], I0: MTFHIP_BUF_I0 (all offset to bv's first target) */
 void launch_scv_update(const BatchView &bv, const ImgView &im, const ScvArgs &a, double *part, double *map, double *I0, hipStream_t st);
+
+/* ---- RSCV: the current patch's intensity map of RSCV::updatePixVals (kernels_rscv.hip) ---- */
+constexpr int kRscvMaxBins = 256;
+/* how pass 1 obtains It_orig -- the expression of the fused pass it runs in front of, so that every pixel lands in the bin the fused
+ * pass looks it up in: replay (MATH_REPLAY, every materialising launch); tolerance mode ICLK, chained FCLK / ESM, non-chained FCLK /
+ * ESM (each with its own interior test, mtfhip_fused_device.h); or read from the It_orig buffer (per-function path) */
+enum { RSCV_IT_REPLAY = 0, RSCV_IT_FAST_ICLK = 1, RSCV_IT_FAST_CHAINED = 2, RSCV_IT_FAST_QSTEP = 3, RSCV_IT_FROM_BUF = 4 };
+struct RscvArgs {
+	int nb, kind;                /* n_bins, RSCV_IT_* */
+	double norm_mult, norm_add, grad_eps;
+	const unsigned char *code;   /* [B][N] (int)I0, clamped to [0, nb - 1] */
+	const double *it_orig;       /* [B][N] (RSCV_IT_FROM_BUF) */
+	const int *active;           /* optional [B] mask (device-side loop) */
+	unsigned *part;              /* [B][rscv_hist_blocks(N)][2 nb] per-workgroup sums */
+	unsigned *arrive;            /* [B] arrival counters (0 between launches) */
+	double *map;                 /* [B][nb] */
+};
+int rscv_hist_blocks(int N);
+void launch_rscv_codes(int N, int B, int nb, const double *i0, unsigned char *code, hipStream_t st);
+/* pass 1 and the map (its last-arriving workgroup per target); all pointers of a offset to bv's first target */
+void launch_rscv_hist(const BatchView &bv, const ImgView &im, const RscvArgs &a, hipStream_t st);
+/* It = map(It_orig) (the per-function route's updatePixVals) */
+void launch_rscv_apply(int N, int B, int nb, int linear, const double *map, const double *it_orig, double *It, hipStream_t st);
 
 } // namespace mtfhip
 #endif

@@ -57,6 +57,9 @@ int HipPair::jacobianBuffer(const MatrixXd &J, bool may_register, int preferred)
 void HipPair::setSCV(int hist_type, bool weighted_mapping, bool mapped_gradient) {
 	check(mtfhip_batch_set_scv(b, hist_type, weighted_mapping ? 1 : 0, mapped_gradient ? 1 : 0));
 }
+void HipPair::setRSCV(bool use_bspl, bool weighted_mapping, bool mapped_gradient) {
+	check(mtfhip_batch_set_rscv(b, use_bspl ? 1 : 0, weighted_mapping ? 1 : 0, mapped_gradient ? 1 : 0));
+}
 
 /* same for the SM-owned S^2 x N pixel Hessians (SM/include/mtf/SM/NT/ESM.h: init / curr / mean_pix_hessian) */
 int HipPair::hessianBuffer(const MatrixXd &D, bool may_register) {
@@ -72,7 +75,7 @@ int HipPair::hessianBuffer(const MatrixXd &D, bool may_register) {
 
 /* ------------------------------------------------------------------ AM */
 HipAM::HipAM(std::shared_ptr<HipPair> pair) : p(pair) {
-	name = p->am == MTFHIP_AM_SSD ? "ssd" : (p->am == MTFHIP_AM_NCC ? "ncc" : (p->am == MTFHIP_AM_SCV ? "scv" : "mi"));
+	name = p->am == MTFHIP_AM_SSD ? "ssd" : (p->am == MTFHIP_AM_NCC ? "ncc" : (p->am == MTFHIP_AM_SCV ? "scv" : (p->am == MTFHIP_AM_RSCV ? "rscv" : "mi")));
 	I0.resize(p->N); It.resize(p->N);
 	dI0_dx.resize(p->N, 2); dIt_dx.resize(p->N, 2);
 	d2I0_dx2.resize(4, p->N); d2It_dx2.resize(4, p->N);

@@ -46,6 +46,7 @@ struct HipPair {
 	static void check(int rc);               /* rethrows C-ABI failures as mtf::utils::Exception */
 	int jacobianBuffer(const MatrixXd &J, bool may_register, int preferred = -1);
 	void setSCV(int hist_type, bool weighted_mapping, bool mapped_gradient);   /* mtfhip_batch_set_scv (am = MTFHIP_AM_SCV) */
+	void setRSCV(bool use_bspl, bool weighted_mapping, bool mapped_gradient);  /* mtfhip_batch_set_rscv (am = MTFHIP_AM_RSCV) */
 	int hessianBuffer(const MatrixXd &D, bool may_register);
 };
 
@@ -62,17 +63,30 @@ struct HipSCVParams {
 	int hist_type = 0; int n_bins = 256; double pre_seed = 0; bool partition_of_unity = false;
 	bool weighted_mapping = false; bool mapped_gradient = false;
 };
+/* RSCVParams (AM/include/mtf/AM/RSCV.h), the reference's field names and class defaults (RSCV.cc:6-12).  n_bins <= 0 selects 256.
+ * The device path serves use_bspl 0 (Dirac histograms) with mapped_gradient off; pre_seed and partition_of_unity only act on the BSpline
+ * histograms it refuses, approx_dist_feat only on RSCVDist. */
+struct HipRSCVParams {
+	bool use_bspl = false; int n_bins = 256; double pre_seed = 0; bool partition_of_unity = false;
+	bool weighted_mapping = false; bool mapped_gradient = false; bool approx_dist_feat = true;
+};
 struct HipLink {
 	int am = MTFHIP_AM_SSD, ssm = MTFHIP_SSM_HOMOGRAPHY, resx = 50, resy = 50;   /* AMParams / SSMParams: resx, resy */
 	double grad_eps = 1e-8, likelihood_alpha = 1.0;                           /* AMParams::grad_eps; SSDParams / NCCParams / MIParams::likelihood_alpha */
 	int mi_n_bins = 8; double mi_pre_seed = 10; int mi_pou = 0;                /* MIParams */
 	HipSCVParams scv;                                                          /* am = MTFHIP_AM_SCV ("scv") */
+	HipRSCVParams rscv;                                                        /* am = MTFHIP_AM_RSCV ("rscv") */
 	int device = 0; void *stream = nullptr;
 	std::shared_ptr<HipPair> pair(int n_channels = 1) {
 		if (!p && am == MTFHIP_AM_SCV) {
 			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, scv.n_bins, scv.pre_seed, scv.partition_of_unity ? 1 : 0,
 				device, stream, n_channels);
 			p->setSCV(scv.hist_type, scv.weighted_mapping, scv.mapped_gradient);
+		}
+		if (!p && am == MTFHIP_AM_RSCV) {
+			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, rscv.n_bins, rscv.pre_seed, rscv.partition_of_unity ? 1 : 0,
+				device, stream, n_channels);
+			p->setRSCV(rscv.use_bspl, rscv.weighted_mapping, rscv.mapped_gradient);
 		}
 		if (!p) p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, device, stream, n_channels);
 		else if (n_channels > 1 && n_channels != p->n_channels)   /* (SearchMethod<AM, SSM> constructs the AM first: it fixes the channel count) */

@@ -72,6 +72,17 @@ mtfhost_tracker *mtfhost_create_scv(int sm, int ssm, int resx, int resy, int max
 		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
 	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
+/* the same tracker with HipAM("rscv"): its RSCVParams through the HipLink */
+mtfhost_tracker *mtfhost_create_rscv(int sm, int ssm, int resx, int resy, int max_iters, double epsilon, int jac_type, int hess_type, int chained_warp,
+	int leven_marq, double lm_delta_init, double lm_delta_update, int device, int use_bspl, int n_bins, int weighted_mapping, int mapped_gradient) {
+	try {
+		auto link = std::make_shared<hip::HipLink>();
+		link->am = MTFHIP_AM_RSCV; link->ssm = ssm; link->resx = resx; link->resy = resy; link->device = device;
+		link->rscv.use_bspl = use_bspl != 0; link->rscv.n_bins = n_bins; link->rscv.weighted_mapping = weighted_mapping != 0;
+		link->rscv.mapped_gradient = mapped_gradient != 0;
+		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
+	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
 void mtfhost_destroy(mtfhost_tracker *t) { delete t; }
 /* ESM / FC / IC_ENABLE_LEARNING + the AM's learning_rate: am->updateModel(ssm->getPts()) at the end of every update() */
 int mtfhost_set_learning(mtfhost_tracker *t, int enable, double learning_rate) {

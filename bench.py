@@ -8,6 +8,11 @@ kernel, the fixed-order partial reduction, and the 8x8 solve + compositional upd
 all on the device with no host round trip (mtfhip_batch_track).  A single target does not shard
 (SURVEY.md 8e), so N GPUs run N independent replicas of the per-GPU target set: weak scaling, no
 data-path collective.  Inputs (frame, templates, warps) are resident in HBM before the timed region.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: it sets up, warms up, times the
+K steps, writes --dump-outputs and prints the line.  Everything else the lk line can carry -- the roofline record and its event
+pass, the lean and single-target sub-records, the CPU oracle's baseline and the parity gate, the `configs` block (--gpus 1) and the
+sharded-filter record `pf_strong` (--gpus > 1) -- runs with --full, after the timed regions.
 """
 import argparse
 import json
@@ -378,6 +383,11 @@ def self_spawn_if_needed(args, argv):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+def pf_strong_wanted(args, world):
+    """--pf-strong: 1 = always, 0 = never, -1 (default) = with --full when there is more than one rank"""
+    return args.pf_strong == 1 or (args.pf_strong < 0 and args.full and world > 1)
+
+
 CONFIGS_CHILD_TIMEOUT_S = 90
 
 
@@ -413,7 +423,7 @@ def _compact(line):
 
 
 def configs_block(args):
-    """r05 verdict item 2: configs 3 / 4 / 5 of BASELINE.json in the driver's own line.  Each is this file's secondary workload run as a
+    """r05 verdict item 2: configs 3 / 4 / 5 of BASELINE.json in the lk line of --full.  Each is this file's secondary workload run as a
     child process at a reduced step count (its own context on the same GPU; the parent's device work is over) -- a failure or a hang
     there (timeout: the child is killed) becomes {"error": ...} and cannot take the headline down."""
     import subprocess
@@ -843,7 +853,7 @@ def stub_main(args):
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "stub",
             "config": {"workload": "stub", "parallelism": "replicas x%d" % world}, "pf_strong": None}
-    if args.pf_strong == 1 or (args.pf_strong < 0 and world > 1):
+    if pf_strong_wanted(args, world):
         guardian = LineGuardian(line) if rank == 0 else None
         if os.environ.get("MTFHIP_BENCH_STUB_CRASH") == "1" and rank == 0:   # (tests/test_bench_cpu.py: a fault in native code inside the record)
             import signal
@@ -1337,16 +1347,21 @@ def main():
     ap.add_argument("--math", default="fast", choices=["fast", "replay"],
                     help="arithmetic of the non-materialising kernels: fast = FMA / one reciprocal per point / closed-form gradient "
                          "(within 1e-5), replay = the reference's rounding bit for bit (mtfhip_batch_set_math_mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="lk workload: after the timed regions, also run what the headline figure does not need -- the roofline record and its "
+                         "event pass, the lean and single-target sub-records, the CPU oracle's baseline and the parity gate, the `configs` "
+                         "block (--gpus 1) and the pf_strong record (--gpus > 1).  Without it the line carries the headline alone")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-lean", action="store_true", help="skip the lean and single-target sub-records of the headline line")
-    ap.add_argument("--event-stride", type=int, default=0, help="lk workload: HIP events around every n-th fused launch inside the timed regions; 0 (default) = none -- "
-                    "at the driver's 20 steps a region is 1 ms and even every 4th launch instrumented costs 12 %% of it (1.19 M -> 1.05 M iters/s, r06 A/B)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle's baseline and the parity check (the lk line has them only with --full)")
+    ap.add_argument("--no-lean", action="store_true", help="with --full: skip the lean and single-target sub-records of the headline line")
+    ap.add_argument("--event-stride", type=int, default=0, help="lk workload with --full: HIP events around every n-th fused launch inside the timed regions, for the "
+                    "roofline record; 0 (default) = none -- at the driver's 20 steps a region is 1 ms and even every 4th launch instrumented costs 12 %% "
+                    "of it (1.19 M -> 1.05 M iters/s, r06 A/B)")
     ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each (value = the median region)")
     ap.add_argument("--configs", type=int, default=-1, help="append the `configs` block (BASELINE.json's configs 3 / 4 / 5 at reduced step counts, child "
-                    "processes) to the lk line: -1 = at --gpus 1 with the default workload shape (default), 0 = never, 1 = always")
+                    "processes) to the lk line: -1 = with --full at --gpus 1 with the default workload shape (default), 0 = never, 1 = always")
     ap.add_argument("--pf-strong", type=int, default=-1, help="append the sharded-filter strong-scaling record (pf_strong) to the lk line: "
-                    "-1 = when --gpus > 1 (default), 0 = never, 1 = always (on one GPU it exercises the code path with one rank)")
+                    "-1 = with --full when --gpus > 1 (default), 0 = never, 1 = always (on one GPU it exercises the code path with one rank)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (batch.track: corners, n_iters) as "
                          "DIR/<name>.npy in float64, so that two builds can be compared output for output.  The lk workload (the timed "
@@ -1354,6 +1369,8 @@ def main():
     args = ap.parse_args()
     if args.dump_outputs and (args.workload != "lk" or stub_mode()):
         ap.error("--dump-outputs writes the device results of the lk workload (not of --workload %s%s)" % (args.workload, " / the stub" if stub_mode() else ""))
+    if args.event_stride > 0 and not args.full:
+        ap.error("--event-stride instruments the timed regions for the roofline record, which only --full writes")
     self_spawn_if_needed(args, sys.argv[1:])
     if stub_mode():
         return stub_main(args)
@@ -1460,26 +1477,28 @@ def main():
     region_s = [r[0] for r in regions]
     dt, region_kern_ms, region_kern_n = sorted(regions)[(len(regions) - 1) // 2]   # (an actual region: ms_per_step x steps is one region's wall time)
     dt = float(dt)
+    # from here to the line's print, all but the headline fields of `out` is --full's (module docstring)
     # kernel duration for the roofline: hipEvents around EVERY fused launch of a second, untimed pass of the same loop (at least 200
     # launches whatever --steps is -- with 40 the first launches after the region reset still weighed on the average, 0.720-0.727
     # against 0.734-0.738 for the same code at --steps 200; the events cost ~5 % of a step, which is why they stay out of the timed
     # region above)
     k_steps = max(200, args.steps)
-    ctx.timing(1)
-    ctx.timing_reset()
-    t_ev = time.perf_counter()
-    n_ev, _ = run(k_steps)
-    torch.cuda.synchronize(dev)
-    ev_pass_s = time.perf_counter() - t_ev   # (includes the setRegion in front of the loop: a few hundred microseconds of k_steps steps)
-    kern_ms, kern_n = ctx.timing_get("fused_lk")
-    # launches of the fused kernel overlap when the loop keeps two chunks of targets in flight on two queues: the time the kernel was
-    # executing is the union of the launches' intervals (equal to their sum on one queue)
-    busy_ms, busy_n = ctx.timing_get_busy("fused_lk")
-    fin_ms, fin_n = ctx.timing_get("finish_track")
-    ctx.timing(False)
+    if args.full:
+        ctx.timing(1)
+        ctx.timing_reset()
+        t_ev = time.perf_counter()
+        n_ev, _ = run(k_steps)
+        torch.cuda.synchronize(dev)
+        ev_pass_s = time.perf_counter() - t_ev   # (includes the setRegion in front of the loop: a few hundred microseconds of k_steps steps)
+        kern_ms, kern_n = ctx.timing_get("fused_lk")
+        # launches of the fused kernel overlap when the loop keeps two chunks of targets in flight on two queues: the time the kernel was
+        # executing is the union of the launches' intervals (equal to their sum on one queue)
+        busy_ms, busy_n = ctx.timing_get_busy("fused_lk")
+        fin_ms, fin_n = ctx.timing_get("finish_track")
+        ctx.timing(False)
     # the lean variant of the same workload (nothing materialised: the form the device-side loop needs): FP64-issue / latency bound
     lean = None
-    if rank == 0 and args.mode == "full" and not args.no_lean and CH == 1:
+    if args.full and rank == 0 and args.mode == "full" and not args.no_lean and CH == 1:
         sm_l = mtf_amd.sm_desc(sm_kind, materialize=0, leven_marq=0, epsilon=-1.0, max_iters=k_steps)
         batch.set_region(corners, sm_l); batch.track(sm_l)
         torch.cuda.synchronize(dev)
@@ -1500,7 +1519,7 @@ def main():
     # the single-target, latency-bound figure -- configs 1 / 2 as one MTF tracker runs them (one target, the whole
     # update() on the device: a pixel pass + a finish launch per iteration)
     single = None
-    if rank == 0 and args.mode == "full" and not args.no_lean and CH == 1 and B > 1:
+    if args.full and rank == 0 and args.mode == "full" and not args.no_lean and CH == 1 and B > 1:
         single = {}
         for s_res, s_mat, s_name in ((200, 1, "200x200_full"), (200, 0, "200x200_lean"), (50, 0, "50x50_lean_config1_shape")):
             b1 = mtf_amd.Batch(ctx, am_kind, mtf_amd.SSM_HOMOGRAPHY, s_res, s_res, 1)
@@ -1527,6 +1546,24 @@ def main():
     out = None
     if rank == 0:
         N = res * res * CH       # rows of the per-pixel arrays: (pixel, channel) pairs for the multi-channel models
+        out = {
+            "metric": "LK iters/sec (warp+grad+Hessian), ESM+%s%s+Homography 200x200" % ("MC" if CH > 1 else "", args.am.upper()),
+            "value": B * world * args.steps / dt,
+            "value_min": B * world * args.steps / max(region_s), "value_max": B * world * args.steps / min(region_s),
+            "timed_regions": {"count": len(region_s), "ms": [r * 1e3 for r in region_s],
+                              "note": "each region = W warm-up steps (untimed) + K timed steps between barrier + synchronize, MAX over ranks; value and "
+                                      "ms_per_step are the median region's"},
+            "unit": "iters/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "%s+%s%s+Homography %dx%d%s, %d independent targets per GPU, %s mode, solve+update on device"
+                                   % (args.sm.upper(), "MC" if CH > 1 else "", args.am.upper(), res, res, "x%d" % CH if CH > 1 else "", B, args.mode),
+                       "targets_per_gpu": B, "n_pix": N, "channels": CH, "mode": args.mode, "frame": "%dx%d float32%s" % (H, W, " x %d channels" % CH if CH > 1 else ""),
+                       "parallelism": "replicas x%d" % world},
+        }
+    if out is not None and args.full:
         j0_rec = os.environ.get("MTFHIP_J0_RECOMPUTE", "1") != "0" and args.sm in ("esm", "iclk")
         bpp = algorithmic_bytes_per_pixel(args.sm, materialize, j0_recompute=j0_rec)
         if CH > 1:
@@ -1549,22 +1586,7 @@ def main():
         # cannot disagree (frac = value x bytes per target-iteration / peak).  The wall time contains the solves, cold first passes and call
         # overhead: a lower bound on the rate while the fused kernel runs.  The event-instrumented second pass rides along as `event_pass`.
         achieved = float(bpp) * N * B * args.steps / dt / 1e9
-        out = {
-            "metric": "LK iters/sec (warp+grad+Hessian), ESM+%s%s+Homography 200x200" % ("MC" if CH > 1 else "", args.am.upper()),
-            "value": B * world * args.steps / dt,
-            "value_min": B * world * args.steps / max(region_s), "value_max": B * world * args.steps / min(region_s),
-            "timed_regions": {"count": len(region_s), "ms": [r * 1e3 for r in region_s],
-                              "note": "each region = W warm-up steps (untimed) + K timed steps between barrier + synchronize, MAX over ranks; value and "
-                                      "ms_per_step are the median region's"},
-            "unit": "iters/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "%s+%s%s+Homography %dx%d%s, %d independent targets per GPU, %s mode, solve+update on device"
-                                   % (args.sm.upper(), "MC" if CH > 1 else "", args.am.upper(), res, res, "x%d" % CH if CH > 1 else "", B, args.mode),
-                       "targets_per_gpu": B, "n_pix": N, "channels": CH, "mode": args.mode, "frame": "%dx%d float32%s" % (H, W, " x %d channels" % CH if CH > 1 else ""),
-                       "parallelism": "replicas x%d" % world},
+        out.update({
             "roofline": {"bound": "hbm+infinity-cache" if materialize else "fp64-valu / latency (hbm fraction reported for what it is)",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
@@ -1602,7 +1624,7 @@ def main():
                                            "(2 x FETCH_SIZE + WRITE_SIZE) KiB, the guide's gfx950 correction); counters cannot be read inside a timed run",
                          "traffic_commit": getattr(pmc_traffic, "commit", None), "traffic_note": getattr(pmc_traffic, "note", None),
                          "kernel_sources_sha": kernel_sources_sha()},
-        }
+        })
         if lean is not None:
             out["lean"] = lean
         if single is not None:
@@ -1612,11 +1634,11 @@ def main():
             out["parity"] = parity_gate(ctx, args.am, res, frame0, frame1, corners[0])
         elif not args.no_cpu:
             out["cpu_baseline"] = None
-    # north_star's multi-GPU split is the particle axis: the strong-scaling record of the sharded filter rides on the N > 1 line.  It is
+    # north_star's multi-GPU split is the particle axis: the strong-scaling record of the sharded filter rides on the N > 1 --full line.  It is
     # the one part of this file that has never met more than one real GPU (RCCL with world > 1 needs a multi-GPU node), so it cannot
     # take the headline down with it: an exception becomes {"error": ...}, and a rank that stops answering is cut off by a watchdog
     # that prints the line without the record and ends the process on every rank.
-    if args.pf_strong == 1 or (args.pf_strong < 0 and world > 1):
+    if pf_strong_wanted(args, world):
         import threading
 
         guardian = None
@@ -1642,7 +1664,7 @@ def main():
             guardian.release()
         if out is not None:
             out["pf_strong"] = rec
-    if out is not None and (args.configs == 1 or (args.configs < 0 and world == 1 and not args.no_cpu and CH == 1 and args.mode == "full")):
+    if out is not None and (args.configs == 1 or (args.configs < 0 and args.full and world == 1 and not args.no_cpu and CH == 1 and args.mode == "full")):
         try:
             out["configs"] = configs_block(args)
         except Exception as e:   # noqa: BLE001

@@ -1,6 +1,6 @@
 """CPU: `python bench.py --gpus 2` from a clean environment -- the command the driver types -- launches its own two ranks
 (torch.distributed.run on 127.0.0.1), rendezvouses (gloo here, RCCL on the GPUs), times between barriers with MAX over ranks,
-and rank 0 alone prints ONE JSON line that carries the sharded-filter strong-scaling record (pf_strong).  Device work is replaced
+and rank 0 alone prints ONE JSON line; with --full that line carries the sharded-filter strong-scaling record (pf_strong).  Device work is replaced
 by stand-ins (MTFHIP_BENCH_STUB=1: bench.stub_main / PfStubEngine); the sharded layout is the C ABI's
 (tests/test_dist_cpu.py::test_pf_shard_bounds_partition)."""
 import json
@@ -19,7 +19,7 @@ def _clean_env():
 
 
 def test_bench_gpus2_self_spawns_and_reports_pf_strong():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--repeats", "3"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--repeats", "3", "--full"],
                        env=_clean_env(), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -45,7 +45,7 @@ def test_pf_strong_survives_a_rank_that_cannot_set_the_peer_exchange_up():
     the JSON line are produced as usual."""
     env = _clean_env()
     env["MTFHIP_BENCH_STUB_PEER_FAIL"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1", "--full"],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -60,6 +60,17 @@ def test_bench_single_rank_stub_line():
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["pf_strong"]["n_ranks"] == 1 and "sharded" not in d["pf_strong"]["sizes"][0]
+
+
+def test_plain_gpus2_line_leaves_pf_strong_to_full():
+    """the plain multi-rank command times its steps and prints the headline alone: the sharded-filter record is --full's"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1"],
+                       env=_clean_env(), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0 and d["pf_strong"] is None
 
 
 def test_pf_strong_peer_children_row_from_rank_results():
@@ -90,7 +101,7 @@ def test_headline_line_survives_a_fault_in_native_code_inside_the_pf_record():
     guardian child prints the headline with pf_strong = {"error": ...}.  And when nothing dies the guardian stays silent (the tests above)."""
     env = _clean_env()
     env["MTFHIP_BENCH_STUB_CRASH"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1", "--full"],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, (p.stdout[-1000:], p.stderr[-1000:])

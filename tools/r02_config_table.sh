@@ -3,7 +3,7 @@ here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative p
 # The configurations tabulated in DESIGN.md section 5, one bench.py line each (one gpurun call): gpurun_out/r02_config_table.jsonl
 cd "$here/.." || exit 1
 out=gpurun_out/r02_config_table.jsonl; : > $out
-run() { timeout 300 python bench.py "$@" --no-cpu 2>/dev/null | tail -1 >> $out; }
+run() { timeout 300 python bench.py "$@" --full --no-cpu 2>/dev/null | tail -1 >> $out; }
 run --steps 200 --warmup 20
 run --steps 200 --warmup 20 --targets 256 --no-lean
 run --steps 200 --warmup 20 --mode lean --no-lean

@@ -3,9 +3,9 @@ here=$(dirname "$(readlink -f "$0")")   # (before any cd: $0 may be a relative p
 # The bench.py lines of the round's final code, one gpurun call: gpurun_out/r02_final_bench_lines.jsonl
 cd "$here/.." || exit 1
 out=gpurun_out/r02_final_bench_lines.jsonl; : > $out
-timeout 600 python bench.py 2>/dev/null | tail -1 >> $out
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu 2>/dev/null | tail -1 >> $out
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu 2>/dev/null | tail -1 >> $out
+timeout 600 python bench.py --full 2>/dev/null | tail -1 >> $out
+timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu 2>/dev/null | tail -1 >> $out
+timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu 2>/dev/null | tail -1 >> $out
 for wl in grid pf mi; do
   steps=200; [ $wl = mi ] && steps=5
   timeout 600 python bench.py --workload $wl --steps $steps --warmup 5 --cpu-seconds 4 2>/dev/null | tail -1 >> $out

@@ -13,8 +13,8 @@ bash tools/profile_round.sh $tag --steps 50 --warmup 10 > $out/profile_round.log
 cp gpurun_out/profile/${tag}_* $out/ 2>/dev/null
 # the driver's own command, three times (box-internal variance)
 : > $out/final_bench_lines.jsonl
-timeout 600 python bench.py 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl
-for i in 1 2; do timeout 300 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl; done
+timeout 600 python bench.py --full 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl
+for i in 1 2; do timeout 300 python bench.py --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl; done
 # 2. secondary workloads
 : > $out/secondary_bench_lines.jsonl
 for wl in grid pf mi; do
@@ -40,7 +40,7 @@ python tools/pmc_summary.py $out/pmc_mi > $out/mi_pmc_summary.txt
 python tools/pmc_summary.py $out/pmc_pf > $out/pf_pmc_summary.txt
 # 2b. r04 extras: the sharded-filter record on one rank (exercises the path the N > 1 line takes), the FP64 issue rates the "fraction of
 # peak" figures are read against, the grid frame with and without the fused reset
-timeout 600 python bench.py --pf-strong 1 --steps 50 --warmup 10 --no-cpu --no-lean 2>/dev/null | tail -1 > $out/pf_strong_one_rank.json
+timeout 600 python bench.py --pf-strong 1 --steps 50 --warmup 10 --full --no-cpu --no-lean 2>/dev/null | tail -1 > $out/pf_strong_one_rank.json
 [ -x scratch/fp64_rate_test ] && ./scratch/fp64_rate_test | grep "cycles/instr" > $out/fp64_rates.txt
 : > $out/grid_fused_ab.jsonl
 for gf in 0 1; do MTFHIP_GRID_FUSED=$gf timeout 300 python bench.py --workload grid --steps 300 --warmup 20 --no-cpu 2>/dev/null | tail -1 >> $out/grid_fused_ab.jsonl; done
@@ -49,7 +49,7 @@ timeout 300 python tools/pf_peer_probe.py 2>/dev/null > $out/pf_peer_probe.json
 [ -f scratch/libmtfhip_gtrace.so ] && MTFHIP_LIB=scratch/libmtfhip_gtrace.so timeout 120 python tools/grid_trace.py 2>/dev/null > $out/grid_phase_trace.txt
 # 3. configuration table
 ct=$out/config_table.jsonl; : > $ct
-run() { timeout 300 python bench.py "$@" --no-cpu 2>/dev/null | tail -1 >> $ct; }
+run() { timeout 300 python bench.py "$@" --full --no-cpu 2>/dev/null | tail -1 >> $ct; }
 run --steps 200 --warmup 20
 run --steps 200 --warmup 20 --targets 256 --no-lean
 run --steps 200 --warmup 20 --mode lean --no-lean

@@ -27,8 +27,8 @@ python tools/pmc_summary.py $out/pmc_grid > $out/grid_pmc_summary.txt
 python tools/pmc_secondary_json.py $out profiles/pmc_secondary_latest.json && cp profiles/pmc_secondary_latest.json $out/pmc_secondary_latest.json
 # the driver's own command, three times (box-internal variance)
 : > $out/final_bench_lines.jsonl
-timeout 600 python bench.py 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl
-for i in 1 2; do timeout 300 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl; done
+timeout 600 python bench.py --full 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl
+for i in 1 2; do timeout 300 python bench.py --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl; done
 # 3. secondary workloads
 : > $out/secondary_bench_lines.jsonl
 for wl in grid pf mi; do
@@ -64,11 +64,11 @@ MTFHIP_TRACK_DEBUG_TIMING=1 timeout 300 python tools/grid_modes_probe.py 2>&1 | 
 : > $out/mi_pou_ab.txt
 for r in 1 0 1 0; do MTFHIP_MI_HIST_ROWSUM=$r timeout 300 python tools/mi_pou_probe.py 2>/dev/null | tail -1 >> $out/mi_pou_ab.txt; done
 timeout 300 python tools/grid_reinit_probe.py 2>/dev/null > $out/grid_reinit_probe.txt
-timeout 600 python bench.py --pf-strong 1 --steps 50 --warmup 10 --no-cpu --no-lean 2>/dev/null | tail -1 > $out/pf_strong_one_rank.json
+timeout 600 python bench.py --pf-strong 1 --steps 50 --warmup 10 --full --no-cpu --no-lean 2>/dev/null | tail -1 > $out/pf_strong_one_rank.json
 timeout 300 python tools/pf_peer_probe.py 2>/dev/null > $out/pf_peer_probe.json
 # 4. configuration table
 ct=$out/config_table.jsonl; : > $ct
-run() { timeout 300 python bench.py "$@" --no-cpu 2>/dev/null | tail -1 >> $ct; }
+run() { timeout 300 python bench.py "$@" --full --no-cpu 2>/dev/null | tail -1 >> $ct; }
 run --steps 200 --warmup 20
 run --steps 200 --warmup 20 --targets 256 --no-lean
 run --steps 200 --warmup 20 --mode lean --no-lean

@@ -26,9 +26,9 @@ done
 for wl in mi pf grid nn; do python tools/pmc_summary.py $out/pmc_$wl > $out/${wl}_pmc_summary.txt; done
 python tools/pmc_secondary_json.py $out profiles/pmc_secondary_latest.json && cp profiles/pmc_secondary_latest.json $out/pmc_secondary_latest.json
 rm -rf $out/pmc_mi $out/pmc_pf $out/pmc_grid $out/pmc_nn
-# 3. the driver's own command (configs block included), twice
+# 3. the driver's own command with --full (configs block included), twice
 : > $out/final_bench_lines.jsonl
-for k in 1 2; do timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl; done
+for k in 1 2; do timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $out/final_bench_lines.jsonl; done
 # 4. secondary workloads: full lines + kernel traces
 : > $out/secondary_bench_lines.jsonl
 trace() { # name, bench args...
@@ -54,7 +54,7 @@ done; done
 trace nn --workload nn --steps 20 --warmup 3
 timeout 300 python bench.py --workload dropin --sm esm --steps 200 --warmup 20 --cpu-seconds 3 2>/dev/null | tail -1 >> $out/secondary_bench_lines.jsonl
 timeout 300 python bench.py --workload dropin --sm esm --device-loop --steps 200 --warmup 20 --no-cpu 2>/dev/null | tail -1 >> $out/secondary_bench_lines.jsonl
-timeout 600 python bench.py --pf-strong 1 --steps 30 --warmup 5 --no-cpu --no-lean --configs 0 2>/dev/null | tail -1 > $out/pf_strong_one_rank.json
+timeout 600 python bench.py --pf-strong 1 --steps 30 --warmup 5 --full --no-cpu --no-lean --configs 0 2>/dev/null | tail -1 > $out/pf_strong_one_rank.json
 # the shipped grid frame: one launch against three (same box)
 : > $out/grid_fb_ab.txt
 for f in 1 0 1 0; do MTFHIP_GRID_FB_FUSED=$f timeout 200 python bench.py --workload grid --steps 100 --warmup 10 --no-cpu 2>/dev/null | tail -1 |

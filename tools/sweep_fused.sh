@@ -10,7 +10,7 @@ for v in "$@"; do
   so=/tmp/libmtfhip_${pipe}_${waves}_${ppt}_${coop}_${slots}.so
   make -C mtf_amd/csrc -s -B -j8 OUT=$so EXTRA="-DMTFHIP_FUSED_WAVES=$waves -DMTFHIP_MIN_ROWS=$ppt -DMTFHIP_SLOTS=$slots $SWEEP_EXTRA" 2>&1 | grep -E "error" | head -3
   for mode in full lean; do
-    MTFHIP_LIB=$so python bench.py --steps 40 --warmup 8 --no-cpu --mode $mode 2>&1 | tail -1 | python -c "
+    MTFHIP_LIB=$so python bench.py --steps 40 --warmup 8 --full --no-cpu --mode $mode 2>&1 | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('pipe=$pipe waves=$waves min_rows=$ppt coop=$coop slots=$slots', d['config']['mode'], 'iters/s', round(d['value']), 'kern_ms %.4f' % d['roofline']['avg_kernel_ms'], 'frac %.3f' % d['roofline']['frac'])"

@@ -49,7 +49,10 @@ typedef enum mtfhip_status {
 /* MTFHIP_AM_RSCV: Reversed SCV (AM/src/RSCV.cc), an SSD whose current patch is re-mapped through E[I0 | It] after every sampling
  * (RSCV::updatePixVals, RSCV.cc:170-238); single channel, Dirac histograms, first-order Hessians, the per-function entry points and
  * the fused init_template / iterate / track / track_region (mtfhip_batch_set_rscv below) */
-enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4 };
+/* MTFHIP_AM_LSCV: Localized SCV (AM/src/LSCV.cc), an SSD whose template is re-mapped through one E[It | I0] per overlapping sub-region,
+ * blended with per-pixel weights, before a similarity update (LSCV::updateSimilarity, LSCV.cc:263-304); single channel, first-order
+ * Hessians, the per-function entry points and the fused init_template / iterate / track / track_region (mtfhip_batch_set_lscv below) */
+enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5 };
 enum { MTFHIP_SSM_HOMOGRAPHY = 0, MTFHIP_SSM_AFFINE = 1 };
 enum { MTFHIP_SM_ESM = 0, MTFHIP_SM_FCLK = 1, MTFHIP_SM_ICLK = 2 };
 /* pixel-Jacobian variants of StateSpaceModel.h:170-181 */
@@ -89,7 +92,7 @@ typedef struct mtfhip_patch_desc {
 	int resx, resy;         /* ImgParams / SSMParams resx, resy */
 	double grad_eps;        /* ImgParams::grad_eps (1e-8, AM/include/mtf/AM/ImageBase.h:7-8) */
 	double likelihood_alpha;/* AMParams::likelihood_alpha */
-	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV / MTFHIP_AM_RSCV: SCVParams / RSCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as they do */
+	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV / MTFHIP_AM_RSCV / MTFHIP_AM_LSCV: SCVParams / RSCVParams / LSCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as they do */
 	double mi_pre_seed;     /* MIParams::pre_seed */
 	int mi_partition_of_unity;
 	double hess_eps;        /* ImgParams::hess_eps (1, AM/include/mtf/AM/ImageBase.h:9); <= 0 selects that default */
@@ -584,6 +587,23 @@ int mtfhip_batch_scv_intensity_map(mtfhip_batch *b, double *dst);
 int mtfhip_batch_set_rscv(mtfhip_batch *b, int use_bspl, int weighted_mapping, int mapped_gradient);
 /* RSCV::intensity_map of every target after its last updatePixVals (RSCV.cc:211-229): B x n_bins (map[b] = b before the first one) */
 int mtfhip_batch_rscv_intensity_map(mtfhip_batch *b, double *dst);
+
+/* ---- LSCV (MTFHIP_AM_LSCV) ---- */
+/* LSCVParams n_sub_regions_x / _y, spacing_x / _y, affine_mapping, once_per_frame, weighted_mapping; call before init_template.  Defaults:
+ * the class defaults (3 x 3 sub-regions, spacing 10 x 10, no affine mapping, every similarity update, nearest mapping).  A sub-region
+ * size resx - (n_sub_regions_x - 1) spacing_x (or in y) <= 0 returns MTFHIP_ERR_INVALID_ARG, as the reference throws; a configuration
+ * whose pass-1 histograms exceed 64 KB of LDS per workgroup returns MTFHIP_ERR_NOT_IMPLEMENTED at init_template. */
+int mtfhip_batch_set_lscv(mtfhip_batch *b, int n_sub_regions_x, int n_sub_regions_y, int spacing_x, int spacing_y, int affine_mapping,
+	int once_per_frame, int weighted_mapping);
+/* the intensity maps of every target after its last re-map: B x (n_sub_regions_x n_sub_regions_y) x n_bins, sub-region idy n_x + idx
+ * (map[b] = b before the first one) */
+int mtfhip_batch_lscv_intensity_maps(mtfhip_batch *b, double *dst);
+/* AppearanceModel::first_iter (setFirstIter / clearFirstIter), one flag per batch, clear on a fresh batch.  With once_per_frame, LSCV
+ * re-maps only while it is set: on the per-function update_similarity and on mtfhip_batch_iterate.  mtfhip_batch_track sets it for its
+ * first pass and leaves it clear when it ran at least one iteration (the reference leaves it set for a target that converges in its
+ * first iteration).  Other appearance models ignore it. */
+int mtfhip_batch_set_first_iter(mtfhip_batch *b, int on);
+int mtfhip_batch_first_iter(const mtfhip_batch *b);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ int mtfhip_am_initialize_pix_vals(mtfhip_batch *b, const double *pts) {
 	}
 	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_capture(b));   /* SCV::initializePixVals: I0_orig = I0 (SCV.cc:166) */
 	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_capture(b));   /* RSCV::initializePixVals (RSCV.cc:124-168) */
+	if (b->desc.am == MTFHIP_AM_LSCV) TRY(lscv_capture(b));   /* LSCV::initializePixVals: I0_orig = I0 (LSCV.cc:232) */
 	return MTFHIP_OK;
 }
 /* SSD::updateModel AM/src/SSD.cc:49-75, NCC::updateModel AM/src/NCC.cc:539-566 (the search methods call it at the end of update()
@@ -38,6 +39,7 @@ int mtfhip_am_update_model(mtfhip_batch *b, const double *pts, double learning_r
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: MI has no online template update in the reference either");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: SCV is not available on this entry point (the template update would have to refresh I0_orig)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: RSCV is not available on this entry point (the template update would have to refresh its code plane)");
+	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LSCV is not available on this entry point (the template update would have to refresh I0_orig)");
 	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: appearance model %d", b->desc.am);
 	TRY(single_channel(b, "update_model"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "update_model before initializePixVals");
@@ -416,6 +418,8 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 	}
 	/* SCV::updateSimilarity (SCV.cc:194-230): the intensity map from It and I0_orig, I0 re-mapped, then SSDBase::updateSimilarity */
 	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 1, b->ctx->stream));
+	/* LSCV::updateSimilarity (LSCV.cc:263-304): unless once_per_frame and not the first iteration, the localized re-map of I0 */
+	if (lscv_due(b)) TRY(lscv_enqueue(b, b->view(), 0, nullptr, 1, b->ctx->stream));
 	int nblk = simple_blocks_per_target(b->N);
 	{
 		TimedScope ts(b->ctx, "ssd_residual");

@@ -363,7 +363,11 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	/* the fused kernel addresses a target's arrays with 32-bit byte offsets (ld_off / st_off): 8 columns of N doubles */
 	if ((double)d->resx * d->resy * 3.0 >= (double)(1u << 26)) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: %dx%d sample points per target exceed the 2^26-row limit", d->resx, d->resy);
 	if (d->grad_eps <= 0 || d->hess_eps < 0) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: grad_eps must be positive (got %g)", d->grad_eps);
-	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am == MTFHIP_AM_LSCV && (d->mi_n_bins > kLscvMaxBins || d->mi_n_bins == 1))
+		return fail(MTFHIP_ERR_INVALID_ARG, "LSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kLscvMaxBins);
+	if (d->am == MTFHIP_AM_LSCV && d->n_channels == 3)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "LSCV with n_channels 3 (MCLSCV) is not available on the device path (single channel only)");
 	if (d->am == MTFHIP_AM_RSCV && (d->mi_n_bins > kRscvMaxBins || d->mi_n_bins == 1))
 		return fail(MTFHIP_ERR_INVALID_ARG, "RSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kRscvMaxBins);
 	if (d->am == MTFHIP_AM_RSCV && d->n_channels == 3)
@@ -402,6 +406,13 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		 * PIX_MAX - PIX_MIN = 255, as SCV */
 		b->rscv_nb = d->mi_n_bins <= 0 ? kRscvMaxBins : d->mi_n_bins;
 		b->norm_mult = (b->rscv_nb - 1.0) / (255.0 - 0.0);
+		b->norm_add = 0;
+	}
+	if (d->am == MTFHIP_AM_LSCV) {
+		/* LSCVParams: n_bins <= 0 selects LSCV_N_BINS = 256 (LSCV.cc:8, :39-40); LSCV ctor LSCV.cc:120-135: [0, n_bins - 1] over
+		 * PIX_MAX - PIX_MIN = 255, as SCV */
+		b->lscv_nb = d->mi_n_bins <= 0 ? kLscvMaxBins : d->mi_n_bins;
+		b->norm_mult = (b->lscv_nb - 1.0) / (255.0 - 0.0);
 		b->norm_add = 0;
 	}
 	const size_t N = b->N, S = b->S, NP = b->NP;
@@ -486,8 +497,8 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		b->inline_warp_ok = b->B == 1 && !(iw_env && iw_env[0] == '0') && kernarg_layout_verified(c->stream);
 		const char *lazy_env = std::getenv("MTFHIP_LAZY");
 		/* SSD and NCC have a fused kernel each; MI has its fused passes */
-		/* (SCV: every similarity update re-maps the template first; RSCV: every updatePixVals maps the current patch -- their calls run
-		 * as they come) */
+		/* (SCV / LSCV: every similarity update re-maps the template first; RSCV: every updatePixVals maps the current patch -- their
+		 * calls run as they come) */
 		b->lz.enabled = (d->am == MTFHIP_AM_SSD || d->am == MTFHIP_AM_NCC || d->am == MTFHIP_AM_MI) && b->C == 1 &&
 			!(lazy_env && lazy_env[0] == '0');
 	}
@@ -508,7 +519,8 @@ void mtfhip_batch_destroy(mtfhip_batch *b) {
 		void *ptrs[] = {b->d_slab, b->d_partials, b->d_acc, b->d_scratch_pts, b->d_h0,
 			b->d_cand, b->d_colmean, b->d_mi_tb, b->d_mi_part,
 			b->d_mi_f, b->d_mi_H, b->d_h0inv, b->d_d2_part, b->d_d2_out, b->d_d2_w, b->d_it_shadow, b->d_ncc_tm, b->d_mi_red, b->d_lm, b->d_persist, b->d_trace, b->d_cand_mi, b->d_mi_poly, b->d_nn_warps, b->d_fb, b->d_scv_i0, b->d_scv_code, b->d_scv_part, b->d_scv_map,
-			b->d_rscv_code, b->d_rscv_part, b->d_rscv_arrive, b->d_rscv_map, b->d_rscv_it};
+			b->d_rscv_code, b->d_rscv_part, b->d_rscv_arrive, b->d_rscv_map, b->d_rscv_it, b->d_lscv_i0, b->d_lscv_code, b->d_lscv_cell, b->d_lscv_crng,
+			b->d_lscv_w, b->d_lscv_tot, b->d_lscv_arrive, b->d_lscv_map, b->d_lscv_aff};
 		for (void *p : ptrs)
 			if (p) (void)hipFree(p);
 		if (b->h_fb) (void)hipHostFree(b->h_fb);

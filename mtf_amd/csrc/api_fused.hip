@@ -595,7 +595,7 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 		if (sm->hess_type == 1) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "fused ICLK with hess_type CurrentSelf: use the un-fused entry points");
 		fa.mode = 2;
 	}
-	if (!grid_regen_kernel(b->desc.am == MTFHIP_AM_SCV ? MTFHIP_AM_SSD : b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
+	if (!grid_regen_kernel((b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_LSCV) ? MTFHIP_AM_SSD : b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
 		fa.grid_regen = 0;
 	return MTFHIP_OK;
 }
@@ -886,6 +886,8 @@ int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, d
 	if (second_order_term(sm) >= 0) TRY(ensure_pts(b));   /* k_second_order_ssd reads the current points */
 	/* SCV::updateSimilarity: the intensity map at the current warp and the re-mapped template, then the SSD iteration on it */
 	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 0, b->ctx->stream));
+	/* LSCV::updateSimilarity: unless once_per_frame and not the first iteration, the localized re-map at the current warp */
+	if (lscv_due(b)) TRY(lscv_enqueue(b, b->view(), 0, nullptr, 0, b->ctx->stream));
 	FusedArgs fa;
 	TRY(fused_args(b, sm, fa));
 	/* RSCV::updatePixVals: the intensity map of the current patch at the current warp, applied by the fused pass to every sample */
@@ -1047,7 +1049,13 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 }
 /* the rest of a loop the persistent launch left unfinished: the slab on the device is current (warps, flags, iteration counts) */
 static int track_resume(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) { return track_core(b, sm, n_iters, corners, true, true); }
-int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) { return track_core(b, sm, n_iters, corners, false); }
+/* LSCV: update() sets first_iter in front of its loop and every completed iteration clears it (NT/ESM.cc:178, :291): the device loop
+ * re-maps in front of its first pass (track_core) and leaves the batch's flag clear */
+static int lscv_after_track(mtfhip_batch *b, int rc) {
+	if (rc == MTFHIP_OK && b && b->desc.am == MTFHIP_AM_LSCV) b->lscv_first_iter = 0;
+	return rc;
+}
+int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) { return lscv_after_track(b, track_core(b, sm, n_iters, corners, false)); }
 
 /* setRegion + update of one frame in one call: what GridTracker::update does with every patch tracker (GridTracker.cc:345-363:
  * tracker->setRegion(patch corners); tracker->update()) and a pyramid level with the level above's result.  For the search
@@ -1096,7 +1104,7 @@ static int track_region_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, const do
 		if (rs != MTFHIP_OK) { b->deferred_layout = false; b->deferred_template_check = false; set_corners_finish_deferred(b); return rs; }
 	}
 	const auto t1 = std::chrono::steady_clock::now();
-	const int r = track_core(b, sm, n_iters, corners, folded, false, region_mode);
+	const int r = lscv_after_track(b, track_core(b, sm, n_iters, corners, folded, false, region_mode));
 	set_corners_finish_deferred(b);   /* (a call that failed before its launch: nothing stays pending on the caller's buffer) */
 	if (dbg) {
 		const auto t2 = std::chrono::steady_clock::now();
@@ -1121,7 +1129,7 @@ int mtfhip_batch_track_region(mtfhip_batch *b, const mtfhip_sm_desc *sm, const d
  * robust estimator.  (The layout conversion and the centroids were ~9 of the ~14 us a frame spent in the Python layer.) */
 int mtfhip_grid_update(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *regions_2x4, int *n_iters, double *corners_2x4, double *centroids) {
 	if (!b || !sm || !regions_2x4) return fail(MTFHIP_ERR_INVALID_ARG, "grid_update: NULL argument");
-	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "grid_update: %s is not available on the grid tracker", b->desc.am == MTFHIP_AM_SCV ? "SCV" : "RSCV");
+	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "grid_update: %s is not available on the grid tracker", intensity_mapped_name(b));
 	const size_t B = (size_t)b->B;
 	static thread_local std::vector<double> in, out;
 	in.resize(8 * B); out.resize(8 * B);
@@ -1144,7 +1152,7 @@ static inline void centroid_f(float *dst, const double *c) {
 }
 static int grid_batch_ok(const mtfhip_batch *b, const mtfhip_grid_desc *g, const char *fn) {
 	if (!b || !g) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
-	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s is not available on the grid tracker", fn, b->desc.am == MTFHIP_AM_SCV ? "SCV" : "RSCV");
+	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s is not available on the grid tracker", fn, intensity_mapped_name(b));
 	if (g->grid_size_x <= 0 || g->grid_size_y <= 0 || g->grid_size_x * g->grid_size_y != b->B)   /* GridTracker.cc:124-129 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "%s: mismatch between the grid dimensions (%d x %d) and the batch's %d patch trackers", fn, g->grid_size_x, g->grid_size_y, b->B);
 	return MTFHIP_OK;
@@ -1359,6 +1367,10 @@ static int track_validate(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	if (so_term >= 0 && b->C != 1) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "track: second-order Hessians of the multi-channel models use the per-function entry points");
 	if (so_term > 0 && so_term != 4 && !b->init_pix_hess) return fail(MTFHIP_ERR_LOGIC, "track: init_template was run without sec_ord_hess");
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "track before init_template");
+	/* (a rejected Levenberg-Marquardt step of FCLK repeats a pass within one iteration of its while loop: the passes do not tell which
+	 * iteration is the first) */
+	if (b->desc.am == MTFHIP_AM_LSCV && b->lscv_once && sm->leven_marq && sm->sm == MTFHIP_SM_FCLK)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "track: LSCV once_per_frame with Levenberg-Marquardt FCLK is not available on the device loop (use the per-function entry points)");
 	return need_image(b);
 }
 static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners, bool slab_uploaded, bool resume, bool region_mode) {
@@ -1635,6 +1647,8 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 						continue;
 					}
 					if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, r.bc, r.t0, r.fc.active, 0, r.s));   /* (the chunk's template re-map) */
+					/* (LSCV: the chunk's localized re-map -- with once_per_frame in front of the first pass only, LSCV.cc:264-265) */
+					if (b->desc.am == MTFHIP_AM_LSCV && (!b->lscv_once || it == 0)) TRY(lscv_enqueue(b, r.bc, r.t0, r.fc.active, 0, r.s));
 					RscvMap rm;
 					if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &rm));   /* (the chunk's current maps) */
 					{
@@ -1804,6 +1818,7 @@ int mtfhip_score_candidates_dev(mtfhip_batch *b, const double *dev_states, int C
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: SCV candidates are not available (SCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: RSCV candidates are not available (RSCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: LSCV candidates are not available (LSCVDist is a per-candidate intensity map)");
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "score_candidates before the template was initialised");
 	TRY(need_image(b));
 	TimedScope ts(b->ctx, "score_candidates");
@@ -1838,6 +1853,7 @@ int mtfhip_sample_candidates_dev(mtfhip_batch *b, const double *dev_states, int 
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: MI distance features (5 x N B-spline rows) are not available");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: SCV distance features are not available (SCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: RSCV distance features are not available (RSCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: LSCV distance features are not available (LSCVDist is a per-candidate intensity map)");
 	TRY(single_channel(b, "sample_candidates"));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "sample_candidates before set_corners");
 	TRY(need_image(b));
@@ -1873,6 +1889,7 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 	if (!b || !d || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: SCV is not available on the NN dataset (SCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: RSCV is not available on the NN dataset (RSCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: LSCV is not available on the NN dataset (LSCVDist is a per-candidate intensity map)");
 	if (d->n_samples <= 0 || row_lo < 0 || row_count < 0 || row_lo + row_count > d->n_samples)
 		return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: rows [%d, %d) of %d samples", row_lo, row_lo + row_count, d->n_samples);
 	if (d->additive_update) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: additive_update (NNParams, NT/NN.cc:150-152): the compositional form only");

@@ -51,7 +51,7 @@ int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess) {
 	if (!b || !intensity_mapped(b)) return MTFHIP_OK;
 	if (sec_ord_hess)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with second-order Hessians is not available on the device path (first-order only)", fn,
-			b->desc.am == MTFHIP_AM_SCV ? "SCV" : "RSCV");
+			intensity_mapped_name(b));
 	return MTFHIP_OK;
 }
 

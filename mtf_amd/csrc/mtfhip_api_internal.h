@@ -251,6 +251,16 @@ struct mtfhip_batch {
 	unsigned char *d_rscv_code = nullptr;
 	unsigned *d_rscv_part = nullptr, *d_rscv_arrive = nullptr;
 	double *d_rscv_map = nullptr, *d_rscv_it = nullptr;
+	/* LSCV (am = MTFHIP_AM_LSCV): LSCVParams n_sub_regions_x / _y, spacing_x / _y, affine_mapping, once_per_frame, weighted_mapping,
+	 * n_bins; AppearanceModel::first_iter (one per batch); I0_orig and its code plane; the sub-region geometry (the cell plane, the cells of
+	 * each sub-region, the weights: one copy per batch); the per-target sums and arrival counters, the maps and the affine parameters
+	 * (kernels_lscv.hip) */
+	int lscv_nx = 3, lscv_ny = 3, lscv_sx = 10, lscv_sy = 10, lscv_affine = 0, lscv_once = 0, lscv_linear = 0, lscv_nb = 0;
+	int lscv_first_iter = 0, lscv_ncx = 0, lscv_ncell = 0;
+	double *d_lscv_i0 = nullptr, *d_lscv_w = nullptr, *d_lscv_map = nullptr, *d_lscv_aff = nullptr;
+	unsigned short *d_lscv_code = nullptr, *d_lscv_cell = nullptr;
+	int *d_lscv_crng = nullptr;
+	unsigned *d_lscv_tot = nullptr, *d_lscv_arrive = nullptr;
 	size_t cand_capacity = 0;
 	double *d_cand_mi = nullptr; size_t cand_mi_capacity = 0;   /* MI candidate scoring: histogram rows per candidate */
 	int *d_active = nullptr, *d_iters = nullptr;
@@ -424,9 +434,17 @@ static int push_warps(mtfhip_batch *b) {
 
 /* the BatchView of a fused launch: a stale single-target warp goes into the kernel arguments instead of being uploaded */
 /* SCV is SSD on its re-mapped template, RSCV SSD on its mapped current patch: every SSD branch of the entry points serves them */
-static inline bool ssd_like(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV; }
+static inline bool ssd_like(const mtfhip_batch *b) {
+	return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV;
+}
 /* SCV and RSCV: an intensity map is rebuilt between the fused passes -- the one-launch, persistent and step loops do not take them */
-static inline bool intensity_mapped(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV; }
+static inline bool intensity_mapped(const mtfhip_batch *b) {
+	return b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV;
+}
+/* the name of an intensity-mapped model, for the refusals */
+static inline const char *intensity_mapped_name(const mtfhip_batch *b) {
+	return b->desc.am == MTFHIP_AM_SCV ? "SCV" : (b->desc.am == MTFHIP_AM_RSCV ? "RSCV" : "LSCV");
+}
 /* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
 int scv_capture(mtfhip_batch *b);
 int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
@@ -437,6 +455,12 @@ int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess);
 int rscv_capture(mtfhip_batch *b);
 int rscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, const FusedArgs &fa, hipStream_t st, RscvMap *rm);
 int rscv_update_pix_vals(mtfhip_batch *b, const double *dp);
+/* api_lscv.hip: I0_orig, its code plane and the sub-region geometry (initializePixVals); the localized re-map of I0 in front of an SSD
+ * similarity update, for the targets [t0, t0 + bv.B) */
+int lscv_capture(mtfhip_batch *b);
+int lscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
+/* LSCV.cc:264-265: with once_per_frame the re-map runs only on the first iteration of a frame */
+static inline bool lscv_due(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_LSCV && !(b->lscv_once && !b->lscv_first_iter); }
 static inline BatchView fused_view(mtfhip_batch *b, FusedArgs &fa) {
 	fa.inline_warp = 0;
 	if (b->warps_dirty && b->B == 1) {

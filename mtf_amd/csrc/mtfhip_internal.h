@@ -598,5 +598,30 @@ void launch_rscv_hist(const BatchView &bv, const ImgView &im, const RscvArgs &a,
 /* It = map(It_orig) (the per-function route's updatePixVals) */
 void launch_rscv_apply(int N, int B, int nb, int linear, const double *map, const double *it_orig, double *It, hipStream_t st);
 
+/* ---- LSCV: the localized template re-map of LSCV::updateSimilarity (kernels_lscv.hip) ---- */
+constexpr int kLscvMaxBins = 256;
+/* LDS of a pass-1 workgroup: two u32 sums per (cell, template bin); the re-map's maps, n_sub x n_bins doubles, stay within it too.  The
+ * default dynamic-LDS limit: no kernel attribute raises it. */
+constexpr int kLscvLdsBudget = 64 * 1024;
+struct LscvArgs {
+	int nb, nx, ny, ncx, ncell;  /* n_bins, n_sub_regions_x / _y, cell columns, cells */
+	int from_it;                 /* 1: It from MTFHIP_BUF_IT (per-function path); 0: sampled at the current warp */
+	int affine, linear;          /* affine_mapping, weighted_mapping */
+	double norm_mult, norm_add;
+	const unsigned short *code;  /* [B][N] (int)I0_orig | (int)rint(I0_orig) << 8, clamped to [0, nb - 1] */
+	const double *i0o;           /* [B][N] I0_orig */
+	const unsigned short *cell;  /* [N] (one per batch) the pixel's cell, 0xffff outside every sub-region */
+	const int *crng;             /* [2 nx + 2 ny] (one per batch) sub-region idx: cells cx in [crng[2 idx], crng[2 idx + 1]]; then idy: cy */
+	const double *wts;           /* [nx ny][N] (one per batch) sub_region_wts, sub-region idy nx + idx */
+	const int *active;           /* optional [B] mask (device-side loop) */
+	unsigned *tot;               /* [B][2][ncell nb] per-target sums, zero between launches */
+	unsigned *arrive;            /* [B] arrival counters (0 between launches) */
+	double *map;                 /* [B][nx ny][nb] */
+	double *aff;                 /* [B][nx ny][2] (affine_mapping) */
+};
+int lscv_hist_blocks(int N);
+/* pass 1 and the maps (its last-arriving workgroup per target), then the re-map of I0; all per-target pointers offset to bv's first target */
+void launch_lscv_update(const BatchView &bv, const ImgView &im, const LscvArgs &a, double *I0, hipStream_t st);
+
 } // namespace mtfhip
 #endif

@@ -47,6 +47,8 @@ struct HipPair {
 	int jacobianBuffer(const MatrixXd &J, bool may_register, int preferred = -1);
 	void setSCV(int hist_type, bool weighted_mapping, bool mapped_gradient);   /* mtfhip_batch_set_scv (am = MTFHIP_AM_SCV) */
 	void setRSCV(bool use_bspl, bool weighted_mapping, bool mapped_gradient);  /* mtfhip_batch_set_rscv (am = MTFHIP_AM_RSCV) */
+	void setLSCV(int n_sub_regions_x, int n_sub_regions_y, int spacing_x, int spacing_y, bool affine_mapping, bool once_per_frame,
+		bool weighted_mapping);                                                /* mtfhip_batch_set_lscv (am = MTFHIP_AM_LSCV) */
 	int hessianBuffer(const MatrixXd &D, bool may_register);
 };
 
@@ -70,12 +72,21 @@ struct HipRSCVParams {
 	bool use_bspl = false; int n_bins = 256; double pre_seed = 0; bool partition_of_unity = false;
 	bool weighted_mapping = false; bool mapped_gradient = false; bool approx_dist_feat = true;
 };
+/* LSCVParams (AM/include/mtf/AM/LSCV.h), the reference's field names and class defaults (LSCV.cc:8-16).  n_bins <= 0 selects 256.
+ * pre_seed is accepted and ignored (updateSimilarity passes pre-seeds of 0, LSCV.cc:272-275), as are show_subregions (an OpenCV window)
+ * and approx_dist_feat (LSCVDist only). */
+struct HipLSCVParams {
+	int n_sub_regions_x = 3, n_sub_regions_y = 3; int spacing_x = 10, spacing_y = 10;
+	bool affine_mapping = false; bool once_per_frame = false; int n_bins = 256; double pre_seed = 0;
+	bool weighted_mapping = false; bool show_subregions = false; bool approx_dist_feat = false;
+};
 struct HipLink {
 	int am = MTFHIP_AM_SSD, ssm = MTFHIP_SSM_HOMOGRAPHY, resx = 50, resy = 50;   /* AMParams / SSMParams: resx, resy */
 	double grad_eps = 1e-8, likelihood_alpha = 1.0;                           /* AMParams::grad_eps; SSDParams / NCCParams / MIParams::likelihood_alpha */
 	int mi_n_bins = 8; double mi_pre_seed = 10; int mi_pou = 0;                /* MIParams */
 	HipSCVParams scv;                                                          /* am = MTFHIP_AM_SCV ("scv") */
 	HipRSCVParams rscv;                                                        /* am = MTFHIP_AM_RSCV ("rscv") */
+	HipLSCVParams lscv;                                                        /* am = MTFHIP_AM_LSCV ("lscv") */
 	int device = 0; void *stream = nullptr;
 	std::shared_ptr<HipPair> pair(int n_channels = 1) {
 		if (!p && am == MTFHIP_AM_SCV) {
@@ -87,6 +98,11 @@ struct HipLink {
 			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, rscv.n_bins, rscv.pre_seed, rscv.partition_of_unity ? 1 : 0,
 				device, stream, n_channels);
 			p->setRSCV(rscv.use_bspl, rscv.weighted_mapping, rscv.mapped_gradient);
+		}
+		if (!p && am == MTFHIP_AM_LSCV) {
+			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, lscv.n_bins, lscv.pre_seed, 0, device, stream, n_channels);
+			p->setLSCV(lscv.n_sub_regions_x, lscv.n_sub_regions_y, lscv.spacing_x, lscv.spacing_y, lscv.affine_mapping, lscv.once_per_frame,
+				lscv.weighted_mapping);
 		}
 		if (!p) p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, device, stream, n_channels);
 		else if (n_channels > 1 && n_channels != p->n_channels)   /* (SearchMethod<AM, SSM> constructs the AM first: it fixes the channel count) */
@@ -168,6 +184,7 @@ public:
 		const MatrixXd &d2It_dpssm2) override;
 	void cmptMeanOf(MatrixXd &mean, const MatrixXd &a, const MatrixXd &b) override;
 	void setFirstIter() override;
+	void clearFirstIter() override;
 	void clearInitStatus() override {}
 private:
 	double learning_rate = 0.5;

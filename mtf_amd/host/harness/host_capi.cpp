@@ -83,6 +83,20 @@ mtfhost_tracker *mtfhost_create_rscv(int sm, int ssm, int resx, int resy, int ma
 		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
 	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
+/* the same tracker with HipAM("lscv"): its LSCVParams through the HipLink */
+mtfhost_tracker *mtfhost_create_lscv(int sm, int ssm, int resx, int resy, int max_iters, double epsilon, int jac_type, int hess_type, int chained_warp,
+	int leven_marq, double lm_delta_init, double lm_delta_update, int device, int n_sub_regions_x, int n_sub_regions_y, int spacing_x, int spacing_y,
+	int affine_mapping, int once_per_frame, int n_bins, int weighted_mapping) {
+	try {
+		auto link = std::make_shared<hip::HipLink>();
+		link->am = MTFHIP_AM_LSCV; link->ssm = ssm; link->resx = resx; link->resy = resy; link->device = device;
+		link->lscv.n_sub_regions_x = n_sub_regions_x; link->lscv.n_sub_regions_y = n_sub_regions_y;
+		link->lscv.spacing_x = spacing_x; link->lscv.spacing_y = spacing_y;
+		link->lscv.affine_mapping = affine_mapping != 0; link->lscv.once_per_frame = once_per_frame != 0;
+		link->lscv.n_bins = n_bins; link->lscv.weighted_mapping = weighted_mapping != 0;
+		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
+	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
 void mtfhost_destroy(mtfhost_tracker *t) { delete t; }
 /* ESM / FC / IC_ENABLE_LEARNING + the AM's learning_rate: am->updateModel(ssm->getPts()) at the end of every update() */
 int mtfhost_set_learning(mtfhost_tracker *t, int enable, double learning_rate) {

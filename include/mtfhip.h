@@ -52,7 +52,11 @@ typedef enum mtfhip_status {
 /* MTFHIP_AM_LSCV: Localized SCV (AM/src/LSCV.cc), an SSD whose template is re-mapped through one E[It | I0] per overlapping sub-region,
  * blended with per-pixel weights, before a similarity update (LSCV::updateSimilarity, LSCV.cc:263-304); single channel, first-order
  * Hessians, the per-function entry points and the fused init_template / iterate / track / track_region (mtfhip_batch_set_lscv below) */
-enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5 };
+/* MTFHIP_AM_LRSCV: Localized Reversed SCV (AM/src/LRSCV.cc), an SSD whose current patch is re-mapped through one E[I0 | It] per
+ * overlapping sub-region, blended with per-pixel weights, after a sampling (LRSCV::updatePixVals, LRSCV.cc:224-261); single channel,
+ * first-order Hessians, the per-function entry points and the fused init_template / iterate / track / track_region
+ * (mtfhip_batch_set_lrscv below) */
+enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6 };
 enum { MTFHIP_SSM_HOMOGRAPHY = 0, MTFHIP_SSM_AFFINE = 1 };
 enum { MTFHIP_SM_ESM = 0, MTFHIP_SM_FCLK = 1, MTFHIP_SM_ICLK = 2 };
 /* pixel-Jacobian variants of StateSpaceModel.h:170-181 */
@@ -92,7 +96,7 @@ typedef struct mtfhip_patch_desc {
 	int resx, resy;         /* ImgParams / SSMParams resx, resy */
 	double grad_eps;        /* ImgParams::grad_eps (1e-8, AM/include/mtf/AM/ImageBase.h:7-8) */
 	double likelihood_alpha;/* AMParams::likelihood_alpha */
-	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV / MTFHIP_AM_RSCV / MTFHIP_AM_LSCV: SCVParams / RSCVParams / LSCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as they do */
+	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV / _RSCV / _LSCV / _LRSCV: SCVParams / RSCVParams / LSCVParams / LRSCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as they do */
 	double mi_pre_seed;     /* MIParams::pre_seed */
 	int mi_partition_of_unity;
 	double hess_eps;        /* ImgParams::hess_eps (1, AM/include/mtf/AM/ImageBase.h:9); <= 0 selects that default */
@@ -599,11 +603,23 @@ int mtfhip_batch_set_lscv(mtfhip_batch *b, int n_sub_regions_x, int n_sub_region
  * (map[b] = b before the first one) */
 int mtfhip_batch_lscv_intensity_maps(mtfhip_batch *b, double *dst);
 /* AppearanceModel::first_iter (setFirstIter / clearFirstIter), one flag per batch, clear on a fresh batch.  With once_per_frame, LSCV
- * re-maps only while it is set: on the per-function update_similarity and on mtfhip_batch_iterate.  mtfhip_batch_track sets it for its
- * first pass and leaves it clear when it ran at least one iteration (the reference leaves it set for a target that converges in its
- * first iteration).  Other appearance models ignore it. */
+ * re-maps only while it is set: on the per-function update_similarity and on mtfhip_batch_iterate; LRSCV maps the current patch only
+ * while it is set (on update_pix_vals and mtfhip_batch_iterate), and otherwise leaves it raw, as the reference returns early
+ * (LRSCV.cc:234-235).  mtfhip_batch_track sets it for its first pass and leaves it clear when it ran at least one iteration (the
+ * reference leaves it set for a target that converges in its first iteration).  Other appearance models ignore it. */
 int mtfhip_batch_set_first_iter(mtfhip_batch *b, int on);
 int mtfhip_batch_first_iter(const mtfhip_batch *b);
+
+/* ---- LRSCV (MTFHIP_AM_LRSCV) ---- */
+/* LRSCVParams sub_regions_x / _y, spacing_x / _y, affine_mapping, once_per_frame, weighted_mapping; call before init_template.
+ * Defaults: the class defaults (3 x 3 sub-regions, spacing 10 x 10, no affine mapping, a map at every updatePixVals, nearest mapping).
+ * A sub-region size resx - (n_sub_regions_x - 1) spacing_x (or in y) <= 0 returns MTFHIP_ERR_INVALID_ARG, as the reference throws; a
+ * configuration whose pass-1 table or maps exceed the LDS budget returns MTFHIP_ERR_NOT_IMPLEMENTED at init_template. */
+int mtfhip_batch_set_lrscv(mtfhip_batch *b, int n_sub_regions_x, int n_sub_regions_y, int spacing_x, int spacing_y, int affine_mapping,
+	int once_per_frame, int weighted_mapping);
+/* the intensity maps of every target after its last map: B x (n_sub_regions_x n_sub_regions_y) x n_bins, sub-region idy n_x + idx
+ * (map[b] = b before the first one) */
+int mtfhip_batch_lrscv_intensity_maps(mtfhip_batch *b, double *dst);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTFHIP_LIB", os.path.join(_HERE, "libmtfhip.so"))
 CSRC = os.path.join(_HERE, "csrc")
 
-AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV = 0, 1, 2, 3, 4, 5
+AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV, AM_LRSCV = 0, 1, 2, 3, 4, 5, 6
 SCV_HIST_DIRAC, SCV_HIST_BILINEAR, SCV_HIST_BSPLINE = 0, 1, 2
 SSM_HOMOGRAPHY, SSM_AFFINE = 0, 1
 SM_ESM, SM_FCLK, SM_ICLK = 0, 1, 2
@@ -122,7 +122,7 @@ SYMBOLS = [
     "mtfhip_timing_enable", "mtfhip_timing_reset", "mtfhip_timing_get", "mtfhip_timing_get_busy", "mtfhip_ssm_estimate_state_sigma", "mtfhip_batch_track_queues", "mtfhip_batch_inline_warp",
     "mtfhip_batch_grid_regen", "mtfhip_batch_set_scv", "mtfhip_batch_scv_intensity_map", "mtfhip_batch_set_rscv",
     "mtfhip_batch_rscv_intensity_map", "mtfhip_batch_set_lscv", "mtfhip_batch_lscv_intensity_maps", "mtfhip_batch_set_first_iter",
-    "mtfhip_batch_first_iter",
+    "mtfhip_batch_first_iter", "mtfhip_batch_set_lrscv", "mtfhip_batch_lrscv_intensity_maps",
 ]
 
 
@@ -211,6 +211,8 @@ def lib():
         L.mtfhip_batch_lscv_intensity_maps.argtypes = [C.c_void_p, C.c_void_p]
         L.mtfhip_batch_set_first_iter.argtypes = [C.c_void_p, C.c_int]
         L.mtfhip_batch_first_iter.argtypes = [C.c_void_p]
+        L.mtfhip_batch_set_lrscv.argtypes = [C.c_void_p] + [C.c_int] * 7
+        L.mtfhip_batch_lrscv_intensity_maps.argtypes = [C.c_void_p, C.c_void_p]
         L.mtfhip_ssm_estimate_state_sigma.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.mtfhip_pf_set_distributions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mtfhip_pf_set_distr_draws.argtypes = [C.c_void_p, C.c_void_p]

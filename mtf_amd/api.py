@@ -525,8 +525,25 @@ class Batch:
         L.check(L.lib().mtfhip_batch_lscv_intensity_maps(self._h, _p(out)))
         return out
 
+    def set_lrscv(self, n_sub_regions_x=3, n_sub_regions_y=3, spacing_x=10, spacing_y=10, affine_mapping=0, once_per_frame=0,
+                  weighted_mapping=0):
+        """LRSCVParams of an AM_LRSCV batch, before init_template; the defaults are the reference's class defaults (3 x 3 sub-regions,
+        spacing 10, nearest mapping, a map at every updatePixVals) (mtfhip_batch_set_lrscv)"""
+        L.check(L.lib().mtfhip_batch_set_lrscv(self._h, int(n_sub_regions_x), int(n_sub_regions_y), int(spacing_x), int(spacing_y),
+                                               int(affine_mapping), int(once_per_frame), int(weighted_mapping)))
+        self._lscv_sub = int(n_sub_regions_x) * int(n_sub_regions_y)
+
+    def lrscv_intensity_maps(self):
+        """B x n_sub x n_bins: each target's LRSCV intensity maps after its last map, sub-region idy * n_x + idx
+        (mtfhip_batch_lrscv_intensity_maps)"""
+        nb = self.desc.mi_n_bins if self.desc.mi_n_bins > 0 else 256
+        out = np.empty((self.B, getattr(self, "_lscv_sub", 9), nb))
+        L.check(L.lib().mtfhip_batch_lrscv_intensity_maps(self._h, _p(out)))
+        return out
+
     def set_first_iter(self, on=True):
-        """AppearanceModel::setFirstIter / clearFirstIter: with once_per_frame, LSCV re-maps only while it is set (mtfhip_batch_set_first_iter)"""
+        """AppearanceModel::setFirstIter / clearFirstIter: with once_per_frame, LSCV re-maps and LRSCV maps only while it is set
+        (mtfhip_batch_set_first_iter)"""
         L.check(L.lib().mtfhip_batch_set_first_iter(self._h, 1 if on else 0))
 
     def first_iter(self):

@@ -28,6 +28,7 @@ int mtfhip_am_initialize_pix_vals(mtfhip_batch *b, const double *pts) {
 	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_capture(b));   /* SCV::initializePixVals: I0_orig = I0 (SCV.cc:166) */
 	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_capture(b));   /* RSCV::initializePixVals (RSCV.cc:124-168) */
 	if (b->desc.am == MTFHIP_AM_LSCV) TRY(lscv_capture(b));   /* LSCV::initializePixVals: I0_orig = I0 (LSCV.cc:232) */
+	if (b->desc.am == MTFHIP_AM_LRSCV) TRY(lrscv_capture(b));   /* LRSCV::initializePixVals (LRSCV.cc:197-222) */
 	return MTFHIP_OK;
 }
 /* SSD::updateModel AM/src/SSD.cc:49-75, NCC::updateModel AM/src/NCC.cc:539-566 (the search methods call it at the end of update()
@@ -40,6 +41,7 @@ int mtfhip_am_update_model(mtfhip_batch *b, const double *pts, double learning_r
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: SCV is not available on this entry point (the template update would have to refresh I0_orig)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: RSCV is not available on this entry point (the template update would have to refresh its code plane)");
 	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LSCV is not available on this entry point (the template update would have to refresh I0_orig)");
+	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LRSCV is not available on this entry point (the template update would have to refresh its code plane)");
 	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: appearance model %d", b->desc.am);
 	TRY(single_channel(b, "update_model"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "update_model before initializePixVals");
@@ -68,6 +70,7 @@ static int do_update_pix_vals(mtfhip_batch *b, const double *pts) {
 	const double *dp;
 	TRY(resolve_pts(b, pts, MTFHIP_BUF_CURR_PTS, 2 * (size_t)b->NP, &dp));
 	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_update_pix_vals(b, dp));   /* RSCV::updatePixVals: It = map(It_orig) (RSCV.cc:170-238) */
+	else if (b->desc.am == MTFHIP_AM_LRSCV) TRY(lrscv_update_pix_vals(b, dp));   /* LRSCV::updatePixVals (LRSCV.cc:224-261) */
 	else {
 		TimedScope ts(b->ctx, "sample");
 		launch_sample(b->view(), b->ctx->img, dp, b->buf[MTFHIP_BUF_IT], b->norm_mult, b->norm_add, b->ctx->stream);

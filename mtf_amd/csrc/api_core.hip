@@ -363,7 +363,11 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	/* the fused kernel addresses a target's arrays with 32-bit byte offsets (ld_off / st_off): 8 columns of N doubles */
 	if ((double)d->resx * d->resy * 3.0 >= (double)(1u << 26)) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: %dx%d sample points per target exceed the 2^26-row limit", d->resx, d->resy);
 	if (d->grad_eps <= 0 || d->hess_eps < 0) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: grad_eps must be positive (got %g)", d->grad_eps);
-	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am == MTFHIP_AM_LRSCV && (d->mi_n_bins > kLscvMaxBins || d->mi_n_bins == 1))
+		return fail(MTFHIP_ERR_INVALID_ARG, "LRSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kLscvMaxBins);
+	if (d->am == MTFHIP_AM_LRSCV && d->n_channels == 3)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "LRSCV with n_channels 3 is not available (no multi-channel LRSCV exists in the reference either)");
 	if (d->am == MTFHIP_AM_LSCV && (d->mi_n_bins > kLscvMaxBins || d->mi_n_bins == 1))
 		return fail(MTFHIP_ERR_INVALID_ARG, "LSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kLscvMaxBins);
 	if (d->am == MTFHIP_AM_LSCV && d->n_channels == 3)
@@ -408,9 +412,9 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		b->norm_mult = (b->rscv_nb - 1.0) / (255.0 - 0.0);
 		b->norm_add = 0;
 	}
-	if (d->am == MTFHIP_AM_LSCV) {
+	if (d->am == MTFHIP_AM_LSCV || d->am == MTFHIP_AM_LRSCV) {
 		/* LSCVParams: n_bins <= 0 selects LSCV_N_BINS = 256 (LSCV.cc:8, :39-40); LSCV ctor LSCV.cc:120-135: [0, n_bins - 1] over
-		 * PIX_MAX - PIX_MIN = 255, as SCV */
+		 * PIX_MAX - PIX_MIN = 255, as SCV.  LRSCVParams / LRSCV ctor the same (LRSCV.cc:37-38, :97-110) */
 		b->lscv_nb = d->mi_n_bins <= 0 ? kLscvMaxBins : d->mi_n_bins;
 		b->norm_mult = (b->lscv_nb - 1.0) / (255.0 - 0.0);
 		b->norm_add = 0;
@@ -497,8 +501,8 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		b->inline_warp_ok = b->B == 1 && !(iw_env && iw_env[0] == '0') && kernarg_layout_verified(c->stream);
 		const char *lazy_env = std::getenv("MTFHIP_LAZY");
 		/* SSD and NCC have a fused kernel each; MI has its fused passes */
-		/* (SCV / LSCV: every similarity update re-maps the template first; RSCV: every updatePixVals maps the current patch -- their
-		 * calls run as they come) */
+		/* (SCV / LSCV: every similarity update re-maps the template first; RSCV / LRSCV: every updatePixVals maps the current patch --
+		 * their calls run as they come) */
 		b->lz.enabled = (d->am == MTFHIP_AM_SSD || d->am == MTFHIP_AM_NCC || d->am == MTFHIP_AM_MI) && b->C == 1 &&
 			!(lazy_env && lazy_env[0] == '0');
 	}

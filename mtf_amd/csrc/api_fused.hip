@@ -893,10 +893,14 @@ int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, d
 	/* RSCV::updatePixVals: the intensity map of the current patch at the current warp, applied by the fused pass to every sample */
 	RscvMap rm;
 	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_enqueue(b, b->view(), 0, nullptr, fa, b->ctx->stream, &rm));
+	/* LRSCV::updatePixVals: unless once_per_frame and not the first iteration, the sub-region maps of the current patch, blended into
+	 * every sample by the fused pass; otherwise the SSD pass on the raw patch */
+	LrscvMap lm;
+	if (lrscv_due(b)) TRY(lrscv_enqueue(b, b->view(), 0, nullptr, fa, b->ctx->stream, &lm));
 	int nblk = fused_blocks_per_target(b->N, b->B);
 	{
 		TimedScope ts(b->ctx, "fused_lk");
-		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream, &rm);
+		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream, &rm, &lm);
 	}
 	b->it_valid = fa.materialize;
 	b->dit_valid = fa.materialize && fa.mode != 2;
@@ -1049,10 +1053,10 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 }
 /* the rest of a loop the persistent launch left unfinished: the slab on the device is current (warps, flags, iteration counts) */
 static int track_resume(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) { return track_core(b, sm, n_iters, corners, true, true); }
-/* LSCV: update() sets first_iter in front of its loop and every completed iteration clears it (NT/ESM.cc:178, :291): the device loop
- * re-maps in front of its first pass (track_core) and leaves the batch's flag clear */
+/* LSCV / LRSCV: update() sets first_iter in front of its loop and every completed iteration clears it (NT/ESM.cc:178, :291): the device
+ * loop maps in front of its first pass (track_core) and leaves the batch's flag clear */
 static int lscv_after_track(mtfhip_batch *b, int rc) {
-	if (rc == MTFHIP_OK && b && b->desc.am == MTFHIP_AM_LSCV) b->lscv_first_iter = 0;
+	if (rc == MTFHIP_OK && b && (b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV)) b->lscv_first_iter = 0;
 	return rc;
 }
 int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) { return lscv_after_track(b, track_core(b, sm, n_iters, corners, false)); }
@@ -1369,8 +1373,9 @@ static int track_validate(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "track before init_template");
 	/* (a rejected Levenberg-Marquardt step of FCLK repeats a pass within one iteration of its while loop: the passes do not tell which
 	 * iteration is the first) */
-	if (b->desc.am == MTFHIP_AM_LSCV && b->lscv_once && sm->leven_marq && sm->sm == MTFHIP_SM_FCLK)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "track: LSCV once_per_frame with Levenberg-Marquardt FCLK is not available on the device loop (use the per-function entry points)");
+	if ((b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV) && b->lscv_once && sm->leven_marq && sm->sm == MTFHIP_SM_FCLK)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "track: %s once_per_frame with Levenberg-Marquardt FCLK is not available on the device loop (use the per-function entry points)",
+			intensity_mapped_name(b));
 	return need_image(b);
 }
 static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners, bool slab_uploaded, bool resume, bool region_mode) {
@@ -1651,9 +1656,13 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 					if (b->desc.am == MTFHIP_AM_LSCV && (!b->lscv_once || it == 0)) TRY(lscv_enqueue(b, r.bc, r.t0, r.fc.active, 0, r.s));
 					RscvMap rm;
 					if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &rm));   /* (the chunk's current maps) */
+					/* (LRSCV: the chunk's sub-region maps -- with once_per_frame in front of the first pass only, LRSCV.cc:234-235; the later
+					 * passes are SSD passes on the raw patch) */
+					LrscvMap lm;
+					if (b->desc.am == MTFHIP_AM_LRSCV && (!b->lscv_once || it == 0)) TRY(lrscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &lm));
 					{
 						TimedScope tsc(b->ctx, "fused_lk", r.s);
-						launch_fused_ssd(r.bc, b->ctx->img, r.fc, r.part, r.nblk_c, r.s, &rm);
+						launch_fused_ssd(r.bc, b->ctx->img, r.fc, r.part, r.nblk_c, r.s, &rm, &lm);
 					}
 					if (so_term >= 0) {
 						TimedScope tsc(b->ctx, "second_order", r.s);
@@ -1819,6 +1828,7 @@ int mtfhip_score_candidates_dev(mtfhip_batch *b, const double *dev_states, int C
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: SCV candidates are not available (SCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: RSCV candidates are not available (RSCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: LSCV candidates are not available (LSCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "score_candidates: LRSCV candidates are not available (its maps are per-candidate intensity maps)");
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "score_candidates before the template was initialised");
 	TRY(need_image(b));
 	TimedScope ts(b->ctx, "score_candidates");
@@ -1854,6 +1864,7 @@ int mtfhip_sample_candidates_dev(mtfhip_batch *b, const double *dev_states, int 
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: SCV distance features are not available (SCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: RSCV distance features are not available (RSCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: LSCV distance features are not available (LSCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: LRSCV distance features are not available (its maps are per-candidate intensity maps)");
 	TRY(single_channel(b, "sample_candidates"));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "sample_candidates before set_corners");
 	TRY(need_image(b));
@@ -1890,6 +1901,7 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: SCV is not available on the NN dataset (SCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: RSCV is not available on the NN dataset (RSCVDist is a per-candidate intensity map)");
 	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: LSCV is not available on the NN dataset (LSCVDist is a per-candidate intensity map)");
+	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: LRSCV is not available on the NN dataset (its maps are per-candidate intensity maps)");
 	if (d->n_samples <= 0 || row_lo < 0 || row_count < 0 || row_lo + row_count > d->n_samples)
 		return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: rows [%d, %d) of %d samples", row_lo, row_lo + row_count, d->n_samples);
 	if (d->additive_update) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: additive_update (NNParams, NT/NN.cc:150-152): the compositional form only");

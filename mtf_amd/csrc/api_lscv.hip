@@ -14,14 +14,15 @@
 
 #include <climits>
 
-/* the sub-region extents of LSCV.cc:146-167 and the reference's refusal */
-static int lscv_check_geometry(const mtfhip_batch *b, int nx, int ny, int sx, int sy, const char *fn) {
-	if (nx < 1 || ny < 1) return fail(MTFHIP_ERR_INVALID_ARG, "%s: LSCV needs at least one sub-region per axis (got %d x %d)", fn, nx, ny);
-	if (sx < 0 || sy < 0) return fail(MTFHIP_ERR_INVALID_ARG, "%s: LSCV sub-region spacing must not be negative (got %d x %d)", fn, sx, sy);
+/* the sub-region extents of LSCV.cc:146-167 (LRSCV.cc:122-147) and the reference's refusal */
+int lscv_check_geometry(const mtfhip_batch *b, int nx, int ny, int sx, int sy, const char *fn) {
+	const char *am = intensity_mapped_name(b);
+	if (nx < 1 || ny < 1) return fail(MTFHIP_ERR_INVALID_ARG, "%s: %s needs at least one sub-region per axis (got %d x %d)", fn, am, nx, ny);
+	if (sx < 0 || sy < 0) return fail(MTFHIP_ERR_INVALID_ARG, "%s: %s sub-region spacing must not be negative (got %d x %d)", fn, am, sx, sy);
 	const long long size_x = (long long)b->desc.resx - (long long)(nx - 1) * sx, size_y = (long long)b->desc.resy - (long long)(ny - 1) * sy;
 	if (size_x <= 0 || size_y <= 0)
-		return fail(MTFHIP_ERR_INVALID_ARG, "LSCV :: Patch size : %dx%d is not enough to use the specified region spacing and / or count", b->desc.resx,
-			b->desc.resy);
+		return fail(MTFHIP_ERR_INVALID_ARG, "%s :: Patch size : %dx%d is not enough to use the specified region spacing and / or count", am,
+			b->desc.resx, b->desc.resy);
 	return MTFHIP_OK;
 }
 
@@ -45,24 +46,23 @@ static int lscv_axis_cells(int res, int n, int spacing, std::vector<int> &cell, 
 	return nc;
 }
 
-int lscv_capture(mtfhip_batch *b) {
+int lscv_geometry(mtfhip_batch *b, size_t map_lds_budget) {
 	const int nx = b->lscv_nx, ny = b->lscv_ny, R = nx * ny, resx = b->desc.resx, resy = b->desc.resy;
+	const char *am = intensity_mapped_name(b);
 	TRY(lscv_check_geometry(b, nx, ny, b->lscv_sx, b->lscv_sy, "init_template"));
 	std::vector<int> cx, cy, rx, ry;
 	const int ncx = lscv_axis_cells(resx, nx, b->lscv_sx, cx, rx), ncy = lscv_axis_cells(resy, ny, b->lscv_sy, cy, ry);
 	const size_t B = (size_t)b->B, N = (size_t)b->N, nb = (size_t)b->lscv_nb, ncell = (size_t)ncx * ncy;
-	if (ncell >= 0xffff) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "init_template: LSCV with %zu sub-region cells (at most 65534)", ncell);
+	if (ncell >= 0xffff) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "init_template: %s with %zu sub-region cells (at most 65534)", am, ncell);
 	const size_t lds_hist = 2 * sizeof(unsigned) * ncell * nb, lds_map = sizeof(double) * (size_t)R * nb;
-	if (lds_hist > (size_t)kLscvLdsBudget - 64 || lds_map > (size_t)kLscvLdsBudget)
+	if (lds_hist > (size_t)kLscvLdsBudget - 64 || lds_map > map_lds_budget)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED,
-			"init_template: LSCV with %d x %d sub-regions (%zu cells) at %zu bins needs %zu B of LDS for its histograms and %zu B for its maps "
-			"(the limit is %d B per workgroup)", nx, ny, ncell, nb, lds_hist, lds_map, kLscvLdsBudget - 64);
+			"init_template: %s with %d x %d sub-regions (%zu cells) at %zu bins needs %zu B of LDS for its histograms and %zu B for its maps "
+			"(the limits are %d B and %zu B per workgroup)", am, nx, ny, ncell, nb, lds_hist, lds_map, kLscvLdsBudget - 64, map_lds_budget);
 	if ((double)(nb - 1) * (double)N >= 4294967296.0)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "init_template: LSCV with %zu sample points at %zu bins could overflow its u32 histogram sums", N, nb);
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "init_template: %s with %zu sample points at %zu bins could overflow its u32 histogram sums", am, N, nb);
 	hipStream_t st = b->ctx->stream;
-	if (!b->d_lscv_i0) {
-		HIP_TRY(hipMalloc(&b->d_lscv_i0, sizeof(double) * N * B));
-		HIP_TRY(hipMalloc(&b->d_lscv_code, sizeof(unsigned short) * N * B));
+	if (!b->d_lscv_cell) {
 		HIP_TRY(hipMalloc(&b->d_lscv_cell, sizeof(unsigned short) * N));
 		HIP_TRY(hipMalloc(&b->d_lscv_crng, sizeof(int) * 2 * (nx + ny)));
 		HIP_TRY(hipMalloc(&b->d_lscv_w, sizeof(double) * (size_t)R * N));
@@ -74,9 +74,6 @@ int lscv_capture(mtfhip_batch *b) {
 		HIP_TRY(hipMemsetAsync(b->d_lscv_arrive, 0, sizeof(unsigned) * B, st));
 	}
 	b->lscv_ncx = ncx; b->lscv_ncell = (int)ncell;
-	/* I0_orig = I0 (LSCV.cc:232) and its bins */
-	HIP_TRY(hipMemcpyAsync(b->d_lscv_i0, b->buf[MTFHIP_BUF_I0], sizeof(double) * N * B, hipMemcpyDeviceToDevice, st));
-	launch_scv_codes(b->N, b->B, b->lscv_nb, b->d_lscv_i0, b->d_lscv_code, st);
 	/* pixel i at (i % resx, i / resx): its cell, and sub_region_wts (LSCV.cc:170-197), computed as the reference does -- the centre
 	 * (start + end) / 2.0, the difference truncated toward zero, 1 / (1 + dx^2 + dy^2), each row divided by its sum taken idy outer,
 	 * idx inner */
@@ -113,6 +110,20 @@ int lscv_capture(mtfhip_batch *b) {
 	return MTFHIP_OK;
 }
 
+int lscv_capture(mtfhip_batch *b) {
+	TRY(lscv_geometry(b, (size_t)kLscvLdsBudget));
+	const size_t B = (size_t)b->B, N = (size_t)b->N;
+	hipStream_t st = b->ctx->stream;
+	if (!b->d_lscv_i0) {
+		HIP_TRY(hipMalloc(&b->d_lscv_i0, sizeof(double) * N * B));
+		HIP_TRY(hipMalloc(&b->d_lscv_code, sizeof(unsigned short) * N * B));
+	}
+	/* I0_orig = I0 (LSCV.cc:232) and its bins */
+	HIP_TRY(hipMemcpyAsync(b->d_lscv_i0, b->buf[MTFHIP_BUF_I0], sizeof(double) * N * B, hipMemcpyDeviceToDevice, st));
+	launch_scv_codes(b->N, b->B, b->lscv_nb, b->d_lscv_i0, b->d_lscv_code, st);
+	return MTFHIP_OK;
+}
+
 int lscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st) {
 	if (!b->d_lscv_i0) return fail(MTFHIP_ERR_LOGIC, "lscv :: updateSimilarity before initializePixVals");
 	const size_t N = (size_t)b->N, nb = (size_t)b->lscv_nb, R = (size_t)b->lscv_nx * b->lscv_ny, E = (size_t)b->lscv_ncell * nb;
@@ -142,7 +153,7 @@ int mtfhip_batch_set_lscv(mtfhip_batch *b, int n_sub_regions_x, int n_sub_region
 	int once_per_frame, int weighted_mapping) {
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "set_lscv: NULL batch");
 	if (b->desc.am != MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_INVALID_ARG, "set_lscv: the batch's appearance model is %d, not LSCV", b->desc.am);
-	if (b->d_lscv_i0) return fail(MTFHIP_ERR_LOGIC, "set_lscv: call it before init_template (the sub-region geometry is fixed there)");
+	if (b->d_lscv_cell) return fail(MTFHIP_ERR_LOGIC, "set_lscv: call it before init_template (the sub-region geometry is fixed there)");
 	if ((affine_mapping != 0 && affine_mapping != 1) || (once_per_frame != 0 && once_per_frame != 1) || (weighted_mapping != 0 && weighted_mapping != 1))
 		return fail(MTFHIP_ERR_INVALID_ARG, "set_lscv: affine_mapping, once_per_frame and weighted_mapping must be 0 or 1 (got %d, %d, %d)", affine_mapping,
 			once_per_frame, weighted_mapping);

@@ -34,7 +34,7 @@ int rscv_capture(mtfhip_batch *b) {
 }
 
 /* the It_orig expression of the fused launch fa selects (launch_fused_rscv, kernels_fused_rscv.hip) */
-static int rscv_it_kind(const FusedArgs *fa) {
+int rscv_it_kind(const FusedArgs *fa) {
 	if (!fa) return RSCV_IT_FROM_BUF;
 	if (!(fa->fast_math && !fa->materialize)) return RSCV_IT_REPLAY;
 	if (fa->mode == 2) return RSCV_IT_FAST_ICLK;

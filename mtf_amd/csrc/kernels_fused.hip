@@ -110,11 +110,14 @@ static void launch_fused_fast(const BatchView &bv, const ImgView &im, const Fuse
 	else MTFHIP_LAUNCH((k_fused_fast<AM, SSM, 1, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
 }
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	hipStream_t st, const RscvMap *rm) {
+	hipStream_t st, const RscvMap *rm, const LrscvMap *lm) {
 	if (bv.am == MTFHIP_AM_RSCV) {   /* (the API enqueues RSCV's pass 1 in front and hands its maps over: no map, no launch) */
 		if (rm && rm->map) launch_fused_rscv(bv, im, fa, partials, nblk, *rm, st);
 		return;
 	}
+	/* (LRSCV: with the maps of a pass 1 enqueued in front, the blend; without -- a later pass of a frame under once_per_frame -- an SSD
+	 * pass on the raw patch, LRSCV.cc:234-235) */
+	if (bv.am == MTFHIP_AM_LRSCV && lm && lm->map) { launch_fused_lrscv(bv, im, fa, partials, nblk, *lm, st); return; }
 	const bool hom = bv.ssm == MTFHIP_SSM_HOMOGRAPHY;
 	if (bv.C > 1) { launch_fused_mc(bv, im, fa, partials, nblk, st); return; }   /* MCSSD / MCNCC */
 	if (fa.fast_math && !fa.materialize) {

@@ -251,6 +251,8 @@ struct mtfhip_batch {
 	unsigned char *d_rscv_code = nullptr;
 	unsigned *d_rscv_part = nullptr, *d_rscv_arrive = nullptr;
 	double *d_rscv_map = nullptr, *d_rscv_it = nullptr;
+	/* (LRSCV, am = MTFHIP_AM_LRSCV, uses RSCV's code plane and It_orig buffer, and LSCV's configuration, first-iteration flag, geometry,
+	 * sums, arrival counters, maps and affine parameters: api_lrscv.hip) */
 	/* LSCV (am = MTFHIP_AM_LSCV): LSCVParams n_sub_regions_x / _y, spacing_x / _y, affine_mapping, once_per_frame, weighted_mapping,
 	 * n_bins; AppearanceModel::first_iter (one per batch); I0_orig and its code plane; the sub-region geometry (the cell plane, the cells of
 	 * each sub-region, the weights: one copy per batch); the per-target sums and arrival counters, the maps and the affine parameters
@@ -435,15 +437,16 @@ static int push_warps(mtfhip_batch *b) {
 /* the BatchView of a fused launch: a stale single-target warp goes into the kernel arguments instead of being uploaded */
 /* SCV is SSD on its re-mapped template, RSCV SSD on its mapped current patch: every SSD branch of the entry points serves them */
 static inline bool ssd_like(const mtfhip_batch *b) {
-	return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV;
+	return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV ||
+		b->desc.am == MTFHIP_AM_LRSCV;
 }
 /* SCV and RSCV: an intensity map is rebuilt between the fused passes -- the one-launch, persistent and step loops do not take them */
 static inline bool intensity_mapped(const mtfhip_batch *b) {
-	return b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV;
+	return b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV;
 }
 /* the name of an intensity-mapped model, for the refusals */
 static inline const char *intensity_mapped_name(const mtfhip_batch *b) {
-	return b->desc.am == MTFHIP_AM_SCV ? "SCV" : (b->desc.am == MTFHIP_AM_RSCV ? "RSCV" : "LSCV");
+	return b->desc.am == MTFHIP_AM_SCV ? "SCV" : (b->desc.am == MTFHIP_AM_RSCV ? "RSCV" : (b->desc.am == MTFHIP_AM_LSCV ? "LSCV" : "LRSCV"));
 }
 /* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
 int scv_capture(mtfhip_batch *b);
@@ -455,12 +458,26 @@ int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess);
 int rscv_capture(mtfhip_batch *b);
 int rscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, const FusedArgs &fa, hipStream_t st, RscvMap *rm);
 int rscv_update_pix_vals(mtfhip_batch *b, const double *dp);
+/* the It_orig expression (RSCV_IT_*) of the fused launch fa selects; RSCV_IT_FROM_BUF without one (the per-function route) */
+int rscv_it_kind(const FusedArgs *fa);
 /* api_lscv.hip: I0_orig, its code plane and the sub-region geometry (initializePixVals); the localized re-map of I0 in front of an SSD
  * similarity update, for the targets [t0, t0 + bv.B) */
 int lscv_capture(mtfhip_batch *b);
 int lscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
 /* LSCV.cc:264-265: with once_per_frame the re-map runs only on the first iteration of a frame */
 static inline bool lscv_due(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_LSCV && !(b->lscv_once && !b->lscv_first_iter); }
+/* the sub-region geometry shared by LSCV and LRSCV: the reference's size refusal (fn: the entry point), and at initializePixVals the cell
+ * plane, the cells of each sub-region, the weights, the sums, the identity maps -- refused when the pass-1 table or the maps
+ * (map_lds_budget) exceed their LDS */
+int lscv_check_geometry(const mtfhip_batch *b, int nx, int ny, int sx, int sy, const char *fn);
+int lscv_geometry(mtfhip_batch *b, size_t map_lds_budget);
+/* api_lrscv.hip: the code plane, It_orig and the geometry (initializePixVals); pass 1 + the maps in front of the fused launch fa for the
+ * targets [t0, t0 + bv.B), and the blend that launch applies (lm); the per-function updatePixVals (It, or the blend of It_orig) */
+int lrscv_capture(mtfhip_batch *b);
+int lrscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, const FusedArgs &fa, hipStream_t st, LrscvMap *lm);
+int lrscv_update_pix_vals(mtfhip_batch *b, const double *dp);
+/* LRSCV.cc:234-235: with once_per_frame the current patch is mapped only on the first iteration of a frame */
+static inline bool lrscv_due(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_LRSCV && !(b->lscv_once && !b->lscv_first_iter); }
 static inline BatchView fused_view(mtfhip_batch *b, FusedArgs &fa) {
 	fa.inline_warp = 0;
 	if (b->warps_dirty && b->B == 1) {

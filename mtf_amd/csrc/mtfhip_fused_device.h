@@ -121,11 +121,39 @@ __device__ __forceinline__ double rscv_map_val(const double *m, int nb, int line
  * 2 KB) into the dynamic LDS the grid rebuild would use (RSCV does not take it); every sample It_orig is mapped right after it is taken,
  * so the residual and the materialised It are the reference's It = map(It_orig) (RSCV.cc:230-234), while the gradients stay those of
  * the unmapped image (mapped_gradient 0, ImageBase::updatePixGrad). */
+/* LRSCV.cc:249-254, 279-292: It = 0, then It += mapped_r(x) w(i, r) for r = idy nx + idx in that order (not LSCV's idx-outer order);
+ * mapped_r(x) is a_r x + c_r (affine_mapping) or rscv_map_val's nearest / linear form through sub-region r's map, taken at the raw x.
+ * m: the target's maps ([R][nb], affine: [R][2]); w: sub_region_wts of the pixel, w[r N].  Every product and every sum is rounded on its
+ * own: this library is compiled without FP contraction. */
+__device__ __forceinline__ double lrscv_blend(const double *m, const LrscvMap &lm, const double *w, unsigned N, double x) {
+	const int nb = lm.nb;
+	const double xi = lm.linear ? trunc(x) : rint(x);
+	int k = (int)xi;
+	k = k < 0 ? 0 : (k > nb - 1 ? nb - 1 : k);
+	const int k1 = k + 1 < nb ? k + 1 : nb - 1;
+	const double dx = x - xi;
+	const bool lin = lm.linear && dx != 0;
+	double acc = 0.0;
+	for (int r = 0; r < lm.R; ++r) {
+		double v;
+		if (lm.affine) {
+			v = m[2 * r] * x + m[2 * r + 1];
+		} else {
+			const double *mr = m + r * nb;
+			v = lin ? (1 - dx) * mr[k] + dx * mr[k1] : mr[k];
+		}
+		acc += v * w[(unsigned)r * N];
+	}
+	return acc;
+}
+/* AM = MTFHIP_AM_LRSCV (kernels_fused_lrscv.hip): RSCV's structure with the localized blend.  The prologue copies the target's maps (at
+ * most 64 KB less the kernel's static arrays, launch_fused_lrscv) into the dynamic LDS; every sample It_orig is replaced by
+ * lrscv_blend right after it is taken, reading the pixel's weights from the batch's [R][N] table. */
 /* COHROW: the workgroup's partial row leaves as write-through stores (the persistent loop, and the one-launch-per-pass kernel of
  * kernels_step.hip whose last-arriving workgroup reads every row in the same launch) */
 template <int AM, int SSM, bool CHAINED, int MODE, bool MAT, bool FAST = false, bool PERSIST = false, bool MC = false, bool COHROW = PERSIST>
 __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	const RscvMap &rm = RscvMap{}) {
+	const RscvMap &rm = RscvMap{}, const LrscvMap &lm = LrscvMap{}) {
 	constexpr int S = (SSM == MTFHIP_SSM_HOMOGRAPHY) ? 8 : 6;
 	constexpr bool NCC = AM == MTFHIP_AM_NCC;
 	constexpr int K = NCC ? NCC_ACC_COUNT : 48;
@@ -229,12 +257,20 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 	extern __shared__ double2 grid_tab[];   /* [resx] (W0[0] nx, W0[3] nx) | [resy] (W0[1] ny, W0[4] ny) -- RSCV: its map, [rm.nb] double */
 	constexpr bool RSCV = AM == MTFHIP_AM_RSCV;
 	static_assert(!(RSCV && (GR_OK || NCC || PERSIST || MC || COHROW)), "RSCV: single channel, one launch per pass, no grid rebuild");
+	constexpr bool LRSCV = AM == MTFHIP_AM_LRSCV;
+	static_assert(!(LRSCV && (GR_OK || NCC || PERSIST || MC || COHROW)), "LRSCV: single channel, one launch per pass, no grid rebuild");
 	/* (uniform per workgroup; every thread of the workgroup gets here, nothing before it returns) */
 	auto fill_map = [&]() {
 		if constexpr (RSCV) {
 			double *s_map = reinterpret_cast<double *>(grid_tab);
 			const double *src = rm.map + (size_t)t * (unsigned)rm.nb;
 			for (int k = threadIdx.x; k < rm.nb; k += kBlock) s_map[k] = src[k];
+			__syncthreads();
+		} else if constexpr (LRSCV) {
+			double *s_map = reinterpret_cast<double *>(grid_tab);
+			const int M = lm.affine ? 2 * lm.R : lm.R * lm.nb;
+			const double *src = lm.map + (size_t)t * (unsigned)M;
+			for (int k = threadIdx.x; k < M; k += kBlock) s_map[k] = src[k];
 			__syncthreads();
 		}
 	};
@@ -458,6 +494,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 			}
 		}
 		if constexpr (RSCV) it = rscv_map_val(reinterpret_cast<const double *>(grid_tab), rm.nb, rm.linear, it);
+		if constexpr (LRSCV) it = lrscv_blend(reinterpret_cast<const double *>(grid_tab), lm, lm.wts + i, N, it);
 		const double r = it - cur.i0;
 		if constexpr (NCC) {
 			acc[NCC_IT] += it; acc[NCC_IT2] = fma(it, it, acc[NCC_IT2]); acc[NCC_I0IT] = fma(cur.i0, it, acc[NCC_I0IT]);

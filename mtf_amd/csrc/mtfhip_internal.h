@@ -302,6 +302,14 @@ struct RscvMap {
 	const double *map = nullptr;
 	int nb = 0, linear = 0;
 };
+/* LRSCV (am = MTFHIP_AM_LRSCV): what the fused pass needs to blend every sample (kernels_lrscv.hip builds the maps) -- map: [bv.B][R][nb]
+ * (affine_mapping: [bv.B][R][2], a_r and c_r), offset to bv's first target; wts: [R][N] sub_region_wts, one per batch, sub-region
+ * idy nx + idx; R = nx ny; linear: weighted_mapping */
+struct LrscvMap {
+	const double *map = nullptr;
+	const double *wts = nullptr;
+	int nb = 0, R = 0, affine = 0, linear = 0;
+};
 
 /* one-time probe: does the kernel-argument segment hold (BatchView, ImgView, FusedArgs) where fused_lk_body's inline-warp path reads them? */
 bool kernarg_layout_verified(hipStream_t st);
@@ -479,9 +487,13 @@ void launch_finish_host(double *partials, int nblk, int row_len, double *out_hos
 	unsigned long long seq, int B, hipStream_t st);
 void launch_publish_host(const void *src, void *dst_host, size_t bytes, int *count, unsigned long long *flag_host,
 	unsigned long long seq, hipStream_t st);
-/* the fused LK iteration for SSD (and RSCV: bv.am == MTFHIP_AM_RSCV takes the RSCV instantiations, which need rm) */
+/* the fused LK iteration for SSD (and RSCV: bv.am == MTFHIP_AM_RSCV takes the RSCV instantiations, which need rm; LRSCV: with lm and its
+ * maps the LRSCV instantiations, without them -- a later pass of a frame under once_per_frame -- the SSD ones on the raw patch) */
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials,
-	int nblk, hipStream_t st, const RscvMap *rm = nullptr);
+	int nblk, hipStream_t st, const RscvMap *rm = nullptr, const LrscvMap *lm = nullptr);
+/* kernels_fused_lrscv.hip: the LRSCV instantiations of the fused body (replay and tolerance mode) */
+void launch_fused_lrscv(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const LrscvMap &lm,
+	hipStream_t st);
 /* kernels_fused_rscv.hip: the RSCV instantiations of the fused body (replay and tolerance mode) */
 void launch_fused_rscv(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const RscvMap &rm,
 	hipStream_t st);
@@ -622,6 +634,29 @@ struct LscvArgs {
 int lscv_hist_blocks(int N);
 /* pass 1 and the maps (its last-arriving workgroup per target), then the re-map of I0; all per-target pointers offset to bv's first target */
 void launch_lscv_update(const BatchView &bv, const ImgView &im, const LscvArgs &a, double *I0, hipStream_t st);
+
+/* ---- LRSCV: the localized current-patch maps of LRSCV::updatePixVals (kernels_lrscv.hip) ---- */
+/* room left in the fused LRSCV pass's 64 KB of LDS for its own static arrays: the maps get the rest */
+constexpr int kLrscvFusedStaticLds = 8 * 1024;
+struct LrscvArgs {
+	int nb, kind;                /* n_bins, RSCV_IT_* (how It_orig is obtained: rscv_it_orig, mtfhip_rscv_device.h) */
+	int nx, ny, ncx, ncell;      /* n_sub_regions_x / _y, cell columns, cells */
+	int affine;                  /* affine_mapping */
+	double norm_mult, norm_add, grad_eps;
+	const unsigned char *code;   /* [B][N] (int)I0, clamped to [0, nb - 1] (RSCV's code plane) */
+	const double *it_orig;       /* [B][N] (RSCV_IT_FROM_BUF) */
+	const unsigned short *cell;  /* [N] (one per batch) the pixel's cell, 0xffff outside every sub-region (LSCV's cell plane) */
+	const int *crng;             /* [2 nx + 2 ny] (one per batch) the cells of each sub-region, as LscvArgs::crng */
+	const int *active;           /* optional [B] mask (device-side loop) */
+	unsigned *tot;               /* [B][2][ncell nb] per-target sums keyed by (cell, current bin), zero between launches */
+	unsigned *arrive;            /* [B] arrival counters (0 between launches) */
+	double *map;                 /* [B][nx ny][nb] */
+	double *aff;                 /* [B][nx ny][2] (affine_mapping) */
+};
+/* pass 1 and the maps (its last-arriving workgroup per target); all per-target pointers of a offset to bv's first target */
+void launch_lrscv_hist(const BatchView &bv, const ImgView &im, const LrscvArgs &a, hipStream_t st);
+/* It = the blend of the mapped It_orig (the per-function route's updatePixVals); lm as the fused pass's, offset to target 0 */
+void launch_lrscv_apply(int N, int B, const LrscvMap &lm, const double *it_orig, double *It, hipStream_t st);
 
 } // namespace mtfhip
 #endif

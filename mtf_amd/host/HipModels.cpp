@@ -62,6 +62,11 @@ void HipPair::setLSCV(int n_sub_regions_x, int n_sub_regions_y, int spacing_x, i
 	check(mtfhip_batch_set_lscv(b, n_sub_regions_x, n_sub_regions_y, spacing_x, spacing_y, affine_mapping ? 1 : 0, once_per_frame ? 1 : 0,
 		weighted_mapping ? 1 : 0));
 }
+void HipPair::setLRSCV(int sub_regions_x, int sub_regions_y, int spacing_x, int spacing_y, bool affine_mapping, bool once_per_frame,
+	bool weighted_mapping) {
+	check(mtfhip_batch_set_lrscv(b, sub_regions_x, sub_regions_y, spacing_x, spacing_y, affine_mapping ? 1 : 0, once_per_frame ? 1 : 0,
+		weighted_mapping ? 1 : 0));
+}
 void HipPair::setRSCV(bool use_bspl, bool weighted_mapping, bool mapped_gradient) {
 	check(mtfhip_batch_set_rscv(b, use_bspl ? 1 : 0, weighted_mapping ? 1 : 0, mapped_gradient ? 1 : 0));
 }
@@ -80,7 +85,8 @@ int HipPair::hessianBuffer(const MatrixXd &D, bool may_register) {
 
 /* ------------------------------------------------------------------ AM */
 HipAM::HipAM(std::shared_ptr<HipPair> pair) : p(pair) {
-	name = p->am == MTFHIP_AM_SSD ? "ssd" : (p->am == MTFHIP_AM_NCC ? "ncc" : (p->am == MTFHIP_AM_SCV ? "scv" : (p->am == MTFHIP_AM_RSCV ? "rscv" : (p->am == MTFHIP_AM_LSCV ? "lscv" : "mi"))));
+	name = p->am == MTFHIP_AM_SSD ? "ssd" : (p->am == MTFHIP_AM_NCC ? "ncc" : (p->am == MTFHIP_AM_SCV ? "scv" : (p->am == MTFHIP_AM_RSCV ? "rscv" : (p->am == MTFHIP_AM_LSCV ? "lscv" :
+		(p->am == MTFHIP_AM_LRSCV ? "lrscv" : "mi")))));
 	I0.resize(p->N); It.resize(p->N);
 	dI0_dx.resize(p->N, 2); dIt_dx.resize(p->N, 2);
 	d2I0_dx2.resize(4, p->N); d2It_dx2.resize(4, p->N);
@@ -110,11 +116,12 @@ void HipAM::setCurrImg(const ImageView &im) {
 void HipAM::setFirstIter() {
 	first_iter = true;
 	if (img.data) HipPair::check(mtfhip_image_upload_mc(p->ctx, img.data, img.rows, img.cols, img.step, img.channels));
-	if (p->am == MTFHIP_AM_LSCV) HipPair::check(mtfhip_batch_set_first_iter(p->b, 1));   /* (LSCV::updateSimilarity reads it, LSCV.cc:264) */
+	/* (LSCV::updateSimilarity reads it, LSCV.cc:264; LRSCV::updatePixVals, LRSCV.cc:234) */
+	if (p->am == MTFHIP_AM_LSCV || p->am == MTFHIP_AM_LRSCV) HipPair::check(mtfhip_batch_set_first_iter(p->b, 1));
 }
 void HipAM::clearFirstIter() {
 	first_iter = false;
-	if (p->am == MTFHIP_AM_LSCV) HipPair::check(mtfhip_batch_set_first_iter(p->b, 0));
+	if (p->am == MTFHIP_AM_LSCV || p->am == MTFHIP_AM_LRSCV) HipPair::check(mtfhip_batch_set_first_iter(p->b, 0));
 }
 const PixValT &HipAM::getInitPixVals() { HipPair::check(mtfhip_batch_read(p->b, MTFHIP_BUF_I0, I0.data())); return I0; }
 const PixValT &HipAM::getCurrPixVals() { HipPair::check(mtfhip_batch_read(p->b, MTFHIP_BUF_IT, It.data())); return It; }

@@ -49,6 +49,8 @@ struct HipPair {
 	void setRSCV(bool use_bspl, bool weighted_mapping, bool mapped_gradient);  /* mtfhip_batch_set_rscv (am = MTFHIP_AM_RSCV) */
 	void setLSCV(int n_sub_regions_x, int n_sub_regions_y, int spacing_x, int spacing_y, bool affine_mapping, bool once_per_frame,
 		bool weighted_mapping);                                                /* mtfhip_batch_set_lscv (am = MTFHIP_AM_LSCV) */
+	void setLRSCV(int sub_regions_x, int sub_regions_y, int spacing_x, int spacing_y, bool affine_mapping, bool once_per_frame,
+		bool weighted_mapping);                                                /* mtfhip_batch_set_lrscv (am = MTFHIP_AM_LRSCV) */
 	int hessianBuffer(const MatrixXd &D, bool may_register);
 };
 
@@ -80,6 +82,14 @@ struct HipLSCVParams {
 	bool affine_mapping = false; bool once_per_frame = false; int n_bins = 256; double pre_seed = 0;
 	bool weighted_mapping = false; bool show_subregions = false; bool approx_dist_feat = false;
 };
+/* LRSCVParams (AM/include/mtf/AM/LRSCV.h), the reference's field names and class defaults (LRSCV.cc:40-52).  n_bins <= 0 selects 256.
+ * pre_seed is accepted and ignored (updatePixVals passes pre-seeds of 0, LRSCV.cc:240-243), as are show_subregions (an OpenCV window)
+ * and debug_mode. */
+struct HipLRSCVParams {
+	int sub_regions_x = 3, sub_regions_y = 3; int spacing_x = 10, spacing_y = 10;
+	bool affine_mapping = false; bool once_per_frame = false; int n_bins = 256; double pre_seed = 0;
+	bool weighted_mapping = false; bool show_subregions = false; bool debug_mode = false;
+};
 struct HipLink {
 	int am = MTFHIP_AM_SSD, ssm = MTFHIP_SSM_HOMOGRAPHY, resx = 50, resy = 50;   /* AMParams / SSMParams: resx, resy */
 	double grad_eps = 1e-8, likelihood_alpha = 1.0;                           /* AMParams::grad_eps; SSDParams / NCCParams / MIParams::likelihood_alpha */
@@ -87,6 +97,7 @@ struct HipLink {
 	HipSCVParams scv;                                                          /* am = MTFHIP_AM_SCV ("scv") */
 	HipRSCVParams rscv;                                                        /* am = MTFHIP_AM_RSCV ("rscv") */
 	HipLSCVParams lscv;                                                        /* am = MTFHIP_AM_LSCV ("lscv") */
+	HipLRSCVParams lrscv;                                                      /* am = MTFHIP_AM_LRSCV ("lrscv", "lrsc") */
 	int device = 0; void *stream = nullptr;
 	std::shared_ptr<HipPair> pair(int n_channels = 1) {
 		if (!p && am == MTFHIP_AM_SCV) {
@@ -103,6 +114,11 @@ struct HipLink {
 			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, lscv.n_bins, lscv.pre_seed, 0, device, stream, n_channels);
 			p->setLSCV(lscv.n_sub_regions_x, lscv.n_sub_regions_y, lscv.spacing_x, lscv.spacing_y, lscv.affine_mapping, lscv.once_per_frame,
 				lscv.weighted_mapping);
+		}
+		if (!p && am == MTFHIP_AM_LRSCV) {
+			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, lrscv.n_bins, lrscv.pre_seed, 0, device, stream, n_channels);
+			p->setLRSCV(lrscv.sub_regions_x, lrscv.sub_regions_y, lrscv.spacing_x, lrscv.spacing_y, lrscv.affine_mapping, lrscv.once_per_frame,
+				lrscv.weighted_mapping);
 		}
 		if (!p) p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, device, stream, n_channels);
 		else if (n_channels > 1 && n_channels != p->n_channels)   /* (SearchMethod<AM, SSM> constructs the AM first: it fixes the channel count) */

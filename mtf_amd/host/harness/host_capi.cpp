@@ -97,6 +97,20 @@ mtfhost_tracker *mtfhost_create_lscv(int sm, int ssm, int resx, int resy, int ma
 		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
 	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
+/* the same tracker with HipAM("lrscv"): its LRSCVParams through the HipLink */
+mtfhost_tracker *mtfhost_create_lrscv(int sm, int ssm, int resx, int resy, int max_iters, double epsilon, int jac_type, int hess_type, int chained_warp,
+	int leven_marq, double lm_delta_init, double lm_delta_update, int device, int sub_regions_x, int sub_regions_y, int spacing_x, int spacing_y,
+	int affine_mapping, int once_per_frame, int n_bins, int weighted_mapping) {
+	try {
+		auto link = std::make_shared<hip::HipLink>();
+		link->am = MTFHIP_AM_LRSCV; link->ssm = ssm; link->resx = resx; link->resy = resy; link->device = device;
+		link->lrscv.sub_regions_x = sub_regions_x; link->lrscv.sub_regions_y = sub_regions_y;
+		link->lrscv.spacing_x = spacing_x; link->lrscv.spacing_y = spacing_y;
+		link->lrscv.affine_mapping = affine_mapping != 0; link->lrscv.once_per_frame = once_per_frame != 0;
+		link->lrscv.n_bins = n_bins; link->lrscv.weighted_mapping = weighted_mapping != 0;
+		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
+	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
 void mtfhost_destroy(mtfhost_tracker *t) { delete t; }
 /* ESM / FC / IC_ENABLE_LEARNING + the AM's learning_rate: am->updateModel(ssm->getPts()) at the end of every update() */
 int mtfhost_set_learning(mtfhost_tracker *t, int enable, double learning_rate) {

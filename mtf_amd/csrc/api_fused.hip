@@ -1937,8 +1937,9 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 		warps = b->d_nn_warps;
 	}
 	TimedScope ts(b->ctx, "nn_dataset");
-	launch_nn_dataset(b->view_raw(), b->ctx->img, a, row_count, dev_features, warps, hull, b->ctx->stream);
-	return MTFHIP_OK;
+	const hipError_t le = launch_nn_dataset(b->view_raw(), b->ctx->img, a, row_count, dev_features, warps, hull, b->ctx->stream);
+	if (le != hipSuccess) return fail(MTFHIP_ERR_HIP, "nn_dataset: the row kernel could not be set up: %s", hipGetErrorString(le));
+	return launch_error_pending();   /* a launch the runtime refused (its dynamic LDS, its grid) is this call's error, not a later one's */
 }
 int mtfhip_nn_dataset(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *perturbations_in, double *perturbations_out, double *features) {
 	if (!b || !d || !features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");

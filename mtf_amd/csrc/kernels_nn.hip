@@ -392,41 +392,63 @@ static void launch_nn_ssm(const BatchView &bv, const ImgView &im, const NnArgs &
 	else if (bv.am == MTFHIP_AM_MI) MTFHIP_LAUNCH((k_nn_dataset<SSM, MTFHIP_AM_MI, MC>), g, blk, 0, st, bv, im, a, feat);
 	else MTFHIP_LAUNCH((k_nn_dataset<SSM, MTFHIP_AM_SSD, MC>), g, blk, 0, st, bv, im, a, feat);
 }
+/* the most dynamic LDS a k_nn_rows launch asks for: a full chunk of a grid that is not unit-z (x, y, z: 24 bytes per entry) = 72 KB */
+constexpr size_t kNnRowsMaxLds = (size_t)(4 * 64 * kNnRowKeep) * 24;
+constexpr size_t kNnRowsDefaultLds = 64 * 1024;   /* what a launch may ask for without the attribute */
 template <int SSM>
-static void launch_nn_rows(const BatchView &bv, const ImgView &im, const NnArgs &a, int count, double *feat, const double *hull, double *warps, hipStream_t st) {
+static const void *nn_rows_kernel(int ai) {
+	if (ai == 1) return reinterpret_cast<const void *>(&k_nn_rows<SSM, MTFHIP_AM_NCC>);
+	if (ai == 2) return reinterpret_cast<const void *>(&k_nn_rows<SSM, MTFHIP_AM_MI>);
+	return reinterpret_cast<const void *>(&k_nn_rows<SSM, MTFHIP_AM_SSD>);
+}
+template <int SSM>
+static hipError_t launch_nn_rows(const BatchView &bv, const ImgView &im, const NnArgs &a, int count, double *feat, const double *hull, double *warps, hipStream_t st) {
 	const int ok = hull ? 1 : 0;
 	const double h[8] = {hull ? hull[0] : 0, hull ? hull[1] : 0, hull ? hull[2] : 0, hull ? hull[3] : 0, hull ? hull[4] : 0, hull ? hull[5] : 0, hull ? hull[6] : 0, hull ? hull[7] : 0};
-	MTFHIP_LAUNCH((k_nn_warps<SSM>), dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, count, warps, im.w, im.h, ok, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
 	/* persistent workgroups: as many as the device holds at once (occupancy x compute units), at most one per sample */
-	/* dynamic LDS: the grid points of the chunk the row needs (a 50 x 50 row: 20 pair-rounds = 40 KB, four workgroups per CU; the full 3072-entry
-	 * chunk is 48 KB: three), z behind them for grids that are not unit-z.  The resident count is a property of (kernel, LDS bytes): cached per pair. */
+	/* dynamic LDS: the grid points of the chunk the row needs (a 50 x 50 row: 20 pair-rounds = 40 KB, four workgroups per CU of the 160 KB
+	 * a CU has; the full 3072-entry chunk is 48 KB: three), z behind them for grids that are not unit-z (24 bytes per entry: 60 KB for the
+	 * 50 x 50 row, 72 KB for the full chunk: two workgroups per CU).  More than 64 KB needs the kernel's MaxDynamicSharedMemorySize
+	 * raised: done ONCE per (kernel instantiation, device), by the first launch that needs it and to the largest size any launch asks
+	 * for -- it is never set to less, so that no order of small and large launches lowers it again; a refusal is the call's error,
+	 * nothing is launched.  The resident count is a property of
+	 * (kernel, device, LDS bytes): cached per triple. */
 	constexpr int kChunkEntries = 4 * 64 * kNnRowKeep;
 	const int rounds = (bv.N + 127) / 128, r4 = ((rounds < kChunkEntries / 128 ? rounds : kChunkEntries / 128) + 3) / 4;
 	const int lds_entries = 128 * 4 * r4;
 	const size_t lds = (size_t)lds_entries * (bv.unit_z ? 16 : 24);
-	static std::map<std::tuple<int, int, size_t>, int> resident_cache;
+	static std::map<std::tuple<int, int, int, size_t>, int> resident_cache;   /* (ssm, am, device, lds; lds = 0: the attribute is set) */
 	static std::mutex resident_mutex;   /* (contexts on several host threads: the loopback ranks of the tests) */
-	std::lock_guard<std::mutex> resident_lock(resident_mutex);
 	const int ai = bv.am == MTFHIP_AM_NCC ? 1 : (bv.am == MTFHIP_AM_MI ? 2 : 0), si = SSM == MTFHIP_SSM_HOMOGRAPHY ? 0 : 1;
-	int &resident = resident_cache[std::make_tuple(si, ai, lds)];
-	if (!resident) {
-		int per_cu = 0, dev = 0;
-		hipDeviceProp_t prop;
-		hipError_t e = hipGetDevice(&dev);
-		if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-		if (e == hipSuccess) {
-			if (ai == 1) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nn_rows<SSM, MTFHIP_AM_NCC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_nn_rows<SSM, MTFHIP_AM_NCC>, kBlock, lds); }
-			else if (ai == 2) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nn_rows<SSM, MTFHIP_AM_MI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_nn_rows<SSM, MTFHIP_AM_MI>, kBlock, lds); }
-			else { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nn_rows<SSM, MTFHIP_AM_SSD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_nn_rows<SSM, MTFHIP_AM_SSD>, kBlock, lds); }
+	const void *fn = nn_rows_kernel<SSM>(ai);
+	int dev = 0, resident = 0;
+	hipError_t e = hipGetDevice(&dev);
+	if (e != hipSuccess) return e;
+	{
+		std::lock_guard<std::mutex> resident_lock(resident_mutex);
+		int &attr_set = resident_cache[std::make_tuple(si, ai, dev, (size_t)0)];
+		if (lds > kNnRowsDefaultLds && !attr_set) {
+			e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNnRowsMaxLds);
+			if (e != hipSuccess) return e;
+			attr_set = 1;
 		}
-		resident = (e == hipSuccess && per_cu > 0) ? per_cu * prop.multiProcessorCount : 1024;
+		int &cached = resident_cache[std::make_tuple(si, ai, dev, lds)];
+		if (!cached) {
+			int per_cu = 0, n_cu = 0;
+			e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+			if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, lds);
+			cached = (e == hipSuccess && per_cu > 0 && n_cu > 0) ? per_cu * n_cu : 1024;
+		}
+		resident = cached;
 	}
+	MTFHIP_LAUNCH((k_nn_warps<SSM>), dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, count, warps, im.w, im.h, ok, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
 	const dim3 g((unsigned)(count < resident ? count : resident)), blk(kBlock);
 #define MTFHIP_NN_ROWS(A) MTFHIP_LAUNCH((k_nn_rows<SSM, A>), g, blk, lds, st, bv, im, warps, count, a.norm_mult, a.norm_add, feat)
 	if (bv.am == MTFHIP_AM_NCC) MTFHIP_NN_ROWS(MTFHIP_AM_NCC);
 	else if (bv.am == MTFHIP_AM_MI) MTFHIP_NN_ROWS(MTFHIP_AM_MI);
 	else MTFHIP_NN_ROWS(MTFHIP_AM_SSD);
 #undef MTFHIP_NN_ROWS
+	return hipSuccess;
 }
 /* the scratch the two-launch form needs: kNnWarpStride doubles per sample of the launch */
 size_t nn_warps_bytes(int count) { return sizeof(double) * (size_t)kNnWarpStride * (size_t)(count > 0 ? count : 0); }
@@ -436,19 +458,20 @@ bool nn_two_launch_ok(const BatchView &bv, const ImgView &im, int fast_math) {
 /* rows [a.row_lo, a.row_lo + count) of the dataset into feat[count][F].  warps != NULL (nn_two_launch_ok: the batch's MTFHIP_MATH_FAST, one
  * channel, NCC rows of at most 3072 entries; nn_warps_bytes(count) of scratch): k_nn_warps + k_nn_rows; otherwise the workgroup-per-sample form
  * in the reference's operation order.  hull: the template grid's own corners x0 y0 .. x3 y3 when the grid is a unit-z lattice laid out
- * inside them, else NULL */
-void launch_nn_dataset(const BatchView &bv, const ImgView &im, const NnArgs &a, int count, double *feat, double *warps, const double *hull, hipStream_t st) {
-	if (count <= 0) return;
+ * inside them, else NULL.  -> hipSuccess, or why the two-launch form could not be set up (the device query, the kernel's dynamic-LDS
+ * attribute): nothing has been launched then */
+hipError_t launch_nn_dataset(const BatchView &bv, const ImgView &im, const NnArgs &a, int count, double *feat, double *warps, const double *hull, hipStream_t st) {
+	if (count <= 0) return hipSuccess;
 	const bool hom = bv.ssm == MTFHIP_SSM_HOMOGRAPHY, mc = bv.C > 1;
 	if (warps) {
-		if (hom) launch_nn_rows<MTFHIP_SSM_HOMOGRAPHY>(bv, im, a, count, feat, hull, warps, st);
-		else launch_nn_rows<MTFHIP_SSM_AFFINE>(bv, im, a, count, feat, hull, warps, st);
-		return;
+		if (hom) return launch_nn_rows<MTFHIP_SSM_HOMOGRAPHY>(bv, im, a, count, feat, hull, warps, st);
+		return launch_nn_rows<MTFHIP_SSM_AFFINE>(bv, im, a, count, feat, hull, warps, st);
 	}
 	if (hom && mc) launch_nn_ssm<MTFHIP_SSM_HOMOGRAPHY, true>(bv, im, a, count, feat, st);
 	else if (hom) launch_nn_ssm<MTFHIP_SSM_HOMOGRAPHY, false>(bv, im, a, count, feat, st);
 	else if (mc) launch_nn_ssm<MTFHIP_SSM_AFFINE, true>(bv, im, a, count, feat, st);
 	else launch_nn_ssm<MTFHIP_SSM_AFFINE, false>(bv, im, a, count, feat, st);
+	return hipSuccess;
 }
 
 } // namespace mtfhip

@@ -534,7 +534,7 @@ struct NnArgs {
 	double norm_mult, norm_add;
 };
 void launch_pair_image(const ImgView &im, float *pair /* [h][w][2] */, hipStream_t st);
-void launch_nn_dataset(const BatchView &bv, const ImgView &im, const NnArgs &a, int count, double *feat, double *warps, const double *hull, hipStream_t st);
+hipError_t launch_nn_dataset(const BatchView &bv, const ImgView &im, const NnArgs &a, int count, double *feat, double *warps, const double *hull, hipStream_t st);
 size_t nn_warps_bytes(int count);
 bool nn_two_launch_ok(const BatchView &bv, const ImgView &im, int fast_math);
 void launch_sample_candidates(const BatchView &bv, const ImgView &im, const double *dev_states, int C, double norm_mult,

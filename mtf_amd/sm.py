@@ -804,8 +804,8 @@ class NNDataset:
     """Dataset generation of nt::NN (SM/src/NT/NN.cc:131-191, compositional update) in ONE launch (mtfhip_nn_dataset: perturbation draw or
     the caller's perturbations, invertState, compositionalUpdate, updatePixVals, updateDistFeat per sample -- SSD, NCC and MI features,
     single- and multi-channel).  Several sampler distributions (NN.cc:56-84: state_sigma[k], distr_n_samples[k]) are consecutive row
-    blocks, one launch each.  With `group` (a torch.distributed process group) the rows are block-partitioned over its ranks and one
-    all-gather leaves the whole matrix on every rank (SURVEY.md section 8e's partition; the draws are keyed by the global sample index).
+    blocks, one launch each.  `initialize_sharded` block-partitions the rows over the ranks of a communicator (mtf_amd.sm.Comm) or of a
+    torch.distributed process group and one all-gather leaves the whole matrix on every rank, bit-identical to `initialize` (SURVEY.md section 8e's partition; the draws are keyed by the global sample index).
     The index built over the matrix (FLANN / GNN in the reference, NN.cc:99-128) is outside the path -- `nearest` is the exhaustive search."""
 
     def __init__(self, ctx, am=L.AM_SSD, ssm=L.SSM_HOMOGRAPHY, resx=50, resy=50, n_samples=1000,
@@ -848,30 +848,73 @@ class NNDataset:
         self.perturbations, self.features = np.concatenate(perts), np.concatenate(feats)
         return self.features
 
-    def initialize_sharded(self, corners, group=None, device=None):
-        """the same with the rows block-partitioned over the ranks of `group` (torch.distributed; backend nccl = RCCL on the GPUs of a node, gloo
-        in the CPU tests' stand-in): rank r generates rows mtf_amd.dist.shard_bounds(n, r, world) into its slice of a device buffer and ONE
-        all-gather completes the matrix on every rank.  Single distribution.  -> torch tensor (n, feat_size) on `device`."""
+    @staticmethod
+    def _shard_device(device, batch):
+        """the GPU the sharded rows are generated on: `device` (anything torch.device takes), or the one the batch's context names when None.
+        Anything that is not a GPU is refused HERE, before any native call: the row kernel stores through the buffer's address."""
         import torch
-        import torch.distributed as tdist
+        if device is None:
+            idx = getattr(getattr(batch, "ctx", None), "device", None)
+            if not isinstance(idx, int) or isinstance(idx, bool):
+                raise ValueError("NNDataset.initialize_sharded: no device given and the context names none")
+            device = torch.device("cuda", idx)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("NNDataset.initialize_sharded needs a GPU device (the kernel writes the rows through device pointers), not %r" % (device,))
+        return device
+
+    def initialize_sharded(self, corners, group=None, device=None, comm=None):
+        """`initialize` with the rows block-partitioned over the ranks of `comm` (mtf_amd.sm.Comm: RCCL, or the loopback group whose ranks are
+        threads of one process) or of `group` (torch.distributed; nccl = RCCL on the GPUs of a node): rank r generates rows
+        mtf_amd.dist.padded_shard(n, r, world) -- ceil(n / world) rows per rank, the last blocks ragged or empty -- into its slice of a padded
+        device buffer, the perturbations beside them, and ONE all-gather each completes matrix and perturbations on every rank.  The draws
+        are keyed by the global sample index and several sampler distributions are consecutive row blocks seeded seed + k as in
+        `initialize`, so every rank ends with `features` and `perturbations` (host arrays, what `nearest` searches) BIT-IDENTICAL to the
+        unsharded `initialize`; the pad rows never reach them.  `device`: the GPU (default: the context's); anything else raises before
+        any native call.  -> the (n, feat_size) matrix as a torch tensor on `device` (also kept as `features_dev`)."""
+        import torch
+        device = self._shard_device(device, self.batch)
+        if comm is not None:
+            world, rank = int(comm.world), int(comm.rank)
+        else:
+            import torch.distributed as tdist
+            on = tdist.is_available() and tdist.is_initialized()
+            world = tdist.get_world_size(group) if on else 1
+            rank = tdist.get_rank(group) if on else 0
         from . import dist as mdist
-        world = tdist.get_world_size(group) if tdist.is_initialized() else 1
-        rank = tdist.get_rank(group) if tdist.is_initialized() else 0
         b = self.batch
         b.set_corners(np.asarray(corners, dtype=np.float64).reshape(1, 2, 4))
         b.initialize_pix_vals()
-        F, n = self.feature_size(), self.n
+        F, n, S = self.feature_size(), self.n, self.S
         lo, cnt, m = mdist.padded_shard(n, rank, world)       # rows per rank of the padded buffer (the filter's partition: ceil(n / world))
         buf = torch.zeros((m * world, F), dtype=torch.float64, device=device)
-        d = b.nn_desc(n, self.sigmas[0], self.means[0], self.seed)
-        b.nn_dataset_dev(d, buf[rank * m:].data_ptr(), lo, cnt)
+        pbuf = torch.zeros((m * world, S), dtype=torch.float64, device=device)
+        # this rank's rows [lo, lo + cnt) cut by the distributions' blocks [g0, g0 + ck): rows [a - g0, e - g0) of distribution k's own dataset
+        g0 = 0
+        for k, ck in enumerate(self.distr_n_samples):
+            a, e = max(lo, g0), min(lo + cnt, g0 + ck)
+            if e > a:
+                d = b.nn_desc(ck, self.sigmas[k], self.means[k], self.seed + k)
+                # (the kernel indexes the perturbations it writes by the sample's index in ITS dataset: row a - g0 lands on pbuf[rank * m + a - lo])
+                b.nn_dataset_dev(d, buf[rank * m + (a - lo):].data_ptr(), a - g0, e - a,
+                                 dev_perts_out_ptr=pbuf.data_ptr() + (rank * m - lo + g0) * S * 8)
+            g0 += ck
         b.ctx.synchronize()
         if world > 1:
-            tdist.all_gather_into_tensor(buf, buf[rank * m:(rank + 1) * m].clone(), group=group)
-        self.features = buf[:n]
-        return self.features
+            if comm is not None:
+                for t in (buf, pbuf):       # in place: this rank's block is where the gather puts it
+                    comm.allgather(t[rank * m:].data_ptr(), m * t.shape[1], t.data_ptr(), b.ctx.stream)
+                b.ctx.synchronize()
+            else:
+                import torch.distributed as tdist
+                for t in (buf, pbuf):
+                    tdist.all_gather_into_tensor(t, t[rank * m:(rank + 1) * m].clone(), group=group)
+        self.features_dev = buf[:n]
+        self.features, self.perturbations = self.features_dev.cpu().numpy(), pbuf[:n].cpu().numpy()
+        return self.features_dev
 
     def nearest(self, feature):
+        """the exhaustive search: (index, squared distance) of the stored row nearest to `feature`; of equal distances the first index"""
         d = ((self.features - np.asarray(feature)[None]) ** 2).sum(axis=1)
         k = int(np.argmin(d))
         return k, float(d[k])

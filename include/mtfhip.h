@@ -306,7 +306,9 @@ int mtfhip_batch_set_region(mtfhip_batch *b, const double *corners, const mtfhip
 int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
 /* The whole update() loop on device (solve, compositional update and the corner-change
  * convergence test included) without host round trips; returns per-target iteration counts
- * and final corners.  SM/src/NT/{ESM,FCLK,ICLK}.cc update(). */
+ * and final corners.  SM/src/NT/{ESM,FCLK,ICLK}.cc update().
+ * With sm->materialize the interface arrays (It, dIt_dx, Jt) hold after the call what the last executed pass of each target
+ * produced; within the call they are not observable (the passes before a target's last need not store them). */
 int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters /* B */, double *corners /* B x 8 */);
 /* setRegion(region_corners) followed by update() in one call -- the pair GridTracker::update issues per patch tracker
  * (SM/src/GridTracker.cc:345-363) and PyramidalTracker per level (SM/src/PyramidalTracker.cc:70-96).  Same results as

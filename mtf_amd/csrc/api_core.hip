@@ -522,7 +522,7 @@ void mtfhip_batch_destroy(mtfhip_batch *b) {
 			if (b->buf[i]) (void)hipFree(b->buf[i]);
 		void *ptrs[] = {b->d_slab, b->d_partials, b->d_acc, b->d_scratch_pts, b->d_h0,
 			b->d_cand, b->d_colmean, b->d_mi_tb, b->d_mi_part,
-			b->d_mi_f, b->d_mi_H, b->d_h0inv, b->d_d2_part, b->d_d2_out, b->d_d2_w, b->d_it_shadow, b->d_ncc_tm, b->d_mi_red, b->d_lm, b->d_persist, b->d_trace, b->d_cand_mi, b->d_mi_poly, b->d_nn_warps, b->d_fb, b->d_scv_i0, b->d_scv_code, b->d_scv_part, b->d_scv_map,
+			b->d_mi_f, b->d_mi_H, b->d_h0inv, b->d_d2_part, b->d_d2_out, b->d_d2_w, b->d_it_shadow, b->d_ncc_tm, b->d_mi_red, b->d_lm, b->d_persist, b->d_last_ws, b->d_need_mat, b->d_trace, b->d_cand_mi, b->d_mi_poly, b->d_nn_warps, b->d_fb, b->d_scv_i0, b->d_scv_code, b->d_scv_part, b->d_scv_map,
 			b->d_rscv_code, b->d_rscv_part, b->d_rscv_arrive, b->d_rscv_map, b->d_rscv_it, b->d_lscv_i0, b->d_lscv_code, b->d_lscv_cell, b->d_lscv_crng,
 			b->d_lscv_w, b->d_lscv_tot, b->d_lscv_arrive, b->d_lscv_map, b->d_lscv_aff};
 		for (void *p : ptrs)

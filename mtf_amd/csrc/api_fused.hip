@@ -1011,6 +1011,29 @@ int mtfhip_batch_track_queues(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	return track_queues(b, fa);
 }
 
+/* Deferred materialisation of the two-launch loop.  A materialising pass stores It, dIt_dx and Jt (88 B/px) that the next pass overwrites
+ * and nothing in between reads: only what a target's last executed pass wrote can be seen after the call.  Where this predicate holds, the
+ * passes before the one the host knows to be the last run the non-materialising kernel in the same (replay) arithmetic on the same cut of
+ * the pixel pass -- the same partial rows, so H, g, the update, the corners and n_iters are the parent loop's bits -- the last pass
+ * materialises as before, and a target the finish stops earlier (change < epsilon) gets one trailing materialising launch at the warp of
+ * its last pass (TrackState::warp_last / need_mat).  MTFHIP_TRACK_DEFER_MAT=0 (read per call) keeps every pass materialising. */
+static bool track_defers_materialisation(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const FusedArgs &fa, int so_term, bool resume, bool use_step) {
+	const char *e = std::getenv("MTFHIP_TRACK_DEFER_MAT");   /* (read per call: the tests and the A/B measurement flip it) */
+	if (e && e[0] == '0') return false;
+	if (!fa.materialize) return false;          /* nothing is stored that could be deferred */
+	if (fa.mode == 2) return false;             /* ICLK stores It only (8 B/px): a trailing launch would cost more than it saves */
+	if (sm->max_iters < 3) return false;        /* one or two passes: a lean pass + a trailing pass can cost more than the stores saved */
+	if (sm->leven_marq) return false;           /* an undo pass, FCLK's 2 x max_iters passes: the host does not know the last pass, and the
+	                                             * finish also stops a target on a counter of its own */
+	if (b->d_trace) return false;               /* the debug trace is compared pass by pass against loops that materialise every pass */
+	if (so_term >= 0) return false;             /* the second-order pass runs between the pixel pass and the finish, beside the stored arrays */
+	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return false;   /* MI has its own loop; SCV / RSCV / LSCV / LRSCV re-map from It between the passes */
+	if (b->C != 1) return false;                /* the multi-channel kernels are an instantiation set of their own: not measured */
+	if (use_step) return false;                 /* the one-launch-per-pass form (MTFHIP_STEP=1) has no lean / full pair */
+	if (resume) return false;                   /* the rest of a persistent launch: the iteration counters do not start at zero */
+	return true;
+}
+
 static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners, bool slab_uploaded, bool resume = false, bool region_mode = false);
 static int track_validate(mtfhip_batch *b, const mtfhip_sm_desc *sm);
 /* ---- the persistent one-launch loop (kernels_persist.hip) ---- */
@@ -1575,12 +1598,6 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 		static const double stagger_env = std::getenv("MTFHIP_TRACK_STAGGER_US") ? std::atof(std::getenv("MTFHIP_TRACK_STAGGER_US")) : -1.0;
 		double stagger_us = stagger_env;
 		if (stagger_env < 0) stagger_us = 0.25 * ((double)b->B * b->N * 130.0 / 6.5e6 + 8.0) * (2.0 / n_streams);
-		if (n_streams >= 2) {
-			const int part_sz = (b->B + n_streams - 1) / n_streams;
-			if (chunk > part_sz) chunk = part_sz;
-			HIP_TRY(hipEventRecord(b->ctx->ev_fork, st));   /* the slab upload */
-			for (int q = 0; q + 1 < n_streams; ++q) HIP_TRY(hipStreamWaitEvent(b->ctx->extra_streams[q], b->ctx->ev_fork, 0));
-		}
 		/* small batches (a single tracker's target, a handful of them): one launch per pass instead of two -- the pixel pass's last
 		 * workgroup runs the finish (kernels_step.hip).  MEASURED r05 (one box, ESM + SSD + homography, 200 iterations per call): 200 x 200
 		 * full 12.22 -> 12.54 us per iteration, lean 10.92 -> 10.79, 50 x 50 lean 10.55 -> 10.44: nothing.  The r04 verdict's estimate (a
@@ -1599,7 +1616,22 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 				HIP_TRY(hipMemsetAsync(b->d_persist, 0, 2 * sizeof(int) * (size_t)b->B, st));
 			}
 		}
-		struct ChunkRun { BatchView bc; FusedArgs fc; TrackState tc; int nblk_c, t0, nt; double *part; hipStream_t s; bool done; };
+		/* deferred materialisation (track_defers_materialisation): the passes before the last run the lean kernel */
+		const bool defer = track_defers_materialisation(b, sm, fa, so_term, resume, use_step);
+		if (defer) {
+			if (!b->d_last_ws) HIP_TRY(hipMalloc(&b->d_last_ws, sizeof(double) * 17 * (size_t)b->B));
+			if (!b->d_need_mat) HIP_TRY(hipMalloc(&b->d_need_mat, sizeof(int) * (size_t)b->B));
+			HIP_TRY(hipMemsetAsync(b->d_need_mat, 0, sizeof(int) * (size_t)b->B, st));
+		}
+		if (n_streams >= 2) {
+			const int part_sz = (b->B + n_streams - 1) / n_streams;
+			if (chunk > part_sz) chunk = part_sz;
+			HIP_TRY(hipEventRecord(b->ctx->ev_fork, st));   /* the slab upload */
+			for (int q = 0; q + 1 < n_streams; ++q) HIP_TRY(hipStreamWaitEvent(b->ctx->extra_streams[q], b->ctx->ev_fork, 0));
+		}
+		/* fl / tl: the arguments of a pass that does not materialise (replay arithmetic whatever the batch's math mode: a call that asks for
+		 * the interface arrays has asked for it; the grid rebuild is the materialising kernel's) */
+		struct ChunkRun { BatchView bc; FusedArgs fc, fl; TrackState tc, tl; int nblk_c, t0, nt; double *part; hipStream_t s; bool done; };
 		std::vector<ChunkRun> runs;
 		for (int t0 = 0; t0 < b->B; t0 += chunk) {
 			const int nt = std::min(chunk, b->B - t0);
@@ -1624,7 +1656,12 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 			 * per-dispatch counters are device-wide and would include the launch in flight on the other queue */
 			static const bool serialize = std::getenv("MTFHIP_TRACK_SERIALIZE") && std::getenv("MTFHIP_TRACK_SERIALIZE")[0] == '1';
 			const int q = serialize ? n_streams - 1 : (int)(runs.size() % (size_t)n_streams);
-			runs.push_back(ChunkRun{bc, fc, tc, nblk_c, t0, nt, part, q == n_streams - 1 ? st : b->ctx->extra_streams[q], false});
+			FusedArgs fl = fc;
+			fl.materialize = 0; fl.fast_math = 0; fl.grid_regen = 0;
+			if (defer) { tc.warp_last = b->d_last_ws + 9 * (size_t)t0; tc.state_last = b->d_last_ws + 9 * (size_t)b->B + 8 * (size_t)t0; tc.need_mat = b->d_need_mat + t0; }
+			TrackState tl = tc;
+			tl.lean_pass = 1;
+			runs.push_back(ChunkRun{bc, fc, fl, tc, tl, nblk_c, t0, nt, part, q == n_streams - 1 ? st : b->ctx->extra_streams[q], false});
 		}
 		const auto dbg_t0 = std::chrono::steady_clock::now();
 		/* Every way out of the loop below joins the extra queues: the normal path with an event the context's stream waits on; an
@@ -1639,6 +1676,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 			const size_t g1 = std::min(runs.size(), g0 + (size_t)n_streams);
 			for (int it = 0; it < max_passes; ++it) {
 				bool all_done = true;
+				const bool lean = defer && it + 1 < max_passes;   /* (the pass the host knows to be the last materialises) */
 				for (size_t k = g0; k < g1; ++k) {
 					ChunkRun &r = runs[k];
 					if (r.done) continue;
@@ -1662,7 +1700,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 					if (b->desc.am == MTFHIP_AM_LRSCV && (!b->lscv_once || it == 0)) TRY(lrscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &lm));
 					{
 						TimedScope tsc(b->ctx, "fused_lk", r.s);
-						launch_fused_ssd(r.bc, b->ctx->img, r.fc, r.part, r.nblk_c, r.s, &rm, &lm);
+						launch_fused_ssd(r.bc, b->ctx->img, lean ? r.fl : r.fc, r.part, r.nblk_c, r.s, &rm, &lm);
 					}
 					if (so_term >= 0) {
 						TimedScope tsc(b->ctx, "second_order", r.s);
@@ -1677,13 +1715,25 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 							const int qi = (int)((k - g0) & 1);
 							pc = PhaseCtl{b->ctx->d_phase + qi, b->ctx->d_phase + (1 - qi), phase_frac};
 						}
-						launch_finish_track(r.bc, *sm, r.tc, r.part, r.nblk_c, r.s, pc);
+						launch_finish_track(r.bc, *sm, lean ? r.tl : r.tc, r.part, r.nblk_c, r.s, pc);
 					}
 					if (all_converged(r.tc.active, r.nt, it, r.s)) r.done = true;
 					all_done = all_done && r.done;
 				}
 				if (all_done) break;
 			}
+			/* targets that stopped behind a lean pass: the materialising kernel once more at the warp of that pass (the same pass again, so
+			 * the partial rows it rewrites are the ones already there; no finish follows).  A target whose flag is clear costs an idle pass. */
+			if (defer && sm->epsilon > 0)
+				for (size_t k = g0; k < g1; ++k) {
+					ChunkRun &r = runs[k];
+					BatchView bm = r.bc;
+					bm.warps = r.tc.warp_last; bm.states = r.tc.state_last;
+					FusedArgs fm = r.fc;
+					fm.active = r.tc.need_mat;
+					TimedScope tsc(b->ctx, "fused_lk", r.s);
+					launch_fused_ssd(bm, b->ctx->img, fm, r.part, r.nblk_c, r.s, nullptr, nullptr);
+				}
 		}
 		if (std::getenv("MTFHIP_TRACK_DEBUG_TIMING"))
 			std::fprintf(stderr, "[track] %d queues, %d passes enqueued in %.1f us\n", n_streams, max_passes,

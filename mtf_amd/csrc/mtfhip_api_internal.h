@@ -274,6 +274,10 @@ struct mtfhip_batch {
 	/* k_track_persist: barrier words, the generation counter the host advances per launch; persist_ok is cleared for good when a
 	 * launch could not keep its workgroups resident (the two-launch loop finishes the call and serves the later ones) */
 	int *d_persist = nullptr;
+	/* deferred materialisation of the device-side loop (track_core): warp [B][9] | state [B][8] of the last pass of a target that stopped
+	 * behind a non-materialising pass, and the per-target flags of the trailing materialising launch */
+	double *d_last_ws = nullptr;
+	int *d_need_mat = nullptr;
 	unsigned persist_gen = 0;
 	bool persist_ok = true;
 	bool stage_a_busy = false;   /* ev_a guards an upload from h_stage_a that may still be in flight */

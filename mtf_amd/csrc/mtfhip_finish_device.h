@@ -39,11 +39,21 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	auto LDI = [](const int *p) -> int { if constexpr (COH) return ld_coh(p); else return *p; };
 	auto ST = [](double *p, double v) { if constexpr (COH) st_coh(p, v); else *p = v; };
 	auto STI = [](int *p, int v) { if constexpr (COH) st_coh(p, v); else *p = v; };
+	/* the target stops iterating; behind a pass that did not materialise (TrackState::lean_pass) the warp and the state the pass ran at
+	 * are kept for the trailing materialising launch */
+	auto stop_target = [&](const double *w_old, const double *s_old) {
+		STI(ts.active + t, 0);
+		if (ts.lean_pass) {
+			for (int q = 0; q < 9; ++q) ST(ts.warp_last + 9 * t + q, w_old[q]);
+			for (int q = 0; q < 8; ++q) ST(ts.state_last + 8 * t + q, s_old[q]);
+			STI(ts.need_mat + t, 1);
+		}
+	};
 	FIN_STAMP(0);
 	__shared__ double acc_s[NCC_ACC_COUNT];   /* >= ACC_COUNT */
 	__shared__ double A[8][9];
 	__shared__ double dps[8];
-	__shared__ double h0s[64], Ws[9], crs[8], ics[12], tms[52], ncs[2];
+	__shared__ double h0s[64], Ws[9], crs[8], ics[12], tms[52], ncs[2], sos[8];
 	const int lane = threadIdx.x;
 	const bool wv0 = lane < 64;
 	const int S = bv.S;
@@ -56,10 +66,11 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	 * rest of the routine runs out of LDS / registers */
 	const int act = LDI(ts.active + t);
 	const int n_it_prev = LDI(ts.n_iters + t);   /* passes done so far (uniform: a scalar load) */
-	double v_h0 = 0, v_w = 0, v_cr = 0, v_ic = 0, v_acc = 0, v_tm = 0, v_nc = 0;
+	double v_h0 = 0, v_w = 0, v_cr = 0, v_ic = 0, v_acc = 0, v_tm = 0, v_nc = 0, v_so = 0;
 	if (wv0) {
 		v_h0 = ts.h0[(size_t)t * 64 + lane];
 		if (lane < 9) v_w = LD(bv.warps + 9 * t + lane);
+		if (ts.lean_pass && lane < 8) v_so = LD(bv.states + 8 * t + lane);   /* (the state this pass ran at: stop_target) */
 		if (lane < 8) v_cr = LD(ts.corners + 8 * t + lane);
 		if (lane < 12) v_ic = ts.init_corners_hm[12 * t + lane];
 		if (ncc) {
@@ -99,7 +110,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	if (wv0) {
 		h0s[lane] = v_h0;
 		if (lane < 9) Ws[lane] = v_w;
-		if (lane < 8) crs[lane] = v_cr;
+		if (lane < 8) { crs[lane] = v_cr; sos[lane] = v_so; }
 		if (lane < 12) ics[lane] = v_ic;
 		if (lane < 52) tms[lane] = v_tm;
 		if (lane < 2) ncs[lane] = v_nc;
@@ -362,8 +373,8 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		 * (NT/ESM.cc:179, NT/ICLK.cc:169) but not in FCLK's while loop (NT/FCLK.cc:193-223) */
 		const int id = lm_iter_id + ((undo && sm.sm == MTFHIP_SM_FCLK) ? 0 : 1);
 		ST(lmp + 3, (double)id);
-		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) STI(ts.active + t, 0);
-	} else if (change < sm.epsilon || n_it >= sm.max_iters) STI(ts.active + t, 0);
+		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) stop_target(Ws, sos);
+	} else if (change < sm.epsilon || n_it >= sm.max_iters) stop_target(Ws, sos);
 	FIN_STAMP(6);
 }
 
@@ -385,7 +396,15 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 	auto LDI = [](const int *p) -> int { if constexpr (COH) return ld_coh(p); else return *p; };
 	auto ST = [](double *p, double v) { if constexpr (COH) st_coh(p, v); else *p = v; };
 	auto STI = [](int *p, int v) { if constexpr (COH) st_coh(p, v); else *p = v; };
-	__shared__ double f_acc[ACC_COUNT], f_h0[64], f_w[9], f_cr[8], f_ic[12], f_lm[kLmStride + 1], f_part[3][80];
+	auto stop_target = [&](const double *w_old, const double *s_old) {   /* (as finish_track_body's) */
+		STI(ts.active + t, 0);
+		if (ts.lean_pass) {
+			for (int q = 0; q < 9; ++q) ST(ts.warp_last + 9 * t + q, w_old[q]);
+			for (int q = 0; q < 8; ++q) ST(ts.state_last + 8 * t + q, s_old[q]);
+			STI(ts.need_mat + t, 1);
+		}
+	};
+	__shared__ double f_acc[ACC_COUNT], f_h0[64], f_w[9], f_cr[8], f_ic[12], f_lm[kLmStride + 1], f_part[3][80], f_so[8];
 	const int lane = threadIdx.x;
 	const bool wv0 = lane < 64;
 	const int S = bv.S;
@@ -394,8 +413,9 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 	FIN_STAMP(0);
 	const int n_it_prev = LDI(ts.n_iters + t);
 	double *lmp = ts.lm ? ts.lm + (size_t)t * kLmStride : nullptr;
-	double v_h0 = 0, v_w = 0, v_cr = 0, v_ic = 0, v_acc = 0, v_lm = 0, v_f = 0;
+	double v_h0 = 0, v_w = 0, v_cr = 0, v_ic = 0, v_acc = 0, v_lm = 0, v_f = 0, v_so = 0;
 	if (wv0) {
+		if (ts.lean_pass && lane < 8) v_so = LD(bv.states + 8 * t + lane);   /* (the state this pass ran at: stop_target) */
 		/* (the Levenberg-Marquardt block and an external similarity ride on the same round trip) */
 		if (lmp && lane < kLmStride) v_lm = LD(lmp + lane);
 		if (ts.f_ext && lane == 0) v_f = LD(ts.f_ext + t);
@@ -431,7 +451,7 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 	if (wv0) {
 		f_h0[lane] = v_h0;
 		if (lane < 9) f_w[lane] = v_w;
-		if (lane < 8) f_cr[lane] = v_cr;
+		if (lane < 8) { f_cr[lane] = v_cr; f_so[lane] = v_so; }
 		if (lane < 12) f_ic[lane] = v_ic;
 		if (lane < kLmStride) f_lm[lane] = v_lm;
 		if (lane == 0) f_lm[kLmStride] = v_f;
@@ -612,8 +632,8 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 	if (lmp) {
 		const int id = lm_iter_id + ((undo && sm.sm == MTFHIP_SM_FCLK) ? 0 : 1);
 		ST(lmp + 3, (double)id);
-		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) STI(ts.active + t, 0);
-	} else if (change < sm.epsilon || n_it >= sm.max_iters) STI(ts.active + t, 0);
+		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) stop_target(f_w, f_so);
+	} else if (change < sm.epsilon || n_it >= sm.max_iters) stop_target(f_w, f_so);
 	FIN_STAMP(6);
 }
 

@@ -132,6 +132,14 @@ struct TrackState {
 	 * starts from the identity warp and the zero state at its template's corners, which that kernel left in init_corners_hm -- the slab's warps /
 	 * states / corners are not read, so the host does not upload them (one ingest launch and its gap less per frame, r06) */
 	int fresh_reset;
+	/* deferred materialisation (track_core): a pass launched with the non-materialising pixel kernel sets lean_pass; a target the finish
+	 * stops after such a pass (change < epsilon) leaves the warp and the state that pass ran at in warp_last ([B][9]) / state_last
+	 * ([B][8]) and raises need_mat[t]; one trailing launch of the materialising kernel at that warp then writes It / dIt_dx / Jt for
+	 * it.  NULL / 0: off. */
+	double *warp_last = nullptr;
+	double *state_last = nullptr;
+	int *need_mat = nullptr;
+	int lean_pass = 0;
 };
 constexpr int kLmStride = 12;
 constexpr int kTraceStride = 96;

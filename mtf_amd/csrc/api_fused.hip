@@ -577,7 +577,7 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 	/* the template grid rebuilt in the kernel (16 B per point less): the grid is still the one k_init_grid laid out from d_w0 for these
 	 * corners (grid_w0_epoch; a caller write to INIT_PTS / INIT_Z / INIT_HXY clears grid_from_corners), the maps divide by nothing, and
 	 * the launch is the materialising SSD one -- the only instantiation with the rebuild (fused_lk_body, GR_OK), whose lattice products
-	 * launch_fused_mat gives (resx + resy) double2 of LDS */
+	 * launch_fused_ssd gives (resx + resy) double2 of LDS */
 	fa.grid_regen = (b->unit_z && b->grid_from_corners && b->grid_w0_epoch == b->corners_epoch && b->grid_w0_affine && b->C == 1 &&
 		b->d_w0 && b->desc.resx + b->desc.resy <= kGridTabMax) ? 1 : 0;
 	fa.w0 = b->d_w0;
@@ -595,7 +595,7 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 		if (sm->hess_type == 1) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "fused ICLK with hess_type CurrentSelf: use the un-fused entry points");
 		fa.mode = 2;
 	}
-	if (!grid_regen_kernel((b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_LSCV) ? MTFHIP_AM_SSD : b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
+	if (!grid_regen_kernel(b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
 		fa.grid_regen = 0;
 	return MTFHIP_OK;
 }

@@ -33,12 +33,10 @@ int rscv_capture(mtfhip_batch *b) {
 	return MTFHIP_OK;
 }
 
-/* the It_orig expression of the fused launch fa selects (launch_fused_rscv, kernels_fused_rscv.hip) */
+/* the It_orig expression of the fused launch fa selects (launch_fused_rscv / launch_fused_lrscv: the same for either model and SSM) */
 int rscv_it_kind(const FusedArgs *fa) {
 	if (!fa) return RSCV_IT_FROM_BUF;
-	if (!(fa->fast_math && !fa->materialize)) return RSCV_IT_REPLAY;
-	if (fa->mode == 2) return RSCV_IT_FAST_ICLK;
-	return fa->chained ? RSCV_IT_FAST_CHAINED : RSCV_IT_FAST_QSTEP;
+	return fused_it_kind(fused_select(FUSED_ROUTE_LOOP, MTFHIP_AM_RSCV, 1, MTFHIP_SSM_HOMOGRAPHY, fa->mode, fa->chained, fa->materialize, fa->fast_math));
 }
 
 static RscvArgs rscv_args(mtfhip_batch *b, int t0, const int *active, const FusedArgs *fa) {

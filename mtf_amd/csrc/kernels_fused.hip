@@ -74,64 +74,29 @@ __global__ __launch_bounds__(64) void k_finish_track_mi(BatchView bv, mtfhip_sm_
 /* launchers                                                              */
 /* ===================================================================== */
 
-template <int SSM, bool CHAINED, int MODE>
-static void launch_fused_mat(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	hipStream_t st) {
-	dim3 g = grid2(nblk, bv.B);
-	if (bv.am == MTFHIP_AM_NCC) {
-		if (fa.materialize)
-			MTFHIP_LAUNCH((k_fused_ncc<SSM, CHAINED, MODE, true>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-		else
-			MTFHIP_LAUNCH((k_fused_ncc<SSM, CHAINED, MODE, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-		return;
-	}
-	if (fa.materialize) {   /* (grid_regen: the lattice products, fused_lk_body) */
-		const size_t tab = fa.grid_regen ? sizeof(double2) * (size_t)(fa.g_resx + fa.g_resy) : 0;
-		MTFHIP_LAUNCH((k_fused_ssd<SSM, CHAINED, MODE, true>), g, dim3(kBlock), tab, st, bv, im, fa, partials, nblk);
-	}
-	else
-		MTFHIP_LAUNCH((k_fused_ssd<SSM, CHAINED, MODE, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-}
-template <int SSM, bool CHAINED>
-static void launch_fused_mode(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	hipStream_t st) {
-	if (fa.mode == 0) launch_fused_mat<SSM, CHAINED, 0>(bv, im, fa, partials, nblk, st);
-	else if (fa.mode == 1) launch_fused_mat<SSM, CHAINED, 1>(bv, im, fa, partials, nblk, st);
-	else launch_fused_mat<SSM, CHAINED, 2>(bv, im, fa, partials, nblk, st);
-}
-template <int AM, int SSM>
-static void launch_fused_fast(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, hipStream_t st) {
-	dim3 g = grid2(nblk, bv.B);
-	/* (ICLK takes no gradient: one instantiation) */
-	if (fa.mode == 2) MTFHIP_LAUNCH((k_fused_fast<AM, SSM, 2, true>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-	else if (fa.mode == 0 && fa.chained) MTFHIP_LAUNCH((k_fused_fast<AM, SSM, 0, true>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-	else if (fa.mode == 0) MTFHIP_LAUNCH((k_fused_fast<AM, SSM, 0, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-	else if (fa.chained) MTFHIP_LAUNCH((k_fused_fast<AM, SSM, 1, true>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-	else MTFHIP_LAUNCH((k_fused_fast<AM, SSM, 1, false>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
-}
+/* the unit's instantiations and the one of a launch: fused_select / fused_visit (mtfhip_fused_dispatch.h) */
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
 	hipStream_t st, const RscvMap *rm, const LrscvMap *lm) {
-	if (bv.am == MTFHIP_AM_RSCV) {   /* (the API enqueues RSCV's pass 1 in front and hands its maps over: no map, no launch) */
-		if (rm && rm->map) launch_fused_rscv(bv, im, fa, partials, nblk, *rm, st);
-		return;
-	}
-	/* (LRSCV: with the maps of a pass 1 enqueued in front, the blend; without -- a later pass of a frame under once_per_frame -- an SSD
-	 * pass on the raw patch, LRSCV.cc:234-235) */
-	if (bv.am == MTFHIP_AM_LRSCV && lm && lm->map) { launch_fused_lrscv(bv, im, fa, partials, nblk, *lm, st); return; }
-	const bool hom = bv.ssm == MTFHIP_SSM_HOMOGRAPHY;
-	if (bv.C > 1) { launch_fused_mc(bv, im, fa, partials, nblk, st); return; }   /* MCSSD / MCNCC */
-	if (fa.fast_math && !fa.materialize) {
-		const bool ncc = bv.am == MTFHIP_AM_NCC;
-		if (hom && ncc) launch_fused_fast<MTFHIP_AM_NCC, MTFHIP_SSM_HOMOGRAPHY>(bv, im, fa, partials, nblk, st);
-		else if (hom) launch_fused_fast<MTFHIP_AM_SSD, MTFHIP_SSM_HOMOGRAPHY>(bv, im, fa, partials, nblk, st);
-		else if (ncc) launch_fused_fast<MTFHIP_AM_NCC, MTFHIP_SSM_AFFINE>(bv, im, fa, partials, nblk, st);
-		else launch_fused_fast<MTFHIP_AM_SSD, MTFHIP_SSM_AFFINE>(bv, im, fa, partials, nblk, st);
-		return;
-	}
-	if (hom && fa.chained) launch_fused_mode<MTFHIP_SSM_HOMOGRAPHY, true>(bv, im, fa, partials, nblk, st);
-	else if (hom) launch_fused_mode<MTFHIP_SSM_HOMOGRAPHY, false>(bv, im, fa, partials, nblk, st);
-	else if (fa.chained) launch_fused_mode<MTFHIP_SSM_AFFINE, true>(bv, im, fa, partials, nblk, st);
-	else launch_fused_mode<MTFHIP_SSM_AFFINE, false>(bv, im, fa, partials, nblk, st);
+	/* (the API enqueues pass 1 of RSCV / LRSCV in front and hands its maps over.  RSCV: no map, no launch; LRSCV without one -- a later
+	 * pass of a frame under once_per_frame -- is an SSD pass on the raw patch, LRSCV.cc:234-235) */
+	const bool mapped = bv.am == MTFHIP_AM_RSCV ? (rm && rm->map) : (bv.am == MTFHIP_AM_LRSCV && lm && lm->map);
+	const FusedKey k = fused_select(FUSED_ROUTE_LOOP, bv.am, bv.C, bv.ssm, fa.mode, fa.chained, fa.materialize, fa.fast_math, mapped);
+	if (!k.served) return;
+	if (k.am == MTFHIP_AM_RSCV) { launch_fused_rscv(bv, im, fa, partials, nblk, *rm, st); return; }
+	if (k.am == MTFHIP_AM_LRSCV) { launch_fused_lrscv(bv, im, fa, partials, nblk, *lm, st); return; }
+	if (k.mc) { launch_fused_mc(bv, im, fa, partials, nblk, st); return; }   /* MCSSD / MCNCC */
+	const dim3 g = grid2(nblk, bv.B);
+	const bool launched = fused_visit<FusedUnit<FUSED_ROUTE_LOOP, false, MTFHIP_AM_SSD, MTFHIP_AM_NCC>>(k, [&](auto AM, auto SSM, auto CH, auto MD, auto MAT, auto FAST) {
+		if constexpr (FAST())
+			MTFHIP_LAUNCH((k_fused_fast<AM(), SSM(), MD(), CH()>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
+		else if constexpr (AM() == MTFHIP_AM_NCC)
+			MTFHIP_LAUNCH((k_fused_ncc<SSM(), CH(), MD(), MAT()>), g, dim3(kBlock), 0, st, bv, im, fa, partials, nblk);
+		else {   /* (grid_regen: the lattice products, fused_lk_body) */
+			const size_t tab = MAT() && fa.grid_regen ? sizeof(double2) * (size_t)(fa.g_resx + fa.g_resy) : 0;
+			MTFHIP_LAUNCH((k_fused_ssd<SSM(), CH(), MD(), MAT()>), g, dim3(kBlock), tab, st, bv, im, fa, partials, nblk);
+		}
+	});
+	if (!launched) note_launch_error(hipErrorInvalidDeviceFunction, __FILE__, __LINE__);   /* (no kernel for this launch: an error, not a skipped pass) */
 }
 void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials,
 	int nblk, hipStream_t st, PhaseCtl pc) {

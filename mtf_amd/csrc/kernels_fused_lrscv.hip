@@ -24,45 +24,18 @@ __global__ __launch_bounds__(kBlock, MTFHIP_FAST_WAVES) void k_fused_lrscv_fast(
 /* the maps live in the dynamic LDS: R nb doubles, or 2 R with affine_mapping (api_lrscv.hip keeps them within 64 KB less the kernel's
  * static arrays) */
 static size_t lrscv_lds(const LrscvMap &lm) { return sizeof(double) * (size_t)(lm.affine ? 2 * lm.R : lm.R * lm.nb); }
-template <int SSM, bool CHAINED, int MODE>
-static void launch_lrscv_mat(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const LrscvMap &lm,
-	hipStream_t st) {
-	const dim3 g = grid2(nblk, bv.B);
-	const size_t lds = lrscv_lds(lm);
-	if (fa.materialize) MTFHIP_LAUNCH((k_fused_lrscv<SSM, CHAINED, MODE, true>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
-	else MTFHIP_LAUNCH((k_fused_lrscv<SSM, CHAINED, MODE, false>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
-}
-template <int SSM, bool CHAINED>
-static void launch_lrscv_mode(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const LrscvMap &lm,
-	hipStream_t st) {
-	if (fa.mode == 0) launch_lrscv_mat<SSM, CHAINED, 0>(bv, im, fa, partials, nblk, lm, st);
-	else if (fa.mode == 1) launch_lrscv_mat<SSM, CHAINED, 1>(bv, im, fa, partials, nblk, lm, st);
-	else launch_lrscv_mat<SSM, CHAINED, 2>(bv, im, fa, partials, nblk, lm, st);
-}
-/* the same choice of instantiation as launch_fused_fast (kernels_fused.hip): rscv_it_kind (api_rscv.hip) mirrors it for pass 1 (k_lrscv_hist) */
-template <int SSM>
-static void launch_lrscv_fast(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const LrscvMap &lm,
-	hipStream_t st) {
-	const dim3 g = grid2(nblk, bv.B);
-	const size_t lds = lrscv_lds(lm);
-	if (fa.mode == 2) MTFHIP_LAUNCH((k_fused_lrscv_fast<SSM, 2, true>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
-	else if (fa.mode == 0 && fa.chained) MTFHIP_LAUNCH((k_fused_lrscv_fast<SSM, 0, true>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
-	else if (fa.mode == 0) MTFHIP_LAUNCH((k_fused_lrscv_fast<SSM, 0, false>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
-	else if (fa.chained) MTFHIP_LAUNCH((k_fused_lrscv_fast<SSM, 1, true>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
-	else MTFHIP_LAUNCH((k_fused_lrscv_fast<SSM, 1, false>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
-}
 void launch_fused_lrscv(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const LrscvMap &lm,
 	hipStream_t st) {
-	const bool hom = bv.ssm == MTFHIP_SSM_HOMOGRAPHY;
-	if (fa.fast_math && !fa.materialize) {
-		if (hom) launch_lrscv_fast<MTFHIP_SSM_HOMOGRAPHY>(bv, im, fa, partials, nblk, lm, st);
-		else launch_lrscv_fast<MTFHIP_SSM_AFFINE>(bv, im, fa, partials, nblk, lm, st);
-		return;
-	}
-	if (hom && fa.chained) launch_lrscv_mode<MTFHIP_SSM_HOMOGRAPHY, true>(bv, im, fa, partials, nblk, lm, st);
-	else if (hom) launch_lrscv_mode<MTFHIP_SSM_HOMOGRAPHY, false>(bv, im, fa, partials, nblk, lm, st);
-	else if (fa.chained) launch_lrscv_mode<MTFHIP_SSM_AFFINE, true>(bv, im, fa, partials, nblk, lm, st);
-	else launch_lrscv_mode<MTFHIP_SSM_AFFINE, false>(bv, im, fa, partials, nblk, lm, st);
+	const dim3 g = grid2(nblk, bv.B);
+	const size_t lds = lrscv_lds(lm);
+	const FusedKey k = fused_select(FUSED_ROUTE_LOOP, MTFHIP_AM_LRSCV, bv.C, bv.ssm, fa.mode, fa.chained, fa.materialize, fa.fast_math);
+	const bool launched = fused_visit<FusedUnit<FUSED_ROUTE_LOOP, false, MTFHIP_AM_LRSCV>>(k, [&](auto, auto SSM, auto CH, auto MD, auto MAT, auto FAST) {
+		if constexpr (FAST())
+			MTFHIP_LAUNCH((k_fused_lrscv_fast<SSM(), MD(), CH()>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
+		else
+			MTFHIP_LAUNCH((k_fused_lrscv<SSM(), CH(), MD(), MAT()>), g, dim3(kBlock), lds, st, bv, im, fa, partials, nblk, lm);
+	});
+	if (!launched) note_launch_error(hipErrorInvalidDeviceFunction, __FILE__, __LINE__);   /* (no kernel for this launch: an error, not a skipped pass) */
 }
 
 } // namespace mtfhip

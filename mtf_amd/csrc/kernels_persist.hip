@@ -61,35 +61,15 @@ __global__ __launch_bounds__(kBlock, 1) void k_track_persist(BatchView bv, ImgVi
 	}
 }
 
-template <int AM, int SSM, bool FAST>
-static void launch_persist_mode(const BatchView &bv, const ImgView &im, const FusedArgs &fa, const mtfhip_sm_desc &sm, const TrackState &ts,
-	double *partials, int nblk, const PersistState &ps, int max_passes, hipStream_t st) {
-	const dim3 g = grid2(nblk, bv.B);
-#define MTFHIP_PERSIST(CH, MD) MTFHIP_LAUNCH((k_track_persist<AM, SSM, CH, MD, FAST>), g, dim3(kBlock), 0, st, bv, im, fa, sm, ts, partials, nblk, ps, max_passes)
-	if (fa.chained || (FAST && fa.mode == 2)) {   /* (ICLK takes no gradient: the tolerance-mode body is instantiated once for it) */
-		if (fa.mode == 0) MTFHIP_PERSIST(true, 0); else if (fa.mode == 1) MTFHIP_PERSIST(true, 1); else MTFHIP_PERSIST(true, 2);
-	} else {
-		if (fa.mode == 0) MTFHIP_PERSIST(false, 0); else if (fa.mode == 1) MTFHIP_PERSIST(false, 1); else MTFHIP_PERSIST(false, 2);
-	}
-#undef MTFHIP_PERSIST
-}
-template <int AM, bool FAST>
-static void launch_persist_ssm(const BatchView &bv, const ImgView &im, const FusedArgs &fa, const mtfhip_sm_desc &sm, const TrackState &ts,
-	double *partials, int nblk, const PersistState &ps, int max_passes, hipStream_t st) {
-	if (bv.ssm == MTFHIP_SSM_HOMOGRAPHY) launch_persist_mode<AM, MTFHIP_SSM_HOMOGRAPHY, FAST>(bv, im, fa, sm, ts, partials, nblk, ps, max_passes, st);
-	else launch_persist_mode<AM, MTFHIP_SSM_AFFINE, FAST>(bv, im, fa, sm, ts, partials, nblk, ps, max_passes, st);
-}
-/* fa.materialize must be 0 (the interface-visible arrays of an iteration are the two-launch loop's business) */
+/* fa.materialize must be 0 (FUSED_ROUTE_PERSIST, mtfhip_fused_dispatch.h) */
 void launch_track_persist(const BatchView &bv, const ImgView &im, const FusedArgs &fa, const mtfhip_sm_desc &sm, const TrackState &ts,
 	double *partials, int nblk, const PersistState &ps, int max_passes, hipStream_t st) {
-	const bool ncc = bv.am == MTFHIP_AM_NCC;
-	if (fa.fast_math) {
-		if (ncc) launch_persist_ssm<MTFHIP_AM_NCC, true>(bv, im, fa, sm, ts, partials, nblk, ps, max_passes, st);
-		else launch_persist_ssm<MTFHIP_AM_SSD, true>(bv, im, fa, sm, ts, partials, nblk, ps, max_passes, st);
-	} else {
-		if (ncc) launch_persist_ssm<MTFHIP_AM_NCC, false>(bv, im, fa, sm, ts, partials, nblk, ps, max_passes, st);
-		else launch_persist_ssm<MTFHIP_AM_SSD, false>(bv, im, fa, sm, ts, partials, nblk, ps, max_passes, st);
-	}
+	const dim3 g = grid2(nblk, bv.B);
+	const FusedKey k = fused_select(FUSED_ROUTE_PERSIST, bv.am, bv.C, bv.ssm, fa.mode, fa.chained, fa.materialize, fa.fast_math);
+	const bool launched = fused_visit<FusedUnit<FUSED_ROUTE_PERSIST, false, MTFHIP_AM_SSD, MTFHIP_AM_NCC>>(k, [&](auto AM, auto SSM, auto CH, auto MD, auto, auto FAST) {
+		MTFHIP_LAUNCH((k_track_persist<AM(), SSM(), CH(), MD(), FAST()>), g, dim3(kBlock), 0, st, bv, im, fa, sm, ts, partials, nblk, ps, max_passes);
+	});
+	if (!launched) note_launch_error(hipErrorInvalidDeviceFunction, __FILE__, __LINE__);   /* (no kernel for this launch: an error, not a skipped pass) */
 }
 
 } // namespace mtfhip

@@ -42,40 +42,18 @@ __global__ __launch_bounds__(kBlock) void k_track_step(BatchView bv, ImgView im,
 	else finish_track_body<true>(bv, sm, ts, partials, nblk, t);
 }
 
-template <int AM, int SSM, bool MAT, bool FAST>
-static void launch_step_mode(const BatchView &bv, const ImgView &im, const FusedArgs &fa, const mtfhip_sm_desc &sm, const TrackState &ts,
-	double *partials, int nblk, int *arrive, hipStream_t st) {
-	const dim3 g = grid2(nblk, bv.B);
-#define MTFHIP_STEP(CH, MD) MTFHIP_LAUNCH((k_track_step<AM, SSM, CH, MD, MAT, FAST>), g, dim3(kBlock), 0, st, bv, im, fa, sm, ts, partials, nblk, arrive)
-	if (fa.chained || (FAST && fa.mode == 2)) {   /* (ICLK takes no gradient: the tolerance-mode body is instantiated once for it) */
-		if (fa.mode == 0) MTFHIP_STEP(true, 0); else if (fa.mode == 1) MTFHIP_STEP(true, 1); else MTFHIP_STEP(true, 2);
-	} else {
-		if (fa.mode == 0) MTFHIP_STEP(false, 0); else if (fa.mode == 1) MTFHIP_STEP(false, 1); else MTFHIP_STEP(false, 2);
-	}
-#undef MTFHIP_STEP
+/* what this unit serves -- the two forms the device-side loop launches by default -- is FUSED_ROUTE_STEP of fused_select */
+static FusedKey step_key(const BatchView &bv, const FusedArgs &fa) {
+	return fused_select(FUSED_ROUTE_STEP, bv.am, bv.C, bv.ssm, fa.mode, fa.chained, fa.materialize, fa.fast_math);
 }
-template <int AM, bool MAT, bool FAST>
-static void launch_step_ssm(const BatchView &bv, const ImgView &im, const FusedArgs &fa, const mtfhip_sm_desc &sm, const TrackState &ts,
-	double *partials, int nblk, int *arrive, hipStream_t st) {
-	if (bv.ssm == MTFHIP_SSM_HOMOGRAPHY) launch_step_mode<AM, MTFHIP_SSM_HOMOGRAPHY, MAT, FAST>(bv, im, fa, sm, ts, partials, nblk, arrive, st);
-	else launch_step_mode<AM, MTFHIP_SSM_AFFINE, MAT, FAST>(bv, im, fa, sm, ts, partials, nblk, arrive, st);
-}
-/* the two forms the device-side loop launches by default: tolerance mode without materialised arrays (the lean loop), replay
- * arithmetic with them (the full loop); track_step_available() says which (fa) this unit serves */
-bool track_step_available(const BatchView &bv, const FusedArgs &fa) {
-	if (bv.C != 1) return false;
-	return (fa.fast_math && !fa.materialize) || (!fa.fast_math && fa.materialize);
-}
+bool track_step_available(const BatchView &bv, const FusedArgs &fa) { return step_key(bv, fa).served; }
 void launch_track_step(const BatchView &bv, const ImgView &im, const FusedArgs &fa, const mtfhip_sm_desc &sm, const TrackState &ts,
 	double *partials, int nblk, int *arrive, hipStream_t st) {
-	const bool ncc = bv.am == MTFHIP_AM_NCC;
-	if (fa.fast_math && !fa.materialize) {
-		if (ncc) launch_step_ssm<MTFHIP_AM_NCC, false, true>(bv, im, fa, sm, ts, partials, nblk, arrive, st);
-		else launch_step_ssm<MTFHIP_AM_SSD, false, true>(bv, im, fa, sm, ts, partials, nblk, arrive, st);
-	} else {
-		if (ncc) launch_step_ssm<MTFHIP_AM_NCC, true, false>(bv, im, fa, sm, ts, partials, nblk, arrive, st);
-		else launch_step_ssm<MTFHIP_AM_SSD, true, false>(bv, im, fa, sm, ts, partials, nblk, arrive, st);
-	}
+	const dim3 g = grid2(nblk, bv.B);
+	const bool launched = fused_visit<FusedUnit<FUSED_ROUTE_STEP, false, MTFHIP_AM_SSD, MTFHIP_AM_NCC>>(step_key(bv, fa), [&](auto AM, auto SSM, auto CH, auto MD, auto MAT, auto FAST) {
+		MTFHIP_LAUNCH((k_track_step<AM(), SSM(), CH(), MD(), MAT(), FAST()>), g, dim3(kBlock), 0, st, bv, im, fa, sm, ts, partials, nblk, arrive);
+	});
+	if (!launched) note_launch_error(hipErrorInvalidDeviceFunction, __FILE__, __LINE__);   /* (no kernel for this launch: an error, not a skipped pass) */
 }
 
 } // namespace mtfhip

@@ -439,12 +439,14 @@ static int push_warps(mtfhip_batch *b) {
 }
 
 /* the BatchView of a fused launch: a stale single-target warp goes into the kernel arguments instead of being uploaded */
-/* SCV is SSD on its re-mapped template, RSCV SSD on its mapped current patch: every SSD branch of the entry points serves them */
+/* SCV and LSCV are SSD on a re-mapped template, RSCV and LRSCV SSD on a mapped current patch: every SSD branch of the entry points serves
+ * them */
 static inline bool ssd_like(const mtfhip_batch *b) {
 	return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV ||
 		b->desc.am == MTFHIP_AM_LRSCV;
 }
-/* SCV and RSCV: an intensity map is rebuilt between the fused passes -- the one-launch, persistent and step loops do not take them */
+/* SCV, RSCV, LSCV and LRSCV: an intensity map is rebuilt between the fused passes -- the one-launch, persistent and step loops do not take
+ * them (fused_select, mtfhip_fused_dispatch.h) */
 static inline bool intensity_mapped(const mtfhip_batch *b) {
 	return b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV;
 }

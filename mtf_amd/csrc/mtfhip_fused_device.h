@@ -251,7 +251,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 	 * grid_regen_kernel names carry it -- the materialising SSD kernel whose time is its byte stream; the lean (tolerance-mode) kernels
 	 * are FP64 bound and the NCC ones sit at the register limit.  k_init_grid's point is (W0[0] nx + W0[1] ny) + W0[2] 1.0
 	 * with every product rounded on its own (grid_point_xy, no contraction), so the products that depend on the column alone and on the
-	 * row alone are tabulated once per workgroup in LDS (launch_fused_mat sizes it: (resx + resy) double2): a row costs two LDS reads
+	 * row alone are tabulated once per workgroup in LDS (launch_fused_ssd sizes it: (resx + resy) double2): a row costs two LDS reads
 	 * and four additions, and the loop keeps two scalars of the map (W0[2] 1.0, W0[5] 1.0) instead of the map and the lattice. */
 	constexpr bool GR_OK = grid_regen_kernel(AM, SSM, CHAINED, MODE, MAT) && !FAST && !PERSIST && !MC && !COHROW;
 	extern __shared__ double2 grid_tab[];   /* [resx] (W0[0] nx, W0[3] nx) | [resy] (W0[1] ny, W0[4] ny) -- RSCV: its map, [rm.nb] double */

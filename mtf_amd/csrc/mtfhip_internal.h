@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include "../../include/mtfhip.h"
+#include "mtfhip_fused_dispatch.h"
 
 namespace mtfhip {
 
@@ -59,13 +60,7 @@ constexpr int kGridTabMax = 2048; /* FusedArgs::grid_regen: columns + rows of th
  * first row's loads, which pays off in a streaming launch (64 x 200 x 200: 20 rows, 54.4 -> 49.4 us) and not in a latency-bound one
  * (one 200 x 200 target, 4 rows: 12.2 -> 12.8 us per iteration with it) */
 constexpr int kGridRegenMinRows = 8;
-/* the fused instantiations that carry the grid rebuild (FusedArgs::grid_regen): the materialising SSD launch, homography, chained
- * warp, FCLK or ESM -- the headline's kernel and its FCLK sibling, which keep their occupancy and stay clear of scratch with it
- * (-Rpass-analysis=kernel-resource-usage, profiles/r07_resource_usage.txt); the others (lean / NCC / affine / non-chained / ICLK)
- * would lose a wave per SIMD or spill, and read INIT_PTS */
-constexpr bool grid_regen_kernel(int am, int ssm, bool chained, int mode, bool mat) {
-	return am == MTFHIP_AM_SSD && ssm == MTFHIP_SSM_HOMOGRAPHY && chained && mode != 2 && mat;
-}
+/* (which instantiations carry the rebuild: grid_regen_kernel, mtfhip_fused_dispatch.h) */
 #ifndef MTFHIP_SLOTS
 #define MTFHIP_SLOTS 512          /* resident workgroups of the fused kernel: 256 CUs x 2 (2 waves/SIMD, 4-wave groups) */
 #endif
@@ -597,10 +592,7 @@ void launch_scv_update(const BatchView &bv, const ImgView &im, const ScvArgs &a,
 
 /* ---- RSCV: the current patch's intensity map of RSCV::updatePixVals (kernels_rscv.hip) ---- */
 constexpr int kRscvMaxBins = 256;
-/* how pass 1 obtains It_orig -- the expression of the fused pass it runs in front of, so that every pixel lands in the bin the fused
- * pass looks it up in: replay (MATH_REPLAY, every materialising launch); tolerance mode ICLK, chained FCLK / ESM, non-chained FCLK /
- * ESM (each with its own interior test, mtfhip_fused_device.h); or read from the It_orig buffer (per-function path) */
-enum { RSCV_IT_REPLAY = 0, RSCV_IT_FAST_ICLK = 1, RSCV_IT_FAST_CHAINED = 2, RSCV_IT_FAST_QSTEP = 3, RSCV_IT_FROM_BUF = 4 };
+/* (how pass 1 obtains It_orig: RSCV_IT_*, mtfhip_fused_dispatch.h) */
 struct RscvArgs {
 	int nb, kind;                /* n_bins, RSCV_IT_* */
 	double norm_mult, norm_add, grad_eps;

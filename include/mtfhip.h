@@ -161,7 +161,7 @@ int mtfhip_image_shape(mtfhip_ctx *ctx, int *rows, int *cols);
  * cv::Mat buffer, which the caller overwrites in place every frame, so upload must be
  * repeated per frame; `borrow` adopts a float32 image that is already in HBM.
  * A BORROWED image must stay unchanged until the next call of this library that synchronises with the context's stream
- * (mtfhip_ctx_synchronize, any call that returns results to the host): since r05 mtfhip_batch_init_template (its fused form) and
+ * (mtfhip_ctx_synchronize, any call that returns results to the host, mtfhip_image_keep_prev of the borrowed image): since r05 mtfhip_batch_init_template (its fused form) and
  * mtfhip_grid_reset(reinit) return with their sampling kernel still running.  Uploaded images are safe: the next upload is
  * ordered behind that kernel on the stream. */
 int mtfhip_image_upload(mtfhip_ctx *ctx, const float *host_img, int height, int width, int row_stride);
@@ -365,7 +365,9 @@ typedef struct mtfhip_grid_fb_desc {
 } mtfhip_grid_fb_desc;
 /* prev_img = curr_img.clone() (GridTracker.cc:241-243, :266): the current image of the context becomes its previous image.  An image
  * the context owns (mtfhip_image_upload / _preprocess) is kept without a copy -- the next frame goes to the other of two device
- * buffers --, a borrowed one is copied device-to-device on the context's stream. */
+ * buffers --, a borrowed one is copied device-to-device on the context's stream and the call returns when the copy is complete: it
+ * synchronises with the context's stream (see mtfhip_image_borrow), so the caller may write its next frame into the borrowed buffer
+ * as soon as the call has returned. */
 int mtfhip_image_keep_prev(mtfhip_ctx *ctx);
 int mtfhip_image_has_prev(mtfhip_ctx *ctx);
 /* setImage(prev_img) / setImage(curr_img) of every tracker on the context (GridTracker.cc:300, :304): current and previous image change

@@ -196,6 +196,8 @@ int mtfhip_image_keep_prev(mtfhip_ctx *c) {
 	}
 	HIP_TRY(hipMemcpy2DAsync(c->prev_owned, row * sizeof(float), c->img.data, (size_t)c->img.stride * sizeof(float), row * sizeof(float), (size_t)c->img.h,
 		hipMemcpyDeviceToDevice, c->stream));
+	/* a clone: the caller writes its next frame into the same buffer right after, on a stream of its own (as after mtfhip_image_upload) */
+	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->prev = ImgView{c->prev_owned, c->img.h, c->img.w, (int)row, c->img.channels};
 	return MTFHIP_OK;
 }

@@ -625,6 +625,50 @@ int mtfhip_batch_set_lrscv(mtfhip_batch *b, int n_sub_regions_x, int n_sub_regio
  * (map[b] = b before the first one) */
 int mtfhip_batch_lrscv_intensity_maps(mtfhip_batch *b, double *dst);
 
+/* ---- ssm.estimateWarpFromPts: the robust fit of the grid SSM to point pairs ---- */
+/* SSMEstimatorParams (SSM/include/mtf/SSM/SSMEstimatorParams.h:11-25; defaults SSMEstimatorParams.cc:5-13; the shipped values
+ * Config/modules.cfg:37-45 are method 1, thresh 5, 4 model points, 10000 iterations, 300 attempts, confidence 0.995, refine 1, 10 LM iterations) */
+enum { MTFHIP_EST_RANSAC = 0, MTFHIP_EST_LMEDS = 1, MTFHIP_EST_LEAST_SQUARES = 2 };   /* EstType SSMEstimatorParams.h:11 */
+enum { MTFHIP_EST_MAX_PTS = 1024, MTFHIP_EST_MAX_MODEL_PTS = 8 };
+typedef struct mtfhip_est_params {
+	int method;                   /* MTFHIP_EST_*; default RANSAC (SSMEstimatorParams.cc:5) */
+	double ransac_reproj_thresh;  /* default 10; <= 0 means 3 (SSMEstimatorParams.cc:9,54-56); a point is an inlier when err <= thresh^2 (SSMEstimator.cc:43-45) */
+	int n_model_pts;              /* default 4 (SSMEstimatorParams.cc:10); >= 4 for the homography, >= 3 for the affine SSM (HomographyEstimator.cc:12, AffineEstimator.cc:13) */
+	int max_iters;                /* default 2000 (SSMEstimatorParams.cc:6): RANSAC's initial niters SSMEstimator.cc:81, LMedS' cap :173 */
+	int max_subset_attempts;      /* default 300 (SSMEstimatorParams.cc:7): getSubset SSMEstimator.cc:234 */
+	double confidence;            /* default 0.995 (SSMEstimatorParams.cc:13): cvRANSACUpdateNumIters SSMEstimator.cc:50-71, LMedS :172 */
+	int refine;                   /* default 1 (SSMEstimatorParams.cc:11): the Levenberg-Marquardt refinement HomographyEstimator.cc:212-214 */
+	int lm_max_iters;             /* default 10 (SSMEstimatorParams.cc:12): LevMarq's iteration cap SSMEstimator.cc:348-349 */
+} mtfhip_est_params;
+/* estimateHomography / estimateAffine (HomographyEstimator.cc:166-228, AffineEstimator.cc:127-190) for n_sets independent point sets in ONE
+ * launch (a workgroup per set): sampling, runKernel, scoring, the reference's sequential accept / stop rule (SSMEstimator.cc:101-128,
+ * 172-213), the inlier mask, the re-fit on the inliers (RANSAC) and the LM refinement, all on the device and all FP64 except the
+ * reprojection errors, which the reference rounds to float (HomographyEstimator.cc:96).  Host pointers: one upload, one launch sequence, one
+ * synchronisation.
+ *   n_pts[s] pairs per set, n_model_pts <= n_pts[s] <= max_pts <= MTFHIP_EST_MAX_PTS (more: MTFHIP_ERR_NOT_IMPLEMENTED); in_pts / out_pts:
+ *   n_sets x max_pts x 2 floats (cv::Point2f); the model maps in_pts onto out_pts.
+ *   subsets != NULL: n_sets x n_hyp x n_model_pts point indices -- hypothesis k of a set uses row k as given and counts as found;
+ *   subsets == NULL: hypothesis k draws its own subset as getSubset does with checkPartialSubsets == false (SSMEstimator.cc:219-259:
+ *   u32 % count, a repeated index is redrawn, checkSubset :262-296 on both subsets, at most max_subset_attempts attempts) from
+ *   Philox4x32-10 keyed by (seed, k, attempt); the reference seeds from random_device (:22-24), so any stream conforms.
+ *   The rule walks hypotheses 0, 1, ... and never goes past n_hyp: pass n_hyp >= max_iters (RANSAC) or >= the LMedS count
+ *   clamp(cvRound(log(1 - confidence) / log(1 - 0.55^n_model_pts)), 3, max_iters) (:172-173) for the reference's own loop bounds.
+ * Outputs per set: state_update[8] in the SSM's own parameterisation (Homography.cc:889-896, Affine.cc:363-368; the affine SSM uses six, the
+ * rest is zero) -- of the ZERO matrix when the fit failed, i.e. (-1, 0, 0, 0, -1, 0, 0, 0) / (0, 0, -1, 0, 0, -1), as the reference returns
+ * (HomographyEstimator.cc:161-162); mask[max_pts]: 1 = inlier (all ones on a failure of the sampling, :190-193); info[4]: ok, the winning
+ * hypothesis (-1: none), the number of hypotheses the rule walked (`iter` when its loop ends), the number of ones in the mask;
+ * stats[2]: minMedian and sigma (LMedS, SSMEstimator.cc:207-209; else 0); subsets_used (may be NULL): n_sets x n_hyp x n_model_pts, the rows
+ * the evaluated hypotheses used, -1 where none was drawn.  A failed fit is an ordinary result (MTFHIP_OK with ok = 0). */
+int mtfhip_ssm_estimate_from_pts(mtfhip_ctx *ctx, int ssm, const mtfhip_est_params *params, int n_sets, const int *n_pts, int max_pts,
+	const float *in_pts, const float *out_pts, const int *subsets, int n_hyp, unsigned long long seed, double *state_update,
+	unsigned char *mask, int *info, double *stats, int *subsets_used);
+/* the same on device pointers, only enqueued on the context's stream (no copy, no synchronisation); host_n_pts: the host's copy of
+ * dev_n_pts for the argument checks (may be NULL: unchecked); dev_subsets (n_sets x n_hyp x n_model_pts, required) holds the caller's rows
+ * when subsets_given, else it receives the drawn ones (fill it with -1 first to tell the unevaluated rows) */
+int mtfhip_ssm_estimate_from_pts_dev(mtfhip_ctx *ctx, int ssm, const mtfhip_est_params *params, int n_sets, const int *dev_n_pts,
+	const int *host_n_pts, int max_pts, const float *dev_in_pts, const float *dev_out_pts, int *dev_subsets, int subsets_given, int n_hyp,
+	unsigned long long seed, double *dev_state_update, unsigned char *dev_mask, int *dev_info, double *dev_stats);
+
 #ifdef __cplusplus
 }
 #endif

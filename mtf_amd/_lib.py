@@ -16,6 +16,8 @@ SSM_HOMOGRAPHY, SSM_AFFINE = 0, 1
 SM_ESM, SM_FCLK, SM_ICLK = 0, 1, 2
 JAC_INIT, JAC_PIX, JAC_WARPED, JAC_APPROX = 0, 1, 2, 3
 MATH_REPLAY, MATH_FAST = 0, 1
+EST_RANSAC, EST_LMEDS, EST_LEAST_SQUARES = 0, 1, 2     # EstType SSMEstimatorParams.h:11
+EST_MAX_PTS, EST_MAX_MODEL_PTS = 1024, 8
 (BUF_I0, BUF_IT, BUF_DI0_DX, BUF_DIT_DX, BUF_DF_DI0, BUF_DF_DIT, BUF_J0, BUF_JT, BUF_JM,
  BUF_INIT_PTS, BUF_CURR_PTS, BUF_GRAD_PTS, BUF_INIT_Z, BUF_CURR_Z, BUF_INIT_HXY, BUF_CURR_HXY,
  BUF_D2I0_DX2, BUF_D2IT_DX2, BUF_HESS_PTS, BUF_D2I0_DP2, BUF_D2IT_DP2, BUF_D2IM_DP2) = range(22)
@@ -78,6 +80,31 @@ class GridFbDesc(C.Structure):
     _fields_ = [("fb_err_thresh", C.c_double), ("fb_reinit", C.c_int), ("n_model_pts", C.c_int)]
 
 
+class EstParams(C.Structure):
+    """mtfhip_est_params = SSMEstimatorParams (SSM/include/mtf/SSM/SSMEstimatorParams.h:11-25, defaults SSMEstimatorParams.cc:5-13)"""
+    _fields_ = [("method", C.c_int), ("ransac_reproj_thresh", C.c_double), ("n_model_pts", C.c_int), ("max_iters", C.c_int),
+                ("max_subset_attempts", C.c_int), ("confidence", C.c_double), ("refine", C.c_int), ("lm_max_iters", C.c_int)]
+
+
+def est_params(method=EST_RANSAC, ransac_reproj_thresh=10.0, n_model_pts=4, refine=True, max_iters=2000, max_subset_attempts=300,
+               confidence=0.995, lm_max_iters=10):
+    """SSMEstimatorParams with the class defaults (SSMEstimatorParams.cc:5-13, argument order :42-44 without use_boost_rng); the shipped
+    configuration (Config/modules.cfg:37-45) is est_params(EST_LMEDS, 5, 4, True, 10000, 300, 0.995, 10)"""
+    return EstParams(int(method), float(ransac_reproj_thresh), int(n_model_pts), int(max_iters), int(max_subset_attempts), float(confidence),
+                     int(bool(refine)), int(lm_max_iters))
+
+
+def est_n_hyp(p):
+    """the number of hypotheses the reference's loop can reach: max_iters for RANSAC (SSMEstimator.cc:81), the up-front count of LMedS
+    (:172-173, cvRound = round half to even), one for plain least squares"""
+    import math
+    if p.method == EST_RANSAC:
+        return p.max_iters
+    if p.method == EST_LMEDS:
+        return min(max(round(math.log(1 - p.confidence) / math.log(1 - math.pow(1 - 0.45, p.n_model_pts))), 3), p.max_iters)
+    return 1
+
+
 class NnDesc(C.Structure):
     """mtfhip_nn_desc: NN::generateDataset's parameters (SM/src/NT/NN.cc:56-84, 131-191)"""
     _fields_ = [("n_samples", C.c_int), ("additive_update", C.c_int), ("sigma", C.c_double * 8), ("mean", C.c_double * 8), ("seed", C.c_ulonglong)]
@@ -123,6 +150,7 @@ SYMBOLS = [
     "mtfhip_batch_grid_regen", "mtfhip_batch_set_scv", "mtfhip_batch_scv_intensity_map", "mtfhip_batch_set_rscv",
     "mtfhip_batch_rscv_intensity_map", "mtfhip_batch_set_lscv", "mtfhip_batch_lscv_intensity_maps", "mtfhip_batch_set_first_iter",
     "mtfhip_batch_first_iter", "mtfhip_batch_set_lrscv", "mtfhip_batch_lrscv_intensity_maps",
+    "mtfhip_ssm_estimate_from_pts", "mtfhip_ssm_estimate_from_pts_dev",
 ]
 
 
@@ -217,6 +245,10 @@ def lib():
         L.mtfhip_pf_set_distributions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mtfhip_pf_set_distr_draws.argtypes = [C.c_void_p, C.c_void_p]
         L.mtfhip_pf_get_distributions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mtfhip_ssm_estimate_from_pts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_ulonglong] + [C.c_void_p] * 5
+        L.mtfhip_ssm_estimate_from_pts_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 4
         L.mtfhip_timing_get_busy.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         _lib = L
     return _lib

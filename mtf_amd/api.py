@@ -56,6 +56,17 @@ def _close_all_contexts():
 atexit.register(_close_all_contexts)
 
 
+class EstResult:
+    """What mtfhip_ssm_estimate_from_pts returns for one point set: state_update (the SSM's own parameterisation; of the zero matrix
+    when ok is False), mask (uint8 per point), ok, winner (index of the winning hypothesis, -1: none), n_walked (hypotheses the
+    sequential rule walked), n_inliers, min_median / sigma (LMedS), subsets (n_hyp, n_model_pts; -1 rows were never evaluated)."""
+    __slots__ = ("state_update", "mask", "ok", "winner", "n_walked", "n_inliers", "min_median", "sigma", "subsets")
+
+    def __init__(self, *a):
+        for k, v in zip(self.__slots__, a):
+            setattr(self, k, v)
+
+
 class Context:
     """Device + stream + the current image (ImageBase::setCurrImg)."""
 
@@ -153,6 +164,49 @@ class Context:
         """Adopt a float32 image already resident in HBM (e.g. a torch tensor's data_ptr())."""
         self._img_keep = keep
         L.check(L.lib().mtfhip_image_borrow(self._h, C.c_void_p(dev_ptr), height, width, row_stride or width))
+
+    def estimate_warp_from_pts(self, ssm, in_pts, out_pts, est_params=None, subsets=None, seed=0, n_hyp=None, want_subsets=True):
+        """ssm.estimateWarpFromPts (SSM/src/Homography.cc:885-897, Affine.cc:359-369) on the device (mtfhip_ssm_estimate_from_pts): the
+        RANSAC / LMedS / least-squares fit of the SSM's warp to in_pts -> out_pts with SSMEstimatorParams `est_params` (_lib.est_params(...);
+        default: the class defaults).  One set: in_pts / out_pts (n, 2); several: lists of such arrays (different lengths allowed) --
+        one launch for all of them, an EstResult per set.  subsets: the (n_hyp, n_model_pts) index rows the hypotheses use (one array,
+        or one per set), default: drawn on the device from `seed`.  n_hyp: how far the rule may walk (default: the reference's bound)."""
+        p = est_params if est_params is not None else L.est_params()
+        single = not isinstance(in_pts, (list, tuple))
+        ins = [in_pts] if single else list(in_pts)
+        outs = [out_pts] if single else list(out_pts)
+        ins = [np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 2)) for a in ins]
+        outs = [np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 2)) for a in outs]
+        if len(ins) != len(outs) or not ins or any(a.shape != b.shape for a, b in zip(ins, outs)):
+            raise L.InvalidArgument(-1, "estimate_warp_from_pts: in_pts and out_pts must pair up")
+        S = len(ins)
+        n_pts = np.array([len(a) for a in ins], dtype=np.int32)
+        max_pts = max(int(n_pts.max()), 1)
+        pin, pout = np.zeros((S, max_pts, 2), dtype=np.float32), np.zeros((S, max_pts, 2), dtype=np.float32)
+        for s in range(S):
+            pin[s, :n_pts[s]], pout[s, :n_pts[s]] = ins[s], outs[s]
+        mp = p.n_model_pts
+        sub = None
+        if subsets is not None:
+            subs = [subsets] * S if (single or not isinstance(subsets, (list, tuple))) else list(subsets)
+            subs = [np.asarray(q, dtype=np.int32).reshape(-1, mp) for q in subs]
+            if len(subs) != S or any(len(q) != len(subs[0]) for q in subs):
+                raise L.InvalidArgument(-1, "estimate_warp_from_pts: one subset list per set, all of one length")
+            sub = np.ascontiguousarray(np.stack(subs))
+            n_hyp = sub.shape[1]
+        elif n_hyp is None:
+            n_hyp = L.est_n_hyp(p)
+        n_hyp = max(int(n_hyp), 1)
+        upd, mask = np.zeros((S, 8)), np.zeros((S, max_pts), dtype=np.uint8)
+        info, stats = np.zeros((S, 4), dtype=np.int32), np.zeros((S, 2))
+        used = np.empty((S, n_hyp, mp), dtype=np.int32) if want_subsets else None
+        L.check(L.lib().mtfhip_ssm_estimate_from_pts(self._h, int(ssm), C.byref(p), S, _p(n_pts), max_pts, _p(pin), _p(pout),
+                                                     _p(sub) if sub is not None else None, n_hyp, int(seed), _p(upd), _p(mask), _p(info), _p(stats),
+                                                     _p(used) if used is not None else None))
+        ns = 8 if ssm == SSM_HOMOGRAPHY else 6
+        res = [EstResult(upd[s, :ns].copy(), mask[s, :n_pts[s]].copy(), bool(info[s, 0]), int(info[s, 1]), int(info[s, 2]), int(info[s, 3]),
+                         float(stats[s, 0]), float(stats[s, 1]), used[s].copy() if used is not None else None) for s in range(S)]
+        return res[0] if single else res
 
     def timing(self, on=True):
         """on: False/0 off, True/1 every launch, n > 1 every n-th launch of a kernel family"""

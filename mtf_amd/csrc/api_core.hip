@@ -84,6 +84,7 @@ void mtfhip_ctx_destroy(mtfhip_ctx *c) {
 		}
 		if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
 		if (c->d_phase) (void)hipFree(c->d_phase);
+		if (c->est_ws) (void)hipFree(c->est_ws);
 		if (c->ev_ref) (void)hipEventDestroy(c->ev_ref);
 		if (c->own_stream) (void)hipStreamDestroy(c->stream);
 	} catch (...) {

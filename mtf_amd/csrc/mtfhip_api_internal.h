@@ -152,6 +152,7 @@ struct mtfhip_ctx {
 	hipEvent_t ev_ref = nullptr;   /* recorded by timing_reset: origin of Timer::spans */
 	std::vector<hipEvent_t> free_events;
 	std::vector<struct mtfhip_batch *> batches;   /* live batches: deferred work is flushed before the image changes */
+	unsigned char *est_ws = nullptr; size_t est_ws_capacity = 0;   /* mtfhip_ssm_estimate_from_pts: device staging of its arguments and results */
 };
 
 struct TimedScope {

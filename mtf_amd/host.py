@@ -71,6 +71,7 @@ def lib():
         H.mtfhost_grid_set_estimator.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         H.mtfhost_grid_call.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         H.mtfhost_grid_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        H.mtfhost_grid_set_est_params.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_ulonglong]
         _h = H
     return _h
 
@@ -325,7 +326,9 @@ class CppGridTracker:
     def __init__(self, grid_size=10, patch_size=10, patch_sm=_lib.SM_ICLK, patch_am=_lib.AM_NCC, patch_ssm=_lib.SSM_AFFINE,
                  grid_ssm=_lib.SSM_HOMOGRAPHY, reset_at_each_frame=1, dyn_patch_size=0, patch_centroid_inside=1, max_iters=30, epsilon=1e-4,
                  hess_type=-1, leven_marq=0, device=0, estimator=None, grid_size_y=None, patch_size_y=None, fb_err_thresh=0.0, fb_reinit=1,
-                 n_model_pts=4):
+                 n_model_pts=4, est_params=None, est_seed=1):
+        # est_params (_lib.est_params(...)): mtf::hip::Grid::setEstimatorParams -- the device RANSAC / LMedS estimator instead of the
+        # least-squares fit / the callback, with pix_mask() and est_ok / est_info() after every update
         gy, py = grid_size_y or grid_size, patch_size_y or patch_size
         h = lib().mtfhost_grid_create(grid_size, gy, patch_size, py, reset_at_each_frame, dyn_patch_size, patch_centroid_inside, patch_sm,
                                       patch_am, patch_ssm, grid_ssm, max_iters, epsilon, hess_type, leven_marq, device, float(fb_err_thresh),
@@ -335,7 +338,12 @@ class CppGridTracker:
         self._h = C.c_void_p(h)
         self.n, self.S = grid_size * gy, 8 if grid_ssm == _lib.SSM_HOMOGRAPHY else 6
         self._img, self._cb = None, None
-        if estimator is not None:
+        self.est_params = est_params
+        if est_params is not None:
+            p = est_params
+            _check(lib().mtfhost_grid_set_est_params(self._h, p.method, p.ransac_reproj_thresh, p.n_model_pts, p.refine, p.max_iters,
+                                                     p.max_subset_attempts, p.confidence, p.lm_max_iters, int(est_seed)))
+        elif estimator is not None:
             S = self.S
 
             def cb(_user, cnt, prev, curr, out):
@@ -400,6 +408,24 @@ class CppGridTracker:
     def fb_err_mask(self):
         return self._get(8, self.n).astype(bool)
 
+    def pix_mask(self):
+        return self._get(9, self.n).astype(np.uint8)
+
+    def est_info(self):
+        """the device estimator's report of the last update: ok, winner, n_walked, n_inliers, min_median, sigma"""
+        v = self._get(10, 6)
+        return dict(ok=bool(v[0]), winner=int(v[1]), n_walked=int(v[2]), n_inliers=int(v[3]), min_median=float(v[4]), sigma=float(v[5]))
+
+    @property
+    def est_ok(self):
+        return self.est_info()["ok"]
+
+    def est_pairs(self):
+        """(in_pts (m, 2), out_pts (m, 2), seed) of the last fit, float32"""
+        m, seed = self._get(11, 2)
+        v = self._get(12, 4 * int(m)).reshape(int(m), 4).astype(np.float32)
+        return v[:, :2].copy(), v[:, 2:].copy(), int(seed)
+
     def patch_iters(self):
         return self._get(5, self.n).astype(np.int32)
 
@@ -423,3 +449,6 @@ class CppGridTracker:
         fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         _check(fn(self._h, int(what), int(n_frames), c.ctypes.data_as(C.c_void_p), C.byref(us)))
         return us.value
+
+
+GridTracker = CppGridTracker   # mtf::hip::Grid under the name the Python driver (sm.GridTracker) uses

@@ -103,12 +103,17 @@ void Grid::update() {
 		std::vector<GridPt> pm(n_masked), cm(n_masked);
 		for (int k = 0; k < n_masked; ++k) { pm[k].x = prev_masked[2 * k]; pm[k].y = prev_masked[2 * k + 1]; cm[k].x = curr_masked[2 * k]; cm[k].y = curr_masked[2 * k + 1]; }
 		for (int k = 0; k < n; ++k) { curr_pts[k].x = cen[2 * k]; curr_pts[k].y = cen[2 * k + 1]; fb_prev_pts[k].x = fb_cen[2 * k]; fb_prev_pts[k].y = fb_cen[2 * k + 1]; }
-		estimator(ssm_update, pm, cm);                                                     /* :334-335 */
+		estimate(pm, cm);                                                                  /* :332-334 */
+		if (device_estimator) {                                                            /* :335-340 */
+			int est_pt_id = 0;
+			for (int k = 0; k < n; ++k) pix_mask[k] = fb_err_mask[k] ? pix_mask_est[est_pt_id++] : 0;
+		}
 	} else {
 		HipPair::check(mtfhip_grid_frame(b, &d, &gd, have_pending ? pending_region.data() : nullptr, n_iters.data(), patch_regions.data(), cen.data()));
 		have_pending = false;
 		for (int k = 0; k < n; ++k) { curr_pts[k].x = cen[2 * k]; curr_pts[k].y = cen[2 * k + 1]; }
-		estimator(ssm_update, prev_pts, curr_pts);                                         /* :267 */
+		estimate(prev_pts, curr_pts);                                                      /* :269 */
+		if (device_estimator) pix_mask = pix_mask_est;
 	}
 	/* :270-272 ssm.applyWarpToCorners(opt_warped_corners, ssm.getCorners(), ssm_update); ssm.setCorners(opt_warped_corners) */
 	CornersT warped;
@@ -116,6 +121,25 @@ void Grid::update() {
 	region = warped;
 	if (params.reset_at_each_frame) resetTrackers(reinit_at_each_frame);                   /* :273-274 */
 	else prev_pts = curr_pts;                                                              /* :275-280 */
+}
+
+void Grid::setEstimatorParams(const SSMEstimatorParams &ep, unsigned long long seed) {
+	const int min_mp = grid_ssm == MTFHIP_SSM_HOMOGRAPHY ? 4 : 3;
+	if (ep.n_model_pts < min_mp || ep.n_model_pts > MTFHIP_EST_MAX_MODEL_PTS) throw utils::InvalidArgument("GridTracker :: est_params.n_model_pts out of range");
+	if (n > MTFHIP_EST_MAX_PTS) throw utils::InvalidArgument("GridTracker :: more patches than the device estimator fits in one set");
+	if (n < ep.n_model_pts) throw utils::InvalidArgument("GridTracker :: fewer patches than est_params.n_model_pts");
+	est_params = ep; est_seed = seed; device_estimator = true;
+	fbd.n_model_pts = ep.n_model_pts;
+	pix_mask.assign(n, 1);
+}
+
+/* ssm.estimateWarpFromPts(ssm_update, mask, in_pts, out_pts, est_params): the device estimator, or the callback */
+void Grid::estimate(const std::vector<GridPt> &a, const std::vector<GridPt> &c) {
+	if (!device_estimator) { estimator(ssm_update, a, c); return; }
+	est_in = a; est_out = c;
+	pix_mask_est.resize(a.size());
+	est_seed_used = est_seed++;
+	estimateWarpFromPts(ctx, grid_ssm, ssm_update.data(), pix_mask_est.data(), a.data(), c.data(), (int)a.size(), est_params, est_seed_used, &est_info);
 }
 
 /* all-points least squares: affine = two 3-unknown normal systems; homography = normalised DLT as an 8 x 8 normal system with

@@ -9,8 +9,9 @@
  * TrackerBase-shaped: setImage / initialize / update / setRegion / getRegion with the reference's parameter block.
  *
  * The robust fit of the grid SSM to the patch centroids -- ssm.estimateWarpFromPts (SSM/src/Homography.cc:885-897, Affine.cc:359-369 ->
- * utils::estimateHomography / estimateAffine: RANSAC / LMedS; SURVEY.md section 2: out of scope) -- is a std::function the
- * maintainer points at the SSM's own estimateWarpFromPts; the default is an all-points least-squares fit.
+ * utils::estimateHomography / estimateAffine: RANSAC / LMedS) -- runs on the device once setEstimatorParams() has been called
+ * (mtfhip_ssm_estimate_from_pts), with the reference's pix_mask (GridTracker.cc:335-340).  Without that call the
+ * fit is a std::function (setEstimator) whose default is an all-points least-squares fit, as before.
  */
 #ifndef MTF_AMD_HOST_DEVICE_GRID_H
 #define MTF_AMD_HOST_DEVICE_GRID_H
@@ -23,11 +24,7 @@
 
 namespace mtf {
 
-#ifdef MTF_AMD_USE_OPENCV
-typedef cv::Point2f GridPt;
-#else
-struct GridPt { float x = 0, y = 0; };   /* cv::Point2f (GridTracker.h:102-103) */
-#endif
+typedef EstPt GridPt;   /* cv::Point2f (GridTracker.h:102-103) */
 
 /* GridTrackerParams (SM/src/GridTracker.cc:20-94); class defaults GridTracker.h:8-24 / Config/parameters.h:505-512 */
 struct GridTrackerParams {
@@ -74,6 +71,18 @@ public:
 	void setRegion(const CornersT &corners);    /* :287-292 */
 	const CornersT &getRegion() { return region; }
 	void setEstimator(Estimator e) { estimator = e; }
+	/* est_params of GridTracker (GridTracker.h:93, Config/modules.cfg:37-45): the device estimator takes the place of the callback.  Frame f
+	 * (counted from this call) draws its subsets from seed + f.  est_params.n_model_pts also becomes the count the forward-backward mask is
+	 * filled up to (GridTracker.cc:321). */
+	void setEstimatorParams(const SSMEstimatorParams &est_params, unsigned long long seed = 1);
+	const std::vector<unsigned char> &getPixMask() const { return pix_mask; }   /* one byte per patch; all ones before the first update */
+	bool estimatorOk() const { return est_info.ok; }
+	int estimatorWalked() const { return est_info.n_walked; }
+	const EstimatorInfo &getEstimatorInfo() const { return est_info; }
+	/* the point pairs the last update() handed the estimator and the seed it drew from (for a replay of the fit) */
+	const std::vector<GridPt> &getEstInPts() const { return est_in; }
+	const std::vector<GridPt> &getEstOutPts() const { return est_out; }
+	unsigned long long getEstSeed() const { return est_seed_used; }
 
 	const std::vector<GridPt> &getPrevPts() const { return prev_pts; }
 	const std::vector<GridPt> &getCurrPts() const { return curr_pts; }
@@ -106,6 +115,13 @@ private:
 	std::vector<double> patch_corners, patch_regions;
 	VectorXd ssm_update;
 	Estimator estimator;
+	bool device_estimator = false;
+	SSMEstimatorParams est_params;
+	unsigned long long est_seed = 1, est_seed_used = 0;
+	EstimatorInfo est_info;
+	std::vector<unsigned char> pix_mask, pix_mask_est;
+	std::vector<GridPt> est_in, est_out;
+	void estimate(const std::vector<GridPt> &in_pts, const std::vector<GridPt> &out_pts);
 	void resetTrackers(bool reinit);
 	static void leastSquaresFit(int ssm, VectorXd &state_update, const std::vector<GridPt> &in_pts, const std::vector<GridPt> &out_pts);
 };

@@ -284,6 +284,28 @@ void HipSSM::estimateWarpFromCorners(VectorXd &out, const CornersT &in, const Co
 	if (out.size() != p->S) throw utils::InvalidArgument("estimateWarpFromCorners: state update has invalid size");   /* validate_ssm_state */
 	HipPair::check(mtfhip_ssm_estimate_warp_from_corners(p->ssm, in.data(), oc.data(), out.data()));
 }
+void estimateWarpFromPts(mtfhip_ctx *ctx, int ssm, double *state_update, unsigned char *mask, const EstPt *in_pts, const EstPt *out_pts, int n_pts,
+	const SSMEstimatorParams &est_params, unsigned long long seed, EstimatorInfo *info) {
+	static_assert(sizeof(EstPt) == 2 * sizeof(float), "EstPt is two packed floats");
+	const mtfhip_est_params d = est_params.desc();
+	/* the rule never walks past max_iters hypotheses (LMedS: its own, smaller count); plain least squares draws none */
+	const int n_hyp = d.method == MTFHIP_EST_LEAST_SQUARES ? 1 : d.max_iters;
+	double upd[8], stats[2];
+	int inf[4];
+	HipPair::check(mtfhip_ssm_estimate_from_pts(ctx, ssm, &d, 1, &n_pts, n_pts, reinterpret_cast<const float *>(in_pts), reinterpret_cast<const float *>(out_pts),
+		nullptr, n_hyp, seed, upd, mask, inf, stats, nullptr));
+	const int S = ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6;
+	for (int k = 0; k < S; ++k) state_update[k] = upd[k];
+	if (info) { info->ok = inf[0] != 0; info->winner = inf[1]; info->n_walked = inf[2]; info->n_inliers = inf[3]; info->min_median = stats[0]; info->sigma = stats[1]; }
+}
+
+void HipSSM::estimateWarpFromPts(VectorXd &out, std::vector<unsigned char> &mask, const std::vector<EstPt> &in_pts, const std::vector<EstPt> &out_pts,
+	const SSMEstimatorParams &est_params) {
+	if (out.size() != p->S) throw utils::InvalidArgument("estimateWarpFromPts: state update has invalid size");
+	if (in_pts.size() != out_pts.size() || in_pts.empty()) throw utils::InvalidArgument("estimateWarpFromPts: the point lists must pair up");
+	mask.resize(in_pts.size());   /* _mask.create(n_pts, 1, CV_8U) HomographyEstimator.cc:157 */
+	hip::estimateWarpFromPts(p->ctx, p->ssm, out.data(), mask.data(), in_pts.data(), out_pts.data(), (int)in_pts.size(), est_params, est_seed++, &est_info);
+}
 int HipSSM::gradBuffer(const PixGradT &g) {
 	if (g.data() == p->init_grad_key) return MTFHIP_BUF_DI0_DX;
 	if (g.data() == p->curr_grad_key) return MTFHIP_BUF_DIT_DX;

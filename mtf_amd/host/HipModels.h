@@ -14,6 +14,7 @@
 
 #include "AppearanceModel.h"
 #include "StateSpaceModel.h"
+#include "SSMEstimatorParams.h"
 #include "../../include/mtfhip.h"
 
 namespace mtf {
@@ -267,6 +268,12 @@ public:
 	void getIdentityWarp(VectorXd &identity_warp) override;
 	void composeWarps(VectorXd &composed, const VectorXd &state_1, const VectorXd &state_2) override;
 	void estimateWarpFromCorners(VectorXd &state_update, const CornersT &in_corners, const CornersT &out_corners) override;
+	/* the robust fit to point pairs (Homography.cc:885-897, Affine.cc:359-369) with the reference's signature, on the device
+	 * (mtfhip_ssm_estimate_from_pts); every call draws its subsets from the next seed (setEstimatorSeed fixes the first) */
+	void estimateWarpFromPts(VectorXd &state_update, std::vector<unsigned char> &mask, const std::vector<EstPt> &in_pts, const std::vector<EstPt> &out_pts,
+		const SSMEstimatorParams &est_params);
+	void setEstimatorSeed(unsigned long long seed) { est_seed = seed; }
+	const EstimatorInfo &getEstimatorInfo() const { return est_info; }
 	/* stochastic sampler (ProjectiveBase.cc:163-317, Homography.cc:899-942) on the host, one state per call as the interface
 	 * has it -- what the literal nt::PF / nt::NN loops call.  The device filter (hip::PF, mtfhip_pf_*) generates all particles
 	 * of an iteration in one launch instead.  The reference draws from boost::mt11213b seeded by random_device; here
@@ -303,6 +310,8 @@ private:
 	VectorXd sampler_sigma, sampler_mean;
 	bool corner_based_sampling = true, sampler_ready = false;
 	int pt_based_sampling = 0;
+	unsigned long long est_seed = 1;
+	EstimatorInfo est_info;
 	[[noreturn]] void affineAdditiveRefused(const char *fn) const;
 	struct Rng;
 	std::shared_ptr<Rng> rng;

@@ -342,6 +342,18 @@ int mtfhost_grid_set_estimator(mtfhost_grid *h, mtfhost_grid_estimator est, void
 	});
 	return 0;
 }
+/* hip::Grid::setEstimatorParams: SSMEstimatorParams field by field (method: 0 RANSAC, 1 LeastMedian, 2 LeastSquares) */
+int mtfhost_grid_set_est_params(mtfhost_grid *h, int method, double ransac_reproj_thresh, int n_model_pts, int refine, int max_iters, int max_subset_attempts,
+	double confidence, int lm_max_iters, unsigned long long seed) {
+	try {
+		if (!h) { g_err = "NULL grid"; return -1; }
+		if (method < 0 || method > 2) { g_err = "Invalid estimation method specified"; return -1; }
+		const SSMEstimatorParams ep(static_cast<SSMEstimatorParams::EstType>(method), ransac_reproj_thresh, n_model_pts, refine != 0, max_iters, max_subset_attempts,
+			false, confidence, lm_max_iters);
+		h->g->setEstimatorParams(ep, seed);
+		return 0;
+	} catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
 /* what: 0 setImage(img) 1 initialize(corners) 2 update() 3 setRegion(corners) */
 int mtfhost_grid_call(mtfhost_grid *h, int what, const double *corners, const float *img, int rows, int cols, int step) {
 	try {
@@ -359,7 +371,9 @@ int mtfhost_grid_call(mtfhost_grid *h, int what, const double *corners, const fl
 	catch (const std::exception &e) { g_err = e.what(); return -2; }
 }
 /* what: 0 region (8) 1 patch corners of the last reset (n x 8) 2 prev_pts (n x 2) 3 curr_pts (n x 2) 4 ssm_update (S) 5 patch iteration
- * counts (n, as doubles) 6 the patch trackers' regions after the last update (n x 8) 7 fb_prev_pts (n x 2) 8 fb_err_mask (n, 0 / 1) */
+ * counts (n, as doubles) 6 the patch trackers' regions after the last update (n x 8) 7 fb_prev_pts (n x 2) 8 fb_err_mask (n, 0 / 1)
+ * 9 pix_mask (n, 0 / 1) 10 the device estimator's report (6: ok, winner, walked, inliers, minMedian, sigma) 11 the number m of point pairs the
+ * last fit used and its seed (2) 12 those pairs (m x 4: in x, in y, out x, out y) */
 int mtfhost_grid_get(mtfhost_grid *h, int what, double *dst) {
 	try {
 		hip::Grid &g = *h->g;
@@ -373,6 +387,10 @@ int mtfhost_grid_get(mtfhost_grid *h, int what, double *dst) {
 		case 6: std::memcpy(dst, g.getPatchRegions().data(), sizeof(double) * g.getPatchRegions().size()); break;
 		case 7: for (size_t i = 0; i < g.getFbPrevPts().size(); ++i) { dst[2 * i] = g.getFbPrevPts()[i].x; dst[2 * i + 1] = g.getFbPrevPts()[i].y; } break;
 		case 8: for (size_t i = 0; i < g.getFbErrMask().size(); ++i) dst[i] = g.getFbErrMask()[i]; break;
+		case 9: for (size_t i = 0; i < g.getPixMask().size(); ++i) dst[i] = g.getPixMask()[i]; break;
+		case 10: { const hip::EstimatorInfo &e = g.getEstimatorInfo(); dst[0] = e.ok; dst[1] = e.winner; dst[2] = e.n_walked; dst[3] = e.n_inliers; dst[4] = e.min_median; dst[5] = e.sigma; break; }
+		case 11: dst[0] = (double)g.getEstInPts().size(); dst[1] = (double)g.getEstSeed(); break;
+		case 12: for (size_t i = 0; i < g.getEstInPts().size(); ++i) { dst[4 * i] = g.getEstInPts()[i].x; dst[4 * i + 1] = g.getEstInPts()[i].y; dst[4 * i + 2] = g.getEstOutPts()[i].x; dst[4 * i + 3] = g.getEstOutPts()[i].y; } break;
 		default: g_err = "mtfhost_grid_get: unknown selector"; return -1;
 		}
 		return 0;

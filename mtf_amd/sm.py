@@ -357,13 +357,21 @@ class GridTracker:
     frame's update every patch tracker -- re-initialised at its tracked location when fb_reinit (shipped 1) -- runs on the PREVIOUS frame,
     and the patches whose round trip misses their starting centroid by more than the threshold are left out of the fit (filled up to
     n_model_pts = est_params.n_model_pts, shipped 4).
-    The robust fit of the grid SSM to the patch centroids (estimateWarpFromPts: RANSAC / LMedS) is out of scope (SURVEY.md section
-    2): `estimator(prev_pts, curr_pts) -> state update` is pluggable, default an all-points least-squares fit."""
+    The fit of the grid SSM to the patch centroids (ssm.estimateWarpFromPts): with est_params (the reference's SSMEstimatorParams,
+    _lib.est_params) the device RANSAC / LMedS estimator, with `pix_mask` and `est_ok` after every update; without it
+    `estimator(prev_pts, curr_pts) -> state update` is pluggable, default an all-points least-squares fit."""
 
     def __init__(self, ctx, grid_size=10, patch_size=10, am=L.AM_NCC, ssm=L.SSM_AFFINE, max_iters=30, epsilon=1e-4, sm=L.SM_ICLK,
                  reset_at_each_frame=1, dyn_patch_size=0, patch_centroid_inside=1, grid_ssm=L.SSM_HOMOGRAPHY, estimator=None,
-                 grid_size_y=None, patch_size_y=None, fb_err_thresh=0.0, fb_reinit=1, n_model_pts=4, **sm_params):
+                 grid_size_y=None, patch_size_y=None, fb_err_thresh=0.0, fb_reinit=1, n_model_pts=4, est_params=None, est_seed=1, **sm_params):
         self.ctx = ctx
+        # est_params (_lib.est_params(...) = SSMEstimatorParams): the device RANSAC / LMedS estimator (Context.estimate_warp_from_pts) takes the
+        # place of `estimator`; pix_mask / est_ok / est_result follow every update (GridTracker.cc:269, 332-340); frame f draws from est_seed + f
+        self.est_params, self.est_seed = est_params, int(est_seed)
+        self.pix_mask = self.est_result = self.est_in_pts = self.est_out_pts = None
+        self.est_ok = None
+        if est_params is not None:
+            n_model_pts = est_params.n_model_pts              # the forward-backward mask is filled up to est_params.n_model_pts :321
         self.fb = L.GridFbDesc(float(fb_err_thresh), int(bool(fb_reinit)), int(n_model_pts)) if fb_err_thresh > 0 else None   # enable_fb_err_est :186-190
         self.fb_prev_pts = self.fb_err_mask = None
         self.grid_size, self.patch_size = grid_size, patch_size
@@ -381,6 +389,16 @@ class GridTracker:
         self.prev_pts = np.zeros((self.n, 2), dtype=np.float32)
         self.curr_pts = np.zeros((self.n, 2), dtype=np.float32)
         self.ssm_update = np.zeros(8 if grid_ssm == L.SSM_HOMOGRAPHY else 6)
+        if est_params is not None:
+            self.pix_mask = np.ones(self.n, dtype=np.uint8)
+
+    def _estimate(self, in_pts, out_pts):
+        """ssm.estimateWarpFromPts(ssm_update, mask, in_pts, out_pts, est_params) on the device"""
+        self.est_in_pts, self.est_out_pts = in_pts.copy(), out_pts.copy()
+        r = self.ctx.estimate_warp_from_pts(self.grid_ssm, in_pts, out_pts, self.est_params, seed=self.est_seed)
+        self.est_seed += 1
+        self.est_result, self.est_ok = r, r.ok
+        return r
 
     def res(self):
         """GridTrackerParams::updateRes: the sampling resolution of the grid SSM"""
@@ -450,13 +468,23 @@ class GridTracker:
             self.curr_pts[...] = r["centroids"]
             self.fb_prev_pts, self.fb_err_mask = r["fb_prev_pts"], r["fb_err_mask"]
             self.ctx.keep_prev()
-            upd = np.asarray(self.estimator(r["prev_masked"].astype(np.float64), r["curr_masked"].astype(np.float64)), dtype=np.float64)
+            if self.est_params is not None:
+                e = self._estimate(r["prev_masked"], r["curr_masked"])
+                upd = e.state_update
+                self.pix_mask = np.zeros(self.n, dtype=np.uint8)                # :335-340
+                self.pix_mask[np.asarray(self.fb_err_mask, dtype=bool)] = e.mask
+            else:
+                upd = np.asarray(self.estimator(r["prev_masked"].astype(np.float64), r["curr_masked"].astype(np.float64)), dtype=np.float64)
         else:
             n, _, cen = self.tracker.batch.grid_frame(self.gd, self.tracker.sm, self._pending_region)
             self._pending_region = None
             self.tracker.n_iters = n.copy()
             self.curr_pts[...] = cen
-            upd = np.asarray(self.estimator(self.prev_pts.astype(np.float64), self.curr_pts.astype(np.float64)), dtype=np.float64)
+            if self.est_params is not None:
+                e = self._estimate(self.prev_pts, self.curr_pts)
+                upd, self.pix_mask = e.state_update, e.mask.copy()
+            else:
+                upd = np.asarray(self.estimator(self.prev_pts.astype(np.float64), self.curr_pts.astype(np.float64)), dtype=np.float64)
         self.ssm_update = upd
         from .api import apply_warp_to_pts
         # ssm.applyWarpToCorners(opt_warped_corners, ssm.getCorners(), ssm_update); ssm.setCorners(opt_warped_corners) :270-272

@@ -528,7 +528,7 @@ int mtfhip_comm_create_detached(int rank, int world, int device, mtfhip_comm **o
 /* the partition mtfhip_pf_set_comm uses (host arithmetic, no device): rank's block [lo, lo + count), per_rank = ceil(n / world) */
 int mtfhip_pf_shard_bounds(int n_particles, int world, int rank, int *lo, int *count, int *per_rank);
 
-/* ---- NN-SM dataset generation (the second batch axis of the path; the search itself stays with FLANN) ----
+/* ---- NN-SM dataset generation (the second batch axis of the path; the search and NN::update: mtfhip_nn below) ----
  * Row c of the C x N feature matrix = updateDistFeat() of the patch sampled under state c:
  * setState / compositionalUpdate -> updatePixVals -> updateDistFeat (SM/src/NT/NN.cc:131-191;
  * SSD feature = It, AM/include/mtf/AM/SSDBase.h:116-125; NCC feature = (It - mean)/||It - mean||, AM/src/NCC.cc:530-537) */
@@ -556,6 +556,45 @@ int mtfhip_nn_dataset(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *pe
  * matrix into dev_features[row_count][feat_size]; dev_perturbations_in / _out are indexed by the GLOBAL sample index (n_samples x S) */
 int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out,
 	double *dev_features, int row_lo, int row_count);
+
+/* ---- nt::NN's per-frame half: the exact search over the resident dataset and NN::update (SM/src/NT/NN.cc:236-277) ----
+ * The handle sits on a batch of ONE target (its appearance model, SSM, template grid and current image) and owns the device copies of the
+ * n_samples x feat_size dataset (eig_dataset), the perturbations (ssm_perturbations), the search's partial results, the per-iteration log
+ * and the stop flag.  The index is the exhaustive one -- what FLANN's Linear index type computes (SM/include/mtf/SM/FLANNParams.h:13) and
+ * GNN and the KD-trees approximate --: one streaming read of the matrix per query with the appearance model's distance functor, SSD
+ * sum (a - b)^2 (SSDBaseDist::operator(), AM/src/SSDBase.cc:576-603, without the worst_dist early return, which does not change the argmin) or
+ * NCC -sum a b on the centred unit-norm rows (NCCDist::operator(), AM/src/NCC.cc:568-591); multi-channel models: rows of n_pix x n_channels
+ * entries.  Of equal distances the lower index wins; no floating-point atomics: a call is bit-reproducible.
+ * MTFHIP_ERR_NOT_IMPLEMENTED (the reason in mtfhip_last_error): MI (MIDist, AM/src/MI.cc:749, is a joint histogram per dataset row), the SCV
+ * family (per-candidate intensity maps), additive_update, and a feat_size above MTFHIP_NN_MAX_FEAT_SIZE (the query is staged in LDS). */
+enum { MTFHIP_NN_MAX_FEAT_SIZE = 8000 };
+typedef struct mtfhip_nn mtfhip_nn;
+/* the batch must outlive the handle; MTFHIP_NN_HOST_STEPPED=1 at creation selects the host-stepped form of mtfhip_nn_update */
+int mtfhip_nn_create(mtfhip_batch *b, int n_samples, mtfhip_nn **out);
+int mtfhip_nn_destroy(mtfhip_nn *nn);
+/* NN::initialize's dataset half (NT/NN.cc:97-109: generateDataset, NN.cc:131-191) into the handle's own matrix, on the device: the n_distr
+ * distributions are consecutive row blocks of desc[k].n_samples rows (their sum must be the handle's n_samples; NN.cc:56-84), each drawn
+ * with its own desc[k].seed as mtfhip_nn_dataset_dev draws them */
+int mtfhip_nn_build(mtfhip_nn *nn, const mtfhip_nn_desc *desc, int n_distr);
+/* loadDataset / saveDataset (NT/NN.cc:193-234) without the file: features n_samples x feat_size, perturbations n_samples x S; the _dev
+ * forms take device pointers (a matrix gathered by the ranks of a sharded initialisation) and only enqueue the copies.  get: either may be NULL. */
+int mtfhip_nn_set_dataset(mtfhip_nn *nn, const double *features, const double *perturbations);
+int mtfhip_nn_set_dataset_dev(mtfhip_nn *nn, const double *dev_features, const double *dev_perturbations);
+int mtfhip_nn_get_dataset(mtfhip_nn *nn, double *features, double *perturbations);
+int mtfhip_nn_get_dataset_dev(mtfhip_nn *nn, double *dev_features, double *dev_perturbations);
+/* the nearest stored row of each of n_queries rows (n_queries x feat_size): idx[q] and dist[q] (the functor's value: SSD the squared distance,
+ * NCC minus the correlation); the _dev form takes device pointers and only enqueues */
+int mtfhip_nn_search(mtfhip_nn *nn, const double *queries, int n_queries, int *idx, double *dist);
+int mtfhip_nn_search_dev(mtfhip_nn *nn, const double *dev_queries, int n_queries, int *dev_idx, double *dev_dist);
+/* NN::update (NT/NN.cc:236-277) on the batch's current image, from the batch's current warp: per iteration updatePixVals + updateDistFeat
+ * at the current state (the dataset kernel run for one sample with the zero perturbation), the search, compositionalUpdate(
+ * ssm_perturbations[best_idx]) (Homography.cc:73-92, Affine.cc:87-109) and update_norm = ||prev_corners - corners||^2 (NN.cc:263); stops
+ * behind the iteration whose update_norm < epsilon (NN.cc:268; NNParams max_iters / epsilon, SM/src/NNParams.cc:6-7).  max_iters iterations
+ * are enqueued back to back -- the warp, the corners and the stop flag live on the device, every launch returns at once when the flag is
+ * set -- and read back once; the host-stepped form launches one iteration at a time and reads the flag back: the same kernels, the same
+ * bits.  corners_out: x0 y0 x1 y1 x2 y2 x3 y3; n_iters: iterations run; log_out (max_iters x 3, or NULL): best_idx, best_dist, update_norm
+ * per iteration run.  The batch's SSM is left at the new state. */
+int mtfhip_nn_update(mtfhip_nn *nn, int max_iters, double epsilon, double *corners_out, int *n_iters, double *log_out);
 
 /* ---- measurement hooks ---- */
 /* average duration in milliseconds of the launches of the named kernel family since the last

@@ -151,6 +151,8 @@ SYMBOLS = [
     "mtfhip_batch_rscv_intensity_map", "mtfhip_batch_set_lscv", "mtfhip_batch_lscv_intensity_maps", "mtfhip_batch_set_first_iter",
     "mtfhip_batch_first_iter", "mtfhip_batch_set_lrscv", "mtfhip_batch_lrscv_intensity_maps",
     "mtfhip_ssm_estimate_from_pts", "mtfhip_ssm_estimate_from_pts_dev",
+    "mtfhip_nn_create", "mtfhip_nn_destroy", "mtfhip_nn_build", "mtfhip_nn_set_dataset", "mtfhip_nn_set_dataset_dev", "mtfhip_nn_get_dataset",
+    "mtfhip_nn_get_dataset_dev", "mtfhip_nn_search", "mtfhip_nn_search_dev", "mtfhip_nn_update",
 ]
 
 
@@ -250,6 +252,14 @@ def lib():
         L.mtfhip_ssm_estimate_from_pts_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 4
         L.mtfhip_timing_get_busy.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        L.mtfhip_nn_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.mtfhip_nn_destroy.argtypes = [C.c_void_p]
+        L.mtfhip_nn_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        for fn in ("mtfhip_nn_set_dataset", "mtfhip_nn_set_dataset_dev", "mtfhip_nn_get_dataset", "mtfhip_nn_get_dataset_dev"):
+            getattr(L, fn).argtypes = [C.c_void_p] * 3
+        for fn in ("mtfhip_nn_search", "mtfhip_nn_search_dev"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mtfhip_nn_update.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

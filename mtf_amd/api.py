@@ -753,6 +753,62 @@ class Batch:
         L.check(L.lib().mtfhip_nn_dataset_dev(self._h, C.addressof(desc), C.c_void_p(dev_perts_in_ptr) if dev_perts_in_ptr else None,
                                               C.c_void_p(dev_perts_out_ptr) if dev_perts_out_ptr else None, C.c_void_p(dev_features_ptr), int(row_lo), int(row_count)))
 
+    # ---------------------------------------------------------- NN search and update (mtfhip_nn: NN.cc:236-277)
+    def nn_create(self, n_samples):
+        """an mtfhip_nn handle over this (one-target) batch: the resident dataset, the exact search, NN::update; MTFHIP_NN_HOST_STEPPED=1 in
+        the environment at this call selects the host-stepped loop.  Destroy it (nn_destroy) before the batch."""
+        h = C.c_void_p()
+        L.check(L.lib().mtfhip_nn_create(self._h, int(n_samples), C.byref(h)))
+        return h
+
+    @staticmethod
+    def nn_destroy(h):
+        if h:
+            L.lib().mtfhip_nn_destroy(h)
+
+    def nn_build(self, h, descs):
+        """generateDataset on the device into the handle's matrix: `descs` (nn_desc) are consecutive row blocks"""
+        arr = (L.NnDesc * len(descs))(*descs)
+        L.check(L.lib().mtfhip_nn_build(h, arr, len(descs)))
+
+    def nn_set_dataset(self, h, features, perturbations):
+        f, p = _f64(features), _f64(perturbations)
+        n = p.reshape(-1, self.S).shape[0]
+        if f.size != n * self.nn_feature_size():
+            raise ValueError("nn_set_dataset: features must be (n_samples, feat_size)")
+        L.check(L.lib().mtfhip_nn_set_dataset(h, _p(f), _p(p)))
+
+    @staticmethod
+    def nn_set_dataset_dev(h, dev_features_ptr, dev_perturbations_ptr):
+        L.check(L.lib().mtfhip_nn_set_dataset_dev(h, C.c_void_p(dev_features_ptr), C.c_void_p(dev_perturbations_ptr)))
+
+    def nn_get_dataset(self, h, n_samples):
+        f, p = np.empty((n_samples, self.nn_feature_size())), np.empty((n_samples, self.S))
+        L.check(L.lib().mtfhip_nn_get_dataset(h, _p(f), _p(p)))
+        return f, p
+
+    @staticmethod
+    def nn_get_dataset_dev(h, dev_features_ptr, dev_perturbations_ptr):
+        L.check(L.lib().mtfhip_nn_get_dataset_dev(h, C.c_void_p(dev_features_ptr) if dev_features_ptr else None,
+                                                  C.c_void_p(dev_perturbations_ptr) if dev_perturbations_ptr else None))
+
+    def nn_search(self, h, queries):
+        """the nearest stored row of every row of `queries` (Q, feat_size) -> (idx (Q,) int32, dist (Q,)); ties: the lower index"""
+        q = _f64(queries).reshape(-1, self.nn_feature_size())
+        idx, dist = np.empty(q.shape[0], dtype=np.int32), np.empty(q.shape[0])
+        L.check(L.lib().mtfhip_nn_search(h, _p(q), q.shape[0], _p(idx), _p(dist)))
+        return idx, dist
+
+    @staticmethod
+    def nn_search_dev(h, dev_queries_ptr, n_queries, dev_idx_ptr, dev_dist_ptr):
+        L.check(L.lib().mtfhip_nn_search_dev(h, C.c_void_p(dev_queries_ptr), int(n_queries), C.c_void_p(dev_idx_ptr), C.c_void_p(dev_dist_ptr)))
+
+    def nn_update(self, h, max_iters, epsilon):
+        """NN::update (mtfhip_nn_update) -> corners (2, 4), n_iters, log (n_iters, 3): best_idx, best_dist, update_norm"""
+        c, n, log = np.empty(8), C.c_int(), np.zeros((max(int(max_iters), 1), 3))
+        L.check(L.lib().mtfhip_nn_update(h, int(max_iters), C.c_double(float(epsilon)), _p(c), C.byref(n), _p(log)))
+        return self._corners_out(c)[0], n.value, log[:n.value].copy()
+
     # ---------------------------------------------------------- candidate scoring
     def score_candidates(self, states, want_similarity=False):
         s = _f64(states).reshape(-1, self.S)

@@ -1944,8 +1944,10 @@ int mtfhip_nn_feature_size(mtfhip_batch *b, int *feat_size) {
 	*feat_size = b->desc.am == MTFHIP_AM_MI ? 5 * b->N : b->N;   /* MI.cc:122: feat_size = 5 * patch_size; SSDBase.h:116-125, NCC.cc:530-537: patch_size */
 	return MTFHIP_OK;
 }
-int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out, double *dev_features,
-	int row_lo, int row_count) {
+/* the launch behind mtfhip_nn_dataset_dev; base_dev / done (api_nn.hip: the query feature of the NN tracker's loop): the warp is read from
+ * device memory instead of the host mirror, and the kernels return at once when *done is set */
+int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out, double *dev_features,
+	int row_lo, int row_count, const double *base_dev, const int *done) {
 	FLUSH(b);
 	if (!b || !d || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
 	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: SCV is not available on the NN dataset (SCVDist is a per-candidate intensity map)");
@@ -1961,6 +1963,7 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 	for (int s = 0; s < b->S; ++s) if (!(d->sigma[s] >= 0)) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: sigma[%d] = %g", s, d->sigma[s]);
 	NnArgs a;
 	a.perts_in = dev_perturbations_in; a.perts_out = dev_perturbations_out;
+	a.base_dev = base_dev; a.done = done;
 	for (int s = 0; s < 8; ++s) { a.sigma[s] = s < b->S ? d->sigma[s] : 0.0; a.mean[s] = s < b->S ? d->mean[s] : 0.0; }
 	a.seed = d->seed;
 	std::memcpy(a.base, b->th[0].warp.m, sizeof(a.base));
@@ -1990,6 +1993,10 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 	const hipError_t le = launch_nn_dataset(b->view_raw(), b->ctx->img, a, row_count, dev_features, warps, hull, b->ctx->stream);
 	if (le != hipSuccess) return fail(MTFHIP_ERR_HIP, "nn_dataset: the row kernel could not be set up: %s", hipGetErrorString(le));
 	return launch_error_pending();   /* a launch the runtime refused (its dynamic LDS, its grid) is this call's error, not a later one's */
+}
+int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out, double *dev_features,
+	int row_lo, int row_count) {
+	return nn_dataset_enqueue(b, d, dev_perturbations_in, dev_perturbations_out, dev_features, row_lo, row_count, nullptr, nullptr);
 }
 int mtfhip_nn_dataset(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *perturbations_in, double *perturbations_out, double *features) {
 	if (!b || !d || !features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");

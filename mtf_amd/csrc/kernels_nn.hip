@@ -58,6 +58,7 @@ __global__ __launch_bounds__(kBlock) void k_nn_dataset(BatchView bv, ImgView im,
 	const int local = blockIdx.x;
 	const unsigned g = (unsigned)(a.row_lo + local);   /* the sample's global index: what its draws are keyed by */
 	const int tid = threadIdx.x;
+	if (a.done && *a.done) return;   /* (uniform: the NN tracker's loop has stopped) */
 	/* the perturbation: given, or drawn -- lane q < S / 2 draws the pair (2 q, 2 q + 1) */
 	if (tid < 8) {
 		double v = 0.0;
@@ -86,7 +87,10 @@ __global__ __launch_bounds__(kBlock) void k_nn_dataset(BatchView bv, ImgView im,
 		for (int q = 0; q < 9; ++q) Pi[q] /= n22;
 	}
 	if constexpr (SSM == MTFHIP_SSM_AFFINE) { Pi[6] = 0; Pi[7] = 0; Pi[8] = 1; }   /* (getStateFromWarp -> getWarpFromState drops the last row's rounding, Affine.cc:132-143) */
-	m3_mul_dev(a.base, Pi, W);
+	double base[9];
+#pragma unroll
+	for (int q = 0; q < 9; ++q) base[q] = a.base_dev ? a.base_dev[q] : a.base[q];
+	m3_mul_dev(base, Pi, W);
 	if constexpr (SSM == MTFHIP_SSM_HOMOGRAPHY) {
 		const double n22 = W[8];
 #pragma unroll
@@ -178,6 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_nn_warps(NnArgs a, int count, double
 	constexpr int S = SSM == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6;
 	const int local = blockIdx.x * kBlock + threadIdx.x;
 	if (local >= count) return;
+	if (a.done && *a.done) return;
 	const unsigned g = (unsigned)(a.row_lo + local);
 	double p[8];
 #pragma unroll
@@ -206,7 +211,10 @@ __global__ __launch_bounds__(kBlock) void k_nn_warps(NnArgs a, int count, double
 		for (int q = 0; q < 9; ++q) Pi[q] /= n22;
 	}
 	if constexpr (SSM == MTFHIP_SSM_AFFINE) { Pi[6] = 0; Pi[7] = 0; Pi[8] = 1; }
-	m3_mul_dev(a.base, Pi, W);
+	double base[9];
+#pragma unroll
+	for (int q = 0; q < 9; ++q) base[q] = a.base_dev ? a.base_dev[q] : a.base[q];
+	m3_mul_dev(base, Pi, W);
 	if constexpr (SSM == MTFHIP_SSM_HOMOGRAPHY) {
 		const double n22 = W[8];
 #pragma unroll
@@ -233,10 +241,11 @@ __global__ __launch_bounds__(kBlock) void k_nn_warps(NnArgs a, int count, double
 }
 
 template <int SSM, int AM>
-__global__ __launch_bounds__(kBlock) void k_nn_rows(BatchView bv, ImgView im, const double *warps, int count, double norm_mult, double norm_add, double *feat) {
+__global__ __launch_bounds__(kBlock) void k_nn_rows(BatchView bv, ImgView im, const double *warps, int count, double norm_mult, double norm_add, double *feat, const int *done) {
 	__shared__ double red[16];
 	extern __shared__ double2 nn_lds[];                          /* the chunk's grid points (x, y), then -- grids that are not unit-z -- their z */
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	if (done && *done) return;   /* (uniform, in front of every barrier) */
 	const int N = bv.N;
 	const bool uz = bv.unit_z != 0;
 	const double2 *ip = reinterpret_cast<const double2 *>(bv.buf[uz ? MTFHIP_BUF_INIT_PTS : MTFHIP_BUF_INIT_HXY]);
@@ -443,7 +452,7 @@ static hipError_t launch_nn_rows(const BatchView &bv, const ImgView &im, const N
 	}
 	MTFHIP_LAUNCH((k_nn_warps<SSM>), dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, count, warps, im.w, im.h, ok, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
 	const dim3 g((unsigned)(count < resident ? count : resident)), blk(kBlock);
-#define MTFHIP_NN_ROWS(A) MTFHIP_LAUNCH((k_nn_rows<SSM, A>), g, blk, lds, st, bv, im, warps, count, a.norm_mult, a.norm_add, feat)
+#define MTFHIP_NN_ROWS(A) MTFHIP_LAUNCH((k_nn_rows<SSM, A>), g, blk, lds, st, bv, im, warps, count, a.norm_mult, a.norm_add, feat, a.done)
 	if (bv.am == MTFHIP_AM_NCC) MTFHIP_NN_ROWS(MTFHIP_AM_NCC);
 	else if (bv.am == MTFHIP_AM_MI) MTFHIP_NN_ROWS(MTFHIP_AM_MI);
 	else MTFHIP_NN_ROWS(MTFHIP_AM_SSD);

@@ -699,6 +699,8 @@ int ncc_hessian_from_cache(mtfhip_batch *b, int j_buf, int kind, double *H);
 int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa);
 int mi_blocks(const mtfhip_batch *b);
 int push_ncc(mtfhip_batch *b);
+int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out, double *dev_features,
+	int row_lo, int row_count, const double *base_dev, const int *done);   /* api_fused.hip */
 int score_block_dev(mtfhip_batch *b, const double *dev_states, int lo, int cnt, double *wts, double *sim, int likelihood_func,
 	double measurement_sigma, double max_similarity, const mtfhip::PfPeerPush *peer = nullptr);   /* api_fused.hip; peer: also store the
 	                                                                                       weights to the other ranks' mailboxes */

@@ -535,11 +535,24 @@ struct NnArgs {
 	double base[9];           /* the SSM's current warp */
 	int row_lo;               /* global index of the launch's first sample (row sharding: draws are keyed by the global index) */
 	double norm_mult, norm_add;
+	const double *base_dev;   /* device [9] or NULL: read the warp from here instead of `base` (the NN tracker's loop: the previous iteration moved it on the device) */
+	const int *done;          /* device flag or NULL: every kernel of the launch returns at once when it is set (the NN tracker's loop) */
 };
 void launch_pair_image(const ImgView &im, float *pair /* [h][w][2] */, hipStream_t st);
 hipError_t launch_nn_dataset(const BatchView &bv, const ImgView &im, const NnArgs &a, int count, double *feat, double *warps, const double *hull, hipStream_t st);
 size_t nn_warps_bytes(int count);
 bool nn_two_launch_ok(const BatchView &bv, const ImgView &im, int fast_math);
+/* nt::NN's per-frame half (kernels_nn_search.hip): the exact search over the resident dataset, and the compositional update with the winner */
+struct NnBest { double dist; int idx; int pad; };
+constexpr int kNnSearchMaxFeat = 8000;   /* the query is staged in LDS: (feat_size + 2) doubles within the 64 KB a launch may ask for unasked */
+int nn_search_resident(int ncc, int F);
+int nn_search_blocks(int n_samples, int resident);
+void launch_nn_search(int ncc, const double *feat, int n_samples, int F, const double *queries, int Q, NnBest *partials /* [Q][nblk] */, int nblk,
+	const int *done, hipStream_t st);
+void launch_nn_search_finish(const NnBest *partials, int nblk, int Q, int *idx, double *dist, hipStream_t st);
+/* state: W (9) | corners (8) | init_corners_hm (12); ctl: done | n_iters; log[it]: best_idx | best_dist | update_norm */
+void launch_nn_pick_update(int ssm, const NnBest *partials, int nblk, const double *perts, int n_samples, double *state, int *ctl, double *log, int it,
+	double epsilon, hipStream_t st);
 void launch_sample_candidates(const BatchView &bv, const ImgView &im, const double *dev_states, int C, double norm_mult,
 	double norm_add, double *dev_feat, hipStream_t st);
 /* whole ICLK loop in one launch, one workgroup per target (N <= 16 * kBlock); false if N is too large */

@@ -72,6 +72,9 @@ def lib():
         H.mtfhost_grid_call.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         H.mtfhost_grid_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         H.mtfhost_grid_set_est_params.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_ulonglong]
+        H.mtfhost_nn_create.restype = C.c_void_p
+        H.mtfhost_nn_create.argtypes = [C.c_int] * 6 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
+        H.mtfhost_nn_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _h = H
     return _h
 

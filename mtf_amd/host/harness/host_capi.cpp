@@ -4,6 +4,7 @@
  * (Examples/cpp/pyMTF.cc:35-62), so that the test-suite can drive the C++ objects.  HARNESS (libmtfharness.so): it constructs the
  * product's adapters and device drivers (libmtfhost.so) AND the restated reference callers that live next to it.
  */
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -12,6 +13,7 @@
 #include "../HipModels.h"
 #include "../DeviceLK.h"
 #include "../DevicePF.h"
+#include "../DeviceNN.h"
 #include "../DeviceGrid.h"
 #include "SearchMethods.h"
 #include "PF.h"
@@ -178,6 +180,34 @@ int mtfhost_dist_feat(mtfhost_tracker *t, double *feat, int *size) {
 		if (feat) { am->initializeDistFeat(); am->updateDistFeat(); std::memcpy(feat, am->getDistFeat(), sizeof(double) * am->getDistFeatSize()); }
 		return 0;
 	} catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+/* mtf::hip::NN (mtfhip_nn_*): n_distr sampler distributions (ssm_sigma / ssm_mean: rows of 8; distr_n_samples: n_distr counts or NULL) */
+mtfhost_tracker *mtfhost_nn_create(int am, int ssm, int resx, int resy, int n_samples, int max_iters, double epsilon, int n_distr,
+	const double *ssm_sigma, const double *ssm_mean, const int *distr_n_samples, unsigned long long seed, int device, int n_channels) {
+	try {
+		if (n_distr < 1 || !ssm_sigma) throw utils::InvalidArgument("mtfhost_nn_create: n_distr must be positive");
+		std::unique_ptr<mtfhost_tracker> t(new mtfhost_tracker());   /* (a constructor below may throw: nothing leaks) */
+		t->pair = std::make_shared<hip::HipPair>(am, ssm, resx, resy, 1e-8, 1.0, 8, 10.0, 0, device, nullptr, n_channels);
+		t->am = std::make_shared<hip::HipAM>(t->pair);
+		t->ssm = std::make_shared<hip::HipSSM>(t->pair);
+		NNParams p;
+		p.n_samples = n_samples; p.max_iters = max_iters; p.epsilon = epsilon; p.seed = seed;
+		for (int i = 0; i < n_distr; ++i) {
+			p.ssm_sigma.emplace_back(ssm_sigma + 8 * i, ssm_sigma + 8 * i + t->pair->S);
+			if (ssm_mean) p.ssm_mean.emplace_back(ssm_mean + 8 * i, ssm_mean + 8 * i + t->pair->S);
+		}
+		if (distr_n_samples) p.distr_n_samples.assign(distr_n_samples, distr_n_samples + n_distr);
+		t->sm.reset(new hip::NN(t->am, t->ssm, p));
+		return t.release();
+	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+/* best_idx, best_dist, update_norm of the iterations of the last update() of an mtfhost_nn_create tracker: up to max_rows rows -> rows written */
+int mtfhost_nn_log(mtfhost_tracker *t, double *log, int max_rows) {
+	hip::NN *nn = t ? dynamic_cast<hip::NN *>(t->sm.get()) : nullptr;
+	if (!nn || !log) { g_err = "mtfhost_nn_log: not an NN tracker"; return -1; }
+	const int rows = std::min((int)(nn->getLog().size() / 3), max_rows);
+	std::memcpy(log, nn->getLog().data(), sizeof(double) * 3 * (size_t)rows);
+	return rows;
 }
 /* the particle filter: device = 1 -> mtf::hip::PF (mtfhip_pf_*), 0 -> mtf::nt::PF over the AM / SSM virtuals (one C-ABI round trip
  * per particle: the literal drop-in of SM/src/NT/PF.cc) */

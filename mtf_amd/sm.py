@@ -948,6 +948,78 @@ class NNDataset:
         return k, float(d[k])
 
 
+class NNTracker:
+    """nt::NN (SM/src/NT/NN.cc) with the exhaustive index, dataset and search resident on the device: `initialize` builds the dataset at the
+    template (NN.cc:85-113, mtfhip_nn_build: nothing comes to the host), `update` is NN::update (NN.cc:236-277) in one C-ABI call
+    (mtfhip_nn_update: per iteration the patch's distance feature, the exact search, compositionalUpdate with the winner's perturbation,
+    all enqueued back to back).  max_iters / epsilon: NNParams (SM/src/NNParams.cc:6-7).  SSD and NCC, single- and multi-channel.
+    `set_dataset` hands over a matrix made elsewhere (NNDataset.initialize_sharded's features_dev, or host arrays: the reference's
+    loadDataset, NN.cc:193-220)."""
+
+    def __init__(self, ctx, am=L.AM_SSD, ssm=L.SSM_HOMOGRAPHY, resx=50, resy=50, n_samples=1000,
+                 ssm_sigma=(0.01, 0.01, 2.0, 0.01, 0.01, 2.0, 1e-5, 1e-5), ssm_mean=None, distr_n_samples=None, max_iters=1, epsilon=0.01,
+                 seed=0, am_params=None):
+        self._h = None
+        self.ds = NNDataset(ctx, am, ssm, resx, resy, n_samples, ssm_sigma, ssm_mean, seed, am_params, distr_n_samples)
+        self.batch = self.ds.batch
+        self.n, self.S = self.ds.n, self.ds.S
+        self.max_iters, self.epsilon = int(max_iters), float(epsilon)
+        self._h = self.batch.nn_create(self.n)
+        self.n_iters, self.log = 0, np.zeros((0, 3))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.batch.nn_destroy(self._h)
+            self._h = None
+        if getattr(self, "batch", None) is not None:
+            self.batch.close()
+
+    def __del__(self):   # a tracker dropped without close() must not keep its device buffers until the Context goes
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _template(self, corners):
+        self.batch.set_corners(np.asarray(corners, dtype=np.float64).reshape(1, 2, 4))
+        self.batch.initialize_pix_vals()
+
+    def initialize(self, corners, features=None, perturbations=None, features_dev_ptr=None, perturbations_dev_ptr=None):
+        """NN::initialize (NN.cc:85-113): the template at `corners` and the dataset -- built on the device (several distributions: consecutive
+        row blocks seeded seed + k, as NNDataset.initialize), or the given one"""
+        self._template(corners)
+        if features is not None or features_dev_ptr is not None:
+            self.set_dataset(features, perturbations, features_dev_ptr, perturbations_dev_ptr)
+            return
+        d = self.ds
+        self.batch.nn_build(self._h, [self.batch.nn_desc(cnt, d.sigmas[k], d.means[k], d.seed + k) for k, cnt in enumerate(d.distr_n_samples)])
+
+    def set_dataset(self, features=None, perturbations=None, features_dev_ptr=None, perturbations_dev_ptr=None):
+        if features_dev_ptr is not None:
+            self.batch.nn_set_dataset_dev(self._h, features_dev_ptr, perturbations_dev_ptr)
+        else:
+            self.batch.nn_set_dataset(self._h, np.asarray(features, dtype=np.float64).reshape(self.n, -1),
+                                      np.asarray(perturbations, dtype=np.float64).reshape(self.n, self.S))
+
+    def get_dataset(self):
+        """(features (n, feat_size), perturbations (n, S)) read back: the reference's saveDataset (NN.cc:222-234) without the file"""
+        return self.batch.nn_get_dataset(self._h, self.n)
+
+    def search(self, features):
+        """the nearest stored row of each query row -> (idx, dist)"""
+        return self.batch.nn_search(self._h, features)
+
+    def update(self):
+        corners, self.n_iters, self.log = self.batch.nn_update(self._h, self.max_iters, self.epsilon)
+        return corners
+
+    def set_region(self, corners):
+        self.batch.set_corners(np.asarray(corners, dtype=np.float64).reshape(1, 2, 4))
+
+    def get_region(self):
+        return self.batch.get_corners()[0]
+
+
 class PyramidalTracker:
     """PyramidalTracker (SM/src/PyramidalTracker.cc): one tracker per pyramid level, coarse to fine.  Each level owns
     a Context whose image is derived on the device from the level above (cv::pyrDown for scale_factor 0.5, else

@@ -58,7 +58,15 @@ typedef enum mtfhip_status {
  * (mtfhip_batch_set_lrscv below) */
 enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6 };
 enum { MTFHIP_SSM_HOMOGRAPHY = 0, MTFHIP_SSM_AFFINE = 1 };
-enum { MTFHIP_SM_ESM = 0, MTFHIP_SM_FCLK = 1, MTFHIP_SM_ICLK = 2 };
+/* MTFHIP_SM_FALK / _IALK: the additive Lucas-Kanade formulations (SM/src/NT/FALK.cc, IALK.cc): the state moves by
+ * StateSpaceModel::additiveUpdate (ProjectiveBase.cc:51-55) instead of a compositional update.  FALK takes the image gradient at the
+ * current points and cmptPixJacobian per iteration; IALK forms cmptApproxPixJacobian from the template's stored gradient.  Served by
+ * mtfhip_batch_init_template / _iterate / _track (k_alk_pass + k_alk_finish, kernels_alk.hip) for SSD and NCC, single channel, homography
+ * and affine, first-order Hessians, every hess_type, with or without Levenberg-Marquardt; anything else returns MTFHIP_ERR_NOT_IMPLEMENTED
+ * (MI, the SCV family, n_channels 3, sec_ord_hess, set_region / track_region / the grid entry points).  Defaults of
+ * SM/src/FALKParams.cc:3-15 and IALKParams.cc:4-11: max_iters 10, epsilon 0.01, hess_type 0 (InitialSelf), sec_ord_hess 0, leven_marq 0,
+ * lm_delta_init 0.01, lm_delta_update 10 (FALK also: enable_learning 0). */
+enum { MTFHIP_SM_ESM = 0, MTFHIP_SM_FCLK = 1, MTFHIP_SM_ICLK = 2, MTFHIP_SM_FALK = 3, MTFHIP_SM_IALK = 4 };
 /* pixel-Jacobian variants of StateSpaceModel.h:170-181 */
 enum { MTFHIP_JAC_INIT = 0, MTFHIP_JAC_PIX = 1, MTFHIP_JAC_WARPED = 2, MTFHIP_JAC_APPROX = 3 };
 /* device-resident buffers of a batch (per target sizes in doubles) */
@@ -114,8 +122,8 @@ typedef struct mtfhip_sm_desc {
 	int sm;            /* MTFHIP_SM_* */
 	int jac_type;      /* ESM: 0 Original, 1 DiffOfJacs */
 	int hess_type;     /* ESM: 0 InitialSelf 1 CurrentSelf 2 SumOfSelf 3 Original 4 SumOfStd 5 Std
-	                      FCLK/ICLK: 0 InitialSelf 1 CurrentSelf 2 Std */
-	int chained_warp;
+	                      FCLK/ICLK/FALK/IALK: 0 InitialSelf 1 CurrentSelf 2 Std (FALKParams.h:9, IALKParams.h:9) */
+	int chained_warp;  /* (not read by FALK / IALK: they have no such switch) */
 	int materialize;   /* 1: It, dIt_dx and Jt are written to HBM as the interface exposes them;
 	                      0: kept in registers only (getters for them then fail with ERR_LOGIC) */
 	int max_iters;     /* used by mtfhip_batch_track only */

@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV, AM_LRSCV = 0, 1, 2, 3, 4, 5, 6
 SCV_HIST_DIRAC, SCV_HIST_BILINEAR, SCV_HIST_BSPLINE = 0, 1, 2
 SSM_HOMOGRAPHY, SSM_AFFINE = 0, 1
-SM_ESM, SM_FCLK, SM_ICLK = 0, 1, 2
+SM_ESM, SM_FCLK, SM_ICLK, SM_FALK, SM_IALK = 0, 1, 2, 3, 4
 JAC_INIT, JAC_PIX, JAC_WARPED, JAC_APPROX = 0, 1, 2, 3
 MATH_REPLAY, MATH_FAST = 0, 1
 EST_RANSAC, EST_LMEDS, EST_LEAST_SQUARES = 0, 1, 2     # EstType SSMEstimatorParams.h:11

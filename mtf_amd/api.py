@@ -17,7 +17,7 @@ from . import _lib as L
 from ._lib import (AM_MI, AM_NCC, AM_SCV, AM_SSD, BUF_CURR_PTS, BUF_D2I0_DP2, BUF_D2I0_DX2, BUF_D2IM_DP2, BUF_D2IT_DP2, BUF_D2IT_DX2,
                    BUF_DF_DI0, BUF_DF_DIT, BUF_DI0_DX, BUF_DIT_DX, BUF_HESS_PTS,
                    BUF_GRAD_PTS, BUF_I0, BUF_INIT_PTS, BUF_IT, BUF_J0, BUF_JM, BUF_JT, JAC_APPROX, JAC_INIT,
-                   JAC_PIX, JAC_WARPED, SM_ESM, SM_FCLK, SM_ICLK, SSM_AFFINE, SSM_HOMOGRAPHY, PatchDesc, SMDesc)
+                   JAC_PIX, JAC_WARPED, SM_ESM, SM_FALK, SM_FCLK, SM_IALK, SM_ICLK, SSM_AFFINE, SSM_HOMOGRAPHY, PatchDesc, SMDesc)
 
 
 def _p(a):
@@ -32,8 +32,9 @@ def _f64(a):
 
 
 def sm_desc(sm, **kw):
-    """Class defaults of the reference (SM/src/ESMParams.cc:4-15, FCLKParams.cc:4-17, ICLKParams.cc:4-14)."""
-    base = dict(sm=sm, jac_type=1, hess_type={SM_ESM: 2, SM_FCLK: 1, SM_ICLK: 0}[sm], chained_warp=1,
+    """Class defaults of the reference (SM/src/ESMParams.cc:4-15, FCLKParams.cc:4-17, ICLKParams.cc:4-14; hess_type of
+    FALKParams.cc:5 / IALKParams.cc:6: InitialSelf)."""
+    base = dict(sm=sm, jac_type=1, hess_type={SM_ESM: 2, SM_FCLK: 1, SM_ICLK: 0, SM_FALK: 0, SM_IALK: 0}[sm], chained_warp=1,
                 materialize=1, max_iters=30, epsilon=1e-4, leven_marq=0, lm_delta_init=0.01, lm_delta_update=10.0,
                 sec_ord_hess=0)
     base.update(kw)

@@ -12,6 +12,11 @@ extern "C" {
 /* ------------------------------------------------------------------ fused path */
 static int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn) {
 	if (!b || !sm) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
+	/* the additive methods live behind init_template / iterate / track alone (api_alk.hip): what else comes here with them -- set_region,
+	 * track_region, the grid tracker's frames -- is refused */
+	if (alk_sm(sm->sm))
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: the additive search methods (FALK / IALK) are served by init_template / iterate / track only (set_region, track_region "
+			"and the grid frames are not available with them)", fn);
 	if (sm->sm < MTFHIP_SM_ESM || sm->sm > MTFHIP_SM_ICLK) return fail(MTFHIP_ERR_INVALID_ARG, "%s: unknown search method %d", fn, sm->sm);
 	int max_h = sm->sm == MTFHIP_SM_ESM ? 5 : 2;
 	if (sm->hess_type < 0 || sm->hess_type > max_h) return fail(MTFHIP_ERR_INVALID_ARG, "%s: hess_type %d invalid for search method %d", fn, sm->hess_type, sm->sm);
@@ -113,7 +118,7 @@ static void ncc_x(const mtfhip_batch *b, const TargetHost &h, const double *M, i
 	X.gram = which == 0 ? h.ncc_gram0 : ((which == 2) == gram_is_mean ? M + NCC_GRAM : nullptr);
 }
 /* one target's reduced moment row -> the SM's f, g, H (before LM damping); NT/ESM.cc:298-377, NT/FCLK.cc:260-288, NT/ICLK.cc:206-251 */
-static int ncc_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, const double *M, TargetHost &h,
+int ncc_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, const double *M, TargetHost &h,
 	double *f, double *g, double *H) {
 	const int S = b->S;
 	const NccScalars q = ncc_scalars(b, h, M);
@@ -436,6 +441,7 @@ static int grid_reinit_fused(mtfhip_batch *b, const mtfhip_sm_desc *sm, const do
 	return rc;
 }
 int mtfhip_batch_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
+	if (sm && alk_sm(sm->sm)) return alk_init_template(b, sm);
 	FLUSH(b);
 	if (b) { touch_all(b); b->lz.it_epoch = -1; TRY(ensure_df(b)); }
 	TRY(check_sm(b, sm, "init_template"));
@@ -623,7 +629,7 @@ static int second_order_term(const mtfhip_sm_desc *sm, int am = MTFHIP_AM_SSD) {
 
 /* turns one target's reduced accumulators into the SM's g and H (before LM damping):
  * NT/FCLK.cc:260-288 ; NT/ESM.cc:298-377 with SSDBase.cc:169-191,287-311 ; NT/ICLK.cc:206-251 */
-static void assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0,
+void assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0,
 	double *f, double *g, double *H) {
 	const int S = b->S;
 	if (f) *f = -acc[ACC_RR] / 2;
@@ -874,6 +880,7 @@ static int mi_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, doub
 }
 
 int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H) {
+	if (sm && alk_sm(sm->sm)) return alk_iterate(b, sm, f, g, H);
 	FLUSH_AM(b);   /* the fused kernels derive the sample points from the warp: CURR_PTS may stay stale */
 	if (b) { touch_all(b); b->lz.it_epoch = -1; TRY(ensure_df(b)); }
 	TRY(check_sm(b, sm, "iterate"));
@@ -1082,7 +1089,10 @@ static int lscv_after_track(mtfhip_batch *b, int rc) {
 	if (rc == MTFHIP_OK && b && (b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV)) b->lscv_first_iter = 0;
 	return rc;
 }
-int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) { return lscv_after_track(b, track_core(b, sm, n_iters, corners, false)); }
+int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) {
+	if (sm && alk_sm(sm->sm)) return alk_track(b, sm, n_iters, corners);
+	return lscv_after_track(b, track_core(b, sm, n_iters, corners, false));
+}
 
 /* setRegion + update of one frame in one call: what GridTracker::update does with every patch tracker (GridTracker.cc:345-363:
  * tracker->setRegion(patch corners); tracker->update()) and a pyramid level with the level above's result.  For the search
@@ -1190,6 +1200,7 @@ static int grid_track_plain(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_it
 	 * loop kernel reads nothing of that kernel's host record, so it is enqueued behind it right away (r05: the host used to wait for the
 	 * record and copy 1 KB per patch first -- launch latency + 256 KB of memcpy exposed in every frame); the record is folded into the
 	 * mirrors by the next call that flushes without this flag.  MTFHIP_GRID_HOLD_PULL=0: the r05 first form. */
+	if (alk_sm(sm->sm)) TRY(check_sm(b, sm, "grid_frame"));   /* (mtfhip_batch_track itself serves the additive search methods: the grid frames do not) */
 	const size_t B = (size_t)b->B;
 	const char *e_hp = std::getenv("MTFHIP_GRID_HOLD_PULL");
 	const bool hold = b->init_mirror_seq != 0 && !(e_hp && e_hp[0] == '0') && b->h_stage_b_dev && b->h_pub_dev && b->desc.am != MTFHIP_AM_MI && !sm->leven_marq &&
@@ -1351,6 +1362,7 @@ int mtfhip_grid_frame_fb(mtfhip_batch *b, const mtfhip_sm_desc *sm, const mtfhip
 int mtfhip_grid_reset(mtfhip_batch *b, const mtfhip_sm_desc *sm, const mtfhip_grid_desc *g, const double *region, int reinit, double *patch_corners, float *prev_pts) {
 	if (!sm || !region) return fail(MTFHIP_ERR_INVALID_ARG, "grid_reset: NULL argument");
 	TRY(grid_batch_ok(b, g, "grid_reset"));
+	if (alk_sm(sm->sm)) TRY(check_sm(b, sm, "grid_reset"));   /* (before anything is laid out: an additive search method has no grid frame) */
 	const size_t B = (size_t)b->B;
 	static thread_local std::vector<double> patches;
 	patches.resize(8 * B);

@@ -697,6 +697,14 @@ int ncc_template_moments(mtfhip_batch *b);
 int ncc_lazy_outputs(mtfhip_batch *b, int trig, int j_a, bool hess_mean, double *g);
 int ncc_hessian_from_cache(mtfhip_batch *b, int j_buf, int kind, double *H);
 int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa);
+/* api_fused.hip: one target's reduced row -> the search method's f, g and H (before damping), SSD and NCC */
+void assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H);
+int ncc_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, const double *M, TargetHost &h, double *f, double *g, double *H);
+/* api_alk.hip: MTFHIP_SM_FALK / _IALK behind mtfhip_batch_init_template / _iterate / _track */
+static inline bool alk_sm(int sm) { return sm == MTFHIP_SM_FALK || sm == MTFHIP_SM_IALK; }
+int alk_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm);
+int alk_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
+int alk_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners);
 int mi_blocks(const mtfhip_batch *b);
 int push_ncc(mtfhip_batch *b);
 int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out, double *dev_features,

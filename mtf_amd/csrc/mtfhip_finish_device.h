@@ -32,7 +32,12 @@ __device__ unsigned long long g_fin_trace[16];
  * must call it: it contains workgroup barriers). */
 /* COH (k_track_persist): everything the loop rewrites between passes -- partial rows, warp, state, corners, counters, flags, the
  * Levenberg-Marquardt block -- is read and written with the coherent accessors of mtfhip_device.h (st_coh / ld_coh). */
-template <bool COH = false>
+/* ADDITIVE (k_alk_finish, kernels_alk.hip: nt::FALK / nt::IALK, NT/FALK.cc:229-246, NT/IALK.cc:180-194): the solved update is ADDED to the
+ * state -- StateSpaceModel::additiveUpdate, ProjectiveBase.cc:51-55: curr_state += state_update, the warp rebuilt from the state
+ * (getWarpFromState), the corners from the warp -- and a Levenberg-Marquardt undo adds its negative (NT/FALK.cc:156-158); the `continue`
+ * behind an undo consumes an iteration of their for loops (NT/FALK.cc:141,166).  The caller hands in the search method as FCLK: g and H
+ * are FCLK's functions of the reduced row (cmptCurrJacobian / cmptSelfHessian / cmptCurrHessian of the pass's own pixel Jacobian). */
+template <bool COH = false, bool ADDITIVE = false>
 __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
 	const double *partials, int nblk, int t) {
 	auto LD = [](const double *p) -> double { if constexpr (COH) return ld_coh(p); else return *p; };
@@ -70,7 +75,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	if (wv0) {
 		v_h0 = ts.h0[(size_t)t * 64 + lane];
 		if (lane < 9) v_w = LD(bv.warps + 9 * t + lane);
-		if (ts.lean_pass && lane < 8) v_so = LD(bv.states + 8 * t + lane);   /* (the state this pass ran at: stop_target) */
+		if ((ADDITIVE || ts.lean_pass) && lane < 8) v_so = LD(bv.states + 8 * t + lane);   /* (the state this pass ran at: stop_target, the additive update) */
 		if (lane < 8) v_cr = LD(ts.corners + 8 * t + lane);
 		if (lane < 12) v_ic = ts.init_corners_hm[12 * t + lane];
 		if (ncc) {
@@ -279,6 +284,25 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	double dp[8];
 #pragma unroll
 	for (int s = 0; s < 8; ++s) dp[s] = dps[s];
+	double Wn[9];
+	double *Wp = bv.warps + 9 * t, *st = bv.states + 8 * t;
+	if constexpr (ADDITIVE) {
+		/* curr_state += state_update (undo: its negative), then setState: getWarpFromState (Homography.cc:94-107, Affine.cc:116-130) */
+		double sn[8];
+#pragma unroll
+		for (int s = 0; s < 8; ++s) sn[s] = sos[s] + (undo ? -dp[s] : dp[s]);
+		if (hom) {
+			Wn[0] = 1 + sn[0]; Wn[1] = sn[1]; Wn[2] = sn[2]; Wn[3] = sn[3]; Wn[4] = 1 + sn[4]; Wn[5] = sn[5];
+			Wn[6] = sn[6]; Wn[7] = sn[7]; Wn[8] = 1;
+		} else {
+			Wn[0] = 1 + sn[2]; Wn[1] = sn[3]; Wn[2] = sn[0]; Wn[3] = sn[4]; Wn[4] = 1 + sn[5]; Wn[5] = sn[1];
+			Wn[6] = 0; Wn[7] = 0; Wn[8] = 1;
+		}
+		double sq = 0;
+#pragma unroll
+		for (int q = 0; q < 8; ++q) if (lane == q) sq = sn[q];
+		if (lane < S) ST(st + lane, sq);
+	} else {
 	double U[9];
 	if (hom) {
 		U[0] = 1 + dp[0]; U[1] = dp[1]; U[2] = dp[2]; U[3] = dp[3]; U[4] = 1 + dp[4]; U[5] = dp[5];
@@ -312,7 +336,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		U[0] = 1 + (U[0] - 1); U[4] = 1 + (U[4] - 1); U[8] = 1;
 		if (!hom) { U[6] = 0; U[7] = 0; }
 	}
-	double Wo[9], Wn[9];
+	double Wo[9];
 #pragma unroll
 	for (int q = 0; q < 9; ++q) Wo[q] = Ws[q];
 #pragma unroll
@@ -320,7 +344,6 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 #pragma unroll
 		for (int c2 = 0; c2 < 3; ++c2)
 			Wn[3 * r + c2] = Wo[3 * r] * U[c2] + Wo[3 * r + 1] * U[3 + c2] + Wo[3 * r + 2] * U[6 + c2];
-	double *Wp = bv.warps + 9 * t, *st = bv.states + 8 * t;
 	if (hom) {
 		double n22 = Wn[8];
 		double wq = 0;
@@ -337,6 +360,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	} else if (lane == 0) {
 		ST(st + 0, Wn[2]); ST(st + 1, Wn[5]); ST(st + 2, Wn[0] - 1); ST(st + 3, Wn[1]); ST(st + 4, Wn[3]); ST(st + 5, Wn[4] - 1);
 	}
+	}   /* (!ADDITIVE) */
 	{
 		double wq = 0;
 #pragma unroll
@@ -371,7 +395,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	if (lmp) {
 		/* an undo pass skips the convergence test (`continue`); it consumes an iteration in the for loops of ESM and ICLK
 		 * (NT/ESM.cc:179, NT/ICLK.cc:169) but not in FCLK's while loop (NT/FCLK.cc:193-223) */
-		const int id = lm_iter_id + ((undo && sm.sm == MTFHIP_SM_FCLK) ? 0 : 1);
+		const int id = lm_iter_id + ((undo && sm.sm == MTFHIP_SM_FCLK && !ADDITIVE) ? 0 : 1);
 		ST(lmp + 3, (double)id);
 		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) stop_target(Ws, sos);
 	} else if (change < sm.epsilon || n_it >= sm.max_iters) stop_target(Ws, sos);

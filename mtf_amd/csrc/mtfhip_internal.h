@@ -588,6 +588,19 @@ struct PhaseCtl { unsigned long long *mine; const unsigned long long *other; dou
 void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials,
 	int nblk, hipStream_t st, PhaseCtl pc = PhaseCtl{nullptr, nullptr, 0.0});
 
+/* ---- the additive search methods nt::FALK / nt::IALK (kernels_alk.hip) ---- */
+struct AlkArgs {
+	int ialk;            /* 0 FALK: gradient at the current points + cmptPixJacobian; 1 IALK: cmptApproxPixJacobian of dI0_dx */
+	int materialize;     /* It, dIt_dx (FALK) and Jt are written to the interface buffers */
+	int rows_per_block;  /* 256-pixel rows walked by one workgroup (fused_decomposition) */
+	double grad_eps, norm_mult, norm_add;
+	const int *active;   /* optional [B] mask: targets with 0 are skipped (device-side loop) */
+};
+/* the pixel pass: one partial row per workgroup, ACC_COUNT (SSD) or NCC_ACC_COUNT (NCC) wide, FCLK-type */
+void launch_alk_pass(const BatchView &bv, const ImgView &im, const AlkArgs &a, double *partials, int nblk, hipStream_t st);
+/* row sums, g and H by sm.hess_type (sm.sm = MTFHIP_SM_FCLK: the row's type), Levenberg-Marquardt, solve, additiveUpdate, convergence test */
+void launch_alk_finish(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials, int nblk, hipStream_t st);
+
 /* ---- SCV: the template re-map of SCV::updateSimilarity (kernels_scv.hip) ---- */
 constexpr int kScvMaxBins = 256;
 struct ScvArgs {

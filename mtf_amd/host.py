@@ -89,8 +89,9 @@ def _check(rc):
 
 
 class CppTracker:
-    """mtf::nt::{ESM,FCLK,ICLK} (or, with device_loop, mtf::hip::LK) over mtf::hip::{HipAM,HipSSM}; parameter names and defaults
-    are the reference's (leven_marq defaults to true as in ESMParams.cc / FCLKParams.cc / ICLKParams.cc)."""
+    """mtf::nt::{ESM,FCLK,ICLK,FALK,IALK} (or, with device_loop, mtf::hip::LK) over mtf::hip::{HipAM,HipSSM}; parameter names and defaults
+    are the reference's (leven_marq defaults to true as in ESMParams.cc / FCLKParams.cc / ICLKParams.cc; FALKParams.cc / IALKParams.cc
+    default it to false: pass leven_marq=0 for their class default)."""
 
     def __init__(self, sm, am=_lib.AM_SSD, ssm=_lib.SSM_HOMOGRAPHY, resx=50, resy=50, max_iters=30, epsilon=1e-4,
                  jac_type=1, hess_type=-1, chained_warp=1, leven_marq=1, lm_delta_init=0.01, lm_delta_update=10.0,

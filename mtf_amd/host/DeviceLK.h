@@ -1,5 +1,5 @@
 /*
- * DeviceLK.h -- mtf::hip::LK: nt::ESM / nt::FCLK / nt::ICLK as ONE C-ABI call per update().
+ * DeviceLK.h -- mtf::hip::LK: nt::ESM / nt::FCLK / nt::ICLK / nt::FALK / nt::IALK as ONE C-ABI call per update().
  *
  * mtf::nt::ESM / FCLK / ICLK (harness/SearchMethods.h: restated callers, test infrastructure) are the literal search methods: a loop over the AM / SSM virtuals, as
  * SM/src/NT/ESM.cc:170-296, NT/FCLK.cc:187-342 and NT/ICLK.cc:160-298 write it, which the library serves call by call
@@ -12,7 +12,9 @@
 #ifndef MTF_AMD_HOST_DEVICE_LK_H
 #define MTF_AMD_HOST_DEVICE_LK_H
 
+#include "FALKParams.h"
 #include "HipModels.h"
+#include "IALKParams.h"
 #include "SearchMethod.h"
 
 namespace mtf {
@@ -20,7 +22,8 @@ namespace hip {
 
 class LK : public nt::SearchMethod {
 public:
-	/* sm_kind: MTFHIP_SM_ESM / MTFHIP_SM_FCLK / MTFHIP_SM_ICLK */
+	/* sm_kind: MTFHIP_SM_ESM / _FCLK / _ICLK, or the additive MTFHIP_SM_FALK / _IALK (parameters: FALKParams.h / IALKParams.h convert to
+	 * nt::SMParams; SSD and NCC, single channel, first-order Hessians -- anything else throws FunctonNotImplemented at initialize()) */
 	LK(int sm_kind, std::shared_ptr<HipAM> am, std::shared_ptr<HipSSM> ssm, const nt::SMParams &params);
 	void initialize(const CornersT &corners) override;
 	void update() override;

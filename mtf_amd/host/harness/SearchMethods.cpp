@@ -333,5 +333,85 @@ void ICLK::update() {
 	if (params.enable_learning) am->updateModel(ssm->getPts());
 }
 
+/* ------------------------------------------------------------------ FALK / IALK */
+AdditiveLK::AdditiveLK(AM a, SSM s, const SMParams &p, bool inv) : LKSearchMethod(a, s, p), inverse(inv) {
+	if (params.hess_type < 0) params.hess_type = InitialSelf;
+	if (params.sec_ord_hess) {   /* NT/FALK.cc:47-53, NT/IALK.cc:45-51 */
+		const int n = (int)am->getPatchSize(), s2 = ssm_state_size * ssm_state_size;
+		if (params.hess_type == InitialSelf) init_pix_hessian.resize(s2, n);
+		else curr_pix_hessian.resize(s2, n);
+	}
+}
+void AdditiveLK::initialize(const CornersT &corners) {   /* NT/FALK.cc:93-130, NT/IALK.cc:55-88 */
+	am->clearInitStatus(); ssm->clearInitStatus();
+	ssm->initialize(corners, am->getNChannels());
+	am->initializePixVals(ssm->getPts());
+	am->initializePixGrad(ssm->getPts());
+	am->initializeSimilarity(); am->initializeGrad(); am->initializeHess();
+	if (params.sec_ord_hess) am->initializePixHess(ssm->getPts());
+	if (params.hess_type == InitialSelf) {
+		ssm->cmptPixJacobian(init_pix_jacobian, am->getInitPixGrad());
+		if (params.sec_ord_hess) ssm->cmptPixHessian(init_pix_hessian, am->getInitPixHess(), am->getInitPixGrad());
+		selfHessian(hessian, init_pix_jacobian, init_pix_hessian);
+		if (params.leven_marq) init_self_hessian = hessian;
+	}
+}
+void AdditiveLK::update() {   /* NT/FALK.cc:132-257, NT/IALK.cc:90-199 */
+	double prev_similarity = 0, leven_marq_delta = params.lm_delta_init;
+	bool state_reset = false;
+	iters_done = 0;
+	if (!inverse) am->setFirstIter();   /* (NT/FALK.cc:140; IALK does not) */
+	for (int iter_id = 0; iter_id < params.max_iters; ++iter_id) {
+		++iters_done;
+		am->updatePixVals(ssm->getPts());
+		am->updateSimilarity(false);
+		if (params.leven_marq && !state_reset) {
+			const double curr_similarity = am->getSimilarity();
+			if (iter_id > 0) {
+				if (curr_similarity < prev_similarity) {
+					leven_marq_delta *= params.lm_delta_update;
+					for (int i = 0; i < ssm_state_size; ++i) inv_update[i] = -state_update[i];   /* undo the last update */
+					ssm->additiveUpdate(inv_update);
+					state_reset = true;
+					continue;
+				}
+				if (curr_similarity > prev_similarity) leven_marq_delta /= params.lm_delta_update;
+			}
+			prev_similarity = curr_similarity;
+		}
+		state_reset = false;
+		if (inverse) {
+			ssm->cmptApproxPixJacobian(curr_pix_jacobian, am->getInitPixGrad());
+		} else {
+			am->updatePixGrad(ssm->getPts());
+			ssm->cmptPixJacobian(curr_pix_jacobian, am->getCurrPixGrad());
+		}
+		am->updateCurrGrad();
+		am->cmptCurrJacobian(jacobian, curr_pix_jacobian);
+		if (params.sec_ord_hess && params.hess_type != InitialSelf) {
+			if (inverse) ssm->cmptApproxPixHessian(curr_pix_hessian, am->getInitPixHess(), am->getInitPixGrad());
+			else {
+				am->updatePixHess(ssm->getPts());
+				ssm->cmptPixHessian(curr_pix_hessian, am->getCurrPixHess(), am->getCurrPixGrad());
+			}
+		}
+		switch (params.hess_type) {
+		case InitialSelf: if (params.leven_marq) hessian = init_self_hessian; break;
+		case CurrentSelf: selfHessian(hessian, curr_pix_jacobian, curr_pix_hessian); break;
+		default:
+			if (params.sec_ord_hess) am->cmptCurrHessian(hessian, curr_pix_jacobian, curr_pix_hessian);
+			else am->cmptCurrHessian(hessian, curr_pix_jacobian);
+			break;
+		}
+		dampAndSolve(leven_marq_delta);
+		prev_corners = ssm->getCorners();
+		ssm->additiveUpdate(state_update);
+		const double update_norm = utils::squaredDistance(prev_corners, ssm->getCorners());
+		if (update_norm < params.epsilon) break;
+		am->clearFirstIter();
+	}
+	if (!inverse && params.enable_learning) am->updateModel(ssm->getPts());   /* NT/FALK.cc:251-253 */
+}
+
 } // namespace nt
 } // namespace mtf

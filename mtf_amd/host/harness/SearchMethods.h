@@ -1,5 +1,5 @@
 /*
- * SearchMethods.h -- nt::ESM, nt::FCLK, nt::ICLK written against the abstract AppearanceModel /
+ * SearchMethods.h -- nt::ESM, nt::FCLK, nt::ICLK, nt::FALK, nt::IALK written against the abstract AppearanceModel /
  * StateSpaceModel interface only (SM/include/mtf/SM/NT/SearchMethod.h:15-84; update loops
  * SM/src/NT/ESM.cc:170-296, NT/FCLK.cc:171-358, NT/ICLK.cc:160-299), parameters with the reference's names,
  * enums and class defaults (SM/src/ESMParams.cc:4-15, FCLKParams.cc:4-17, ICLKParams.cc:4-14).
@@ -60,6 +60,26 @@ public:
 	ICLK(AM am, SSM ssm, const SMParams &params);
 	void initialize(const CornersT &corners) override;
 	void update() override;
+};
+/* the additive formulations (SM/src/NT/FALK.cc:93-257, NT/IALK.cc:55-199; class defaults FALKParams.cc:3-15, IALKParams.cc:4-11): one
+ * class body, the pixel Jacobian of a pass being cmptPixJacobian of the current gradient (FALK) or cmptApproxPixJacobian of the
+ * template's (IALK); the update is ssm->additiveUpdate, a Levenberg-Marquardt undo its negative */
+class AdditiveLK : public LKSearchMethod {
+public:
+	enum HessType { InitialSelf, CurrentSelf, Std };
+	void initialize(const CornersT &corners) override;
+	void update() override;
+protected:
+	AdditiveLK(AM am, SSM ssm, const SMParams &params, bool inverse);
+	bool inverse;
+};
+class FALK : public AdditiveLK {
+public:
+	FALK(AM am, SSM ssm, const SMParams &params) : AdditiveLK(am, ssm, params, false) { name = "falk_nt"; }
+};
+class IALK : public AdditiveLK {
+public:
+	IALK(AM am, SSM ssm, const SMParams &params) : AdditiveLK(am, ssm, params, true) { name = "ialk_nt"; }
 };
 
 } // namespace nt

@@ -1,6 +1,6 @@
 /*
  * host_capi.cpp -- a small C wrapper around the C++ host layer (mtf::hip::HipAM / HipSSM driven by
- * mtf::nt::ESM / FCLK / ICLK), the equivalent of the reference's pyMTF create / setRegion / getRegion
+ * mtf::nt::ESM / FCLK / ICLK / FALK / IALK), the equivalent of the reference's pyMTF create / setRegion / getRegion
  * (Examples/cpp/pyMTF.cc:35-62), so that the test-suite can drive the C++ objects.  HARNESS (libmtfharness.so): it constructs the
  * product's adapters and device drivers (libmtfhost.so) AND the restated reference callers that live next to it.
  */
@@ -51,6 +51,8 @@ static mtfhost_tracker *create_on(std::shared_ptr<hip::HipPair> pair, int sm, in
 		else if (sm == MTFHIP_SM_ESM) t->sm.reset(new nt::ESM(t->am, t->ssm, p));
 		else if (sm == MTFHIP_SM_FCLK) t->sm.reset(new nt::FCLK(t->am, t->ssm, p));
 		else if (sm == MTFHIP_SM_ICLK) t->sm.reset(new nt::ICLK(t->am, t->ssm, p));
+		else if (sm == MTFHIP_SM_FALK) t->sm.reset(new nt::FALK(t->am, t->ssm, p));
+		else if (sm == MTFHIP_SM_IALK) t->sm.reset(new nt::IALK(t->am, t->ssm, p));
 		else { g_err = "unknown search method"; return nullptr; }
 		return t.release();
 	}

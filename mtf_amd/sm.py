@@ -1,7 +1,8 @@
 """Search methods that drive the device hot path: the callers of SURVEY.md section 8a rows A12 / A13.
 
 ESM / FCLK / ICLK mirror nt::ESM / nt::FCLK / nt::ICLK (SM/src/NT/{ESM,FCLK,ICLK}.cc): `initialize`,
-`update`, `set_region`, `get_region` with the reference's parameter names and defaults.  Two execution
+`update`, `set_region`, `get_region` with the reference's parameter names and defaults.  FALK / IALK (NT/FALK.cc,
+NT/IALK.cc) are the additive formulations: the same drivers with StateSpaceModel::additiveUpdate (no set_region).  Two execution
 modes: host_solve=True keeps the S x S solve, Levenberg-Marquardt and the compositional update on the
 host exactly as the reference does (one fused launch + one small read-back per iteration);
 host_solve=False runs the whole loop on the device (mtfhip_batch_track).
@@ -26,7 +27,8 @@ def _solve(H, g):
 
 
 class LKTracker:
-    """One or many (B) independent targets tracked with ESM / FCLK / ICLK + SSD, NCC or MI on one GPU through the fused path
+    """One or many (B) independent targets tracked with ESM / FCLK / ICLK (or the additive FALK / IALK: SSD and NCC, k_alk_pass +
+    k_alk_finish) + SSD, NCC or MI on one GPU through the fused path
     (mtfhip_batch_iterate: k_fused_ssd / k_fused_ncc, or the fused MI passes): host_solve=True = fused launch(es) per
     iteration + the reference's pivoted QR and Levenberg-Marquardt on the host; False = the whole loop on the device
     (mtfhip_batch_track)."""
@@ -67,6 +69,7 @@ class LKTracker:
             return corners
         sm, b = self.sm, self.batch
         B = self.B
+        additive = sm.sm in (L.SM_FALK, L.SM_IALK)
         active = np.ones(B, dtype=bool)
         prev_f = np.zeros(B)
         delta = np.full(B, sm.lm_delta_init)
@@ -106,8 +109,12 @@ class LKTracker:
                 if not active[t]:
                     continue
                 if undo[t]:
-                    # undo the last update: FCLK / ESM apply the inverse, ICLK re-applies the forward update
-                    dps[t] = last_dp[t] if sm.sm == L.SM_ICLK else b.invert_state(np.tile(last_dp[t], (B, 1)))[0]
+                    # undo the last update: FCLK / ESM apply the inverse, ICLK re-applies the forward update, FALK / IALK add the
+                    # negative (NT/FALK.cc:156-158)
+                    if additive:
+                        dps[t] = -last_dp[t]
+                    else:
+                        dps[t] = last_dp[t] if sm.sm == L.SM_ICLK else b.invert_state(np.tile(last_dp[t], (B, 1)))[0]
                     continue
                 Ht = H[t].copy()
                 if sm.leven_marq:
@@ -115,7 +122,7 @@ class LKTracker:
                 dp = _solve(Ht, g[t])
                 last_dp[t] = dp
                 dps[t] = b.invert_state(np.tile(dp, (B, 1)))[0] if sm.sm == L.SM_ICLK else dp
-            b.compositional_update(dps)
+            (b.additive_update if additive else b.compositional_update)(dps)
             corners = b.get_corners()
             change = ((prev_corners - corners) ** 2).reshape(B, -1).sum(axis=1)
             for t in range(B):
@@ -139,9 +146,9 @@ class LKTracker:
 
 
 class NTSearchMethod:
-    """nt::ESM / nt::FCLK / nt::ICLK written against the AM / SSM interface only, one C-ABI call per
+    """nt::ESM / nt::FCLK / nt::ICLK / nt::FALK / nt::IALK written against the AM / SSM interface only, one C-ABI call per
     reference virtual, exactly in the reference's order (SM/src/NT/ESM.cc:170-296, NT/FCLK.cc:171-358,
-    NT/ICLK.cc:160-299).  Works for every appearance model the device path implements (SSD, NCC, MI);
+    NT/ICLK.cc:160-299, NT/FALK.cc:132-257, NT/IALK.cc:90-199).  Works for every appearance model the device path implements (SSD, NCC, MI);
     this is the literal drop-in shape -- LKTracker is the fused fast path for SSD.  Levenberg-Marquardt
     is not vectorised here (use LKTracker(host_solve=True) for SSD)."""
 
@@ -208,6 +215,16 @@ class NTSearchMethod:
             if sm.hess_type == 0:
                 if so:
                     self._pix_hessian(True)
+                self.H0 = self._self_hessian(L.BUF_J0, L.BUF_D2I0_DP2)
+        elif sm.sm in (L.SM_FALK, L.SM_IALK):   # NT/FALK.cc:96-122, NT/IALK.cc:58-82
+            b.initialize_pix_grad()
+            b.initialize_similarity(); b.initialize_grad(); b.initialize_hess()
+            if so:
+                b.initialize_pix_hess()
+            if sm.hess_type == 0:
+                b.cmpt_pix_jacobian(L.JAC_PIX, L.BUF_DI0_DX, L.BUF_J0)
+                if so:
+                    b.cmpt_pix_hessian(L.JAC_PIX, L.BUF_D2I0_DX2, L.BUF_DI0_DX, L.BUF_D2I0_DP2)
                 self.H0 = self._self_hessian(L.BUF_J0, L.BUF_D2I0_DP2)
         else:
             self._pix_jacobian(True)
@@ -289,9 +306,38 @@ class NTSearchMethod:
             H = b.cmpt_init_hessian2() if sm.sec_ord_hess else b.cmpt_init_hessian(L.BUF_J0)
         return g, H
 
+    # NT/FALK.cc:144-221 (ialk False) / NT/IALK.cc:101-171 (True)
+    def _alk_iter(self, ialk):
+        b, sm = self.batch, self.sm
+        b.update_pix_vals()
+        b.update_similarity(False)
+        if ialk:
+            b.cmpt_pix_jacobian(L.JAC_APPROX, L.BUF_DI0_DX, L.BUF_JT)
+        else:
+            b.update_pix_grad()
+            b.cmpt_pix_jacobian(L.JAC_PIX, L.BUF_DIT_DX, L.BUF_JT)
+        b.update_curr_grad()
+        g = b.cmpt_curr_jacobian(L.BUF_JT)
+        so = bool(sm.sec_ord_hess)
+        if so and sm.hess_type != 0:
+            if ialk:
+                b.cmpt_pix_hessian(L.JAC_APPROX, L.BUF_D2I0_DX2, L.BUF_DI0_DX, L.BUF_D2IT_DP2)
+            else:
+                b.update_pix_hess()
+                b.cmpt_pix_hessian(L.JAC_PIX, L.BUF_D2IT_DX2, L.BUF_DIT_DX, L.BUF_D2IT_DP2)
+        if sm.hess_type == 0:
+            H = self.H0
+        elif sm.hess_type == 1:
+            H = self._self_hessian(L.BUF_JT, L.BUF_D2IT_DP2)
+        else:
+            H = b.cmpt_curr_hessian2() if so else b.cmpt_curr_hessian(L.BUF_JT)
+        return g, H
+
     def update(self):
         b, sm = self.batch, self.sm
-        step = {L.SM_ESM: self._esm_iter, L.SM_FCLK: self._fclk_iter, L.SM_ICLK: self._iclk_iter}[sm.sm]
+        step = {L.SM_ESM: self._esm_iter, L.SM_FCLK: self._fclk_iter, L.SM_ICLK: self._iclk_iter,
+                L.SM_FALK: lambda: self._alk_iter(False), L.SM_IALK: lambda: self._alk_iter(True)}[sm.sm]
+        additive = sm.sm in (L.SM_FALK, L.SM_IALK)
         active = np.ones(self.B, dtype=bool)
         self.trace = []
         for _ in range(sm.max_iters):
@@ -305,7 +351,7 @@ class NTSearchMethod:
             prev = b.get_corners()
             upd = b.invert_state(dps) if sm.sm == L.SM_ICLK else dps
             upd[~active] = 0
-            b.compositional_update(upd)
+            (b.additive_update if additive else b.compositional_update)(upd)
             change = ((prev - b.get_corners()) ** 2).reshape(self.B, -1).sum(axis=1)
             active &= ~(change < sm.epsilon)
             if not active.any():

@@ -601,7 +601,7 @@ int ncc_lazy_outputs(mtfhip_batch *b, int trig, int j_a, bool hess_mean, double 
  *   FCLK  NT/FCLK.cc:171-358: updatePixVals, updateSimilarity, updateCurrGrad, pixel gradient + pixel Jacobian, cmptCurrJacobian(Jt)
  *   ESM   NT/ESM.cc:170-296: ... updateInitGrad, cmptDifferenceOfJacobians(J0, Jt)   (jac_type Original: cmptCurrJacobian(Jm))
  *   ICLK  NT/ICLK.cc:160-299: updatePixVals, updateSimilarity, updateInitGrad, cmptInitJacobian(J0) */
-/* Deferred fusion, MI: the recognised sequence is served by the fused MI passes (api_fused.hip: mi_iterate describes
+/* Deferred fusion, MI: the recognised sequence is served by the fused MI passes (api_mi_iter.hip: mi_enqueue describes
  * them) -- the fused LK kernel materialising It / dIt_dx / Jt, one histogram pass (with the self histogram when the search
  * method has been asking for self Hessians), one table kernel, one gradient + Jacobian-product pass that also writes the
  * gradient vectors the recorded update*Grad calls would have written.  `sm` carries what lazy_try_fused classified. */
@@ -1030,10 +1030,7 @@ static int add_second_order(mtfhip_batch *b, int d2a, int d2b, const double *dev
 	if (!d2_buf_ok(d2a) || (d2b >= 0 && !d2_buf_ok(d2b))) return fail(MTFHIP_ERR_INVALID_ARG, "pixel-Hessian buffer must be D2I0_DP2, D2IT_DP2 or D2IM_DP2");
 	if (!b->buf[d2a] || (d2b >= 0 && !b->buf[d2b])) return fail(MTFHIP_ERR_LOGIC, "second-order Hessian: pixel Hessian buffer was never computed");
 	const int nblk = simple_blocks_per_target(b->N), S = b->S;
-	if (!b->d_d2_part) {
-		HIP_TRY(hipMalloc(&b->d_d2_part, sizeof(double) * 64 * (size_t)nblk * b->B));
-		HIP_TRY(hipMalloc(&b->d_d2_out, sizeof(double) * 64 * (size_t)b->B));
-	}
+	TRY(ensure_second_order_scratch(b));
 	{
 		TimedScope ts(b->ctx, "pix_hess_weighted_sum");
 		launch_weighted_plane_sum(b->view(), b->buf[d2a], d2b >= 0 ? b->buf[d2b] : nullptr, dev_w, b->d_d2_part, nblk, b->d_d2_out, b->ctx->stream);

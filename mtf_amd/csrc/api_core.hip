@@ -659,7 +659,7 @@ int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, boo
 	b->fresh_reinit = false;   /* (grid_reinit_fused sets it again behind this call) */
 	FLUSH_AM(b);   /* pending calls are replayed (with the points they need); the points themselves are about to change */
 	if (b) ++b->lz.epoch;
-	if (b) { touch_all(b); b->lz.it_epoch = -1; TRY(ensure_df(b)); }
+	TRY(begin_entry(b));
 	if (!b || (!corners && !layout_later)) return fail(MTFHIP_ERR_INVALID_ARG, "set_corners: NULL argument");
 	const bool hom = b->desc.ssm == MTFHIP_SSM_HOMOGRAPHY;
 	if (layout_later && !(defer_grid && !hom)) return fail(MTFHIP_ERR_LOGIC, "set_corners: a layout behind the launch needs the deferred affine reset");

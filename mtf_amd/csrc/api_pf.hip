@@ -290,10 +290,7 @@ static int pf_pick_sampler(const mtfhip_batch *b, const mtfhip_pf_desc *d, int *
 static size_t pf_round_chunk(size_t n) { const size_t c = (size_t)pf_chunk(); return (n + c - 1) / c * c; }
 int mtfhip_pf_create(mtfhip_batch *b, const mtfhip_pf_desc *d, mtfhip_pf **out) {
 	if (!b || !d || !out) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: NULL argument");
-	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "pf_create: SCV is not available on the particle filter (SCVDist is a per-candidate intensity map)");
-	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "pf_create: RSCV is not available on the particle filter (RSCVDist is a per-candidate intensity map)");
-	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "pf_create: LSCV is not available on the particle filter (LSCVDist is a per-candidate intensity map)");
-	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "pf_create: LRSCV is not available on the particle filter (its maps are per-candidate intensity maps)");
+	TRY(refuse_intensity_mapped(b, "pf_create", " is not available on the particle filter"));
 	if (b->B != 1) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: the particle filter tracks one target (batch of %d)", b->B);
 	if (d->n_particles < 1) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: n_particles must be positive");
 	if (d->dynamic_model < 0 || d->dynamic_model > 1 || d->update_type < 0 || d->update_type > 1 || d->likelihood_func < 0 || d->likelihood_func > 2 ||

@@ -2,7 +2,7 @@
  * mtfhip_api_internal.h -- what the translation units of the C-ABI implementation share: error plumbing, the small
  * host-side math (3x3 warps, 4-corner DLT), the context / batch handles and their helpers, and the declarations of
  * the functions that cross unit boundaries (the deferred-fusion layer lives in api_am.hip, the NCC moment forms in
- * api_fused.hip).  Not installed: include/mtfhip.h is the public contract.
+ * api_ncc_moments.hip, the skeleton of the device-side loops in api_track.hip).  Not installed: include/mtfhip.h is the public contract.
  */
 #ifndef MTFHIP_API_INTERNAL_H
 #define MTFHIP_API_INTERNAL_H
@@ -123,7 +123,7 @@ struct mtfhip_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;
 	bool own_stream = false;
-	/* second queue of the device-side loop (track_core: two chunks of independent targets in flight, one's solve + update under the
+	/* second queue of the device-side loop (track_loop_chunked: two chunks of independent targets in flight, one's solve + update under the
 	 * other's pixel pass); created on first use, ordered against `stream` by the two events */
 	hipStream_t extra_streams[3] = {nullptr, nullptr, nullptr};
 	hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
@@ -275,7 +275,7 @@ struct mtfhip_batch {
 	/* k_track_persist: barrier words, the generation counter the host advances per launch; persist_ok is cleared for good when a
 	 * launch could not keep its workgroups resident (the two-launch loop finishes the call and serves the later ones) */
 	int *d_persist = nullptr;
-	/* deferred materialisation of the device-side loop (track_core): warp [B][9] | state [B][8] of the last pass of a target that stopped
+	/* deferred materialisation of the device-side loop (track_loop_chunked): warp [B][9] | state [B][8] of the last pass of a target that stopped
 	 * behind a non-materialising pass, and the per-target flags of the trailing materialising launch */
 	double *d_last_ws = nullptr;
 	int *d_need_mat = nullptr;
@@ -403,6 +403,14 @@ static int ensure_buf(mtfhip_batch *b, int id) {
 	if (b->buf[id]) return MTFHIP_OK;
 	HIP_TRY(hipMalloc(&b->buf[id], sizeof(double) * b->per_target[id] * b->B));
 	HIP_TRY(hipMemsetAsync(b->buf[id], 0, sizeof(double) * b->per_target[id] * b->B, b->ctx->stream));
+	return MTFHIP_OK;
+}
+
+/* the second-order term's block rows and [B][64] sums (k_second_order_ssd, k_weighted_plane_sum), allocated by the first call that needs them */
+static int ensure_second_order_scratch(mtfhip_batch *b) {
+	if (b->d_d2_part) return MTFHIP_OK;
+	HIP_TRY(hipMalloc(&b->d_d2_part, sizeof(double) * 64 * (size_t)simple_blocks_per_target(b->N) * b->B));
+	HIP_TRY(hipMalloc(&b->d_d2_out, sizeof(double) * 64 * (size_t)b->B));
 	return MTFHIP_OK;
 }
 
@@ -646,6 +654,11 @@ static inline void touch(mtfhip_batch *b, int id) { ++b->lz.ver[id]; }
 static inline void touch_all(mtfhip_batch *b) { for (int i = 0; i < MTFHIP_BUF_COUNT; ++i) ++b->lz.ver[i]; }
 int lazy_flush(mtfhip_batch *b, bool pts = true);
 int ensure_df(mtfhip_batch *b);
+/* what an entry point that rewrites the batch's arrays does behind its FLUSH / FLUSH_AM: every cached version is void */
+static inline int begin_entry(mtfhip_batch *b) {
+	if (b) { touch_all(b); b->lz.it_epoch = -1; TRY(ensure_df(b)); }
+	return MTFHIP_OK;
+}
 static int ensure_one(mtfhip_batch *b, bool curr);
 void stale_clear(mtfhip_batch *b, bool df0, bool dft);
 int protect_stale(mtfhip_batch *b, bool w0, bool wt);
@@ -684,6 +697,24 @@ static inline mtfhip::MiJ0Rebuild mi_j0_rebuild(const mtfhip_batch *b) {
 	return rb;
 }
 
+/* the template lattice's extents and resolution as the kernels that lay a grid out themselves take them (set_corners_core's extents:
+ * ProjectiveBase.cc:14, Affine.cc:56-57); everything else of the record is zero */
+static inline mtfhip::RegionIngest region_geometry(const mtfhip_batch *b) {
+	const bool homg = b->desc.ssm == MTFHIP_SSM_HOMOGRAPHY;
+	mtfhip::RegionIngest rg{};
+	rg.lo_x = homg ? -0.5 : 1 - b->desc.resx / 2.0; rg.lo_y = homg ? -0.5 : 1 - b->desc.resy / 2.0;
+	rg.hi_x = homg ? 0.5 : b->desc.resx / 2.0; rg.hi_y = homg ? 0.5 : b->desc.resy / 2.0;
+	rg.resx = b->desc.resx; rg.resy = b->desc.resy; rg.force_unit_z = homg ? 0 : 1;
+	return rg;
+}
+/* ... and the deferred layout (b->deferred_gdesc / _region_map): the kernel lays its patches out itself from the grid's region */
+static inline void region_deferred_layout(const mtfhip_batch *b, mtfhip::RegionIngest &rg) {
+	const mtfhip_grid_desc &gd = b->deferred_gdesc;
+	rg.layout = 1;
+	rg.grid = mtfhip::GridLayoutHD{gd.grid_size_x, gd.grid_size_y, gd.patch_size_x, gd.patch_size_y, gd.dyn_patch_size ? 1 : 0, gd.patch_centroid_inside ? 1 : 0};
+	std::memcpy(rg.region_map, b->deferred_region_map, sizeof(rg.region_map));
+}
+
 /* ---- functions defined in one api_*.hip unit and used in another ---- */
 enum { LAZY_CURR_JAC = 0, LAZY_DIFF_JAC = 1, LAZY_INIT_JAC = 2 };
 int ensure_pts(mtfhip_batch *b);
@@ -693,24 +724,72 @@ int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, boo
 void set_corners_finish_deferred(mtfhip_batch *b);
 int do_update_grad_pts(mtfhip_batch *b, double grad_eps);
 int gemv_to_host(mtfhip_batch *b, const double *v1, int j1, const double *v2, int j2, int sum_mode, double *g, int diff);
+int mi_blocks(const mtfhip_batch *b);
+int push_ncc(mtfhip_batch *b);
+/* api_ncc_moments.hip (ncc_assemble: one target's reduced row -> f, g and H before damping; ncc_refresh_mirrors: its scalars -> It_mean / b / a / f) */
 int ncc_template_moments(mtfhip_batch *b);
 int ncc_lazy_outputs(mtfhip_batch *b, int trig, int j_a, bool hess_mean, double *g);
 int ncc_hessian_from_cache(mtfhip_batch *b, int j_buf, int kind, double *H);
-int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa);
-/* api_fused.hip: one target's reduced row -> the search method's f, g and H (before damping), SSD and NCC */
-void assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H);
 int ncc_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, const double *M, TargetHost &h, double *f, double *g, double *H);
+void ncc_refresh_mirrors(const mtfhip_batch *b, TargetHost &h, const double *M);
+/* api_fused.hip (second_order_term: -1 for none; assemble: one target's reduced SSD row -> f, g and H; assemble_rows: every target of an SSD / NCC
+ * pass; store_h0: th[].h0, d_h0 and d_h0inv from H0 [B][S x S] -- enqueued only: the caller synchronises the stream before it returns) */
+int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn);
+bool template_init_fused_ok(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
+int init_template_fused(mtfhip_batch *b, const mtfhip_sm_desc *sm, const mtfhip::RegionIngest *rg = nullptr, bool publish_host = true);
+int set_region_core(mtfhip_batch *b, const double *corners, const mtfhip_sm_desc *sm, bool for_track, bool defer_grid = false, bool layout_later = false);
+static inline bool region_refreshes(const mtfhip_sm_desc *sm) { return sm->sm == MTFHIP_SM_ESM || (sm->sm == MTFHIP_SM_FCLK && sm->hess_type == 0); }
+int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa);
+int second_order_term(const mtfhip_sm_desc *sm, int am = MTFHIP_AM_SSD);
+void assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H);
+int assemble_rows(mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, int nblk, const double *so, double so_scale, double *f, double *g, double *H);
+int store_h0(mtfhip_batch *b, const double *H0, bool with_inverse);
+/* api_mi_iter.hip.  What an MI iteration of the search method needs from the AM (NT/ESM.cc:315-377, NT/FCLK.cc:262-283, NT/ICLK.cc:204-252) */
+struct MiPlan {
+	enum { H_CONST, H_SELF_JT, H_CURR_JT, H_CURR_JM, H_SUM_STD, H_INIT_J0 };
+	int hk;
+	bool iclk, esm, fclk, self, need_jt, orig_jac, need_mean;
+	explicit MiPlan(const mtfhip_sm_desc *sm) {
+		iclk = sm->sm == MTFHIP_SM_ICLK; esm = sm->sm == MTFHIP_SM_ESM; fclk = sm->sm == MTFHIP_SM_FCLK;
+		const int ht = sm->hess_type;
+		hk = ht == 0 ? H_CONST
+			: esm ? (ht <= 2 ? H_SELF_JT : (ht == 3 ? H_CURR_JM : (ht == 4 ? H_SUM_STD : H_CURR_JT)))
+			: fclk ? (ht == 1 ? H_SELF_JT : H_CURR_JT)
+			: (ht == 1 ? H_SELF_JT : H_INIT_J0);
+		self = hk == H_SELF_JT;                /* cmptSelfHessian(Jt): the self histogram rides along with pass 1 */
+		need_jt = !iclk || self;               /* ICLK's CurrentSelf refreshes the current pixel Jacobian (NT/ICLK.cc:215-237) */
+		orig_jac = esm && sm->jac_type == 0;   /* cmptCurrJacobian(mean Jacobian) */
+		need_mean = orig_jac || hk == H_CURR_JM;
+	}
+};
+int mi_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
+/* api_track.hip.  What track_core hands its drivers: second-order term or -1, passes to enqueue, block rows of the second-order pass, ... */
+struct TrackCtx { int so_term, max_passes, nb2; bool resume, region_mode; };
+int track_loop_mi(mtfhip_batch *b, const mtfhip_sm_desc *sm, mtfhip::TrackState &ts, const TrackCtx &cx);   /* (api_mi_iter.hip) */
+/* ... and the skeleton every device-side loop shares (track_core, alk_track): the upload of the state slab, the initial Levenberg-Marquardt
+ * state, the look at the stop flags every eighth pass, the read-back of the slab, the tail of a loop that ran to its read-back */
+int loop_upload_slab(mtfhip_batch *b, hipStream_t st, bool keep_ncc);
+int loop_lm_state(mtfhip_batch *b, const mtfhip_sm_desc *sm, hipStream_t st, double **lm);
+bool loop_all_stopped(const mtfhip_sm_desc *sm, int max_passes, int it, const int *d_flags, int n, hipStream_t on, std::vector<int> &h_flags, hipError_t *err = nullptr);
+int loop_read_back(mtfhip_batch *b, hipStream_t st, unsigned long long pub_seq, int *n_iters, double *corners, const char **h_res);
+static inline void loop_done(mtfhip_batch *b) {
+	b->pts_stale = true;       /* CURR_PTS follow the final warp when an un-fused kernel next needs them */
+	b->stage_a_busy = false;   /* the stream has drained: whatever set_corners staged has been consumed */
+}
+bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
+int track_validate(mtfhip_batch *b, const mtfhip_sm_desc *sm);
+int track_region_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *region_corners, int *n_iters, double *corners, const mtfhip_grid_desc *grid);
+extern const bool g_track_dbg_timing;   /* MTFHIP_TRACK_DEBUG_TIMING: host-side stamps of the loop and the grid frames on stderr */
 /* api_alk.hip: MTFHIP_SM_FALK / _IALK behind mtfhip_batch_init_template / _iterate / _track */
 static inline bool alk_sm(int sm) { return sm == MTFHIP_SM_FALK || sm == MTFHIP_SM_IALK; }
 int alk_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int alk_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
 int alk_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners);
-int mi_blocks(const mtfhip_batch *b);
-int push_ncc(mtfhip_batch *b);
+/* api_cand.hip (peer: also store the weights to the other ranks' mailboxes; refuse_intensity_mapped: "<fn>: <model><what> (<why>)") */
 int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out, double *dev_features,
-	int row_lo, int row_count, const double *base_dev, const int *done);   /* api_fused.hip */
+	int row_lo, int row_count, const double *base_dev, const int *done);
 int score_block_dev(mtfhip_batch *b, const double *dev_states, int lo, int cnt, double *wts, double *sim, int likelihood_func,
-	double measurement_sigma, double max_similarity, const mtfhip::PfPeerPush *peer = nullptr);   /* api_fused.hip; peer: also store the
-	                                                                                       weights to the other ranks' mailboxes */
+	double measurement_sigma, double max_similarity, const mtfhip::PfPeerPush *peer = nullptr);
+int refuse_intensity_mapped(const mtfhip_batch *b, const char *fn, const char *what);
 } /* extern "C" */
 #endif

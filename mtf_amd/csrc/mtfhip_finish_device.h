@@ -160,7 +160,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	const bool use_h0 = (sm.hess_type == 0) || (sm.sm == MTFHIP_SM_ICLK && !ts.h_from_acc);
 	const bool sum_h0 = (sm.sm == MTFHIP_SM_ESM) && (sm.hess_type == 2 || (sm.hess_type == 4 && !ts.h_from_acc));   /* (MI's SumOfStd arrives summed) */
 	const double gscale = (sm.sm == MTFHIP_SM_ESM) ? 0.5 : 1.0;
-	/* NCC from its moments (ncc_assemble in api_fused.hip is the host twin; formulas and citations there) */
+	/* NCC from its moments (ncc_assemble in api_ncc_moments.hip is the host twin; formulas and citations there) */
 	const double nN = (double)bv.N;
 	const double n_mt = ncc ? acc_s[NCC_IT] / nN : 0.0, n_m0 = ncs[0], n_c = ncc ? ncs[1] : 1.0;
 	const double n_b2 = ncc ? acc_s[NCC_IT2] - nN * n_mt * n_mt : 1.0, n_b = ncc ? sqrt(n_b2) : 1.0;

@@ -72,7 +72,7 @@ struct Tex {
 
 /* AM = MTFHIP_AM_SSD: the residual-weighted sums above.  AM = MTFHIP_AM_NCC: the same pass accumulates the raw moments
  * NCC's similarity, Jacobians and first-order Hessians are functions of (NCC.cc:124-389 restated in ncc_from_moments,
- * api_fused.hip) -- Gram(row) | sum Jt | sum It Jt | sum I0 Jt | sum It J0 | sum It, It^2, I0 It -- so an NCC iteration
+ * api_ncc_moments.hip) -- Gram(row) | sum Jt | sum It Jt | sum I0 Jt | sum It J0 | sum It, It^2, I0 It -- so an NCC iteration
  * needs no second pass over the pixels for the means; the partial rows are NCC_ACC_COUNT wide. */
 /* FAST (lean launches only, MAT = false): tolerance-mode arithmetic -- one reciprocal per point, FMA-contracted warp / interpolant /
  * rows, and on the wave-uniform interior path the closed-form slope of the bilinear cell times the ROUNDED step the reference's 1e-8

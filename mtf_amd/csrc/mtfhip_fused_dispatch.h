@@ -45,7 +45,7 @@ constexpr FusedKey fused_select(int route, int am, int channels, int ssm, int mo
 	bool mapped = true) {
 	FusedKey k{};
 	/* the appearance model of the kernel: SCV and LSCV re-map the template between the passes and run SSD on it; MI takes It and the
-	 * Jacobians a materialising SSD pass writes and ignores its sums (mi_enqueue, api_fused.hip); RSCV and LRSCV map the current patch
+	 * Jacobians a materialising SSD pass writes and ignores its sums (mi_enqueue, api_mi_iter.hip); RSCV and LRSCV map the current patch
 	 * inside the pass (an LRSCV pass without maps is an SSD pass on the raw patch; an RSCV one is not launched) */
 	switch (am) {
 	case MTFHIP_AM_SSD: case MTFHIP_AM_SCV: case MTFHIP_AM_LSCV: case MTFHIP_AM_MI: k.am = MTFHIP_AM_SSD; break;

@@ -1,6 +1,6 @@
 /*
  * mtfhip_internal.h -- shared between the HIP kernel translation units (kernels_*.hip) and the C-ABI
- * implementation (api_core.hip, api_am.hip, api_fused.hip).  Not installed; the public contract is include/mtfhip.h.
+ * implementation (the api_*.hip units).  Not installed; the public contract is include/mtfhip.h.
  */
 #ifndef MTFHIP_INTERNAL_H
 #define MTFHIP_INTERNAL_H
@@ -127,7 +127,7 @@ struct TrackState {
 	 * starts from the identity warp and the zero state at its template's corners, which that kernel left in init_corners_hm -- the slab's warps /
 	 * states / corners are not read, so the host does not upload them (one ingest launch and its gap less per frame, r06) */
 	int fresh_reset;
-	/* deferred materialisation (track_core): a pass launched with the non-materialising pixel kernel sets lean_pass; a target the finish
+	/* deferred materialisation (track_loop_chunked, api_track.hip): a pass launched with the non-materialising pixel kernel sets lean_pass; a target the finish
 	 * stops after such a pass (change < epsilon) leaves the warp and the state that pass ran at in warp_last ([B][9]) / state_last
 	 * ([B][8]) and raises need_mat[t]; one trailing launch of the materialising kernel at that warp then writes It / dIt_dx / Jt for
 	 * it.  NULL / 0: off. */

@@ -100,7 +100,7 @@ LOOP_KEY = {
     (2, 1, 0, 0): (1, 2, 0, 0, REPLAY), (2, 1, 0, 1): (1, 2, 0, 1, FAST_ICLK), (2, 1, 1, 0): (1, 2, 1, 0, REPLAY), (2, 1, 1, 1): (1, 2, 1, 0, REPLAY),
 }
 # the one-launch routes serve single-channel SSD and NCC only (their callers turn the intensity-mapped models and C = 3 away:
-# track_core's use_step and persist_fits), with the arguments of LOOP_KEY, and:
+# api_track.hip's track_takes_step and persist_fits), with the arguments of LOOP_KEY, and:
 # step (track_step_available, launch_track_step): (fast_math && !materialize) -> <MAT = false, FAST = true>, (!fast_math && materialize)
 # -> <true, false>, nothing else; persist (launch_track_persist, "fa.materialize must be 0"): FAST = fast_math, never materialising.
 STEP_SERVES = {(0, 0): False, (0, 1): True, (1, 0): True, (1, 1): False}      # (materialize, fast_math)

@@ -456,3 +456,68 @@ def test_grid_frame_is_refused(gpu_ctx, method):
         assert np.isfinite(c).all()
     finally:
         b.close()
+
+
+# ------------------------------------------------------------------ the loop skeleton the additive methods share with track_core
+# (api_track.hip: slab upload, Levenberg-Marquardt state, the look at the stop flags every eighth pass, read-back).  Three targets, an 11 x 9
+# patch (99 pixels: no multiple of the block size), ten passes and a convergence threshold no update falls below, so that the look at
+# the flags behind pass 8 is taken and finds every target active.  CurrentSelf Hessian: InitialSelf's constant Hessian is a host
+# reduction whose summation order follows the read-back transport (test_gpu_trackers.py::test_copy_and_sync_fallback_gives_the_same_results).
+SKEL_SIZE = (11, 9)
+SKEL_ITERS = 10
+SKEL_EPS = 1e-30
+SKEL_CASES = [(m, am, lm) for m in METHODS for am in (AC.SSD, AC.NCC) for lm in (0, 1)]
+SKEL_IDS = ["%s_%s_%s" % (AC.name(m), "ssd" if am == AC.SSD else "ncc", "lm" if lm else "gn") for m, am, lm in SKEL_CASES]
+
+
+def skeleton_run(ctx, method, am, lm, epsilon=SKEL_EPS, trace=False):
+    sm = mtf_amd.sm_desc(method, hess_type=1, leven_marq=lm, max_iters=SKEL_ITERS, epsilon=epsilon)
+    ctx.set_image(AC.frame0())
+    b = mtf_amd.Batch(ctx, am, AC.HOM, SKEL_SIZE[0], SKEL_SIZE[1], 3)
+    try:
+        b.set_corners(AC.BATCH_REGIONS)
+        b.init_template(sm)
+        b.set_state(np.stack([AC.batch_start(AC.HOM, t) for t in range(3)]))
+        ctx.set_image(AC.warped(AC.P_HOM))
+        if trace:
+            b.track_trace(SKEL_ITERS)
+        n_it, corners = b.track(sm)
+        recs = b.read_track_trace(n_it) if trace else None
+        return n_it.copy(), corners.copy(), b.get_state().copy(), recs
+    finally:
+        b.close()
+
+
+@pytest.mark.parametrize("method,am,lm", SKEL_CASES, ids=SKEL_IDS)
+def test_loop_skeleton_copy_and_sync_transport(gpu_ctx, monkeypatch, method, am, lm):
+    """A batch created under MTFHIP_ZERO_COPY=0 (slab up by hipMemcpyAsync, back by copy + synchronisation) gives the corners, n_iters and
+    final state of a default batch (ingest and publish kernels), bit for bit."""
+    want = skeleton_run(gpu_ctx, method, am, lm)
+    monkeypatch.setenv("MTFHIP_ZERO_COPY", "0")
+    got = skeleton_run(gpu_ctx, method, am, lm)
+    print("skeleton transport: n_iters %s / %s, max |d corners| %.3e, max |d state| %.3e" % (want[0], got[0], np.abs(want[1] - got[1]).max(),
+                                                                                            np.abs(want[2] - got[2]).max()))
+    assert list(want[0]) == [SKEL_ITERS] * 3      # no target stopped: the flags were looked at behind pass 8 and the loop went on
+    assert np.array_equal(want[0], got[0]) and np.array_equal(want[1], got[1]) and np.array_equal(want[2], got[2])
+
+
+@pytest.mark.parametrize("method,am,lm", SKEL_CASES, ids=SKEL_IDS)
+def test_loop_skeleton_trace_is_reproducible(gpu_ctx, method, am, lm):
+    """With mtfhip_batch_track_trace on, the recorded passes equal those of the same call on a second batch, bit for bit"""
+    a, b = skeleton_run(gpu_ctx, method, am, lm, trace=True), skeleton_run(gpu_ctx, method, am, lm, trace=True)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    for t in range(3):
+        assert len(a[3][t]) == len(b[3][t]) == int(a[0][t]) > 8
+        for ra, rb in zip(a[3][t], b[3][t]):
+            for k in ("H", "g", "dp", "corners"):
+                assert np.array_equal(ra[k], rb[k]), (t, k)
+            assert ra["f"] == rb["f"] and ra["undo"] == rb["undo"] and ra["lm_delta"] == rb["lm_delta"] and ra["has_H"] == rb["has_H"], t
+
+
+@pytest.mark.parametrize("method,am,lm", SKEL_CASES, ids=SKEL_IDS)
+def test_loop_skeleton_runs_every_pass_without_a_threshold(gpu_ctx, method, am, lm):
+    """epsilon = 0: nothing can stop a target, so every target reports max_iters passes -- a look at the flags that ended the loop when it
+    should not would leave fewer"""
+    n_it, corners, states, _ = skeleton_run(gpu_ctx, method, am, lm, epsilon=0.0)
+    assert list(n_it) == [SKEL_ITERS] * 3
+    assert np.isfinite(corners).all() and np.isfinite(states).all()

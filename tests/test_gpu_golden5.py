@@ -121,7 +121,7 @@ def test_mi_golden5_candidates(gpu_ctx, math):
 
 @pytest.mark.parametrize("n_bins,pou", [(10, 1), (8, 0)])
 def test_mi_fused_reproducible(gpu_ctx, frame, n_bins, pou):
-    """Run to run on one device the fused MI passes give the same bits (the comment at api_fused.hip's mi_enqueue_fast):
+    """Run to run on one device the fused MI passes give the same bits (the comment at api_mi_iter.hip's mi_enqueue_fast):
     the self-Hessian plan (HK = 1, the sorted pass with its moment tables), 8 targets of 200 x 200, ten Batch.iterate from one state in
     MATH_FAST, and two device-side Batch.track from one set of corners.  8 bins is the control."""
     rng = np.random.default_rng(91)

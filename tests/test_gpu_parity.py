@@ -1039,7 +1039,7 @@ def test_inline_warp_probe_and_equivalence(gpu_ctx, frame, frame2, ssm, am, monk
                          ids=lambda v: "_".join("%s%s" % kv for kv in v.items()) if isinstance(v, dict) else str(v))
 def test_two_queue_device_loop_equals_single_queue(oracle, gpu_ctx, frame, frame2, sm_kind, am, extra, monkeypatch):
     """The device-side loop keeps two chunks of independent targets in flight on two queues when the launches materialise the
-    interface arrays (track_queues in api_fused.hip): same per-target arithmetic, another cut of the pixel pass (half the resident
+    interface arrays (track_queues in api_track.hip): same per-target arithmetic, another cut of the pixel pass (half the resident
     workgroups per chunk), so the results agree with the single-queue loop to summation order -- iteration counts, final corners,
     and the arrays the last pass materialised -- and with the oracle's tracker."""
     rng = np.random.default_rng(23)

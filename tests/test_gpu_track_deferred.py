@@ -1,4 +1,4 @@
-"""Deferred materialisation of the device-side LK loop (track_core): with MTFHIP_TRACK_DEFER_MAT unset / 1 the passes before a target's
+"""Deferred materialisation of the device-side LK loop (track_loop_chunked, api_track.hip): with MTFHIP_TRACK_DEFER_MAT unset / 1 the passes before a target's
 last run the non-materialising kernel and the interface arrays are written once -- by the pass the host knows to be the last, or by one
 trailing launch for the targets the finish stopped earlier; with 0 every pass materialises.  Both loops take the same cut of the pixel
 pass and the same arithmetic, so everything a caller can see after the call is the same BITS."""

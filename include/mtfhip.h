@@ -171,7 +171,8 @@ int mtfhip_image_shape(mtfhip_ctx *ctx, int *rows, int *cols);
  * A BORROWED image must stay unchanged until the next call of this library that synchronises with the context's stream
  * (mtfhip_ctx_synchronize, any call that returns results to the host, mtfhip_image_keep_prev of the borrowed image): since r05 mtfhip_batch_init_template (its fused form) and
  * mtfhip_grid_reset(reinit) return with their sampling kernel still running.  Uploaded images are safe: the next upload is
- * ordered behind that kernel on the stream. */
+ * ordered behind that kernel on the stream.  mtfhip_batch_track / _track_region return results and remain such a point: where kernels
+ * that sample the image could follow the delivery of the results (a reachable epsilon), a call on a borrowed image waits for them. */
 int mtfhip_image_upload(mtfhip_ctx *ctx, const float *host_img, int height, int width, int row_stride);
 /* CV_32FC3 input of the multi-channel appearance models: `channels` (1 or 3) interleaved floats per pixel, row_stride in floats */
 int mtfhip_image_upload_mc(mtfhip_ctx *ctx, const float *host_img, int height, int width, int row_stride, int channels);

@@ -8,14 +8,22 @@
 extern "C" {
 
 /* active = 1, iters = 0, corners, warps, states, NCC scalars (unless keep_ncc): one pinned async copy of the whole slab (w0 is copied along:
- * init_grid consumed it long ago).  h_stage_b needs no guard: every return path of a loop has waited for the device to finish its work. */
-int loop_upload_slab(mtfhip_batch *b, hipStream_t st, bool keep_ncc) {
+ * init_grid consumed it long ago).  h_stage_b needs no guard: every return path of a loop has waited for its results, i.e. the stream has drained or
+ * -- the chunked loop's in-loop delivery -- all B targets have arrived, so the head of the call, which reads the buffer, has run. */
+/* lw (the chunked driver's fused head, track_core): the same launch also sets the loop's words (k_track_prologue); the copy fallback -- no host-visible
+ * staging buffer -- keeps its copy and sets them with that kernel behind it */
+int loop_upload_slab(mtfhip_batch *b, hipStream_t st, bool keep_ncc, const LoopWords *lw) {
 	const size_t Bt = (size_t)b->B;
 	std::memcpy(b->h_stage_b + 45 * sizeof(double) * Bt, b->h_stage_a + 45 * sizeof(double) * Bt, 9 * sizeof(double) * Bt);
 	fill_stage(b, b->h_stage_b, nullptr, 1, true);
-	if (b->h_stage_b_dev) launch_ingest_host(b->h_stage_b_dev, b->d_slab, b->slab_bytes, st, keep_ncc ? 37 * sizeof(double) * Bt : 0, keep_ncc ? 8 * sizeof(double) * Bt : 0);
+	const size_t skip_off = keep_ncc ? 37 * sizeof(double) * Bt : 0, skip_len = keep_ncc ? 8 * sizeof(double) * Bt : 0;
+	if (b->h_stage_b_dev && lw) { TimedScope tsc(b->ctx, "track_prologue", st); launch_track_prologue(b->h_stage_b_dev, b->d_slab, b->slab_bytes, skip_off, skip_len, *lw, st); }
+	else if (b->h_stage_b_dev) launch_ingest_host(b->h_stage_b_dev, b->d_slab, b->slab_bytes, st, skip_off, skip_len);
 	else if (keep_ncc) return fail(MTFHIP_ERR_LOGIC, "track: a held template-initialisation record needs the host-visible staging buffer");
-	else HIP_TRY(hipMemcpyAsync(b->d_slab, b->h_stage_b, b->slab_bytes, hipMemcpyHostToDevice, st));
+	else {
+		HIP_TRY(hipMemcpyAsync(b->d_slab, b->h_stage_b, b->slab_bytes, hipMemcpyHostToDevice, st));
+		if (lw) { TimedScope tsc(b->ctx, "track_prologue", st); launch_track_prologue(nullptr, nullptr, 0, 0, 0, *lw, st); }
+	}
 	b->warps_dirty = false;   /* the slab carries the warps */
 	return MTFHIP_OK;
 }
@@ -48,7 +56,7 @@ int loop_read_back(mtfhip_batch *b, hipStream_t st, unsigned long long pub_seq, 
 	if (pub_seq) TRY(wait_host_flag(b, pub_seq));
 	else if (b->h_pub_dev) {
 		const unsigned long long seq = ++b->acc_seq;
-		launch_publish_host(b->d_slab, b->h_pub_dev, b->slab_bytes, b->d_fin_count, b->h_flag_dev, seq, st);
+		{ TimedScope tsc(b->ctx, "publish_host", st); launch_publish_host(b->d_slab, b->h_pub_dev, b->slab_bytes, b->d_fin_count, b->h_flag_dev, seq, st); }
 		TRY(wait_host_flag(b, seq));
 	} else {
 		HIP_TRY(hipMemcpyAsync(b->h_stage_b, b->d_slab, b->slab_bytes, hipMemcpyDeviceToHost, st));
@@ -401,6 +409,13 @@ static void track_materialise_stopped(mtfhip_batch *b, const ChunkRun &r) {
 }
 /* the extra queues of the loop and the phase stamps that keep two of them apart (PhaseCtl); what cannot be created leaves one queue.
  * MTFHIP_TRACK_PHASE: the fraction of a period the queues are kept apart; 0 = no control */
+static double track_phase_frac() {
+	const char *e_ph = std::getenv("MTFHIP_TRACK_PHASE");
+	return e_ph ? std::atof(e_ph) : 0.35;
+}
+static void track_phase_words(mtfhip_ctx *c) {
+	if (!c->d_phase && hipMalloc(&c->d_phase, sizeof(unsigned long long) * 4) != hipSuccess) { (void)hipGetLastError(); c->d_phase = nullptr; }
+}
 static int track_open_queues(mtfhip_batch *b, int n_streams, double &phase_frac) {
 	mtfhip_ctx *c = b->ctx;
 	if (n_streams >= 2) {
@@ -409,10 +424,9 @@ static int track_open_queues(mtfhip_batch *b, int n_streams, double &phase_frac)
 			if (!c->extra_streams[q] && (hipStreamCreateWithFlags(&c->extra_streams[q], hipStreamNonBlocking) != hipSuccess ||
 				hipEventCreateWithFlags(&c->ev_join[q], hipEventDisableTiming) != hipSuccess)) { (void)hipGetLastError(); n_streams = 1; break; }
 	}
-	const char *e_ph = std::getenv("MTFHIP_TRACK_PHASE");
-	phase_frac = e_ph ? std::atof(e_ph) : 0.35;
+	phase_frac = track_phase_frac();
 	if (n_streams == 2 && phase_frac > 0) {
-		if (!c->d_phase && hipMalloc(&c->d_phase, sizeof(unsigned long long) * 4) != hipSuccess) { (void)hipGetLastError(); c->d_phase = nullptr; }
+		track_phase_words(c);
 	}
 	return n_streams;
 }
@@ -436,8 +450,9 @@ static bool track_takes_step(const mtfhip_batch *b, const FusedArgs &fa, int so_
 	return (e_st && e_st[0] == '1') && so_term < 0 && !intensity_mapped(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
 }
 /* one pass of one chunk on its queue: the intensity re-maps, the pixel pass (lean: the non-materialising one), the second-order pass, the finish */
+struct FinishCtl { PhaseCtl pc; HostPublish pub; int prio; };
 static int track_chunk_pass(mtfhip_batch *b, const mtfhip_sm_desc *sm, const FusedArgs &fa, const TrackCtx &cx, const ChunkRun &r, int it, bool lean, bool use_step,
-	const PhaseCtl &pc) {
+	const FinishCtl &fc) {
 	if (use_step) {
 		TimedScope tsc(b->ctx, "track_step", r.s);
 		launch_track_step(r.bc, b->ctx->img, r.fc, *sm, r.tc, r.part, r.nblk_c, b->d_persist + r.t0, r.s);
@@ -463,7 +478,10 @@ static int track_chunk_pass(mtfhip_batch *b, const mtfhip_sm_desc *sm, const Fus
 			b->desc.am == MTFHIP_AM_NCC ? SecondOrderNcc{r.part, r.nblk_c, r.tc.ncc} : SecondOrderNcc{nullptr, 0, nullptr});
 	}
 	TimedScope tsc(b->ctx, "finish_track", r.s);
-	launch_finish_track(r.bc, *sm, lean ? r.tl : r.tc, r.part, r.nblk_c, r.s, pc);
+	TrackState tf = lean ? r.tl : r.tc;
+	tf.last_pass = it + 1 == cx.max_passes ? 1 : 0;
+	tf.finish_prio = fc.prio;
+	launch_finish_track(r.bc, *sm, tf, r.part, r.nblk_c, r.s, fc.pc, fc.pub, r.t0);
 	return MTFHIP_OK;
 }
 /* Targets are independent, so the loops commute: all passes of a chunk of targets (track_chunk) run before the next chunk starts, two
@@ -475,15 +493,22 @@ static int track_chunk_pass(mtfhip_batch *b, const mtfhip_sm_desc *sm, const Fus
  * MTFHIP_TRACK_STAGGER_US: > 0 that many microseconds, 0 none.
  * The context's own stream takes the LATER chunk of a pair: it is then the last to finish, and the join at the end of the call finds
  * the other queue's event already signalled instead of paying a cross-queue wait (~12 us) in front of the result read-back. */
-static int track_loop_chunked(mtfhip_batch *b, const mtfhip_sm_desc *sm, const FusedArgs &fa, const TrackState &ts, const TrackCtx &cx) {
+/* The end of a call (cx.fused_io): the finish that stops a target, or the last one enqueued, hands the target to the host (k_finish_track's HostPublish), so
+ * the host neither waits for the queues' join nor launches k_publish_host: it is released when the last of the B targets has arrived.  The join
+ * events are still recorded and waited on the context's stream before the host starts to wait: whatever is enqueued there next runs behind
+ * both queues, and wait_host_flag's fall-back synchronisation covers them.  The trailing materialising launches of an epsilon > 0 call may
+ * end after the flag: they are in front of that join too, i.e. stream-ordered in front of everything that can read It / dIt_dx / Jt.  That
+ * covers the arrays, not the image those launches sample: the context's own image is only replaced by work on the context's stream, a
+ * BORROWED one is the caller's to rewrite from any stream after the call, so epsilon > 0 on a borrowed image keeps the old delivery (below).
+ * A set trace (one queue, compared pass by pass), the one-launch-per-pass form, the rest of a persistent launch (targets that are no longer
+ * active would never arrive) and a batch without host-coherent mirrors (MTFHIP_ZERO_COPY=0) keep k_publish_host / the copy. */
+static int track_loop_chunked(mtfhip_batch *b, const mtfhip_sm_desc *sm, const FusedArgs &fa, const TrackState &ts, const TrackCtx &cx, unsigned long long &pub_seq) {
 	hipStream_t st = b->ctx->stream;
 	int chunk = track_chunk(b, sm, fa);
 	double phase_frac;
 	const int n_streams = track_open_queues(b, track_queues(b, fa), phase_frac);
-	if (n_streams == 2 && phase_frac > 0 && b->ctx->d_phase) HIP_TRY(hipMemsetAsync(b->ctx->d_phase, 0, sizeof(unsigned long long) * 4, st));
-	static const double stagger_env = std::getenv("MTFHIP_TRACK_STAGGER_US") ? std::atof(std::getenv("MTFHIP_TRACK_STAGGER_US")) : -1.0;
-	double stagger_us = stagger_env;
-	if (stagger_env < 0) stagger_us = 0.25 * ((double)b->B * b->N * 130.0 / 6.5e6 + 8.0) * (2.0 / n_streams);
+	/* (words_ready: the head of the call has zeroed the stamps and the flags -- k_track_prologue, track_core) */
+	if (!cx.words_ready && n_streams == 2 && phase_frac > 0 && b->ctx->d_phase) HIP_TRY(hipMemsetAsync(b->ctx->d_phase, 0, sizeof(unsigned long long) * 4, st));
 	const bool use_step = track_takes_step(b, fa, cx.so_term, n_streams);
 	if (use_step) TRY(ensure_persist_words(b, st));
 	/* deferred materialisation (track_defers_materialisation): the passes before the last run the lean kernel */
@@ -491,7 +516,27 @@ static int track_loop_chunked(mtfhip_batch *b, const mtfhip_sm_desc *sm, const F
 	if (defer) {
 		if (!b->d_last_ws) HIP_TRY(hipMalloc(&b->d_last_ws, sizeof(double) * 17 * (size_t)b->B));
 		if (!b->d_need_mat) HIP_TRY(hipMalloc(&b->d_need_mat, sizeof(int) * (size_t)b->B));
-		HIP_TRY(hipMemsetAsync(b->d_need_mat, 0, sizeof(int) * (size_t)b->B, st));
+		if (!cx.words_ready) HIP_TRY(hipMemsetAsync(b->d_need_mat, 0, sizeof(int) * (size_t)b->B, st));
+	}
+	/* the later queue's start-up delay: a quarter of the period of the pass kind that runs.  Materialising passes are store-bound (130 B per pixel
+	 * at 6.5 TB/s + the solve); the lean passes of a deferred call are issue-bound: 30.4 us per step of 64 x 200 x 200 on two queues
+	 * (profiles/track_call_cost.md), i.e. 8.75 us per million pixels + the same 8 */
+	const char *e_sg = std::getenv("MTFHIP_TRACK_STAGGER_US");   /* (read per call: the A/B and the tests flip it) */
+	double stagger_us = e_sg ? std::atof(e_sg) : -1.0;
+	if (stagger_us < 0) stagger_us = 0.25 * ((double)b->B * b->N * (defer ? 8.75e-6 : 130.0 / 6.5e6) + 8.0) * (2.0 / n_streams);
+	FinishCtl fin{PhaseCtl{nullptr, nullptr, 0.0}, HostPublish{nullptr, 0, 0, nullptr, nullptr, 0, 0}, 0};
+	{
+		const char *e_pr = std::getenv("MTFHIP_FINISH_PRIO");   /* (read per call) */
+		fin.prio = (e_pr && e_pr[0] == '0') ? 0 : 1;
+	}
+	/* a borrowed image may be rewritten by its owner, on a stream of the owner's, once a call that returns results has returned (mtfhip.h).  With a
+	 * reachable epsilon, pixel passes follow the delivery -- the trailing materialising launches, which sample the image, and passes enqueued
+	 * for targets that have all stopped -- so such a call keeps the delivery behind the join, which waits for them */
+	const mtfhip_ctx *c = b->ctx;
+	const bool borrowed = c->img.data != c->img_owned && c->img.data != c->prev_owned;
+	if (cx.fused_io && b->h_pub_dev && !b->d_trace && !use_step && !cx.resume && !(borrowed && sm->epsilon > 0)) {
+		pub_seq = ++b->acc_seq;
+		fin.pub = HostPublish{b->h_pub_dev, b->slab_dbl_bytes, b->B, b->d_fin_count, b->h_flag_dev, pub_seq, publish_fenced()};
 	}
 	if (n_streams >= 2) {
 		const int part_sz = (b->B + n_streams - 1) / n_streams;
@@ -514,12 +559,12 @@ static int track_loop_chunked(mtfhip_batch *b, const mtfhip_sm_desc *sm, const F
 				ChunkRun &r = runs[k];
 				if (r.done) continue;
 				if (n_streams >= 2 && it == 0 && k > g0 && stagger_us > 0) launch_queue_delay(stagger_us * (double)(k - g0), r.s);
-				PhaseCtl pc{nullptr, nullptr, 0.0};
+				fin.pc = PhaseCtl{nullptr, nullptr, 0.0};
 				if (n_streams == 2 && phase_frac > 0 && b->ctx->d_phase) {
 					const int qi = (int)((k - g0) & 1);
-					pc = PhaseCtl{b->ctx->d_phase + qi, b->ctx->d_phase + (1 - qi), phase_frac};
+					fin.pc = PhaseCtl{b->ctx->d_phase + qi, b->ctx->d_phase + (1 - qi), phase_frac};
 				}
-				TRY(track_chunk_pass(b, sm, fa, cx, r, it, lean, use_step, pc));
+				TRY(track_chunk_pass(b, sm, fa, cx, r, it, lean, use_step, fin));
 				if (loop_all_stopped(sm, cx.max_passes, it, r.tc.active, r.nt, r.s, h_flags)) r.done = true;
 				all_done = all_done && r.done;
 			}
@@ -559,8 +604,33 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 	const bool fresh = b->fresh_reinit && one_launch && !region_mode && !slab_uploaded && !resume && b->h_pub_dev && b->d_trace == nullptr;
 	b->fresh_reinit = false;
 	/* (a pending fused initialisation, hold_init_pull: the mirrors' NCC scalars are older than d_ncc, which k_template_init wrote) */
-	if (!slab_uploaded && !fresh) TRY(loop_upload_slab(b, st, b->hold_init_pull && b->init_mirror_seq != 0));
-	else b->warps_dirty = false;   /* the slab on the device carries the warps */
+	/* the chunked driver's call path: one launch in front of the loop -- the slab ingest, the deferred-materialisation flags, the queues' phase stamps
+	 * and the Levenberg-Marquardt start state (k_track_prologue) instead of the ingest, two memsets and a pageable copy + synchronisation -- and the
+	 * delivery from inside the loop (track_loop_chunked).  MTFHIP_TRACK_FUSED_IO=0 (read per call) keeps the separate steps (A/B, the tests).
+	 * Where the slab is on the device already (a folded track_region) the kernel runs without the ingest: still one launch for all the words. */
+	const bool persisted = !mi && !one_launch && cx.so_term < 0 && persist_fits(b, sm, fa);
+	{
+		const char *e_io = std::getenv("MTFHIP_TRACK_FUSED_IO");
+		cx.fused_io = !mi && !one_launch && !persisted && !(e_io && e_io[0] == '0');
+	}
+	LoopWords lw{nullptr, 0, nullptr, nullptr, 0, 0.0, nullptr};
+	if (cx.fused_io && !resume) {
+		/* (the flags only for a call that can defer -- the one-launch-per-pass form, decided with the queues, may still turn it down: the
+		 * flags are then zeroed for nothing; the stamps only where two queues will use them; words that exist from earlier calls cost nothing) */
+		if (track_defers_materialisation(b, sm, fa, cx.so_term, resume, false)) {
+			if (!b->d_last_ws) HIP_TRY(hipMalloc(&b->d_last_ws, sizeof(double) * 17 * (size_t)b->B));
+			if (!b->d_need_mat) HIP_TRY(hipMalloc(&b->d_need_mat, sizeof(int) * (size_t)b->B));
+		}
+		if (sm->leven_marq && !b->d_lm) HIP_TRY(hipMalloc(&b->d_lm, sizeof(double) * kLmStride * (size_t)b->B));
+		if (track_queues(b, fa) == 2 && track_phase_frac() > 0) track_phase_words(b->ctx);
+		lw = LoopWords{b->d_need_mat, b->d_need_mat ? b->B : 0, b->ctx->d_phase, sm->leven_marq ? b->d_lm : nullptr, b->B, sm->lm_delta_init, b->d_fin_count};
+		cx.words_ready = true;
+	}
+	if (!slab_uploaded && !fresh) TRY(loop_upload_slab(b, st, b->hold_init_pull && b->init_mirror_seq != 0, cx.words_ready ? &lw : nullptr));
+	else {
+		b->warps_dirty = false;   /* the slab on the device carries the warps */
+		if (cx.words_ready) { TimedScope tsc(b->ctx, "track_prologue", st); launch_track_prologue(nullptr, nullptr, 0, 0, 0, lw, st); }
+	}
 	fa.active = b->d_active;
 	if (ncc && !one_launch && !b->d_ncc_tm) return fail(MTFHIP_ERR_LOGIC, "track before init_template");
 	TrackState ts{b->d_acc, b->d_h0, b->d_corners, b->d_init_corners_hm, b->d_active, b->d_iters, ncc ? b->d_ncc : nullptr, ncc ? b->d_ncc_tm : nullptr, 0, nullptr, nullptr,
@@ -569,7 +639,7 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 	if (b->d_trace && !resume) HIP_TRY(hipMemsetAsync(b->d_trace, 0, sizeof(double) * kTraceStride * (size_t)b->trace_cap * b->B, st));
 	if (mi && b->d_trace) ts.f_ext = b->d_mi_f;   /* (the trace records the similarity; Levenberg-Marquardt sets it below as well) */
 	if (sm->leven_marq) {
-		if (resume) ts.lm = b->d_lm;
+		if (resume || cx.words_ready) ts.lm = b->d_lm;   /* (words_ready: the head of the call has written the start state) */
 		else TRY(loop_lm_state(b, sm, st, &ts.lm));
 		if (mi) ts.f_ext = b->d_mi_f;
 	}
@@ -588,11 +658,10 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && !ncc && !mi && cx.so_term < 0) ? 1 : 0;
 	}
 	unsigned long long pub_seq = 0;   /* non-zero: the loop's own kernel delivers the results to the host */
-	bool persisted = false;
 	if (mi) TRY(track_loop_mi(b, sm, ts, cx));
 	else if (one_launch) TRY(track_loop_one_launch(b, sm, ts, cx, pub_seq));
-	else if ((persisted = cx.so_term < 0 && persist_fits(b, sm, fa))) TRY(track_loop_persist(b, sm, fa, ts, cx));
-	else TRY(track_loop_chunked(b, sm, fa, ts, cx));
+	else if (persisted) TRY(track_loop_persist(b, sm, fa, ts, cx));
+	else TRY(track_loop_chunked(b, sm, fa, ts, cx, pub_seq));
 	const char *h_res;
 	TRY(loop_read_back(b, st, pub_seq, n_iters, corners, &h_res));
 	const int *act = reinterpret_cast<const int *>(h_res + b->slab_dbl_bytes), *iters = act + b->B;

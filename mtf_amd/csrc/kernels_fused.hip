@@ -4,6 +4,7 @@
  */
 #include "mtfhip_finish_device.h"
 #include "mtfhip_fused_device.h"
+#include "mtfhip_grid_device.h"
 
 namespace mtfhip {
 
@@ -27,10 +28,36 @@ __global__ __launch_bounds__(kBlock, MTFHIP_FAST_WAVES) void k_fused_fast(BatchV
  * step of 64 x 200 x 200, the two pixel passes starting 23-25 us apart) -- but started together, or on some boxes by themselves, they
  * stay close to lockstep (55-56 us).  Each queue's solve stamps the wall clock when it ends, and ends no sooner than `frac` of its own
  * last period after the other queue's stamp: a queue that runs too close behind the other is held back until it is not. */
+/* ts.finish_prio: the waves of this launch raise their issue priority once, at entry (a kernel argument: a scalar branch around one
+ * s_setprio, no per-segment flips) and drop it again in front of the phase spin, which sleeps.
+ * pub.host (the chunked loop's fused delivery, api_track.hip): a target's wave hands the target's warp, state, corners and iteration count to
+ * the host exactly once -- in the pass that stops it, or in the last pass the host enqueues (ts.last_pass) if it is still active then -- with
+ * the hand-over of publish_target; the arrivals of all passes and both queues count to pub.B, the last one raises the host's flag.  pub_t0:
+ * the launch's first target in the batch (bv and ts are the chunk's views). */
 __global__ __launch_bounds__(256) void k_finish_track(BatchView bv, mtfhip_sm_desc sm, TrackState ts,
-	const double *partials, int nblk, PhaseCtl pc) {
-	if (ts.fast_finish) finish_track_fast_body(bv, sm, ts, partials, nblk, blockIdx.x);
-	else finish_track_body(bv, sm, ts, partials, nblk, blockIdx.x);
+	const double *partials, int nblk, PhaseCtl pc, HostPublish pub, int pub_t0) {
+	if (ts.finish_prio) __builtin_amdgcn_s_setprio(3);
+	const int t = blockIdx.x;
+	__shared__ int s_stopped;
+	if (pub.host && threadIdx.x == 0) __hip_atomic_store(&s_stopped, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+	if (ts.fast_finish) finish_track_fast_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
+	else finish_track_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
+	if (pub.host && threadIdx.x < 64) {
+		/* the first wave alone: its lane 0 cleared and set the flag (1: active at entry, 3: stopped by this pass), and everything the bodies leave
+		 * for the host is stored by lanes of this wave -- the warp's entry q by lane q; the state by lane 0 (finish_track_body) or entry q by
+		 * lane q (the fast body); the corners' entries 2q and 2q + 1 by lane q < 4 (finish_track_body) or entry q by lane q; the iteration
+		 * count by lane 0.  Lane q reads entry q back, so some entries cross lanes: that is in order at wavefront scope (the stores are
+		 * issued before the loads of the same wave, to the same addresses), which is all this needs -- no barrier and no wait for the stores
+		 * on the passes that deliver nothing */
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		const int ran = __hip_atomic_load(&s_stopped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+		if (ran == 3 || (ran && ts.last_pass)) {
+			const int lane = threadIdx.x;
+			const double wq = lane < 9 ? bv.warps[9 * t + lane] : 0.0, sq = lane < 8 ? bv.states[8 * t + lane] : 0.0, cq = lane < 8 ? ts.corners[8 * t + lane] : 0.0;
+			publish_target(pub, pub_t0 + t, wq, sq, cq, __hip_atomic_load(ts.n_iters + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT), pub.B);
+		}
+	}
+	if (ts.finish_prio) __builtin_amdgcn_s_setprio(0);
 	if (pc.mine && blockIdx.x == 0 && threadIdx.x == 0) {
 		const unsigned long long prev = ld_coh(pc.mine), other = ld_coh(pc.other);
 		unsigned long long now = wall_clock64();   /* 100 MHz */
@@ -99,9 +126,9 @@ void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &f
 	if (!launched) note_launch_error(hipErrorInvalidDeviceFunction, __FILE__, __LINE__);   /* (no kernel for this launch: an error, not a skipped pass) */
 }
 void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials,
-	int nblk, hipStream_t st, PhaseCtl pc) {
+	int nblk, hipStream_t st, PhaseCtl pc, const HostPublish &pub, int pub_t0) {
 	/* NCC rows are 72 wide: two waves load them, the first one solves; many block rows (a single large target): 240 lanes sum them */
-	MTFHIP_LAUNCH(k_finish_track, dim3(bv.B), dim3(nblk > 8 ? 256 : (bv.am == MTFHIP_AM_NCC ? 128 : 64)), 0, st, bv, sm, ts, partials, nblk, pc);
+	MTFHIP_LAUNCH(k_finish_track, dim3(bv.B), dim3(nblk > 8 ? 256 : (bv.am == MTFHIP_AM_NCC ? 128 : 64)), 0, st, bv, sm, ts, partials, nblk, pc, pub, pub_t0);
 }
 
 void launch_finish_track_mi(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, int sum_std, int gmode,

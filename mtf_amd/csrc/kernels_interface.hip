@@ -556,6 +556,19 @@ __global__ __launch_bounds__(256) void k_ingest_host(const uint4 *src_host, uint
 	if (i < n16 && !(i >= skip_lo && i < skip_hi)) dst[i] = src_host[i];
 	if (i < n_tail) dst_tail[i] = src_tail[i];
 }
+/* the head of a chunked device-side loop (api_track.hip) in one launch: k_ingest_host's copy (n16 = n_tail = 0: the slab is on the device already)
+ * and the words the loop expects at their start values -- the deferred-materialisation flags, the queues' phase stamps and the delivery's arrival counter zero, the
+ * Levenberg-Marquardt block of every target at {prev_similarity 0, leven_marq_delta = lm_delta_init, no pending reset, iteration 0, no update} */
+__global__ __launch_bounds__(256) void k_track_prologue(const uint4 *src_host, uint4 *dst, unsigned n16, const unsigned *src_tail, unsigned *dst_tail, unsigned n_tail,
+	unsigned skip_lo, unsigned skip_hi, LoopWords lw) {
+	const unsigned i = blockIdx.x * 256 + threadIdx.x;
+	if (i < n16 && !(i >= skip_lo && i < skip_hi)) dst[i] = src_host[i];
+	if (i < n_tail) dst_tail[i] = src_tail[i];
+	if (lw.zero_i && i < (unsigned)lw.n_zero_i) lw.zero_i[i] = 0;
+	if (lw.phase && i < 4) lw.phase[i] = 0ull;
+	if (lw.count && i == 0) *lw.count = 0;
+	if (lw.lm && i < (unsigned)lw.n_lm * kLmStride) lw.lm[i] = (i % kLmStride == 1) ? lw.lm_delta_init : 0.0;
+}
 /* fixed-order sum of the per-workgroup rows: out[t][k] = sum_b partials[t][b][k] */
 __global__ __launch_bounds__(64) void k_finish(const double *partials, int nblk, double *out) {
 	const int t = blockIdx.x, k = threadIdx.x;
@@ -701,6 +714,14 @@ void launch_ingest_host(const void *src_host, void *dst, size_t bytes, hipStream
 	MTFHIP_LAUNCH(k_ingest_host, dim3(blocks), dim3(256), 0, st, static_cast<const uint4 *>(src_host), static_cast<uint4 *>(dst), n16,
 		reinterpret_cast<const unsigned *>(static_cast<const char *>(src_host) + 16 * (size_t)n16),
 		reinterpret_cast<unsigned *>(static_cast<char *>(dst) + 16 * (size_t)n16), n_tail, (unsigned)(skip_off / 16), (unsigned)((skip_off + skip_len) / 16));
+}
+void launch_track_prologue(const void *src_host, void *dst, size_t bytes, size_t skip_off, size_t skip_len, const LoopWords &lw, hipStream_t st) {
+	const unsigned n16 = src_host ? (unsigned)(bytes / 16) : 0, n_tail = src_host ? (unsigned)((bytes % 16) / 4) : 0;
+	const unsigned n_words = std::max(std::max((unsigned)(lw.zero_i ? lw.n_zero_i : 0), lw.lm ? (unsigned)lw.n_lm * kLmStride : 0u), 4u);
+	const unsigned blocks = (std::max(std::max(n16, n_tail), n_words) + 255) / 256;
+	MTFHIP_LAUNCH(k_track_prologue, dim3(blocks), dim3(256), 0, st, static_cast<const uint4 *>(src_host), static_cast<uint4 *>(dst), n16,
+		reinterpret_cast<const unsigned *>(static_cast<const char *>(src_host) + 16 * (size_t)n16),
+		reinterpret_cast<unsigned *>(static_cast<char *>(dst) + 16 * (size_t)n16), n_tail, (unsigned)(skip_off / 16), (unsigned)((skip_off + skip_len) / 16), lw);
 }
 void launch_finish_rows(double *partials, int nblk, int row_len, double *out, int B, hipStream_t st) {
 	MTFHIP_LAUNCH(k_finish_rows, dim3(B, (row_len + 127) / 128), dim3(128), 0, st, partials, nblk, row_len, out);

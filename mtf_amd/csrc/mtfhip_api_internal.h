@@ -764,17 +764,20 @@ struct MiPlan {
 };
 int mi_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
 /* api_track.hip.  What track_core hands its drivers: second-order term or -1, passes to enqueue, block rows of the second-order pass, ... */
-struct TrackCtx { int so_term, max_passes, nb2; bool resume, region_mode; };
+/* fused_io: the chunked driver's one-launch head and in-loop delivery (track_core; MTFHIP_TRACK_FUSED_IO=0: the memsets, the copy and the
+ * k_publish_host launch); words_ready: the head has set the loop's words (need_mat, d_phase, the Levenberg-Marquardt state) */
+struct TrackCtx { int so_term, max_passes, nb2; bool resume, region_mode; bool fused_io = false, words_ready = false; };
 int track_loop_mi(mtfhip_batch *b, const mtfhip_sm_desc *sm, mtfhip::TrackState &ts, const TrackCtx &cx);   /* (api_mi_iter.hip) */
 /* ... and the skeleton every device-side loop shares (track_core, alk_track): the upload of the state slab, the initial Levenberg-Marquardt
  * state, the look at the stop flags every eighth pass, the read-back of the slab, the tail of a loop that ran to its read-back */
-int loop_upload_slab(mtfhip_batch *b, hipStream_t st, bool keep_ncc);
+int loop_upload_slab(mtfhip_batch *b, hipStream_t st, bool keep_ncc, const LoopWords *lw = nullptr);
 int loop_lm_state(mtfhip_batch *b, const mtfhip_sm_desc *sm, hipStream_t st, double **lm);
 bool loop_all_stopped(const mtfhip_sm_desc *sm, int max_passes, int it, const int *d_flags, int n, hipStream_t on, std::vector<int> &h_flags, hipError_t *err = nullptr);
 int loop_read_back(mtfhip_batch *b, hipStream_t st, unsigned long long pub_seq, int *n_iters, double *corners, const char **h_res);
 static inline void loop_done(mtfhip_batch *b) {
 	b->pts_stale = true;       /* CURR_PTS follow the final warp when an un-fused kernel next needs them */
-	b->stage_a_busy = false;   /* the stream has drained: whatever set_corners staged has been consumed */
+	b->stage_a_busy = false;   /* the results have arrived, so the head of the call has run (the stream has drained, or -- the chunked loop's
+	                            * in-loop delivery -- all B targets have reported in): whatever set_corners staged has been consumed */
 }
 bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int track_validate(mtfhip_batch *b, const mtfhip_sm_desc *sm);

@@ -37,9 +37,11 @@ __device__ unsigned long long g_fin_trace[16];
  * (getWarpFromState), the corners from the warp -- and a Levenberg-Marquardt undo adds its negative (NT/FALK.cc:156-158); the `continue`
  * behind an undo consumes an iteration of their for loops (NT/FALK.cc:141,166).  The caller hands in the search method as FCLK: g and H
  * are FCLK's functions of the reduced row (cmptCurrJacobian / cmptSelfHessian / cmptCurrHessian of the pass's own pixel Jacobian). */
+/* stop_flag (k_finish_track's delivery to the host; LDS, cleared by the caller, or NULL): 1 once the target is known to have been active at entry,
+ * 3 when this pass stops it -- written by lane 0 of the first wave, the wave that reads it afterwards */
 template <bool COH = false, bool ADDITIVE = false>
 __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
-	const double *partials, int nblk, int t) {
+	const double *partials, int nblk, int t, int *stop_flag = nullptr) {
 	auto LD = [](const double *p) -> double { if constexpr (COH) return ld_coh(p); else return *p; };
 	auto LDI = [](const int *p) -> int { if constexpr (COH) return ld_coh(p); else return *p; };
 	auto ST = [](double *p, double v) { if constexpr (COH) st_coh(p, v); else *p = v; };
@@ -48,6 +50,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	 * are kept for the trailing materialising launch */
 	auto stop_target = [&](const double *w_old, const double *s_old) {
 		STI(ts.active + t, 0);
+		if (stop_flag) __hip_atomic_store(stop_flag, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 		if (ts.lean_pass) {
 			for (int q = 0; q < 9; ++q) ST(ts.warp_last + 9 * t + q, w_old[q]);
 			for (int q = 0; q < 8; ++q) ST(ts.state_last + 8 * t + q, s_old[q]);
@@ -111,6 +114,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		}
 	}
 	if (!act) return;
+	if (stop_flag && lane == 0) __hip_atomic_store(stop_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 	FIN_STAMP(1);
 	if (wv0) {
 		h0s[lane] = v_h0;
@@ -415,13 +419,14 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
  * --------------------------------------------------------------------------------------------------------------------- */
 template <bool COH = false>
 __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
-	const double *partials, int nblk, int t) {
+	const double *partials, int nblk, int t, int *stop_flag = nullptr) {
 	auto LD = [](const double *p) -> double { if constexpr (COH) return ld_coh(p); else return *p; };
 	auto LDI = [](const int *p) -> int { if constexpr (COH) return ld_coh(p); else return *p; };
 	auto ST = [](double *p, double v) { if constexpr (COH) st_coh(p, v); else *p = v; };
 	auto STI = [](int *p, int v) { if constexpr (COH) st_coh(p, v); else *p = v; };
 	auto stop_target = [&](const double *w_old, const double *s_old) {   /* (as finish_track_body's) */
 		STI(ts.active + t, 0);
+		if (stop_flag) __hip_atomic_store(stop_flag, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 		if (ts.lean_pass) {
 			for (int q = 0; q < 9; ++q) ST(ts.warp_last + 9 * t + q, w_old[q]);
 			for (int q = 0; q < 8; ++q) ST(ts.state_last + 8 * t + q, s_old[q]);
@@ -471,6 +476,7 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 		}
 	}
 	if (!act) return;
+	if (stop_flag && lane == 0) __hip_atomic_store(stop_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 	FIN_STAMP(1);
 	if (wv0) {
 		f_h0[lane] = v_h0;

@@ -116,7 +116,9 @@ __device__ __forceinline__ void block_allsum_h12(double *v, double *lds) {
  * release per workgroup orders them before the counter -- a system-scope fence in every wave of every workgroup walks the L2
  * for dirty lines 1024 times and cost 25 us of a 47 us launch -- and (fenced form) only the last arriver pays the system-scope release
  * before it raises the flag. */
-__device__ __forceinline__ void publish_target(const HostPublish &pub, int t, double wq, double sq, double cq, int n_it) {
+/* n_expected: the arrivals that release the host -- 0: one per workgroup of this launch; k_finish_track passes the batch's target count,
+ * its arrivals being spread over the passes and the queues of a loop */
+__device__ __forceinline__ void publish_target(const HostPublish &pub, int t, double wq, double sq, double cq, int n_it, int n_expected = 0) {
 	const int lane = threadIdx.x;
 	double *p = reinterpret_cast<double *>(pub.host);
 	const size_t Bt = (size_t)pub.B;
@@ -136,7 +138,7 @@ __device__ __forceinline__ void publish_target(const HostPublish &pub, int t, do
 	if (lane == 0) {
 		const int done = pub.fenced ? __hip_atomic_fetch_add(pub.count, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT)
 		                            : __hip_atomic_fetch_add(pub.count, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (done == (int)gridDim.x - 1) {
+		if (done == (n_expected ? n_expected : (int)gridDim.x) - 1) {
 			__hip_atomic_store(pub.count, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			/* Every workgroup's results left as system-scope (write-through) stores that were acknowledged before it counted itself in,
 			 * and this one has read the counter they all bumped (a RELAXED read-modify-write at the memory side, not an acquire): the

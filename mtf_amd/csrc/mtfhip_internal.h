@@ -135,6 +135,11 @@ struct TrackState {
 	double *state_last = nullptr;
 	int *need_mat = nullptr;
 	int lean_pass = 0;
+	/* the two-launch loop's finish (k_finish_track; the other routes leave both at 0).  last_pass: the host enqueues no pass behind this one, so a
+	 * target that is still active after it is delivered to the host now (HostPublish of k_finish_track).  finish_prio: the finish waves raise
+	 * their issue priority -- one wave per target beside the other queue's pixel pass, where it is always the younger wave of its SIMD */
+	int last_pass = 0;
+	int finish_prio = 0;
 };
 constexpr int kLmStride = 12;
 constexpr int kTraceStride = 96;
@@ -586,7 +591,13 @@ bool launch_init_grid_ingest(const BatchView &bv, const double *host_w0_dev, int
 /* phase control of the two-queue loop (k_finish_track): this queue's and the other queue's time stamps, the fraction of a period to keep */
 struct PhaseCtl { unsigned long long *mine; const unsigned long long *other; double frac; };
 void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials,
-	int nblk, hipStream_t st, PhaseCtl pc = PhaseCtl{nullptr, nullptr, 0.0});
+	int nblk, hipStream_t st, PhaseCtl pc = PhaseCtl{nullptr, nullptr, 0.0}, const HostPublish &pub = HostPublish{nullptr, 0, 0, nullptr, nullptr, 0, 0}, int pub_t0 = 0);
+/* the head of a chunked device-side loop in one launch (k_track_prologue): the slab ingest (src_host NULL: none; skip_*: launch_ingest_host's),
+ * zero_i[n_zero_i] = 0, phase[0..3] = 0, the Levenberg-Marquardt start state lm[t] = {0, lm_delta_init, 0 ...} of n_lm targets, and the
+ * arrival counter of the in-loop delivery *count = 0 (a call that failed between its passes can have left it part-counted)
+ * (every pointer may be NULL) */
+struct LoopWords { int *zero_i; int n_zero_i; unsigned long long *phase; double *lm; int n_lm; double lm_delta_init; int *count; };
+void launch_track_prologue(const void *src_host, void *dst, size_t bytes, size_t skip_off, size_t skip_len, const LoopWords &lw, hipStream_t st);
 
 /* ---- the additive search methods nt::FALK / nt::IALK (kernels_alk.hip) ---- */
 struct AlkArgs {

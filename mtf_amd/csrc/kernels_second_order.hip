@@ -467,7 +467,10 @@ __global__ __launch_bounds__(kBlock) void k_second_order_ssd(BatchView bv, ImgVi
 		}
 		if (term != 0 && term != 4) {
 			const double2 ma = h0[2 * i], mb = h0[2 * i + 1];
-			pix_hessian_block<SSM>(d2, d0_variant, Wid, st0, p0.x, p0.y, p0.x, p0.y, 1.0, ma.x, ma.y, mb.x, mb.y, g0[i], g0[N + i]);
+			/* the template block at the identity warp: its denominator is the third homogeneous coordinate of the template point
+			 * (Homography.cc:515-618 reads curr_pts_hm(2, .), which setCorners leaves un-normalised) -- 1 only on a rectangular region */
+			const double z0 = (SSM == MTFHIP_SSM_HOMOGRAPHY && !bv.unit_z) ? (bv.buf[MTFHIP_BUF_INIT_Z] + (size_t)t * N)[i] : 1.0;
+			pix_hessian_block<SSM>(d2, d0_variant, Wid, st0, p0.x, p0.y, p0.x, p0.y, z0, ma.x, ma.y, mb.x, mb.y, g0[i], g0[N + i]);
 #pragma unroll
 			for (int k = 0; k < S * S; ++k) acc[k] = fma(w0, d2[k], acc[k]);
 		}

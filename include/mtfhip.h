@@ -57,7 +57,20 @@ typedef enum mtfhip_status {
  * first-order Hessians, the per-function entry points and the fused init_template / iterate / track / track_region
  * (mtfhip_batch_set_lrscv below) */
 enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6 };
-enum { MTFHIP_SSM_HOMOGRAPHY = 0, MTFHIP_SSM_AFFINE = 1 };
+/* MTFHIP_SSM_SIMILITUDE / _ISOMETRY / _TRANSLATION: the low-order rigid models (SSM/src/Similitude.cc, Isometry.cc, Translation.cc), states
+ * [tx, ty, a, b] (warp [[1 + a, -b, tx], [b, 1 + a, ty]]), [tx, ty, theta] (warp [[cos, -sin, tx], [sin, cos, ty]]) and [tx, ty], S = 4 / 3 / 2.
+ * Served: the StateSpaceModel entry points below (set_corners with normalized_init = 0, set_state, compositional_update, invert_state,
+ * update_grad_pts, cmpt_pix_jacobian INIT and WARPED, the getters, apply_warp_to_corners and the four batch-free functions), over them
+ * the per-function AppearanceModel entry points, and mtfhip_batch_init_template / _set_region / _iterate / _track / _track_region with
+ * ESM, FCLK and ICLK -- SSD and NCC, single channel, first-order Hessians, every hess_type and jac_type served for Affine, chained or
+ * not, with or without Levenberg-Marquardt, both arithmetic modes.  The fused path runs the AFFINE pixel pass at the model's warp matrix
+ * (the model's pixel Jacobian is the affine one times a constant 6 x S matrix of +-1 entries) and projects the affine-coordinate
+ * system in front of the solve, on the two-launch route.  Every N x S buffer (MTFHIP_BUF_J0 / _JT / _JM) holds the
+ * model's own S columns, after a materialising fused call too.  Everything else returns MTFHIP_ERR_NOT_IMPLEMENTED with its reason in
+ * mtfhip_last_error(): MI and the SCV family and n_channels 3 (at mtfhip_batch_create), sec_ord_hess and every second-order entry
+ * point, MTFHIP_SM_FALK / _IALK, the Pix / Approx pixel Jacobians, additive_update, estimate_state_sigma, estimate_from_pts, the grid
+ * tracker, the candidate scorer / sampler, the particle filter and the NN entry points. */
+enum { MTFHIP_SSM_HOMOGRAPHY = 0, MTFHIP_SSM_AFFINE = 1, MTFHIP_SSM_SIMILITUDE = 2, MTFHIP_SSM_ISOMETRY = 3, MTFHIP_SSM_TRANSLATION = 4 };
 /* MTFHIP_SM_FALK / _IALK: the additive Lucas-Kanade formulations (SM/src/NT/FALK.cc, IALK.cc): the state moves by
  * StateSpaceModel::additiveUpdate (ProjectiveBase.cc:51-55) instead of a compositional update.  FALK takes the image gradient at the
  * current points and cmptPixJacobian per iteration; IALK forms cmptApproxPixJacobian from the template's stored gradient.  Served by

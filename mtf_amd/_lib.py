@@ -12,7 +12,10 @@ CSRC = os.path.join(_HERE, "csrc")
 
 AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV, AM_LRSCV = 0, 1, 2, 3, 4, 5, 6
 SCV_HIST_DIRAC, SCV_HIST_BILINEAR, SCV_HIST_BSPLINE = 0, 1, 2
-SSM_HOMOGRAPHY, SSM_AFFINE = 0, 1
+SSM_HOMOGRAPHY, SSM_AFFINE, SSM_SIMILITUDE, SSM_ISOMETRY, SSM_TRANSLATION = 0, 1, 2, 3, 4
+# state sizes (StateSpaceModel::getStateSize): Homography.cc:36, Affine.cc:47, Similitude.cc:63, Isometry.cc:52, Translation.cc:48
+SSM_STATE_SIZE = {SSM_HOMOGRAPHY: 8, SSM_AFFINE: 6, SSM_SIMILITUDE: 4, SSM_ISOMETRY: 3, SSM_TRANSLATION: 2}
+SSM_LOW_ORDER = (SSM_SIMILITUDE, SSM_ISOMETRY, SSM_TRANSLATION)
 SM_ESM, SM_FCLK, SM_ICLK, SM_FALK, SM_IALK = 0, 1, 2, 3, 4
 JAC_INIT, JAC_PIX, JAC_WARPED, JAC_APPROX = 0, 1, 2, 3
 MATH_REPLAY, MATH_FAST = 0, 1
@@ -44,6 +47,13 @@ class LogicError(MtfHipError):
 
 
 _ERR = {-1: InvalidArgument, -2: FunctionNotImplemented, -3: LogicError}
+
+
+def ssm_state_size(ssm):
+    try:
+        return SSM_STATE_SIZE[int(ssm)]
+    except KeyError:
+        raise InvalidArgument(-1, "unknown state space model %r" % (ssm,))
 
 
 class PatchDesc(C.Structure):

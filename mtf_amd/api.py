@@ -204,7 +204,7 @@ class Context:
         L.check(L.lib().mtfhip_ssm_estimate_from_pts(self._h, int(ssm), C.byref(p), S, _p(n_pts), max_pts, _p(pin), _p(pout),
                                                      _p(sub) if sub is not None else None, n_hyp, int(seed), _p(upd), _p(mask), _p(info), _p(stats),
                                                      _p(used) if used is not None else None))
-        ns = 8 if ssm == SSM_HOMOGRAPHY else 6
+        ns = L.ssm_state_size(ssm)
         res = [EstResult(upd[s, :ns].copy(), mask[s, :n_pts[s]].copy(), bool(info[s, 0]), int(info[s, 1]), int(info[s, 2]), int(info[s, 3]),
                          float(stats[s, 0]), float(stats[s, 1]), used[s].copy() if used is not None else None) for s in range(S)]
         return res[0] if single else res
@@ -243,7 +243,7 @@ class Batch:
         self.C = n_channels
         self.NP = resx * resy            # sample points (ImageBase::getNPix)
         self.N = self.NP * n_channels    # rows of every per-pixel AM array (getPatchSize); == NP for single channel
-        self.S = 8 if ssm == SSM_HOMOGRAPHY else 6
+        self.S = L.ssm_state_size(ssm)
 
     def close(self):
         if self._h:
@@ -833,7 +833,7 @@ class Batch:
 # ---- SSM functions that are 3 x 3 algebra on the host (no device, no context): ProjectiveBase.cc:142-160,321-331,
 # Homography.cc:877-883, Affine.cc:352-357,382-393 ----
 def _state_size(ssm):
-    return 8 if ssm == L.SSM_HOMOGRAPHY else 6
+    return L.ssm_state_size(ssm)
 
 
 def identity_warp(ssm):

@@ -937,6 +937,7 @@ static int d2_buf_ok(int id) { return id == MTFHIP_BUF_D2I0_DP2 || id == MTFHIP_
 int mtfhip_ssm_update_hess_pts(mtfhip_batch *b, double hess_eps) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "update_hess_pts: NULL batch");
+	TRY(lowdof_refuse(b, "update_hess_pts"));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "update_hess_pts before set_corners");
 	TRY(ensure_buf(b, MTFHIP_BUF_HESS_PTS));
 	TimedScope ts(b->ctx, "hess_pts");
@@ -977,27 +978,32 @@ static int pix_hess_common(mtfhip_batch *b, const double *pts, const double *hes
 int mtfhip_am_initialize_pix_hess(mtfhip_batch *b, const double *pts) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "initialize_pix_hess: NULL batch");
+	TRY(lowdof_refuse(b, "initialize_pix_hess"));
 	return pix_hess_common(b, pts, nullptr, false, true);
 }
 int mtfhip_am_update_pix_hess(mtfhip_batch *b, const double *pts) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "update_pix_hess: NULL batch");
+	TRY(lowdof_refuse(b, "update_pix_hess"));
 	return pix_hess_common(b, pts, nullptr, false, false);
 }
 int mtfhip_am_initialize_pix_hess_warped(mtfhip_batch *b, const double *pts, const double *hess_pts) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "initialize_pix_hess_warped: NULL batch");
+	TRY(lowdof_refuse(b, "initialize_pix_hess_warped"));
 	return pix_hess_common(b, pts, hess_pts, true, true);
 }
 int mtfhip_am_update_pix_hess_warped(mtfhip_batch *b, const double *pts, const double *hess_pts) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "update_pix_hess_warped: NULL batch");
+	TRY(lowdof_refuse(b, "update_pix_hess_warped"));
 	return pix_hess_common(b, pts, hess_pts, true, false);
 }
 
 int mtfhip_ssm_cmpt_pix_hessian(mtfhip_batch *b, int variant, int hess_buf, int grad_buf, int dst_buf) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_pix_hessian: NULL batch");
+	TRY(lowdof_refuse(b, "cmpt_pix_hessian"));
 	if (variant < MTFHIP_JAC_INIT || variant > MTFHIP_JAC_APPROX) return fail(MTFHIP_ERR_INVALID_ARG, "unknown pixel Hessian variant %d", variant);
 	if (!hess_buf_ok(hess_buf)) return fail(MTFHIP_ERR_INVALID_ARG, "hess_buf must be D2I0_DX2 or D2IT_DX2");
 	if (grad_buf != MTFHIP_BUF_DI0_DX && grad_buf != MTFHIP_BUF_DIT_DX) return fail(MTFHIP_ERR_INVALID_ARG, "grad_buf must be DI0_DX or DIT_DX");
@@ -1017,6 +1023,7 @@ int mtfhip_ssm_cmpt_pix_hessian(mtfhip_batch *b, int variant, int hess_buf, int 
 int mtfhip_sm_mean_pix_hessian(mtfhip_batch *b) {
 	FLUSH_AM(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "mean_pix_hessian: NULL batch");
+	TRY(lowdof_refuse(b, "mean_pix_hessian"));
 	if (!b->buf[MTFHIP_BUF_D2I0_DP2] || !b->buf[MTFHIP_BUF_D2IT_DP2]) return fail(MTFHIP_ERR_LOGIC, "mean_pix_hessian: init / curr pixel Hessians not computed");
 	TRY(ensure_buf(b, MTFHIP_BUF_D2IM_DP2));
 	TimedScope ts(b->ctx, "mean_pix_hessian");
@@ -1045,6 +1052,7 @@ static int add_second_order(mtfhip_batch *b, int d2a, int d2b, const double *dev
 int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_init_hessian (second order)", 1));
+	TRY(lowdof_refuse(b, "cmpt_init_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_init_hessian(b, j0_buf, H));
 	return add_second_order(b, d2_buf, -1, b->buf[MTFHIP_BUF_DF_DI0], H);
@@ -1053,6 +1061,7 @@ int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double
 int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_curr_hessian (second order)", 1));
+	TRY(lowdof_refuse(b, "cmpt_curr_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_curr_hessian(b, jt_buf, H));
 	return add_second_order(b, d2_buf, -1, b->buf[MTFHIP_BUF_DF_DIT], H);
@@ -1061,6 +1070,7 @@ int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_self_hessian (second order)", 1));
+	TRY(lowdof_refuse(b, "cmpt_self_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_self_hessian (second order): NULL argument");
 	if (b->desc.am == MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "ncc :: cmptSelfHessian(second order) :: function not implemented yet");
@@ -1077,6 +1087,7 @@ int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 int mtfhip_am_cmpt_sum_of_hessians2(mtfhip_batch *b, int j0_buf, int jt_buf, int d20_buf, int d2t_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_sum_of_hessians (second order)", 1));
+	TRY(lowdof_refuse(b, "cmpt_sum_of_hessians (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_sum_of_hessians (second order): NULL argument");
 	if (b->desc.am == MTFHIP_AM_SSD) {

@@ -386,14 +386,24 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	if (d->am == MTFHIP_AM_MI && (d->mi_n_bins < 2 || d->mi_n_bins > MI_NB)) return fail(MTFHIP_ERR_INVALID_ARG, "MI: n_bins %d outside [2, %d]", d->mi_n_bins, (int)MI_NB);
 	if (d->am == MTFHIP_AM_MI && d->mi_partition_of_unity && d->mi_n_bins < 4) /* MI.cc:83-87 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "MI::Too few bins %d specified to enforce partition of unity constraint", d->mi_n_bins);
-	if (d->ssm != MTFHIP_SSM_HOMOGRAPHY && d->ssm != MTFHIP_SSM_AFFINE) return fail(MTFHIP_ERR_INVALID_ARG, "unknown state space model %d", d->ssm);
+	if (!ssm_known(d->ssm)) return fail(MTFHIP_ERR_INVALID_ARG, "unknown state space model %d", d->ssm);
 	if (d->n_channels != 0 && d->n_channels != 1 && d->n_channels != 3) return fail(MTFHIP_ERR_INVALID_ARG, "n_channels %d (1 or 3 expected)", d->n_channels);
+	/* Similitude / Isometry / Translation: SSD and NCC, single channel (mtfhip.h) -- refused here, before any kernel could read a six- or
+	 * eight-wide state of theirs */
+	if (ssm_lowdof(d->ssm) && d->am != MTFHIP_AM_SSD && d->am != MTFHIP_AM_NCC)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model is served with SSD and NCC only (MI and the SCV family are not available with it)", ssm_name(d->ssm));
+	if (ssm_lowdof(d->ssm) && d->n_channels == 3)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model with n_channels 3 is not available (single channel only)", ssm_name(d->ssm));
 	HIP_TRY(hipSetDevice(c->device));
 	mtfhip_batch *b = new mtfhip_batch();
 	b->ctx = c; b->desc = *d; b->B = n_targets;
 	b->C = d->n_channels > 1 ? d->n_channels : 1;
 	b->NP = d->resx * d->resy; b->N = b->NP * b->C;   /* ImageBase: patch_size = n_pix * n_channels */
-	b->S = d->ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6;
+	b->S = ssm_state_size(d->ssm);
+	if (ssm_lowdof(d->ssm)) {
+		b->lo_ssm = d->ssm;
+		for (int k = 0; k < 3; ++k) b->pass_j_per_target[k] = (size_t)b->N * 6;   /* (allocated by the first fused entry point: ensure_buf under PassMode) */
+	}
 	if (d->am == MTFHIP_AM_MI) {
 		/* MI ctor AM/src/MI.cc:80-94 */
 		double lo = 0, hi = d->mi_n_bins - 1;
@@ -508,6 +518,10 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		 * their calls run as they come) */
 		b->lz.enabled = (d->am == MTFHIP_AM_SSD || d->am == MTFHIP_AM_NCC || d->am == MTFHIP_AM_MI) && b->C == 1 &&
 			!(lazy_env && lazy_env[0] == '0');
+		/* the low-order models: the per-function calls run as they come (a deferred launch would be the affine pass, whose six-column
+		 * planes are not the interface's), nothing is cached by buffer id (J0 / JT / JM name two sets of planes: PassMode), and the warp
+		 * always travels through the slab (the slab's state is the warp's affine embedding: slab_state) */
+		if (ssm_lowdof(d->ssm)) { b->lz.enabled = false; b->lz.no_cache = true; b->inline_warp_ok = false; }
 	}
 	c->batches.push_back(b);
 	*out = b;
@@ -529,6 +543,8 @@ void mtfhip_batch_destroy(mtfhip_batch *b) {
 			b->d_rscv_code, b->d_rscv_part, b->d_rscv_arrive, b->d_rscv_map, b->d_rscv_it, b->d_lscv_i0, b->d_lscv_code, b->d_lscv_cell, b->d_lscv_crng,
 			b->d_lscv_w, b->d_lscv_tot, b->d_lscv_arrive, b->d_lscv_map, b->d_lscv_aff};
 		for (void *p : ptrs)
+			if (p) (void)hipFree(p);
+		for (double *p : b->pass_j)
 			if (p) (void)hipFree(p);
 		if (b->h_fb) (void)hipHostFree(b->h_fb);
 		if (b->h_init_rec) (void)hipHostFree(b->h_init_rec);
@@ -663,9 +679,13 @@ int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, boo
 	if (!b || (!corners && !layout_later)) return fail(MTFHIP_ERR_INVALID_ARG, "set_corners: NULL argument");
 	const bool hom = b->desc.ssm == MTFHIP_SSM_HOMOGRAPHY;
 	if (layout_later && !(defer_grid && !hom)) return fail(MTFHIP_ERR_LOGIC, "set_corners: a layout behind the launch needs the deferred affine reset");
-	/* normalised grid extents: ProjectiveBase.cc:14 (unit square) ; Affine.cc:56-57 */
+	/* normalised grid extents: ProjectiveBase.cc:14 (unit square: Homography, and Isometry and Translation, which keep ProjectiveBase's) ;
+	 * Affine.cc:56-57, Similitude.cc:66-67.  The three low-order models then take the homography's route to the points -- the 4-corner DLT of
+	 * their normalised corners, dehomogenised (getPtsFromCorners: ProjectiveBase.cc:20-39, Translation.cc:55-64, Similitude.cc:87-100) -- and
+	 * re-homogenise them: the third row is 1, as for Affine */
 	double lo_x = -0.5, lo_y = -0.5, hi_x = 0.5, hi_y = 0.5;
-	if (!hom) { lo_x = 1 - b->desc.resx / 2.0; lo_y = 1 - b->desc.resy / 2.0; hi_x = b->desc.resx / 2.0; hi_y = b->desc.resy / 2.0; }
+	const bool unit_square = hom || b->desc.ssm == MTFHIP_SSM_ISOMETRY || b->desc.ssm == MTFHIP_SSM_TRANSLATION;
+	if (!unit_square) { lo_x = 1 - b->desc.resx / 2.0; lo_y = 1 - b->desc.resy / 2.0; hi_x = b->desc.resx / 2.0; hi_y = b->desc.resy / 2.0; }
 	/* the staging buffer is protected by an event instead of a stream sync; one pass over the targets fills the host mirrors
 	 * AND the staged slab (w | s | corners | init_corners_hm | NCC scalars | w0 | flags: the layout of fill_stage) */
 	if (b->stage_a_busy) HIP_TRY(hipEventSynchronize(b->ev_a));
@@ -805,6 +825,13 @@ int mtfhip_ssm_compositional_update(mtfhip_batch *b, const double *dps) {
 		TargetHost &h = b->th[t];
 		double dp[8] = {0};
 		std::memcpy(dp, dps + (size_t)t * b->S, sizeof(double) * b->S);
+		if (b->desc.ssm == MTFHIP_SSM_TRANSLATION) {
+			/* Translation.cc:75-84: curr_state += state_update, the warp's last column follows */
+			h.state[0] += dp[0]; h.state[1] += dp[1];
+			h.warp.m[2] = h.state[0]; h.warp.m[5] = h.state[1];
+			update_corners(b, t);
+			continue;
+		}
 		M3 upd = warp_from_state(b->desc.ssm, dp);
 		h.warp = m3_mul(h.warp, upd);
 		if (b->desc.ssm == MTFHIP_SSM_HOMOGRAPHY) {
@@ -822,6 +849,11 @@ int mtfhip_ssm_invert_state(mtfhip_batch *b, const double *states, double *inv_s
 	for (int t = 0; t < b->B; ++t) {
 		double p[8] = {0}, q[8];
 		std::memcpy(p, states + (size_t)t * b->S, sizeof(double) * b->S);
+		if (b->desc.ssm == MTFHIP_SSM_TRANSLATION) {   /* Translation.cc:103-105: inv_state = -state */
+			inv_states[(size_t)t * b->S] = -p[0]; inv_states[(size_t)t * b->S + 1] = -p[1];
+			continue;
+		}
+		/* (Similitude and Isometry keep ProjectiveBase::invertState, ProjectiveBase.cc:57-62) */
 		M3 Wi = m3_inverse(warp_from_state(b->desc.ssm, p));
 		double s = Wi.m[8];
 		for (int i = 0; i < 9; ++i) Wi.m[i] /= s;
@@ -863,6 +895,9 @@ int mtfhip_ssm_cmpt_pix_jacobian(mtfhip_batch *b, int variant, int grad_buf, int
 	if (variant < MTFHIP_JAC_INIT || variant > MTFHIP_JAC_APPROX) return fail(MTFHIP_ERR_INVALID_ARG, "unknown Jacobian variant %d", variant);
 	if (grad_buf != MTFHIP_BUF_DI0_DX && grad_buf != MTFHIP_BUF_DIT_DX) return fail(MTFHIP_ERR_INVALID_ARG, "grad_buf must be DI0_DX or DIT_DX");
 	if (!j_buf_ok(dst_buf)) return fail(MTFHIP_ERR_INVALID_ARG, "dst_buf must be J0, JT or JM");
+	if (ssm_lowdof(b->desc.ssm) && (variant == MTFHIP_JAC_PIX || variant == MTFHIP_JAC_APPROX))
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s :: %s is not available (the compositional search methods use cmptInitPixJacobian and cmptWarpedPixJacobian)",
+			ssm_name(b->desc.ssm), variant == MTFHIP_JAC_PIX ? "cmptPixJacobian" : "cmptApproxPixJacobian");
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "cmpt_pix_jacobian before set_corners");
 	if (b->lz.enabled && grad_buf == MTFHIP_BUF_DIT_DX && dst_buf == MTFHIP_BUF_JT &&
 		(variant == MTFHIP_JAC_WARPED || variant == MTFHIP_JAC_INIT)) {
@@ -886,6 +921,8 @@ int mtfhip_ssm_get_corners(mtfhip_batch *b, double *corners) {
  * Affine.cc:152-158) -- how nt::PF turns pix_sigma into sampler sigmas (PF.cc:142-149).  Host arithmetic on the points read back. */
 int mtfhip_ssm_estimate_state_sigma(mtfhip_batch *b, double pix_sigma, double *state_sigma) {
 	if (!b || !state_sigma) return fail(MTFHIP_ERR_INVALID_ARG, "estimate_state_sigma: NULL argument");
+	if (ssm_lowdof(b->desc.ssm))
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "estimate_state_sigma: not available for the %s state space model (it serves the particle filter, which is not either)", ssm_name(b->desc.ssm));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "estimate_state_sigma before set_corners");
 	FLUSH(b);
 	TRY(ensure_pts(b));
@@ -952,19 +989,40 @@ int mtfhip_ssm_apply_warp_to_corners(mtfhip_batch *b, const double *in_corners, 
 
 /* ---- SSM functions that are 3 x 3 algebra on the host: no device, no context (callable on a machine without a GPU) ---- */
 static int ssm_kind_ok(int ssm, const char *fn) {
-	if (ssm != MTFHIP_SSM_HOMOGRAPHY && ssm != MTFHIP_SSM_AFFINE) return fail(MTFHIP_ERR_INVALID_ARG, "%s: unknown state space model %d", fn, ssm);
+	if (!ssm_known(ssm)) return fail(MTFHIP_ERR_INVALID_ARG, "%s: unknown state space model %d", fn, ssm);
 	return MTFHIP_OK;
+}
+/* utils::computeSimilitudeDLT (Utilities/src/warpUtils.cc:494-535): the least-squares [tx, ty, a, b] of out - in = [1 0 x -y; 0 1 y x] p over
+ * the four pairs.  The reference takes the pseudo-inverse through a JacobiSVD; about the centroid of the input corners the normal matrix is
+ * diagonal, so the same minimiser is four sums and two divisions.  false: the four input corners coincide. */
+static bool similitude_dlt(const double *in_corners, const double *out_corners, double x[4]) {
+	double cx = 0, cy = 0, mdx = 0, mdy = 0;
+	for (int q = 0; q < 4; ++q) {
+		cx += in_corners[2 * q]; cy += in_corners[2 * q + 1];
+		mdx += out_corners[2 * q] - in_corners[2 * q]; mdy += out_corners[2 * q + 1] - in_corners[2 * q + 1];
+	}
+	cx /= 4; cy /= 4; mdx /= 4; mdy /= 4;
+	double sxx = 0, sa = 0, sb = 0;
+	for (int q = 0; q < 4; ++q) {
+		const double u = in_corners[2 * q] - cx, v = in_corners[2 * q + 1] - cy;
+		const double dx = out_corners[2 * q] - in_corners[2 * q], dy = out_corners[2 * q + 1] - in_corners[2 * q + 1];
+		sxx += u * u + v * v; sa += u * dx + v * dy; sb += u * dy - v * dx;
+	}
+	if (sxx == 0 || !std::isfinite(sxx)) return false;
+	const double a = sa / sxx, bb = sb / sxx;
+	x[0] = mdx - a * cx + bb * cy; x[1] = mdy - a * cy - bb * cx; x[2] = a; x[3] = bb;
+	return true;
 }
 int mtfhip_ssm_identity_warp(int ssm, double *state) {
 	TRY(ssm_kind_ok(ssm, "identity_warp"));
 	if (!state) return fail(MTFHIP_ERR_INVALID_ARG, "identity_warp: NULL argument");
-	std::memset(state, 0, sizeof(double) * (ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6));
+	std::memset(state, 0, sizeof(double) * ssm_state_size(ssm));
 	return MTFHIP_OK;
 }
 int mtfhip_ssm_compose_warps(int ssm, const double *state_1, const double *state_2, double *composed) {
 	TRY(ssm_kind_ok(ssm, "compose_warps"));
 	if (!state_1 || !state_2 || !composed) return fail(MTFHIP_ERR_INVALID_ARG, "compose_warps: NULL argument");
-	const int S = ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6;
+	const int S = ssm_state_size(ssm);
 	double p1[8] = {0}, p2[8] = {0}, out[8] = {0};
 	std::memcpy(p1, state_1, sizeof(double) * S); std::memcpy(p2, state_2, sizeof(double) * S);
 	/* warp_2 * warp_1, read back entry by entry: the reference does not renormalise by (2, 2) here (ProjectiveBase.cc:324-331) */
@@ -987,6 +1045,24 @@ int mtfhip_ssm_estimate_warp_from_corners(int ssm, const double *in_corners, con
 		for (int i = 0; i < 9; ++i) H.m[i] /= H.m[8];
 		H.m[8] = 1;
 		state_from_warp(ssm, out, H);
+	} else if (ssm == MTFHIP_SSM_TRANSLATION) {
+		/* Translation.cc:164-171: the difference of the centroids (rowwise().mean() of each corner set) */
+		for (int r = 0; r < 2; ++r) {
+			double so = 0, si = 0;
+			for (int q = 0; q < 4; ++q) { so += out_corners[2 * q + r]; si += in_corners[2 * q + r]; }
+			out[r] = so / 4 - si / 4;
+		}
+	} else if (ssm == MTFHIP_SSM_SIMILITUDE || ssm == MTFHIP_SSM_ISOMETRY) {
+		double x[4];
+		if (!similitude_dlt(in_corners, out_corners, x)) return fail(MTFHIP_ERR_INVALID_ARG, "estimate_warp_from_corners: degenerate corners");
+		out[0] = x[0]; out[1] = x[1];
+		if (ssm == MTFHIP_SSM_SIMILITUDE) { out[2] = (1 + x[2]) - 1; out[3] = x[3]; }   /* Similitude.cc:295-301: getStateFromWarp of the fitted matrix */
+		else {
+			/* Isometry.cc:296-322: the fitted matrix's rotation, its scale divided out */
+			const double a_plus_1 = 1 + x[2], bb = x[3];
+			const double s_plus_1 = std::sqrt(a_plus_1 * a_plus_1 + bb * bb);
+			out[2] = std::atan2(bb / s_plus_1, a_plus_1 / s_plus_1);
+		}
 	} else {
 		/* least-squares affine map of the four pairs (computeAffineDLT, warpUtils.cc:276-342: pseudo-inverse of the 8 x 6
 		 * system, whose x and y halves share the 3 x 3 normal matrix) */
@@ -1010,14 +1086,14 @@ int mtfhip_ssm_estimate_warp_from_corners(int ssm, const double *in_corners, con
 		}
 		state_from_warp(ssm, out, W);
 	}
-	std::memcpy(state_update, out, sizeof(double) * (ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6));
+	std::memcpy(state_update, out, sizeof(double) * ssm_state_size(ssm));
 	return MTFHIP_OK;
 }
 int mtfhip_ssm_apply_warp_to_pts(int ssm, const double *in_pts, int n_pts, const double *state, double *out_pts) {
 	TRY(ssm_kind_ok(ssm, "apply_warp_to_pts"));
 	if (!in_pts || !state || !out_pts || n_pts < 0) return fail(MTFHIP_ERR_INVALID_ARG, "apply_warp_to_pts: invalid argument");
 	double p[8] = {0};
-	std::memcpy(p, state, sizeof(double) * (ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6));
+	std::memcpy(p, state, sizeof(double) * ssm_state_size(ssm));
 	const M3 W = warp_from_state(ssm, p);
 	for (int i = 0; i < n_pts; ++i) {
 		const double x = in_pts[2 * i], y = in_pts[2 * i + 1];
@@ -1088,6 +1164,8 @@ int mtfhip_grid_layout(const mtfhip_grid_desc *g, const double *region, double *
 /* ProjectiveBase::additiveUpdate SSM/src/ProjectiveBase.cc:51-55: curr_state += update; setState(curr_state) */
 int mtfhip_ssm_additive_update(mtfhip_batch *b, const double *state_updates) {
 	if (!b || !state_updates) return fail(MTFHIP_ERR_INVALID_ARG, "additive_update: NULL argument");
+	if (ssm_lowdof(b->desc.ssm))
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "additive_update: not available for the %s state space model (the additive search methods FALK / IALK are not served with it)", ssm_name(b->desc.ssm));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "additive_update before set_corners");
 	std::vector<double> st((size_t)b->B * b->S);
 	for (int t = 0; t < b->B; ++t)

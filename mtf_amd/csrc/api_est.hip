@@ -9,6 +9,8 @@
 static int est_prepare(const char *fn, mtfhip_ctx *c, int ssm, const mtfhip_est_params *p, int n_sets, const int *host_n_pts, int max_pts, int n_hyp,
 	unsigned long long seed, EstArgs &a) {
 	if (!c || !p) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
+	if (ssm_lowdof(ssm))
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: the robust estimator of the %s state space model is not available (homography and affine only)", fn, ssm_name(ssm));
 	if (ssm != MTFHIP_SSM_HOMOGRAPHY && ssm != MTFHIP_SSM_AFFINE) return fail(MTFHIP_ERR_INVALID_ARG, "%s: unknown state space model %d", fn, ssm);
 	if (p->method != MTFHIP_EST_RANSAC && p->method != MTFHIP_EST_LMEDS && p->method != MTFHIP_EST_LEAST_SQUARES)
 		return fail(MTFHIP_ERR_INVALID_ARG, "%s: Invalid estimation method specified (%d)", fn, p->method);   /* SSMEstimatorParams.cc:26,38 */

@@ -20,6 +20,9 @@ int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn) {
 	if (sm->sm < MTFHIP_SM_ESM || sm->sm > MTFHIP_SM_ICLK) return fail(MTFHIP_ERR_INVALID_ARG, "%s: unknown search method %d", fn, sm->sm);
 	int max_h = sm->sm == MTFHIP_SM_ESM ? 5 : 2;
 	if (sm->hess_type < 0 || sm->hess_type > max_h) return fail(MTFHIP_ERR_INVALID_ARG, "%s: hess_type %d invalid for search method %d", fn, sm->hess_type, sm->sm);
+	/* the low-order SSMs: first-order Hessians (their pixel Hessians are not available: mtfhip_ssm_cmpt_pix_hessian) */
+	if (b->lo_ssm && sm->sec_ord_hess)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: sec_ord_hess is not available with the %s state space model (first-order Hessians only)", fn, ssm_name(b->lo_ssm));
 	if (b->desc.am == MTFHIP_AM_NCC) {
 		/* NCC overrides the second-order cmptInit / CurrHessian (NCC.cc:391-410) but not cmptSelfHessian: the self types throw
 		 * FunctonNotImplemented in the reference (AppearanceModel.h:188-191) */
@@ -97,6 +100,21 @@ static int init_self_hessian(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *
 	}
 	return mtfhip_am_cmpt_self_hessian(b, MTFHIP_BUF_J0, H0);
 }
+/* A low-order SSM's template in affine coordinates (mtfhip_batch::lo_ssm), behind the interface's own N x S Jacobian: the affine rows of dI0_dx
+ * at the embedded state -- the six-column J0 the pass reads, J_S = J_aff M -- then, as for an affine batch, the constant self Hessian over
+ * them (with_h0) and NCC's template moments.  The finish projects what comes out of these (M^T H M, g M) in front of its solve. */
+static int lowdof_template(mtfhip_batch *b, const mtfhip_sm_desc *sm, int variant, bool with_h0) {
+	PassMode pm(b);
+	TRY(do_cmpt_pix_jacobian(b, variant, MTFHIP_BUF_DI0_DX, MTFHIP_BUF_J0));
+	if (with_h0) {
+		std::vector<double> H0((size_t)b->B * b->S * b->S);
+		TRY(init_self_hessian(b, sm, H0.data()));
+		TRY(store_h0(b, H0.data(), true));
+		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+	}
+	if (b->desc.am == MTFHIP_AM_NCC) TRY(ncc_template_moments(b));
+	return MTFHIP_OK;
+}
 /* nt::ICLK::initialize of small single-channel SSD / NCC patches in ONE launch (kernels_init.hip): the grid tracker re-initialises its
  * 256 patch trackers after every frame with the shipped reset_at_each_frame = 1 (GridTracker.cc:273-274, 345-392), and call by call
  * that was 385 us per frame against 42 us for tracking them (r05, tools/grid_modes_probe.py).  Nothing is waited for: the small
@@ -105,6 +123,7 @@ static int init_self_hessian(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *
 bool template_init_fused_ok(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	const char *e = std::getenv("MTFHIP_INIT_FUSED");   /* (read per call: the tests flip it) */
 	if (e && e[0] == '0') return false;
+	if (b->lo_ssm) return false;   /* (k_template_init writes the SSM's own rows and Hessian: the low-order models keep theirs in affine coordinates) */
 	const int am = b->desc.am;
 	if (am != MTFHIP_AM_SSD && am != MTFHIP_AM_NCC) return false;
 	const bool const_h = sm->hess_type == 0 || (sm->hess_type == 2 && am == MTFHIP_AM_SSD);
@@ -150,6 +169,7 @@ int init_template_fused(mtfhip_batch *b, const mtfhip_sm_desc *sm, const RegionI
 	return MTFHIP_OK;
 }
 int mtfhip_batch_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
+	TRY(lowdof_sm_refuse(b, sm, "init_template"));
 	if (sm && alk_sm(sm->sm)) return alk_init_template(b, sm);
 	FLUSH(b);
 	TRY(begin_entry(b));
@@ -185,11 +205,14 @@ int mtfhip_batch_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	TRY(mtfhip_am_initialize_similarity(b));
 	TRY(mtfhip_am_initialize_grad(b));
 	TRY(mtfhip_am_initialize_hess(b));
-	std::vector<double> H0((size_t)b->B * b->S * b->S);
-	TRY(init_self_hessian(b, sm, H0.data()));
-	TRY(store_h0(b, H0.data(), true));
-	HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-	if (b->desc.am == MTFHIP_AM_NCC) TRY(ncc_template_moments(b));
+	if (b->lo_ssm) TRY(lowdof_template(b, sm, sm->chained_warp ? MTFHIP_JAC_WARPED : MTFHIP_JAC_INIT, true));
+	else {
+		std::vector<double> H0((size_t)b->B * b->S * b->S);
+		TRY(init_self_hessian(b, sm, H0.data()));
+		TRY(store_h0(b, H0.data(), true));
+		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+		if (b->desc.am == MTFHIP_AM_NCC) TRY(ncc_template_moments(b));
+	}
 	b->j0_is_template = true;
 	b->j0_template_corners_epoch = b->corners_epoch;
 	b->j0_variant = sm->chained_warp ? MTFHIP_JAC_WARPED : MTFHIP_JAC_INIT;
@@ -225,14 +248,15 @@ int set_region_core(mtfhip_batch *b, const double *corners, const mtfhip_sm_desc
 	}
 	TRY(mtfhip_ssm_cmpt_pix_jacobian(b, MTFHIP_JAC_INIT, MTFHIP_BUF_DI0_DX, MTFHIP_BUF_J0));
 	const bool need_h0 = sm->hess_type == 0 || (sm->sm == MTFHIP_SM_ESM && sm->hess_type == 2);
-	if (need_h0) {
+	if (b->lo_ssm) TRY(lowdof_template(b, sm, MTFHIP_JAC_INIT, need_h0));
+	else if (need_h0) {
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
 		if (b->desc.am == MTFHIP_AM_MI && sm->sec_ord_hess) b->d0_variant = MTFHIP_JAC_INIT;   /* (setRegion: cmptInitPixHessian, NT/ESM.cc:160-163) */
 		TRY(init_self_hessian(b, sm, H0.data()));
 		TRY(store_h0(b, H0.data(), true));
 		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
 	}
-	if (b->desc.am == MTFHIP_AM_NCC) TRY(ncc_template_moments(b));
+	if (b->desc.am == MTFHIP_AM_NCC && !b->lo_ssm) TRY(ncc_template_moments(b));   /* (a low-order SSM's: over its affine rows, lowdof_template) */
 	b->j0_is_template = true;
 	b->j0_template_corners_epoch = b->corners_epoch;
 	b->j0_variant = MTFHIP_JAC_INIT;
@@ -274,6 +298,7 @@ int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa) {
 	}
 	if (!grid_regen_kernel(b->desc.am, b->desc.ssm, fa.chained != 0, fa.mode, fa.materialize != 0) || fa.rows_per_block < kGridRegenMinRows)
 		fa.grid_regen = 0;
+	if (b->lo_ssm) fa.grid_regen = 0;   /* (a low-order SSM's lattice is not the affine one the pass would rebuild: set_corners_core's extents) */
 	return MTFHIP_OK;
 }
 
@@ -335,8 +360,61 @@ int assemble_rows(mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, int
 	return MTFHIP_OK;
 }
 
+/* A low-order SSM's pixel Jacobian is the affine one times a constant 6 x S matrix M with at most two +-1 entries per column
+ * (Translation.h:45-63, Isometry.cc:115-135,162-185, Similitude.cc:163-210):
+ *   Translation [Ja0, Ja1]    Isometry [Ja0, Ja1, Ja4 - Ja3]    Similitude [Ja0, Ja1, Ja2 + Ja5, Ja4 - Ja3]
+ * and every g and H of the search methods is linear / bilinear in it: g_S = g_aff M, H_S = M^T H_aff M.  col k of M: rows a0 and (a1 >= 0)
+ * a1 with sign s1.  The device twin is in finish_track_body. */
+static void lowdof_col(int lo_ssm, int k, int &a0, int &a1, double &s1) {
+	a0 = k; a1 = -1; s1 = 0.0;
+	if (k >= 2) { const bool sum = lo_ssm == MTFHIP_SSM_SIMILITUDE && k == 2; a0 = sum ? 2 : 4; a1 = sum ? 5 : 3; s1 = sum ? 1.0 : -1.0; }
+}
+/* g6 [6], H6 [6 x 6] column-major of one target -> g [SS], H [SS x SS] column-major */
+static void lowdof_project(int lo_ssm, const double *g6, const double *H6, double *g, double *H) {
+	const int SS = ssm_state_size(lo_ssm);
+	auto h6 = [&](int r, int c) { return H6[c * 6 + r]; };
+	for (int r = 0; r < SS; ++r) {
+		int r0, r1; double sr;
+		lowdof_col(lo_ssm, r, r0, r1, sr);
+		g[r] = g6[r0] + (r1 >= 0 ? sr * g6[r1] : 0.0);
+		for (int c = 0; c < SS; ++c) {
+			int c0, c1; double sc;
+			lowdof_col(lo_ssm, c, c0, c1, sc);
+			double v = h6(r0, c0);
+			if (c1 >= 0) v += sc * h6(r0, c1);
+			if (r1 >= 0) { v += sr * h6(r1, c0); if (c1 >= 0) v += sr * sc * h6(r1, c1); }
+			H[c * SS + r] = v;
+		}
+	}
+}
+static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
 int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H) {
+	TRY(lowdof_sm_refuse(b, sm, "iterate"));
 	if (sm && alk_sm(sm->sm)) return alk_iterate(b, sm, f, g, H);
+	if (!b || !b->lo_ssm) return iterate_core(b, sm, f, g, H);
+	/* a low-order SSM: the affine pass and its host-side assembly in affine coordinates, then the projection; a materialising launch left
+	 * its six Jacobian columns in the scratch planes -- the interface's N x S curr_pix_jacobian is formed from the materialised dIt_dx by
+	 * the model's own expressions (k_pix_jacobian), and ESM's mean_pix_jacobian from that and J0, where the search method keeps one */
+	/* (the checks of iterate_core, in its order and with its answers: the outputs here are this function's own staging arrays) */
+	TRY(check_sm(b, sm, "iterate"));
+	if (!g || !H) return fail(MTFHIP_ERR_INVALID_ARG, "iterate: NULL output");
+	TRY(lowdof_template_current(b, "iterate"));
+	std::vector<double> g6((size_t)6 * b->B), H6((size_t)36 * b->B);
+	{
+		PassMode pm(b);
+		TRY(ensure_buf(b, MTFHIP_BUF_J0));
+		TRY(ensure_buf(b, MTFHIP_BUF_JT));   /* (the pass's six-column planes) */
+		TRY(iterate_core(b, sm, f, g6.data(), H6.data()));
+	}
+	const int SS = b->S;
+	for (int t = 0; t < b->B; ++t) lowdof_project(b->lo_ssm, &g6[(size_t)6 * t], &H6[(size_t)36 * t], g + (size_t)t * SS, H + (size_t)t * SS * SS);
+	if (sm->materialize && sm->sm != MTFHIP_SM_ICLK) {
+		TRY(do_cmpt_pix_jacobian(b, sm->chained_warp ? MTFHIP_JAC_WARPED : MTFHIP_JAC_INIT, MTFHIP_BUF_DIT_DX, MTFHIP_BUF_JT));
+		if (sm->sm == MTFHIP_SM_ESM && (sm->jac_type == 0 || sm->hess_type == 3)) TRY(mtfhip_sm_mean_jacobian(b));   /* NT/ESM.cc:239-242 */
+	}
+	return MTFHIP_OK;
+}
+static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H) {
 	FLUSH_AM(b);   /* the fused kernels derive the sample points from the warp: CURR_PTS may stay stale */
 	TRY(begin_entry(b));
 	TRY(check_sm(b, sm, "iterate"));

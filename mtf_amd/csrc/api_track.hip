@@ -69,7 +69,10 @@ int loop_read_back(mtfhip_batch *b, hipStream_t st, unsigned long long pub_seq, 
 	const int *iters = reinterpret_cast<const int *>(*h_res + b->slab_dbl_bytes) + Bt;
 	for (int t = 0; t < b->B; ++t) {
 		std::memcpy(b->th[t].warp.m, w + 9 * t, sizeof(double) * 9);
-		std::memcpy(b->th[t].state, s + 8 * t, sizeof(double) * 8);
+		/* (a low-order SSM's slab holds the affine embedding of the warp: its own state is getStateFromWarp of the warp, as its
+		 * compositionalUpdate leaves it -- Similitude.cc:111-121, Isometry.cc:56-66; Translation's state is the warp's last column) */
+		if (b->lo_ssm) state_from_warp(b->lo_ssm, b->th[t].state, b->th[t].warp);
+		else std::memcpy(b->th[t].state, s + 8 * t, sizeof(double) * 8);
 		std::memcpy(b->th[t].corners, cr + 8 * t, sizeof(double) * 8);
 		if (n_iters) n_iters[t] = iters[t];
 		if (corners) std::memcpy(corners + 8 * t, cr + 8 * t, sizeof(double) * 8);
@@ -87,7 +90,8 @@ static int iclk_one_launch_max_pix() {
 }
 bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	/* (SCV re-maps its template, RSCV rebuilds its map between the passes: they take the fused launch + finish per pass) */
-	return b->C == 1 && !intensity_mapped(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
+	/* (a low-order SSM takes the two-launch loop, whose finish projects the affine system: the one-launch kernels solve what they accumulate) */
+	return b->C == 1 && !b->lo_ssm && !intensity_mapped(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
 		b->N <= iclk_one_launch_max_pix();
 }
 
@@ -206,6 +210,7 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 	const char *e = std::getenv("MTFHIP_PERSIST");
 	if (!(e && e[0] == '1') || !b->persist_ok || fa.materialize || b->ctx->n_cus <= 0 || b->B > b->ctx->n_cus || !b->h_pub_dev) return false;
 	if (b->C != 1) return false;   /* (no multi-channel instantiation of the persistent kernel) */
+	if (b->lo_ssm) return false;   /* (the low-order SSMs are served by the two-launch loop only) */
 	if (intensity_mapped(b)) return false;   /* (the template re-map / the current map runs between the passes) */
 	if (b->B > 8) return false;   /* a batch is better served by its own decomposition (eight workgroups per target) */
 	if (sm->max_iters < 2) return false;
@@ -220,6 +225,7 @@ static int lscv_after_track(mtfhip_batch *b, int rc) {
 	return rc;
 }
 int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) {
+	TRY(lowdof_sm_refuse(b, sm, "track"));
 	if (sm && alk_sm(sm->sm)) return alk_track(b, sm, n_iters, corners);
 	return lscv_after_track(b, track_core(b, sm, n_iters, corners, false));
 }
@@ -391,7 +397,8 @@ static void track_chunk_runs(mtfhip_batch *b, const FusedArgs &fa, const TrackSt
 		const int q = serialize ? n_streams - 1 : (int)(runs.size() % (size_t)n_streams);
 		FusedArgs fl = fc;
 		fl.materialize = 0; fl.fast_math = 0; fl.grid_regen = 0;
-		if (defer) { tc.warp_last = b->d_last_ws + 9 * (size_t)t0; tc.state_last = b->d_last_ws + 9 * (size_t)b->B + 8 * (size_t)t0; tc.need_mat = b->d_need_mat + t0; }
+		tc.keep_last = ts.keep_last; tc.lo_ssm = ts.lo_ssm; tc.SS = ts.SS;
+		if (defer || ts.keep_last) { tc.warp_last = b->d_last_ws + 9 * (size_t)t0; tc.state_last = b->d_last_ws + 9 * (size_t)b->B + 8 * (size_t)t0; tc.need_mat = b->d_need_mat + t0; }
 		TrackState tl = tc;
 		tl.lean_pass = 1;
 		runs.push_back(ChunkRun{bc, fc, fl, tc, tl, nblk_c, t0, nt, part, q == n_streams - 1 ? b->ctx->stream : b->ctx->extra_streams[q], false});
@@ -447,7 +454,7 @@ static bool track_takes_step(const mtfhip_batch *b, const FusedArgs &fa, int so_
 	const char *e_st = std::getenv("MTFHIP_STEP");   /* (read per call: the tests flip it) */
 	const char *e_mx = std::getenv("MTFHIP_STEP_MAX_TARGETS");
 	const int max_t = e_mx ? std::atoi(e_mx) : 8;
-	return (e_st && e_st[0] == '1') && so_term < 0 && !intensity_mapped(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
+	return (e_st && e_st[0] == '1') && so_term < 0 && !b->lo_ssm && !intensity_mapped(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
 }
 /* one pass of one chunk on its queue: the intensity re-maps, the pixel pass (lean: the non-materialising one), the second-order pass, the finish */
 struct FinishCtl { PhaseCtl pc; HostPublish pub; int prio; };
@@ -513,7 +520,7 @@ static int track_loop_chunked(mtfhip_batch *b, const mtfhip_sm_desc *sm, const F
 	if (use_step) TRY(ensure_persist_words(b, st));
 	/* deferred materialisation (track_defers_materialisation): the passes before the last run the lean kernel */
 	const bool defer = track_defers_materialisation(b, sm, fa, cx.so_term, cx.resume, use_step);
-	if (defer) {
+	if (defer || ts.keep_last) {
 		if (!b->d_last_ws) HIP_TRY(hipMalloc(&b->d_last_ws, sizeof(double) * 17 * (size_t)b->B));
 		if (!b->d_need_mat) HIP_TRY(hipMalloc(&b->d_need_mat, sizeof(int) * (size_t)b->B));
 		if (!cx.words_ready) HIP_TRY(hipMemsetAsync(b->d_need_mat, 0, sizeof(int) * (size_t)b->B, st));
@@ -585,7 +592,34 @@ static int track_loop_chunked(mtfhip_batch *b, const mtfhip_sm_desc *sm, const F
 }
 
 /* validation, the driver's choice, the slab upload, the loop state, the driver, the read-back, and what follows a persistent launch cut short */
+static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners, bool slab_uploaded, bool resume, bool region_mode);
+/* A low-order SSM (mtfhip_batch::lo_ssm): the loop runs on the batch as an affine one (PassMode) -- the affine pixel pass, the finish that
+ * projects its system -- on the two-launch route.  A materialising loop leaves six Jacobian columns in the scratch planes; the interface's
+ * N x S curr_pix_jacobian is written behind the loop by the model's own expressions from the materialised dIt_dx, at the warp every
+ * target's last pass ran at (TrackState::keep_last), and ESM's mean_pix_jacobian from that and J0 where the search method keeps one. */
 static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners, bool slab_uploaded, bool resume, bool region_mode) {
+	if (!b || !b->lo_ssm || b->pass_mode) return track_core_impl(b, sm, n_iters, corners, slab_uploaded, resume, region_mode);
+	TRY(lowdof_template_current(b, "track"));
+	{
+		PassMode pm(b);
+		TRY(ensure_buf(b, MTFHIP_BUF_J0));
+		TRY(ensure_buf(b, MTFHIP_BUF_JT));   /* (the pass's six-column planes) */
+		TRY(track_core_impl(b, sm, n_iters, corners, slab_uploaded, resume, region_mode));
+	}
+	if (sm->materialize && sm->sm != MTFHIP_SM_ICLK) {
+		BatchView v = b->view();
+		v.warps = b->d_last_ws; v.states = b->d_last_ws + 9 * (size_t)b->B;
+		{
+			TimedScope ts(b->ctx, "pix_jacobian");
+			launch_pix_jacobian(v, sm->chained_warp ? MTFHIP_JAC_WARPED : MTFHIP_JAC_INIT, b->buf[MTFHIP_BUF_DIT_DX], b->buf[MTFHIP_BUF_JT], b->ctx->stream);
+		}
+		touch(b, MTFHIP_BUF_JT);
+		b->jt_valid = true;
+		if (sm->sm == MTFHIP_SM_ESM && (sm->jac_type == 0 || sm->hess_type == 3)) TRY(mtfhip_sm_mean_jacobian(b));   /* NT/ESM.cc:239-242 */
+	}
+	return MTFHIP_OK;
+}
+static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners, bool slab_uploaded, bool resume, bool region_mode) {
 	FLUSH_AM(b);   /* (none of the loop's kernels reads CURR_PTS: they warp the template grid themselves) */
 	TRY(begin_entry(b));
 	TRY(track_validate(b, sm));
@@ -656,6 +690,9 @@ static int track_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, d
 		const char *e = std::getenv("MTFHIP_FAST_FINISH");   /* (read per call: the tests compare the two bodies in one process) */
 		const bool enabled = !(e && e[0] == '0');
 		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && !ncc && !mi && cx.so_term < 0) ? 1 : 0;
+		/* a low-order SSM: the projection lives in finish_track_body alone (the register-resident body would index its rows at run time);
+		 * its materialising loop keeps every target's last warp for the Jacobian written behind the loop (track_core) */
+		if (b->lo_ssm) { ts.fast_finish = 0; ts.keep_last = (fa.materialize && fa.mode != 2) ? 1 : 0; ts.lo_ssm = b->lo_ssm; ts.SS = ssm_state_size(b->lo_ssm); }
 	}
 	unsigned long long pub_seq = 0;   /* non-zero: the loop's own kernel delivers the results to the host */
 	if (mi) TRY(track_loop_mi(b, sm, ts, cx));

@@ -34,13 +34,15 @@ __global__ __launch_bounds__(kBlock, MTFHIP_FAST_WAVES) void k_fused_fast(BatchV
  * the host exactly once -- in the pass that stops it, or in the last pass the host enqueues (ts.last_pass) if it is still active then -- with
  * the hand-over of publish_target; the arrivals of all passes and both queues count to pub.B, the last one raises the host's flag.  pub_t0:
  * the launch's first target in the batch (bv and ts are the chunk's views). */
-__global__ __launch_bounds__(256) void k_finish_track(BatchView bv, mtfhip_sm_desc sm, TrackState ts,
-	const double *partials, int nblk, PhaseCtl pc, HostPublish pub, int pub_t0) {
+template <bool LO>
+__device__ __forceinline__ void finish_track_kernel(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
+	const double *partials, int nblk, const PhaseCtl &pc, const HostPublish &pub, int pub_t0) {
 	if (ts.finish_prio) __builtin_amdgcn_s_setprio(3);
 	const int t = blockIdx.x;
 	__shared__ int s_stopped;
 	if (pub.host && threadIdx.x == 0) __hip_atomic_store(&s_stopped, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-	if (ts.fast_finish) finish_track_fast_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
+	if constexpr (LO) finish_track_body<false, false, true>(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
+	else if (ts.fast_finish) finish_track_fast_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
 	else finish_track_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
 	if (pub.host && threadIdx.x < 64) {
 		/* the first wave alone: its lane 0 cleared and set the flag (1: active at entry, 3: stopped by this pass), and everything the bodies leave
@@ -67,6 +69,18 @@ __global__ __launch_bounds__(256) void k_finish_track(BatchView bv, mtfhip_sm_de
 		}
 		st_coh(pc.mine, now);
 	}
+}
+
+
+__global__ __launch_bounds__(256) void k_finish_track(BatchView bv, mtfhip_sm_desc sm, TrackState ts,
+	const double *partials, int nblk, PhaseCtl pc, HostPublish pub, int pub_t0) {
+	finish_track_kernel<false>(bv, sm, ts, partials, nblk, pc, pub, pub_t0);
+}
+/* the same for a batch of a low-order SSM (TrackState::lo_ssm): finish_track_body with the projection and the model's update, in both arithmetic
+ * modes (api_track.hip leaves fast_finish off for it) */
+__global__ __launch_bounds__(256) void k_finish_track_lo(BatchView bv, mtfhip_sm_desc sm, TrackState ts,
+	const double *partials, int nblk, PhaseCtl pc, HostPublish pub, int pub_t0) {
+	finish_track_kernel<true>(bv, sm, ts, partials, nblk, pc, pub, pub_t0);
 }
 
 
@@ -128,7 +142,9 @@ void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &f
 void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials,
 	int nblk, hipStream_t st, PhaseCtl pc, const HostPublish &pub, int pub_t0) {
 	/* NCC rows are 72 wide: two waves load them, the first one solves; many block rows (a single large target): 240 lanes sum them */
-	MTFHIP_LAUNCH(k_finish_track, dim3(bv.B), dim3(nblk > 8 ? 256 : (bv.am == MTFHIP_AM_NCC ? 128 : 64)), 0, st, bv, sm, ts, partials, nblk, pc, pub, pub_t0);
+	const dim3 block(nblk > 8 ? 256 : (bv.am == MTFHIP_AM_NCC ? 128 : 64));
+	if (ts.lo_ssm) MTFHIP_LAUNCH(k_finish_track_lo, dim3(bv.B), block, 0, st, bv, sm, ts, partials, nblk, pc, pub, pub_t0);
+	else MTFHIP_LAUNCH(k_finish_track, dim3(bv.B), block, 0, st, bv, sm, ts, partials, nblk, pc, pub, pub_t0);
 }
 
 void launch_finish_track_mi(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, int sum_std, int gmode,

@@ -274,6 +274,22 @@ __global__ __launch_bounds__(kBlock) void k_pix_jacobian(BatchView bv, int varia
 				double Iy = (a * gy - b * gx) * inv_factor;
 				hom_row(r, Ix, Iy, x, y, c.x, c.y);
 			}
+		} else if (bv.ssm != MTFHIP_SSM_AFFINE) {
+			/* the low-order models, INIT and WARPED (the API refuses the other two).  WARPED turns the gradient by the warp's 2 x 2 block first:
+			 * Similitude.cc:186-210 (a = d = state(2) + 1, c = -b = state(3)), Isometry.cc:162-185 (cos = W(0,0), sin = W(1,0)); Translation's
+			 * block is the identity (Translation.h:45-63).  st is the affine embedding of the warp (BatchView): Similitude's state(2) = W(0,0) - 1
+			 * is st[2], its state(3) = W(1,0) is st[4] */
+			double Ix = gx, Iy = gy;
+			if (variant == MTFHIP_JAC_WARPED && bv.ssm == MTFHIP_SSM_SIMILITUDE) {
+				const double a = st[2] + 1, b = -st[4], c = st[4], d = st[2] + 1;
+				Ix = a * gx + c * gy; Iy = b * gx + d * gy;
+			} else if (variant == MTFHIP_JAC_WARPED && bv.ssm == MTFHIP_SSM_ISOMETRY) {
+				const double cos_theta = W.m[0], sin_theta = W.m[3];
+				Ix = cos_theta * gx + sin_theta * gy; Iy = cos_theta * gy - sin_theta * gx;
+			}
+			r[0] = Ix; r[1] = Iy;
+			if (bv.ssm == MTFHIP_SSM_SIMILITUDE) { r[2] = Ix * x + Iy * y; r[3] = Iy * x - Ix * y; }   /* Similitude.cc:163-184 */
+			else if (bv.ssm == MTFHIP_SSM_ISOMETRY) r[2] = Iy * x - Ix * y;                            /* Isometry.cc:115-135 */
 		} else {
 			double a = st[2] + 1, b = st[3], c = st[4], d = st[5] + 1;
 			double Ixx = gx * x, Ixy = gx * y, Iyy = gy * y, Iyx = gy * x;

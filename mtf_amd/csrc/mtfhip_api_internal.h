@@ -74,13 +74,46 @@ static M3 m3_inverse(const M3 &a) {
 	for (int i = 0; i < 9; ++i) c.m[i] *= inv_det;
 	return c;
 }
-/* getWarpFromState: Homography.cc:94-107, Affine.cc:116-130 */
+/* the low-order rigid models: Similitude (S = 4), Isometry (3), Translation (2) */
+static inline bool ssm_lowdof(int ssm) { return ssm == MTFHIP_SSM_SIMILITUDE || ssm == MTFHIP_SSM_ISOMETRY || ssm == MTFHIP_SSM_TRANSLATION; }
+static inline bool ssm_known(int ssm) { return ssm == MTFHIP_SSM_HOMOGRAPHY || ssm == MTFHIP_SSM_AFFINE || ssm_lowdof(ssm); }
+static inline int ssm_state_size(int ssm) {
+	switch (ssm) {
+	case MTFHIP_SSM_HOMOGRAPHY: return 8;
+	case MTFHIP_SSM_SIMILITUDE: return 4;
+	case MTFHIP_SSM_ISOMETRY: return 3;
+	case MTFHIP_SSM_TRANSLATION: return 2;
+	default: return 6;
+	}
+}
+static inline const char *ssm_name(int ssm) {
+	switch (ssm) {
+	case MTFHIP_SSM_HOMOGRAPHY: return "homography";
+	case MTFHIP_SSM_AFFINE: return "affine";
+	case MTFHIP_SSM_SIMILITUDE: return "similitude";
+	case MTFHIP_SSM_ISOMETRY: return "isometry";
+	case MTFHIP_SSM_TRANSLATION: return "translation";
+	default: return "unknown";
+	}
+}
+/* getWarpFromState: Homography.cc:94-107, Affine.cc:116-130, Similitude.cc:123-141, Isometry.cc:68-86, Translation.cc:86-93 */
 static M3 warp_from_state(int ssm, const double *p) {
 	M3 W;
 	if (ssm == MTFHIP_SSM_HOMOGRAPHY) {
 		W.m[0] = 1 + p[0]; W.m[1] = p[1]; W.m[2] = p[2];
 		W.m[3] = p[3]; W.m[4] = 1 + p[4]; W.m[5] = p[5];
 		W.m[6] = p[6]; W.m[7] = p[7]; W.m[8] = 1;
+	} else if (ssm == MTFHIP_SSM_SIMILITUDE) {
+		W.m[0] = 1 + p[2]; W.m[1] = -p[3]; W.m[2] = p[0];
+		W.m[3] = p[3]; W.m[4] = 1 + p[2]; W.m[5] = p[1];
+		W.m[6] = 0; W.m[7] = 0; W.m[8] = 1;
+	} else if (ssm == MTFHIP_SSM_ISOMETRY) {
+		const double cos_theta = std::cos(p[2]), sin_theta = std::sin(p[2]);
+		W.m[0] = cos_theta; W.m[1] = -sin_theta; W.m[2] = p[0];
+		W.m[3] = sin_theta; W.m[4] = cos_theta; W.m[5] = p[1];
+		W.m[6] = 0; W.m[7] = 0; W.m[8] = 1;
+	} else if (ssm == MTFHIP_SSM_TRANSLATION) {
+		W = M3{{1, 0, p[0], 0, 1, p[1], 0, 0, 1}};
 	} else {
 		W.m[0] = 1 + p[2]; W.m[1] = p[3]; W.m[2] = p[0];
 		W.m[3] = p[4]; W.m[4] = 1 + p[5]; W.m[5] = p[1];
@@ -88,11 +121,16 @@ static M3 warp_from_state(int ssm, const double *p) {
 	}
 	return W;
 }
-/* getStateFromWarp: Homography.cc:116-132, Affine.cc:132-143 */
+/* getStateFromWarp: Homography.cc:116-132, Affine.cc:132-143, Similitude.cc:144-153, Isometry.cc:88-97, Translation.cc:95-101 */
 static void state_from_warp(int ssm, double *p, const M3 &W) {
 	if (ssm == MTFHIP_SSM_HOMOGRAPHY) {
 		p[0] = W.m[0] - 1; p[1] = W.m[1]; p[2] = W.m[2]; p[3] = W.m[3]; p[4] = W.m[4] - 1; p[5] = W.m[5];
 		p[6] = W.m[6]; p[7] = W.m[7];
+	} else if (ssm_lowdof(ssm)) {
+		for (int k = 0; k < 8; ++k) p[k] = 0;
+		p[0] = W.m[2]; p[1] = W.m[5];
+		if (ssm == MTFHIP_SSM_SIMILITUDE) { p[2] = W.m[0] - 1; p[3] = W.m[3]; }
+		else if (ssm == MTFHIP_SSM_ISOMETRY) p[2] = std::atan2(W.m[3], W.m[0]);
 	} else {
 		p[0] = W.m[2]; p[1] = W.m[5]; p[2] = W.m[0] - 1; p[3] = W.m[1]; p[4] = W.m[3]; p[5] = W.m[4] - 1;
 		p[6] = p[7] = 0;
@@ -203,6 +241,15 @@ struct mtfhip_batch {
 	mtfhip_patch_desc desc;
 	int B, N, S;          /* N = patch_size = NP * C (rows of the per-pixel AM arrays) */
 	int NP = 0, C = 1;    /* sample points per target, channels */
+	/* The low-order models (lo_ssm = MTFHIP_SSM_SIMILITUDE / _ISOMETRY / _TRANSLATION, else 0) on the fused path run the AFFINE pixel pass and
+	 * keep everything upstream of the solve in affine coordinates.  While a fused entry point works (PassMode, below) the batch IS an
+	 * affine one -- S = 6, desc.ssm = MTFHIP_SSM_AFFINE, buf[J0 / JT / JM] the six-column scratch planes pass_j[] that no entry point
+	 * exposes -- so the template's constant Hessian th[].h0 / d_h0 and the NCC template moments are the affine ones; outside, S and
+	 * desc.ssm are the model's own and the three buffers the interface's N x S arrays. */
+	int lo_ssm = 0;
+	bool pass_mode = false;
+	double *pass_j[3] = {nullptr, nullptr, nullptr};
+	size_t pass_j_per_target[3] = {0, 0, 0};
 	double norm_mult = 1, norm_add = 0;
 	double *buf[MTFHIP_BUF_COUNT];
 	size_t per_target[MTFHIP_BUF_COUNT];
@@ -414,6 +461,45 @@ static int ensure_second_order_scratch(mtfhip_batch *b) {
 	return MTFHIP_OK;
 }
 
+/* A fused entry point of a low-order SSM works on the batch as an affine one (mtfhip_batch::lo_ssm): the guard turns it into that for its
+ * scope and back.  Nothing for homography / affine batches, and nothing when an outer scope already holds it. */
+struct PassMode {
+	mtfhip_batch *b;
+	bool on;
+	explicit PassMode(mtfhip_batch *b_) : b(b_), on(b_ && b_->lo_ssm && !b_->pass_mode) { if (on) flip(); }
+	~PassMode() { if (on) flip(); }
+	PassMode(const PassMode &) = delete;
+	PassMode &operator=(const PassMode &) = delete;
+	void flip() {
+		static const int ids[3] = {MTFHIP_BUF_J0, MTFHIP_BUF_JT, MTFHIP_BUF_JM};
+		for (int k = 0; k < 3; ++k) { std::swap(b->buf[ids[k]], b->pass_j[k]); std::swap(b->per_target[ids[k]], b->pass_j_per_target[k]); }
+		b->pass_mode = !b->pass_mode;
+		b->S = b->pass_mode ? 6 : ssm_state_size(b->lo_ssm);
+		b->desc.ssm = b->pass_mode ? (int)MTFHIP_SSM_AFFINE : b->lo_ssm;
+	}
+};
+/* what a low-order SSM is not served with: the entry point fn returns MTFHIP_ERR_NOT_IMPLEMENTED before any kernel of its own could read a
+ * six- or eight-wide state */
+static inline int lowdof_refuse(const mtfhip_batch *b, const char *fn) {
+	if (!b || !b->lo_ssm) return MTFHIP_OK;
+	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: not available with the %s state space model (Similitude, Isometry and Translation are served by the "
+		"StateSpaceModel and AppearanceModel entry points and by init_template / set_region / iterate / track / track_region with ESM, FCLK and ICLK, "
+		"first-order Hessians)", fn, ssm_name(b->lo_ssm));
+}
+/* the affine pass of a low-order SSM reads the six-column template copy init_template / set_region left in scratch: a caller who has since
+ * written the interface's N x S template Jacobian (mtfhip_batch_write, mtfhip_ssm_cmpt_pix_jacobian into J0) has a template the pass does not see */
+static inline int lowdof_template_current(const mtfhip_batch *b, const char *fn) {
+	if (b && b->lo_ssm && b->init_pix_vals && !b->j0_is_template)
+		return fail(MTFHIP_ERR_LOGIC, "%s: the template Jacobian of this %s batch was overwritten since init_template / set_region; the fused path "
+			"keeps its own affine-coordinate copy: call one of them again", fn, ssm_name(b->lo_ssm));
+	return MTFHIP_OK;
+}
+/* the state as the device slab holds it: the SSM's own, or for a low-order SSM the affine embedding of its warp (BatchView::states) */
+static inline void slab_state(const mtfhip_batch *b, const TargetHost &h, double *s8) {
+	if (!b->lo_ssm) { std::memcpy(s8, h.state, sizeof(double) * 8); return; }
+	const double *W = h.warp.m;
+	s8[0] = W[2]; s8[1] = W[5]; s8[2] = W[0] - 1; s8[3] = W[1]; s8[4] = W[3]; s8[5] = W[4] - 1; s8[6] = s8[7] = 0;
+}
 /* host state of every target -> one staging image of the slab */
 static void fill_stage(const mtfhip_batch *b, char *stage, const double *w0 /* [B][9] or NULL */, int active, bool zero_iters) {
 	const size_t Bt = (size_t)b->B;
@@ -423,7 +509,7 @@ static void fill_stage(const mtfhip_batch *b, char *stage, const double *w0 /* [
 	for (int t = 0; t < b->B; ++t) {
 		const TargetHost &h = b->th[t];
 		std::memcpy(w + 9 * t, h.warp.m, sizeof(double) * 9);
-		std::memcpy(s + 8 * t, h.state, sizeof(double) * 8);
+		slab_state(b, h, s + 8 * t);
 		std::memcpy(cr + 8 * t, h.corners, sizeof(double) * 8);
 		std::memcpy(ic + 12 * t, h.init_corners_hm, sizeof(double) * 12);
 		double *q = nc + 8 * t;
@@ -440,7 +526,7 @@ static int push_warps(mtfhip_batch *b) {
 	double *w = b->h_wstage[k], *s = w + 9 * (size_t)b->B;   /* d_states follows d_warps in the slab */
 	for (int t = 0; t < b->B; ++t) {
 		std::memcpy(&w[9 * t], b->th[t].warp.m, sizeof(double) * 9);
-		std::memcpy(&s[8 * t], b->th[t].state, sizeof(double) * 8);
+		slab_state(b, b->th[t], &s[8 * t]);
 	}
 	HIP_TRY(hipMemcpyAsync(b->d_warps, w, sizeof(double) * 17 * (size_t)b->B, hipMemcpyHostToDevice, b->ctx->stream));
 	HIP_TRY(hipEventRecord(b->ev_w[k], b->ctx->stream));
@@ -700,10 +786,13 @@ static inline mtfhip::MiJ0Rebuild mi_j0_rebuild(const mtfhip_batch *b) {
 /* the template lattice's extents and resolution as the kernels that lay a grid out themselves take them (set_corners_core's extents:
  * ProjectiveBase.cc:14, Affine.cc:56-57); everything else of the record is zero */
 static inline mtfhip::RegionIngest region_geometry(const mtfhip_batch *b) {
-	const bool homg = b->desc.ssm == MTFHIP_SSM_HOMOGRAPHY;
+	/* (the model itself, also while a fused entry point has the batch in its affine form: PassMode) */
+	const int ssm = b->lo_ssm ? b->lo_ssm : b->desc.ssm;
+	const bool homg = ssm == MTFHIP_SSM_HOMOGRAPHY;
+	const bool unit_sq = homg || ssm == MTFHIP_SSM_ISOMETRY || ssm == MTFHIP_SSM_TRANSLATION;   /* (set_corners_core's unit_square) */
 	mtfhip::RegionIngest rg{};
-	rg.lo_x = homg ? -0.5 : 1 - b->desc.resx / 2.0; rg.lo_y = homg ? -0.5 : 1 - b->desc.resy / 2.0;
-	rg.hi_x = homg ? 0.5 : b->desc.resx / 2.0; rg.hi_y = homg ? 0.5 : b->desc.resy / 2.0;
+	rg.lo_x = unit_sq ? -0.5 : 1 - b->desc.resx / 2.0; rg.lo_y = unit_sq ? -0.5 : 1 - b->desc.resy / 2.0;
+	rg.hi_x = unit_sq ? 0.5 : b->desc.resx / 2.0; rg.hi_y = unit_sq ? 0.5 : b->desc.resy / 2.0;
 	rg.resx = b->desc.resx; rg.resy = b->desc.resy; rg.force_unit_z = homg ? 0 : 1;
 	return rg;
 }
@@ -785,6 +874,12 @@ int track_region_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *r
 extern const bool g_track_dbg_timing;   /* MTFHIP_TRACK_DEBUG_TIMING: host-side stamps of the loop and the grid frames on stderr */
 /* api_alk.hip: MTFHIP_SM_FALK / _IALK behind mtfhip_batch_init_template / _iterate / _track */
 static inline bool alk_sm(int sm) { return sm == MTFHIP_SM_FALK || sm == MTFHIP_SM_IALK; }
+/* ... which a low-order SSM is not served with: refused before anything else looks at the call */
+static inline int lowdof_sm_refuse(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn) {
+	if (b && b->lo_ssm && sm && alk_sm(sm->sm))
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: the additive search methods (FALK / IALK) are not available with the %s state space model", fn, ssm_name(b->lo_ssm));
+	return MTFHIP_OK;
+}
 int alk_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int alk_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
 int alk_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners);

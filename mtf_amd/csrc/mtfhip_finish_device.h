@@ -39,7 +39,10 @@ __device__ unsigned long long g_fin_trace[16];
  * are FCLK's functions of the reduced row (cmptCurrJacobian / cmptSelfHessian / cmptCurrHessian of the pass's own pixel Jacobian). */
 /* stop_flag (k_finish_track's delivery to the host; LDS, cleared by the caller, or NULL): 1 once the target is known to have been active at entry,
  * 3 when this pass stops it -- written by lane 0 of the first wave, the wave that reads it afterwards */
-template <bool COH = false, bool ADDITIVE = false>
+/* LO (k_finish_track_lo, kernels_fused.hip): the finish of a low-order SSM's batch (TrackState::lo_ssm) -- the projection of the affine-coordinate
+ * system and the model's own update.  A template parameter, not a run-time branch: the kernels of homography and affine batches are
+ * compiled without any of it (the Isometry's cos / sin / atan2 alone would raise their register and scratch demand). */
+template <bool COH = false, bool ADDITIVE = false, bool LO = false>
 __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
 	const double *partials, int nblk, int t, int *stop_flag = nullptr) {
 	auto LD = [](const double *p) -> double { if constexpr (COH) return ld_coh(p); else return *p; };
@@ -51,10 +54,10 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	auto stop_target = [&](const double *w_old, const double *s_old) {
 		STI(ts.active + t, 0);
 		if (stop_flag) __hip_atomic_store(stop_flag, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-		if (ts.lean_pass) {
+		if (ts.lean_pass || (LO && ts.keep_last)) {
 			for (int q = 0; q < 9; ++q) ST(ts.warp_last + 9 * t + q, w_old[q]);
 			for (int q = 0; q < 8; ++q) ST(ts.state_last + 8 * t + q, s_old[q]);
-			STI(ts.need_mat + t, 1);
+			if (ts.lean_pass) STI(ts.need_mat + t, 1);
 		}
 	};
 	FIN_STAMP(0);
@@ -65,6 +68,10 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	const int lane = threadIdx.x;
 	const bool wv0 = lane < 64;
 	const int S = bv.S;
+	/* a low-order SSM (LO; TrackState::lo_ssm, uniform over the launch): S is the affine pass's row width 6 and everything up to h_entry /
+	 * g_entry is the affine finish; the system that is damped, equilibrated and eliminated is the SS x SS projection of it */
+	const int lo = LO ? ts.lo_ssm : 0;
+	const int SS = lo ? ts.SS : S;
 	/* NCC: the reduced row holds raw moments (NCC_* slots, NCC_ACC_COUNT wide); tms = sum J0 | sum I0 J0 | Gram(J0) of the
 	 * template, ncs = mean(I0), |I0 - mean|.  The calling workgroup then has at least 128 threads. */
 	const bool ncc = bv.am == MTFHIP_AM_NCC;
@@ -78,7 +85,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	if (wv0) {
 		v_h0 = ts.h0[(size_t)t * 64 + lane];
 		if (lane < 9) v_w = LD(bv.warps + 9 * t + lane);
-		if ((ADDITIVE || ts.lean_pass) && lane < 8) v_so = LD(bv.states + 8 * t + lane);   /* (the state this pass ran at: stop_target, the additive update) */
+		if ((ADDITIVE || ts.lean_pass || (LO && ts.keep_last)) && lane < 8) v_so = LD(bv.states + 8 * t + lane);   /* (the state this pass ran at: stop_target, the additive update) */
 		if (lane < 8) v_cr = LD(ts.corners + 8 * t + lane);
 		if (lane < 12) v_ic = ts.init_corners_hm[12 * t + lane];
 		if (ncc) {
@@ -226,15 +233,55 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	 * from convergence, where the reference's colPivHouseholderQr (NT/FCLK.cc:298) does not care either.  (A row-per-lane
 	 * elimination in registers with v_readlane broadcasts was measured slower than this LDS form: 8.9 k against 6.9 k clocks.) */
 	const bool pivoting = ncc || ts.h_from_acc || ts.h_extra != nullptr;   /* (the search and the row swap are two barriers and eight LDS reads per step: skipped for SSD) */
-	const double si = pow2_scale(h_entry(i, i)), sj = pow2_scale(h_entry(j, j));
+	/* The low-order SSMs: J_S = J_aff M with M constant, 6 x SS, at most two +-1 entries per column (Translation.h:45-63,
+	 * Isometry.cc:115-135,162-185, Similitude.cc:163-210) --
+	 *   Translation [Ja0, Ja1]    Isometry [Ja0, Ja1, Ja4 - Ja3]    Similitude [Ja0, Ja1, Ja2 + Ja5, Ja4 - Ja3]
+	 * -- and every g and H above is linear / bilinear in the rows: g_S = g_aff M, H_S = M^T H_aff M, an entry of H_S a sum of at most four
+	 * of H_aff.  Taken here: behind h_entry / g_entry, in front of the Levenberg-Marquardt scaling (the reference damps the S x S Hessian),
+	 * the equilibration and the elimination; rows and columns >= SS are padded as above.  col k of M: rows a0 and (a1 >= 0) a1 with sign s1. */
+	auto lo_col = [&](int k, int &a0, int &a1, double &s1) {
+		a0 = k; a1 = -1; s1 = 0.0;
+		if (k >= 2) { const bool sum = lo == MTFHIP_SSM_SIMILITUDE && k == 2; a0 = sum ? 2 : 4; a1 = sum ? 5 : 3; s1 = sum ? 1.0 : -1.0; }
+	};
+	auto lo_h = [&](int r, int c) -> double {
+		if (r >= SS || c >= SS) return r == c ? -1.0 : 0.0;
+		int r0, r1, c0, c1; double sr, sc;
+		lo_col(r, r0, r1, sr); lo_col(c, c0, c1, sc);
+		/* (one copy of h_entry, not four: the loops stay loops) */
+		double v = 0.0;
+#pragma unroll 1
+		for (int u = 0; u < 2; ++u) {
+			const int ru = u ? r1 : r0;
+			if (ru < 0) continue;
+#pragma unroll 1
+			for (int w = 0; w < 2; ++w) {
+				const int cw = w ? c1 : c0;
+				if (cw >= 0) v += (u ? sr : 1.0) * (w ? sc : 1.0) * h_entry(ru, cw);
+			}
+		}
+		return v;
+	};
+	auto lo_g = [&](int s) -> double {
+		int a0, a1; double s1;
+		lo_col(s, a0, a1, s1);
+		return g_entry(a0) + (a1 >= 0 ? s1 * g_entry(a1) : 0.0);
+	};
+	double hii, hjj, hij = 0.0, gi = 0.0;
+	if (lo) {
+		hii = lo_h(i, i); hjj = lo_h(j, j);
+		if (wv0) { hij = lo_h(i, j); gi = (j == 0 && i < SS) ? lo_g(i) : 0.0; }
+	} else {
+		hii = h_entry(i, i); hjj = h_entry(j, j);
+		if (wv0) { hij = h_entry(i, j); gi = (j == 0 && i < S) ? g_entry(i) : 0.0; }
+	}
+	const double si = pow2_scale(hii), sj = pow2_scale(hjj);
 	double *trec = (ts.trace && n_it_prev < ts.trace_cap) ? ts.trace + ((size_t)t * ts.trace_cap + n_it_prev) * kTraceStride : nullptr;   /* debug trace */
 	if (wv0) {
 		/* hessian(i, i) += leven_marq_delta * hessian(i, i) (NT/ESM.cc:262-265) */
-		const double hij = h_entry(i, j), gi = (j == 0 && i < S) ? g_entry(i) : 0.0;
-		A[i][j] = hij * si * sj * ((lmp && i == j && i < S) ? 1.0 + lm_delta : 1.0);
+		A[i][j] = hij * si * sj * ((lmp && i == j && i < SS) ? 1.0 + lm_delta : 1.0);
 		if (j == 0) A[i][8] = gi * si;
 		if (trec) {
-			trec[8 * i + j] = (i < S && j < S) ? hij : 0.0;
+			trec[8 * i + j] = (i < SS && j < SS) ? hij : 0.0;
 			if (j == 0) trec[64 + i] = gi;
 			if (lane == 0) {
 				trec[88] = ts.f_ext ? LD(ts.f_ext + t) : (ncc ? n_f : -acc_s[ACC_RR] / 2);
@@ -268,7 +315,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	}
 	if (wv0 && j == 0) {
 		const double d = A[i][i];
-		dps[i] = (i < S && d != 0) ? -(A[i][8] / d) * si : 0.0;
+		dps[i] = (i < SS && d != 0) ? -(A[i][8] / d) * si : 0.0;
 	}
 	__syncthreads();
 	FIN_STAMP(4);
@@ -311,12 +358,23 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	if (hom) {
 		U[0] = 1 + dp[0]; U[1] = dp[1]; U[2] = dp[2]; U[3] = dp[3]; U[4] = 1 + dp[4]; U[5] = dp[5];
 		U[6] = dp[6]; U[7] = dp[7]; U[8] = 1;
+	} else if (lo) {
+		/* getWarpFromState of the model: Translation.cc:86-93, Similitude.cc:123-141, Isometry.cc:68-86 */
+		double u00 = 1.0, u10 = 0.0;
+		if (lo == MTFHIP_SSM_SIMILITUDE) { u00 = 1 + dp[2]; u10 = dp[3]; }
+		else if (lo == MTFHIP_SSM_ISOMETRY) { u00 = cos(dp[2]); u10 = sin(dp[2]); }
+		U[0] = u00; U[1] = -u10; U[2] = dp[0]; U[3] = u10; U[4] = u00; U[5] = dp[1];
+		U[6] = 0; U[7] = 0; U[8] = 1;
 	} else {
 		U[0] = 1 + dp[2]; U[1] = dp[3]; U[2] = dp[0]; U[3] = dp[4]; U[4] = 1 + dp[5]; U[5] = dp[1];
 		U[6] = 0; U[7] = 0; U[8] = 1;
 	}
 	/* forward step: ICLK applies the inverse of the solved update (NT/ICLK.cc:266-267); undo: ESM / FCLK apply the inverse of
 	 * the previous update (NT/ESM.cc:194-195), ICLK re-applies it (NT/ICLK.cc:188) */
+	if (lo == MTFHIP_SSM_TRANSLATION) {
+		/* Translation::invertState negates (Translation.cc:103-105); its compositionalUpdate adds (:75-84), which W * U below does */
+		if ((sm.sm == MTFHIP_SM_ICLK) != undo) { U[2] = -dp[0]; U[5] = -dp[1]; }
+	} else
 	if ((sm.sm == MTFHIP_SM_ICLK) != undo) {
 		/* invertState: inverse through cofactors, normalised by (2,2) */
 		double c[9];
@@ -339,6 +397,13 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		/* round-trip through the state parameterisation as getStateFromWarp / getWarpFromState do */
 		U[0] = 1 + (U[0] - 1); U[4] = 1 + (U[4] - 1); U[8] = 1;
 		if (!hom) { U[6] = 0; U[7] = 0; }
+		if (lo) {
+			/* ... which for Similitude reads (0, 0) - 1 and (1, 0) (Similitude.cc:144-153) and for Isometry atan2((1, 0), (0, 0))
+			 * (Isometry.cc:88-97); the matrix is rebuilt from those alone */
+			double u00 = U[0], u10 = U[3];
+			if (lo == MTFHIP_SSM_ISOMETRY) { const double theta = atan2(U[3], U[0]); u00 = cos(theta); u10 = sin(theta); }
+			U[0] = u00; U[1] = -u10; U[3] = u10; U[4] = u00;
+		}
 	}
 	double Wo[9];
 #pragma unroll

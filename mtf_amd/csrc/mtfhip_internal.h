@@ -20,9 +20,15 @@ struct ImgView {
 
 /* POD view of a batch, passed by value to kernels.  Every buf[i] is [B][per-target size]. */
 struct BatchView {
-	int B, N, S, ssm, am; /* N = patch_size = NP * C rows of every per-pixel AM array */
+	int B, N, S, ssm, am; /* N = patch_size = NP * C rows of every per-pixel AM array; S = columns of the J planes this view addresses */
 	int NP, C;            /* sample points per target, channels (MCSSD / MCNCC / MCMI: 3) */
 	int unit_z;           /* 1: every init_z == 1 (affine SSM or parallelogram corners) */
+	/* The low-order models (Similitude, Isometry, Translation) run the affine pixel pass: in a fused view ssm is MTFHIP_SSM_AFFINE and S
+	 * the pass's row width 6 -- J planes, accumulator layout, the constant Hessian's stride; the model and the size of its solve travel
+	 * with the finish alone (TrackState::lo_ssm / SS), so this struct -- the first kernel argument of every pixel pass -- is what it was.
+	 * In a per-function view of such a batch ssm is the model itself and S its state size.
+	 * `states` of a low-order batch holds, on the device, the affine embedding of its warp [W02, W12, W00 - 1, W01, W10, W11 - 1]:
+	 * what the affine pass reads its 2 x 2 block from, and what the affine state update of the finish writes. */
 	double *buf[MTFHIP_BUF_COUNT];
 	double *warps;        /* [B][9] row-major curr_warp */
 	double *states;       /* [B][8] curr_state */
@@ -140,6 +146,12 @@ struct TrackState {
 	 * their issue priority -- one wave per target beside the other queue's pixel pass, where it is always the younger wave of its SIMD */
 	int last_pass = 0;
 	int finish_prio = 0;
+	/* a low-order SSM's materialising loop: the warp and the state a target's last pass ran at are kept in warp_last / state_last whatever the
+	 * pass kind (need_mat is left alone), for the launch that writes the target's N x S Jacobian behind the loop (api_track.hip) */
+	int keep_last = 0;
+	/* the finish of a low-order SSM's batch (k_finish_track_lo): the model (MTFHIP_SSM_SIMILITUDE / _ISOMETRY / _TRANSLATION) and the size
+	 * of its solve, 4 / 3 / 2 -- bv.S is then the affine pass's row width 6.  0: a homography / affine batch. */
+	int lo_ssm = 0, SS = 0;
 };
 constexpr int kLmStride = 12;
 constexpr int kTraceStride = 96;

@@ -88,6 +88,14 @@ def _check(rc):
         raise HostError(lib().mtfhost_last_error().decode("utf-8", "replace"))
 
 
+def _refuse_low_order(what, *ssms):
+    """the particle filter and the grid tracker are not served with the Similitude / Isometry / Translation state space models
+    (include/mtfhip.h): raised before any device call"""
+    for ssm in ssms:
+        if ssm in _lib.SSM_LOW_ORDER:
+            raise HostError("%s: the Similitude / Isometry / Translation state space models are served by the LK trackers only (got ssm %d)" % (what, ssm))
+
+
 class CppTracker:
     """mtf::nt::{ESM,FCLK,ICLK,FALK,IALK} (or, with device_loop, mtf::hip::LK) over mtf::hip::{HipAM,HipSSM}; parameter names and defaults
     are the reference's (leven_marq defaults to true as in ESMParams.cc / FCLKParams.cc / ICLKParams.cc; FALKParams.cc / IALKParams.cc
@@ -248,6 +256,7 @@ class CppParticleFilter(CppTracker):
                  corner_based_sampling=1, ssm_sigma=(0.01, 0.01, 2.0, 0.01, 0.01, 2.0, 1e-5, 1e-5), likelihood_alpha=1.0, seed=1,
                  device=0, ssm_mean=None, update_distr_wts=0, min_distr_wt=0.1, adaptive_resampling_thresh=0.0, jacobian_as_sigma=0, pix_sigma=None):
         """ssm_sigma: one row, or several rows = several sampler distributions (PFParams::processDistributions)"""
+        _refuse_low_order("CppParticleFilter", ssm)
         rows = [list(ssm_sigma)] if np.ndim(ssm_sigma) == 1 else [list(r) for r in ssm_sigma]
         mrows = [[0.0] * 8 for _ in rows] if ssm_mean is None else ([list(ssm_mean)] if np.ndim(ssm_mean) == 1 else [list(r) for r in ssm_mean])
         while len(mrows) < len(rows): mrows.append(mrows[-1])
@@ -268,7 +277,7 @@ class CppParticleFilter(CppTracker):
         self._img = None
         self.iters = 0
         self.n_channels = 1
-        self.S = 8 if ssm == _lib.SSM_HOMOGRAPHY else 6
+        self.S = _lib.ssm_state_size(ssm)
 
     def random_walk_samples(self, seed, n, sigma):
         """n draws of StateSpaceModel::compositionalRandomWalk from the current state (the SSM sampler virtuals)"""
@@ -333,6 +342,7 @@ class CppGridTracker:
                  n_model_pts=4, est_params=None, est_seed=1):
         # est_params (_lib.est_params(...)): mtf::hip::Grid::setEstimatorParams -- the device RANSAC / LMedS estimator instead of the
         # least-squares fit / the callback, with pix_mask() and est_ok / est_info() after every update
+        _refuse_low_order("CppGridTracker", patch_ssm, grid_ssm)
         gy, py = grid_size_y or grid_size, patch_size_y or patch_size
         h = lib().mtfhost_grid_create(grid_size, gy, patch_size, py, reset_at_each_frame, dyn_patch_size, patch_centroid_inside, patch_sm,
                                       patch_am, patch_ssm, grid_ssm, max_iters, epsilon, hess_type, leven_marq, device, float(fb_err_thresh),
@@ -340,7 +350,7 @@ class CppGridTracker:
         if not h:
             raise HostError(lib().mtfhost_last_error().decode("utf-8", "replace"))
         self._h = C.c_void_p(h)
-        self.n, self.S = grid_size * gy, 8 if grid_ssm == _lib.SSM_HOMOGRAPHY else 6
+        self.n, self.S = grid_size * gy, _lib.ssm_state_size(grid_ssm)
         self._img, self._cb = None, None
         self.est_params = est_params
         if est_params is not None:

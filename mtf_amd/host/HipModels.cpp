@@ -18,10 +18,31 @@ void HipPair::check(int rc) {
 	}
 }
 
+/* StateSpaceModel::getStateSize / name of the MTFHIP_SSM_* kinds (Homography.cc:36, Affine.cc:47, Similitude.cc:62-63, Isometry.cc:51-52,
+ * Translation.cc:47-48) */
+static int stateSizeOf(int ssm) {
+	switch (ssm) {
+	case MTFHIP_SSM_HOMOGRAPHY: return 8;
+	case MTFHIP_SSM_SIMILITUDE: return 4;
+	case MTFHIP_SSM_ISOMETRY: return 3;
+	case MTFHIP_SSM_TRANSLATION: return 2;
+	default: return 6;
+	}
+}
+static const char *ssmNameOf(int ssm) {
+	switch (ssm) {
+	case MTFHIP_SSM_HOMOGRAPHY: return "homography";
+	case MTFHIP_SSM_SIMILITUDE: return "similitude";
+	case MTFHIP_SSM_ISOMETRY: return "isometry";
+	case MTFHIP_SSM_TRANSLATION: return "translation";
+	default: return "affine";
+	}
+}
+
 HipPair::HipPair(int _am, int _ssm, int _resx, int _resy, double _grad_eps, double likelihood_alpha, int mi_n_bins,
 	double mi_pre_seed, int mi_pou, int device, void *stream, int _n_channels) :
 	am(_am), ssm(_ssm), resx(_resx), resy(_resy), N(_resx * _resy * (_n_channels > 1 ? _n_channels : 1)),
-	S(_ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6), n_pix(_resx * _resy), n_channels(_n_channels > 1 ? _n_channels : 1),
+	S(stateSizeOf(_ssm)), n_pix(_resx * _resy), n_channels(_n_channels > 1 ? _n_channels : 1),
 	grad_eps(_grad_eps) {
 	if (resx <= 0 || resy <= 0) throw utils::InvalidArgument("ImageBase::Invalid sampling resolution provided"); /* ImageBase.cc:33-35 */
 	if (const char *e = std::getenv("MTFHIP_EAGER_GETTERS")) eager_getters = e[0] == '1';
@@ -229,7 +250,7 @@ void HipAM::cmptMeanOf(MatrixXd &mean, const MatrixXd &a, const MatrixXd &b) {
 
 /* ------------------------------------------------------------------ SSM */
 HipSSM::HipSSM(std::shared_ptr<HipPair> pair) : p(pair) {
-	name = p->ssm == MTFHIP_SSM_HOMOGRAPHY ? "homography" : "affine";
+	name = ssmNameOf(p->ssm);
 	curr_pts.resize(2, p->n_pix);
 	grad_pts.resize(8, p->n_pix);
 	hess_pts.resize(16, p->n_pix);
@@ -294,7 +315,7 @@ void estimateWarpFromPts(mtfhip_ctx *ctx, int ssm, double *state_update, unsigne
 	int inf[4];
 	HipPair::check(mtfhip_ssm_estimate_from_pts(ctx, ssm, &d, 1, &n_pts, n_pts, reinterpret_cast<const float *>(in_pts), reinterpret_cast<const float *>(out_pts),
 		nullptr, n_hyp, seed, upd, mask, inf, stats, nullptr));
-	const int S = ssm == MTFHIP_SSM_HOMOGRAPHY ? 8 : 6;
+	const int S = stateSizeOf(ssm);
 	for (int k = 0; k < S; ++k) state_update[k] = upd[k];
 	if (info) { info->ok = inf[0] != 0; info->winner = inf[1]; info->n_walked = inf[2]; info->n_inliers = inf[3]; info->min_median = stats[0]; info->sigma = stats[1]; }
 }

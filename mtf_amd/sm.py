@@ -26,6 +26,15 @@ def _solve(H, g):
     return -np.linalg.solve(H / np.outer(d, d), g / d) / d
 
 
+def _refuse_low_order(what, *ssms):
+    """GridTracker, ParticleFilter, NNDataset and NNTracker are not served with the Similitude / Isometry / Translation state space models
+    (include/mtfhip.h): raised before any device call"""
+    for ssm in ssms:
+        if ssm in L.SSM_LOW_ORDER:
+            raise L.FunctionNotImplemented(-2, "%s: the Similitude / Isometry / Translation state space models are served by LKTracker and "
+                                               "NTSearchMethod only (got ssm %d)" % (what, ssm))
+
+
 class LKTracker:
     """One or many (B) independent targets tracked with ESM / FCLK / ICLK (or the additive FALK / IALK: SSD and NCC, k_alk_pass +
     k_alk_finish) + SSD, NCC or MI on one GPU through the fused path
@@ -410,6 +419,7 @@ class GridTracker:
     def __init__(self, ctx, grid_size=10, patch_size=10, am=L.AM_NCC, ssm=L.SSM_AFFINE, max_iters=30, epsilon=1e-4, sm=L.SM_ICLK,
                  reset_at_each_frame=1, dyn_patch_size=0, patch_centroid_inside=1, grid_ssm=L.SSM_HOMOGRAPHY, estimator=None,
                  grid_size_y=None, patch_size_y=None, fb_err_thresh=0.0, fb_reinit=1, n_model_pts=4, est_params=None, est_seed=1, **sm_params):
+        _refuse_low_order("GridTracker", ssm, grid_ssm)
         self.ctx = ctx
         # est_params (_lib.est_params(...) = SSMEstimatorParams): the device RANSAC / LMedS estimator (Context.estimate_warp_from_pts) takes the
         # place of `estimator`; pix_mask / est_ok / est_result follow every update (GridTracker.cc:269, 332-340); frame f draws from est_seed + f
@@ -434,7 +444,7 @@ class GridTracker:
         self._pending_region = None      # reset_at_each_frame = 2: the setRegion of the patch trackers rides in the next frame's launch
         self.prev_pts = np.zeros((self.n, 2), dtype=np.float32)
         self.curr_pts = np.zeros((self.n, 2), dtype=np.float32)
-        self.ssm_update = np.zeros(8 if grid_ssm == L.SSM_HOMOGRAPHY else 6)
+        self.ssm_update = np.zeros(L.ssm_state_size(grid_ssm))
         if est_params is not None:
             self.pix_mask = np.ones(self.n, dtype=np.uint8)
 
@@ -659,6 +669,7 @@ class ParticleFilter:
         thresh * n (PF.cc:381-390); jacobian_as_sigma: the sampler's sigma of every frame is the Gauss-Newton step -H0^-1 g (PF.cc:58-64,
         156-165, 214-227)"""
         import ctypes as C
+        _refuse_low_order("ParticleFilter", ssm)
         # seed 0 = "draw one" (below) -- but only an unsharded filter may: the ranks of a sharded one must propose identical particles
         # (each scores a block of ITS proposals, the all-gather mixes the weights), so there seed 0 is refused before anything is
         # created (mtfhip_pf_set_comm cross-checks the seeds of all ranks as well)
@@ -884,6 +895,7 @@ class NNDataset:
 
     def __init__(self, ctx, am=L.AM_SSD, ssm=L.SSM_HOMOGRAPHY, resx=50, resy=50, n_samples=1000,
                  ssm_sigma=(0.01, 0.01, 2.0, 0.01, 0.01, 2.0, 1e-5, 1e-5), ssm_mean=None, seed=0, am_params=None, distr_n_samples=None):
+        _refuse_low_order("NNDataset", ssm)
         self.batch = Batch(ctx, am, ssm, resx, resy, 1, **(am_params or {}))
         self.S = self.batch.S
         self.n = int(n_samples)
@@ -1006,6 +1018,7 @@ class NNTracker:
                  ssm_sigma=(0.01, 0.01, 2.0, 0.01, 0.01, 2.0, 1e-5, 1e-5), ssm_mean=None, distr_n_samples=None, max_iters=1, epsilon=0.01,
                  seed=0, am_params=None):
         self._h = None
+        _refuse_low_order("NNTracker", ssm)
         self.ds = NNDataset(ctx, am, ssm, resx, resy, n_samples, ssm_sigma, ssm_mean, seed, am_params, distr_n_samples)
         self.batch = self.ds.batch
         self.n, self.S = self.ds.n, self.ds.S

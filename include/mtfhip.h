@@ -582,8 +582,9 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 /* ---- nt::NN's per-frame half: the exact search over the resident dataset and NN::update (SM/src/NT/NN.cc:236-277) ----
  * The handle sits on a batch of ONE target (its appearance model, SSM, template grid and current image) and owns the device copies of the
  * n_samples x feat_size dataset (eig_dataset), the perturbations (ssm_perturbations), the search's partial results, the per-iteration log
- * and the stop flag.  The index is the exhaustive one -- what FLANN's Linear index type computes (SM/include/mtf/SM/FLANNParams.h:13) and
- * GNN and the KD-trees approximate --: one streaming read of the matrix per query with the appearance model's distance functor, SSD
+ * and the stop flag.  The default index is the exhaustive one -- what FLANN's Linear index type computes (SM/include/mtf/SM/FLANNParams.h:13)
+ * and the KD-trees approximate; the reference's own index, the graph index gnn::GNN, is mtfhip_nn_gnn_* below, selected per handle with
+ * mtfhip_nn_set_index --: one streaming read of the matrix per query with the appearance model's distance functor, SSD
  * sum (a - b)^2 (SSDBaseDist::operator(), AM/src/SSDBase.cc:576-603, without the worst_dist early return, which does not change the argmin) or
  * NCC -sum a b on the centred unit-norm rows (NCCDist::operator(), AM/src/NCC.cc:568-591); multi-channel models: rows of n_pix x n_channels
  * entries.  Of equal distances the lower index wins; no floating-point atomics: a call is bit-reproducible.
@@ -617,6 +618,53 @@ int mtfhip_nn_search_dev(mtfhip_nn *nn, const double *dev_queries, int n_queries
  * bits.  corners_out: x0 y0 x1 y1 x2 y2 x3 y3; n_iters: iterations run; log_out (max_iters x 3, or NULL): best_idx, best_dist, update_norm
  * per iteration run.  The batch's SSM is left at the new state. */
 int mtfhip_nn_update(mtfhip_nn *nn, int max_iters, double epsilon, double *corners_out, int *n_iters, double *log_out);
+
+/* ---- nt::NN's graph index gnn::GNN (SM/src/NT/GNN.cc; NN::initialize ends with gnn_index->buildGraph, NT/NN.cc:110-124, NN::update asks
+ * gnn_index->searchGraph for best_idx, NT/NN.cc:250-251) over the handle's resident dataset ----
+ * buildGraph (GNN.cc:59-113): every row's `degree` nearest rows under (distance ascending, index ascending) -- the degree + 1 smallest of its
+ * distances to all rows, the first dropped whatever it is (GNN.cc:98-101: usually the row itself; an identical row at a lower index takes
+ * that place, and the row then keeps itself as a neighbour).  On the device: all-pairs distances in row panels of a fixed scratch budget
+ * (never n x n; cmpt_dist_thresh, which in the reference only decides whether the distances are cached, GNN.cc:60-64, is accepted and
+ * ignored), SSD in the difference form, then a radix select and a sort per row.  The graph is n_samples x degree int32 on the device.
+ * searchGraph with K = 1 (GNN.cc:115-203): from the start node, per step the distances of the query to the node's neighbours -- the
+ * exhaustive search's own row sum, the same bits --, the best under (distance, position in the list) joins the visited set; the walk ends
+ * when parent_dist <= best (GNN.cc:180-183), after max_steps steps (GNN.cc:134), or at a node without neighbours, else it moves to the best
+ * (GNN.cc:184-185).  The answer is the visited node of smallest distance, of equal distances the one visited first (the reference's qsort,
+ * GNN.cc:191, leaves that open), and it is the next search's start node (GNN.cc:198).
+ * Effective degree: GNN's constructor first (GNN.cc:15-19: 0 or > n_samples -> n_samples; negative -> -n_samples / degree), then clamped to
+ * n_samples - 1: at degree = n_samples the reference's list of degree + 1 entries has one slot that its loop over n_samples rows never
+ * fills, and it reads it (GNN.cc:66, 98-100).  degree + 1 > 1024: MTFHIP_ERR_NOT_IMPLEMENTED, before anything is launched.
+ * Start node: kept on the device across iterations and frames, initially 0 (the reference draws it with an unseeded rand(), GNN.cc:28: not
+ * reproduced) or mtfhip_nn_gnn_set_start; with random_start (GNN.cc:123-125) every search draws its start from the library's Philox4x32-10
+ * keyed by (seed, the handle's running search count).  Defaults (SM/src/GNNParams.cc:3-7): degree 250, max_steps 10, cmpt_dist_thresh
+ * 10000, random_start 0. */
+typedef struct mtfhip_gnn_desc {
+	int degree;            /* GNNParams::degree */
+	int max_steps;
+	int cmpt_dist_thresh;  /* accepted, ignored */
+	int random_start;
+	unsigned long long seed;
+} mtfhip_gnn_desc;
+/* buildGraph over the handle's resident dataset; MTFHIP_ERR_LOGIC without one.  mtfhip_nn_build and mtfhip_nn_set_dataset[_dev] invalidate the graph. */
+int mtfhip_nn_gnn_build(mtfhip_nn *nn, const mtfhip_gnn_desc *d);
+/* saveGraph / loadGraph (GNN.cc:206-241) without the file: *degree the effective degree, nns_inds n_samples x degree (or NULL) */
+int mtfhip_nn_gnn_get_graph(mtfhip_nn *nn, int *degree, int *nns_inds);
+int mtfhip_nn_gnn_set_graph(mtfhip_nn *nn, const mtfhip_gnn_desc *d, const int *nns_inds);
+/* independent, stateless walks side by side: query q starts at start_nodes[q] (start_nodes NULL: at the handle's start node, or drawn with
+ * random_start) -> idx[q], dist[q], n_steps[q] (steps taken, the ending one included; may be NULL).  The handle's start node stays.  The _dev
+ * form takes device pointers and only enqueues.  MTFHIP_ERR_LOGIC without a valid graph. */
+int mtfhip_nn_gnn_search(mtfhip_nn *nn, const double *queries, int n_queries, const int *start_nodes, int *idx, double *dist, int *n_steps);
+int mtfhip_nn_gnn_search_dev(mtfhip_nn *nn, const double *dev_queries, int n_queries, const int *dev_start_nodes, int *dev_idx, double *dev_dist,
+	int *dev_n_steps);
+enum { MTFHIP_NN_INDEX_EXACT = 0, MTFHIP_NN_INDEX_GNN = 1 };
+/* what mtfhip_nn_update searches with; default EXACT.  With GNN, per iteration: the feature launch, the walk's step launches (each returns
+ * at once when its walk is done), then the same pick-and-update fed with the walk's (best_idx, best_dist); log_out keeps its three
+ * columns; the host-stepped form gives the same bits.  MTFHIP_ERR_LOGIC from mtfhip_nn_update without a valid graph. */
+int mtfhip_nn_set_index(mtfhip_nn *nn, int index_type);
+int mtfhip_nn_gnn_set_start(mtfhip_nn *nn, int node);
+int mtfhip_nn_gnn_get_start(mtfhip_nn *nn, int *node);
+/* per iteration run by the last mtfhip_nn_update (its n_iters entries each; either may be NULL): the walk's start node and step count */
+int mtfhip_nn_gnn_last_walks(mtfhip_nn *nn, int *start_nodes, int *n_steps);
 
 /* ---- measurement hooks ---- */
 /* average duration in milliseconds of the launches of the named kernel family since the last

@@ -120,6 +120,21 @@ class NnDesc(C.Structure):
     _fields_ = [("n_samples", C.c_int), ("additive_update", C.c_int), ("sigma", C.c_double * 8), ("mean", C.c_double * 8), ("seed", C.c_ulonglong)]
 
 
+class GnnDesc(C.Structure):
+    """mtfhip_gnn_desc: gnn::GNNParams (SM/src/GNNParams.cc:3-7) plus the seed of random_start's draws"""
+    _fields_ = [("degree", C.c_int), ("max_steps", C.c_int), ("cmpt_dist_thresh", C.c_int), ("random_start", C.c_int), ("seed", C.c_ulonglong)]
+
+
+NN_INDEX_EXACT, NN_INDEX_GNN = 0, 1
+
+
+def gnn_desc(degree=250, max_steps=10, cmpt_dist_thresh=10000, random_start=False, seed=0, **_ignored):
+    """the reference's defaults (SM/src/GNNParams.cc:3-7); `start_node` and other keys a GNNParams dict may carry are not the descriptor's"""
+    d = GnnDesc()
+    d.degree, d.max_steps, d.cmpt_dist_thresh, d.random_start, d.seed = int(degree), int(max_steps), int(cmpt_dist_thresh), int(bool(random_start)), int(seed)
+    return d
+
+
 # every exported symbol of include/mtfhip.h (tests check that the library exports all of them)
 SYMBOLS = [
     "mtfhip_last_error", "mtfhip_device_count", "mtfhip_ctx_create", "mtfhip_ctx_destroy",
@@ -163,6 +178,8 @@ SYMBOLS = [
     "mtfhip_ssm_estimate_from_pts", "mtfhip_ssm_estimate_from_pts_dev",
     "mtfhip_nn_create", "mtfhip_nn_destroy", "mtfhip_nn_build", "mtfhip_nn_set_dataset", "mtfhip_nn_set_dataset_dev", "mtfhip_nn_get_dataset",
     "mtfhip_nn_get_dataset_dev", "mtfhip_nn_search", "mtfhip_nn_search_dev", "mtfhip_nn_update",
+    "mtfhip_nn_gnn_build", "mtfhip_nn_gnn_get_graph", "mtfhip_nn_gnn_set_graph", "mtfhip_nn_gnn_search", "mtfhip_nn_gnn_search_dev",
+    "mtfhip_nn_set_index", "mtfhip_nn_gnn_set_start", "mtfhip_nn_gnn_get_start", "mtfhip_nn_gnn_last_walks",
 ]
 
 
@@ -270,6 +287,14 @@ def lib():
         for fn in ("mtfhip_nn_search", "mtfhip_nn_search_dev"):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mtfhip_nn_update.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mtfhip_nn_gnn_build.argtypes = [C.c_void_p, C.c_void_p]
+        for fn in ("mtfhip_nn_gnn_get_graph", "mtfhip_nn_gnn_set_graph", "mtfhip_nn_gnn_last_walks"):
+            getattr(L, fn).argtypes = [C.c_void_p] * 3
+        for fn in ("mtfhip_nn_gnn_search", "mtfhip_nn_gnn_search_dev"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mtfhip_nn_set_index.argtypes = [C.c_void_p, C.c_int]
+        L.mtfhip_nn_gnn_set_start.argtypes = [C.c_void_p, C.c_int]
+        L.mtfhip_nn_gnn_get_start.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

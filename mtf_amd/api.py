@@ -810,6 +810,70 @@ class Batch:
         L.check(L.lib().mtfhip_nn_update(h, int(max_iters), C.c_double(float(epsilon)), _p(c), C.byref(n), _p(log)))
         return self._corners_out(c)[0], n.value, log[:n.value].copy()
 
+    # ---------------------------------------------------------- NN's graph index gnn::GNN (mtfhip_nn_gnn_*: GNN.cc:30-241)
+    @staticmethod
+    def _gnn_desc(params):
+        return params if isinstance(params, L.GnnDesc) else L.gnn_desc(**(params or {}))
+
+    def nn_gnn_build(self, h, params=None):
+        """buildGraph (GNN.cc:59-113) over the handle's resident dataset; `params`: a GnnDesc or the keywords of _lib.gnn_desc"""
+        d = self._gnn_desc(params)
+        L.check(L.lib().mtfhip_nn_gnn_build(h, C.addressof(d)))
+
+    @staticmethod
+    def nn_gnn_get_graph(h, n_samples):
+        """the graph (n_samples, effective degree) int32: the reference's saveGraph (GNN.cc:206-221) without the file"""
+        deg = C.c_int()
+        L.check(L.lib().mtfhip_nn_gnn_get_graph(h, C.addressof(deg), None))
+        g = np.empty((int(n_samples), deg.value), dtype=np.int32)
+        if g.size:
+            L.check(L.lib().mtfhip_nn_gnn_get_graph(h, C.addressof(deg), _p(g)))
+        return g
+
+    def nn_gnn_set_graph(self, h, graph, params=None):
+        """loadGraph (GNN.cc:223-241) without the file: `graph` (n_samples, effective degree of `params`)"""
+        d = self._gnn_desc(params)
+        g = np.ascontiguousarray(np.asarray(graph, dtype=np.int32))
+        L.check(L.lib().mtfhip_nn_gnn_set_graph(h, C.addressof(d), _p(g) if g.size else None))
+
+    def nn_gnn_search(self, h, queries, start_nodes=None):
+        """searchGraph (GNN.cc:115-203, K = 1) for every row of `queries`, independent walks from `start_nodes` (None: the handle's start
+        node, or drawn with random_start) -> (idx (Q,) int32, dist (Q,), n_steps (Q,) int32)"""
+        q = _f64(queries).reshape(-1, self.nn_feature_size())
+        Q = q.shape[0]
+        st = None if start_nodes is None else np.ascontiguousarray(np.asarray(start_nodes, dtype=np.int32).reshape(Q))
+        idx, dist, steps = np.empty(Q, dtype=np.int32), np.empty(Q), np.empty(Q, dtype=np.int32)
+        L.check(L.lib().mtfhip_nn_gnn_search(h, _p(q), Q, None if st is None else _p(st), _p(idx), _p(dist), _p(steps)))
+        return idx, dist, steps
+
+    @staticmethod
+    def nn_gnn_search_dev(h, dev_queries_ptr, n_queries, dev_start_nodes_ptr, dev_idx_ptr, dev_dist_ptr, dev_n_steps_ptr=None):
+        L.check(L.lib().mtfhip_nn_gnn_search_dev(h, C.c_void_p(dev_queries_ptr), int(n_queries), C.c_void_p(dev_start_nodes_ptr) if dev_start_nodes_ptr else None,
+                                                 C.c_void_p(dev_idx_ptr), C.c_void_p(dev_dist_ptr), C.c_void_p(dev_n_steps_ptr) if dev_n_steps_ptr else None))
+
+    @staticmethod
+    def nn_set_index(h, index):
+        """what nn_update searches with: "exact" (the default) or "gnn" """
+        kinds = {"exact": L.NN_INDEX_EXACT, "gnn": L.NN_INDEX_GNN}
+        L.check(L.lib().mtfhip_nn_set_index(h, kinds[index] if isinstance(index, str) else int(index)))
+
+    @staticmethod
+    def nn_gnn_set_start(h, node):
+        L.check(L.lib().mtfhip_nn_gnn_set_start(h, int(node)))
+
+    @staticmethod
+    def nn_gnn_get_start(h):
+        v = C.c_int()
+        L.check(L.lib().mtfhip_nn_gnn_get_start(h, C.addressof(v)))
+        return v.value
+
+    @staticmethod
+    def nn_gnn_last_walks(h, n_iters):
+        """(start nodes, step counts) of the walks of the last nn_update's n_iters iterations"""
+        st, ns = np.zeros(max(int(n_iters), 1), dtype=np.int32), np.zeros(max(int(n_iters), 1), dtype=np.int32)
+        L.check(L.lib().mtfhip_nn_gnn_last_walks(h, _p(st), _p(ns)))
+        return st[:n_iters].copy(), ns[:n_iters].copy()
+
     # ---------------------------------------------------------- candidate scoring
     def score_candidates(self, states, want_similarity=False):
         s = _f64(states).reshape(-1, self.S)

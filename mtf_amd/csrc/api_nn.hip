@@ -3,25 +3,7 @@
  * include/mtfhip.h; the kernels: kernels_nn_search.hip, and kernels_nn.hip for the query feature)
  */
 #include "mtfhip_api_internal.h"
-
-namespace {
-constexpr int kNnStateDoubles = 40;   /* W 9 | corners 8 | init_corners_hm 12 | the zero perturbation 8 | pad 3 */
-constexpr int kNnZeroPert = 29;
-}
-
-struct mtfhip_nn {
-	mtfhip_batch *b = nullptr;
-	int device = 0;                       /* (destroy does not reach through the batch: it may be gone) */
-	int n = 0, F = 0, S = 0, ncc = 0;
-	bool host_stepped = false, have_dataset = false;
-	int resident = 0, nblk = 0;           /* workgroups of a search launch */
-	double *d_feat = nullptr, *d_perts = nullptr;
-	NnBest *d_part = nullptr; int part_q = 0;   /* [part_q][nblk] */
-	double *d_query = nullptr;            /* the tracker's query feature, feat_size */
-	/* W | corners | init_corners_hm | zero perturbation | pad, then ctl (done, n_iters: two ints in one double's place), then the log */
-	double *d_state = nullptr; int log_cap = 0;
-	double *d_q = nullptr; int *d_idx = nullptr; double *d_dist = nullptr; int q_cap = 0;   /* staging of the host form of the search */
-};
+#include "mtfhip_nn_handle.h"
 
 static int nn_ensure_partials(mtfhip_nn *nn, int Q) {
 	if (Q <= nn->part_q) return MTFHIP_OK;
@@ -35,7 +17,7 @@ static int nn_ensure_state(mtfhip_nn *nn, int max_iters) {
 	if (nn->d_state && max_iters <= nn->log_cap) return MTFHIP_OK;
 	HIP_TRY(hipStreamSynchronize(nn->b->ctx->stream));
 	if (nn->d_state) { (void)hipFree(nn->d_state); nn->d_state = nullptr; nn->log_cap = 0; }
-	HIP_TRY(hipMalloc(&nn->d_state, sizeof(double) * (size_t)(kNnStateDoubles + 1 + 3 * (size_t)max_iters)));
+	HIP_TRY(hipMalloc(&nn->d_state, sizeof(double) * (size_t)(kNnStateDoubles + 1 + 4 * (size_t)max_iters)));
 	nn->log_cap = max_iters;
 	return MTFHIP_OK;
 }
@@ -88,6 +70,7 @@ int mtfhip_nn_destroy(mtfhip_nn *nn) {
 	if (hipSetDevice(nn->device) == hipSuccess) (void)hipDeviceSynchronize();
 	(void)hipFree(nn->d_feat); (void)hipFree(nn->d_perts); (void)hipFree(nn->d_part); (void)hipFree(nn->d_query); (void)hipFree(nn->d_state);
 	(void)hipFree(nn->d_q); (void)hipFree(nn->d_idx); (void)hipFree(nn->d_dist);
+	gnn_free(nn);
 	delete nn;
 	return MTFHIP_OK;
 }
@@ -102,7 +85,7 @@ int mtfhip_nn_build(mtfhip_nn *nn, const mtfhip_nn_desc *desc, int n_distr) {
 		total += desc[k].n_samples;
 	}
 	if (total != nn->n) return fail(MTFHIP_ERR_INVALID_ARG, "nn_build: the distributions hold %ld samples, the handle %d", total, nn->n);
-	nn->have_dataset = false;
+	nn->have_dataset = false; nn->g.valid = false;   /* (a graph belongs to the rows it was built over) */
 	size_t lo = 0;
 	for (int k = 0; k < n_distr; ++k) {
 		const int cnt = desc[k].n_samples;
@@ -119,6 +102,7 @@ int mtfhip_nn_set_dataset_dev(mtfhip_nn *nn, const double *dev_features, const d
 	TRY(nn_usable(nn, "nn_set_dataset_dev"));
 	if (!dev_features || !dev_perturbations) return fail(MTFHIP_ERR_INVALID_ARG, "nn_set_dataset_dev: NULL argument");
 	hipStream_t st = nn->b->ctx->stream;
+	nn->g.valid = false;
 	HIP_TRY(hipMemcpyAsync(nn->d_feat, dev_features, sizeof(double) * (size_t)nn->n * nn->F, hipMemcpyDeviceToDevice, st));
 	HIP_TRY(hipMemcpyAsync(nn->d_perts, dev_perturbations, sizeof(double) * (size_t)nn->n * nn->S, hipMemcpyDeviceToDevice, st));
 	nn->have_dataset = true;
@@ -128,6 +112,7 @@ int mtfhip_nn_set_dataset(mtfhip_nn *nn, const double *features, const double *p
 	TRY(nn_usable(nn, "nn_set_dataset"));
 	if (!features || !perturbations) return fail(MTFHIP_ERR_INVALID_ARG, "nn_set_dataset: NULL argument");
 	hipStream_t st = nn->b->ctx->stream;
+	nn->g.valid = false;
 	HIP_TRY(hipMemcpyAsync(nn->d_feat, features, sizeof(double) * (size_t)nn->n * nn->F, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(nn->d_perts, perturbations, sizeof(double) * (size_t)nn->n * nn->S, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipStreamSynchronize(st));   /* the caller's arrays are free again */
@@ -195,15 +180,18 @@ int mtfhip_nn_update(mtfhip_nn *nn, int max_iters, double epsilon, double *corne
 	if (max_iters <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "nn_update: max_iters must be positive");
 	if (!corners_out || !n_iters) return fail(MTFHIP_ERR_INVALID_ARG, "nn_update: NULL argument");
 	TRY(nn_need_dataset(nn, "nn_update"));
+	const bool gnn = nn->g.index_type == MTFHIP_NN_INDEX_GNN;
+	if (gnn) TRY(gnn_need_graph(nn, "nn_update"));
 	mtfhip_batch *b = nn->b;
 	FLUSH(b);
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "nn_update before set_corners");
 	TRY(need_image(b));
 	TRY(nn_ensure_state(nn, max_iters));
+	if (gnn) TRY(gnn_prepare_update(nn, max_iters));
 	hipStream_t st = b->ctx->stream;
 	TargetHost &h = b->th[0];
 	/* the state block goes up from the host mirrors: the batch's SSM may have been moved by any other entry point since the last frame */
-	std::vector<double> up(kNnStateDoubles + 1, 0.0), down(kNnStateDoubles + 1 + 3 * (size_t)max_iters);
+	std::vector<double> up(kNnStateDoubles + 1, 0.0), down(kNnStateDoubles + 1 + (gnn ? 3 * (size_t)nn->log_cap + (size_t)max_iters : 3 * (size_t)max_iters));
 	std::memcpy(&up[0], h.warp.m, sizeof(double) * 9);
 	std::memcpy(&up[9], h.corners, sizeof(double) * 8);
 	std::memcpy(&up[17], h.init_corners_hm, sizeof(double) * 12);
@@ -214,11 +202,12 @@ int mtfhip_nn_update(mtfhip_nn *nn, int max_iters, double epsilon, double *corne
 	qd.n_samples = 1;
 	auto iteration = [&](int it) -> int {
 		TRY(nn_dataset_enqueue(b, &qd, nn->d_state + kNnZeroPert, nullptr, nn->d_query, 0, 1, nn->d_state, d_ctl));
-		{
+		if (gnn) TRY(gnn_enqueue_update_walk(nn, it, d_ctl));   /* searchGraph (NT/NN.cc:250-251) -> the one partial the pick reads */
+		else {
 			TimedScope ts(b->ctx, "nn_search");
 			launch_nn_search(nn->ncc, nn->d_feat, nn->n, nn->F, nn->d_query, 1, nn->d_part, nn->nblk, d_ctl, st);
 		}
-		launch_nn_pick_update(b->desc.ssm, nn->d_part, nn->nblk, nn->d_perts, nn->n, nn->d_state, d_ctl, d_log, it, epsilon, st);
+		launch_nn_pick_update(b->desc.ssm, nn->d_part, gnn ? 1 : nn->nblk, nn->d_perts, nn->n, nn->d_state, d_ctl, d_log, it, epsilon, st);
 		return launch_error_pending();
 	};
 	if (nn->host_stepped) {
@@ -237,6 +226,7 @@ int mtfhip_nn_update(mtfhip_nn *nn, int max_iters, double epsilon, double *corne
 	int ctl[2];
 	std::memcpy(ctl, &down[kNnStateDoubles], sizeof(ctl));
 	const int ran = ctl[1];
+	if (gnn) gnn_finish_update(nn, reinterpret_cast<const int *>(&down[kNnStateDoubles + 1 + 3 * (size_t)nn->log_cap]), ran < max_iters ? ran : max_iters);
 	/* the batch's SSM follows: mirrors from the device's warp and corners, the device copy of the batch refreshed as after compositionalUpdate */
 	++b->lz.epoch;
 	std::memcpy(h.warp.m, &down[0], sizeof(double) * 9);

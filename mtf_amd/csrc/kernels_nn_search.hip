@@ -20,32 +20,9 @@
  */
 #include "mtfhip_device.h"
 #include "mtfhip_rng_device.h"
-#include <climits>
+#include "mtfhip_nn_search_device.h"
 
 namespace mtfhip {
-
-typedef double nns_d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool nn_better(double d, int i, double bd, int bi) { return d < bd || (d == bd && i < bi); }
-
-/* the wave's minimum of (d, i), in every lane */
-__device__ __forceinline__ void nn_wave_min(double &d, int &i) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) {
-		const double od = __shfl_xor(d, m);
-		const int oi = __shfl_xor(i, m);
-		if (nn_better(od, oi, d, i)) { d = od; i = oi; }
-	}
-}
-/* the minimum of n partials, by one wave */
-__device__ __forceinline__ void nn_reduce_partials(const NnBest *part, int n, double &d, int &i) {
-	d = __builtin_inf(); i = INT_MAX;
-	for (int k = (int)(threadIdx.x & 63); k < n; k += 64) {
-		const NnBest p = part[k];
-		if (nn_better(p.dist, p.idx, d, i)) { d = p.dist; i = p.idx; }
-	}
-	nn_wave_min(d, i);
-}
 
 template <bool NCC>
 __global__ __launch_bounds__(kBlock) void k_nn_search(const double *feat, int n_samples, int F, const double *queries, NnBest *partials, const int *done) {
@@ -58,40 +35,10 @@ __global__ __launch_bounds__(kBlock) void k_nn_search(const double *feat, int n_
 	for (int i = threadIdx.x; i < F; i += kBlock) sq[i] = q[i];
 	if (threadIdx.x == 0 && (F & 1)) sq[F] = 0.0;
 	__syncthreads();
-	const int P = F >> 1;               /* whole pairs of a row */
-	auto term = [](double a, double b) { if constexpr (NCC) return a * b; else { const double d = a - b; return d * d; } };
 	double best = __builtin_inf();
 	int bidx = INT_MAX;
 	for (int r = (int)blockIdx.x * 4 + wave; r < n_samples; r += (int)gridDim.x * 4) {
-		const double *row = feat + (size_t)r * F;
-		/* ONE body for both alignments: only the loads differ, the arithmetic and its order do not */
-		auto body = [&](auto wide_tag) -> double {
-			constexpr bool WIDE = decltype(wide_tag)::value;
-			auto ld = [&](int p) -> nns_d2 {
-				if constexpr (WIDE) return reinterpret_cast<const nns_d2 *>(row)[p];
-				else { nns_d2 v; v.x = row[2 * p]; v.y = row[2 * p + 1]; return v; }
-			};
-			double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-			int p = lane;
-			for (; p + 192 < P; p += 256) {   /* four loads in flight per lane */
-				const nns_d2 v0 = ld(p), v1 = ld(p + 64), v2 = ld(p + 128), v3 = ld(p + 192);
-				const nns_d2 q0 = nns_q[p], q1 = nns_q[p + 64], q2 = nns_q[p + 128], q3 = nns_q[p + 192];
-				a0 += term(v0.x, q0.x); a0 += term(v0.y, q0.y);
-				a1 += term(v1.x, q1.x); a1 += term(v1.y, q1.y);
-				a2 += term(v2.x, q2.x); a2 += term(v2.y, q2.y);
-				a3 += term(v3.x, q3.x); a3 += term(v3.y, q3.y);
-			}
-			for (; p < P; p += 64) {
-				const nns_d2 v0 = ld(p), q0 = nns_q[p];
-				a0 += term(v0.x, q0.x); a0 += term(v0.y, q0.y);
-			}
-			if ((F & 1) && lane == (P & 63)) a0 += term(row[F - 1], sq[F - 1]);   /* the last entry of an odd row */
-			return (a0 + a1) + (a2 + a3);
-		};
-		const bool wide = (((size_t)r * (size_t)F) & 1) == 0;   /* (uniform per wave) the row starts on a 16-byte boundary */
-		double s = wide ? body(std::true_type{}) : body(std::false_type{});
-		s = wave_sum_dpp(s);
-		const double d = NCC ? -s : s;
+		const double d = nn_row_dist<NCC>(feat, r, F, lane, nns_q);   /* (mtfhip_nn_search_device.h: the graph walk's rows take the same body) */
 		if (d < best) { best = d; bidx = r; }   /* (a wave's rows ascend: the first of equal distances stays) */
 	}
 	if (lane == 0) { wbest[wave].dist = best; wbest[wave].idx = bidx; }

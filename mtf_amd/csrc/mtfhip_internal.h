@@ -570,6 +570,24 @@ void launch_nn_search_finish(const NnBest *partials, int nblk, int Q, int *idx, 
 /* state: W (9) | corners (8) | init_corners_hm (12); ctl: done | n_iters; log[it]: best_idx | best_dist | update_norm */
 void launch_nn_pick_update(int ssm, const NnBest *partials, int nblk, const double *perts, int n_samples, double *state, int *ctl, double *log, int it,
 	double epsilon, hipStream_t st);
+/* nt::NN's graph index gnn::GNN (kernels_gnn.hip; SM/src/NT/GNN.cc:30-203): the build -- all-pairs distances in row panels, the degree + 1
+ * nearest of every row -- and the greedy walk, one step per launch pair */
+struct GnnWalk { double parent_dist, best_dist; int cur, best_idx, start, n_steps, done, pad; };
+constexpr int kGnnMaxList = 1024;   /* degree + 1 entries are sorted in LDS */
+constexpr int kGnnTile = 64;        /* rows and columns of a workgroup's block of the distance matrix */
+void launch_gnn_dist(int ncc, const double *feat, int n_samples, int F, int row_lo, int rows, double *dist /* [rows][n_samples] */, hipStream_t st);
+void launch_gnn_select(const double *dist, int n_samples, int row_lo, int rows, int degree, int *graph /* [n_samples][degree] */, hipStream_t st);
+int gnn_step_blocks(int degree);
+/* start_nodes != NULL: walk q starts there; else random_start: drawn from (seed, *count + q); else at *handle_start.  *count += Q. */
+void launch_gnn_init(GnnWalk *walks, int Q, const int *start_nodes, const int *handle_start, int random_start, unsigned long long seed,
+	unsigned long long *count, int n_samples, const int *done, hipStream_t st);
+/* begin: the start node's own distance (one row); else one step: the `degree` neighbours of the walk's node, and the reference's rule
+ * applied by the workgroup that finishes last.  partials: [Q][nper]; tickets: [Q], zero between launches */
+void launch_gnn_rows(int ncc, const double *feat, int n_samples, int F, const double *queries, int Q, const int *graph, int degree, GnnWalk *walks,
+	NnBest *partials, unsigned *tickets, int nper, int max_steps, int begin, const int *done, hipStream_t st);
+void launch_gnn_results(const GnnWalk *walks, int Q, int *idx, double *dist, int *n_steps, hipStream_t st);
+/* the tracker's walk: (best_dist, best_idx) as the one partial k_nn_pick_update reads, the next search's start node, the log (start, n_steps) */
+void launch_gnn_to_update(const GnnWalk *walk, NnBest *partial, int *handle_start, int *walk_log, int it, const int *done, hipStream_t st);
 void launch_sample_candidates(const BatchView &bv, const ImgView &im, const double *dev_states, int C, double norm_mult,
 	double norm_add, double *dev_feat, hipStream_t st);
 /* whole ICLK loop in one launch, one workgroup per target (N <= 16 * kBlock); false if N is too large */

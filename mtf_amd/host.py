@@ -75,6 +75,9 @@ def lib():
         H.mtfhost_nn_create.restype = C.c_void_p
         H.mtfhost_nn_create.argtypes = [C.c_int] * 6 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
         H.mtfhost_nn_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        H.mtfhost_nn_create_gnn.restype = C.c_void_p
+        H.mtfhost_nn_create_gnn.argtypes = H.mtfhost_nn_create.argtypes + [C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int]
+        H.mtfhost_nn_walks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _h = H
     return _h
 

@@ -23,6 +23,12 @@ NN::NN(std::shared_ptr<HipAM> a, std::shared_ptr<HipSSM> s, const NNParams &np) 
 	for (int c : nn.distr_n_samples) total += c;
 	if ((int)nn.distr_n_samples.size() != k || total != nn.n_samples) throw utils::InvalidArgument("hip::NN :: distr_n_samples does not match ssm_sigma / n_samples");
 	HipPair::check(mtfhip_nn_create(a->pair()->b, nn.n_samples, &h));
+	if (nn.index_type == NNParams::GNN) {   /* (the handle exists: a refusal from here on must release it) */
+		int rc = mtfhip_nn_set_index(h, MTFHIP_NN_INDEX_GNN);
+		if (rc == MTFHIP_OK && nn.gnn.start_node != 0) rc = mtfhip_nn_gnn_set_start(h, nn.gnn.start_node);
+		if (rc != MTFHIP_OK) { mtfhip_nn_destroy(h); h = nullptr; }
+		HipPair::check(rc);
+	}
 }
 NN::~NN() { if (h) mtfhip_nn_destroy(h); }
 void NN::initialize(const CornersT &corners) {
@@ -41,6 +47,13 @@ void NN::initialize(const CornersT &corners) {
 		for (int k = 0; k < S; ++k) { d[i].sigma[k] = entry(nn.ssm_sigma[i], k, 0.0); d[i].mean[k] = entry(mean, k, 0.0); }
 	}
 	HipPair::check(mtfhip_nn_build(h, d.data(), (int)d.size()));
+	if (nn.index_type == NNParams::GNN) {   /* NT/NN.cc:110-124: gnn_index->buildGraph(eig_dataset.data()) */
+		mtfhip_gnn_desc g;
+		std::memset(&g, 0, sizeof(g));
+		g.degree = nn.gnn.degree; g.max_steps = nn.gnn.max_steps; g.cmpt_dist_thresh = nn.gnn.cmpt_dist_thresh;
+		g.random_start = nn.gnn.random_start ? 1 : 0; g.seed = nn.gnn.seed;
+		HipPair::check(mtfhip_nn_gnn_build(h, &g));
+	}
 }
 void NN::setRegion(const CornersT &corners) {
 	ssm->setCorners(corners);
@@ -51,6 +64,8 @@ void NN::update() {
 	log.assign(3 * (size_t)nn.max_iters, 0.0);
 	HipPair::check(mtfhip_nn_update(h, nn.max_iters, nn.epsilon, region.data(), &iters_done, log.data()));
 	log.resize(3 * (size_t)iters_done);
+	walk_starts.assign((size_t)iters_done, 0); walk_steps.assign((size_t)iters_done, 0);
+	if (nn.index_type == NNParams::GNN && iters_done > 0) HipPair::check(mtfhip_nn_gnn_last_walks(h, walk_starts.data(), walk_steps.data()));
 	hssm->markMoved();
 }
 const CornersT &NN::getRegion() {

@@ -1,6 +1,7 @@
 /*
  * NNParams.h -- the parameters of nt::NN (SM/include/mtf/SM/NNParams.h, defaults SM/src/NNParams.cc:6-18) with the reference's field names,
- * for mtf::hip::NN.  The index is the exhaustive search on the device: the GNN / FLANN index parameters and the index files have no
+ * for mtf::hip::NN.  index_type selects the exhaustive search on the device (the default: what FLANN's Linear index computes) or the
+ * reference's own graph index gnn::GNN with `gnn` (GNNParams.h); FLANN's other index parameters and the index files have no
  * counterpart.  additive_update defaults to true in the reference (NNParams.cc:10); the device path implements the compositional form
  * only, so the default here is false and hip::NN refuses true.
  */
@@ -8,6 +9,8 @@
 #define MTF_AMD_HOST_NN_PARAMS_H
 
 #include <vector>
+
+#include "GNNParams.h"
 
 namespace mtf {
 
@@ -22,6 +25,9 @@ struct NNParams {
 	std::vector<int> distr_n_samples;            /* samples per distribution (NT/NN.cc:60-73); empty: equal shares, the remainder to the last */
 	unsigned long long seed = 0;                 /* distribution k draws with seed + k */
 	bool debug_mode = false;
+	enum IndexType { EXACT = 0, GNN = 1 };
+	IndexType index_type = EXACT;                /* EXACT: hip::NN as it was; GNN: buildGraph behind the dataset, searchGraph per iteration (NT/NN.cc:110-124, 250-251) */
+	GNNParams gnn;
 };
 
 } // namespace mtf

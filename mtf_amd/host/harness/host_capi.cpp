@@ -183,9 +183,10 @@ int mtfhost_dist_feat(mtfhost_tracker *t, double *feat, int *size) {
 		return 0;
 	} catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
-/* mtf::hip::NN (mtfhip_nn_*): n_distr sampler distributions (ssm_sigma / ssm_mean: rows of 8; distr_n_samples: n_distr counts or NULL) */
-mtfhost_tracker *mtfhost_nn_create(int am, int ssm, int resx, int resy, int n_samples, int max_iters, double epsilon, int n_distr,
-	const double *ssm_sigma, const double *ssm_mean, const int *distr_n_samples, unsigned long long seed, int device, int n_channels) {
+/* mtf::hip::NN (mtfhip_nn_*): n_distr sampler distributions (ssm_sigma / ssm_mean: rows of 8; distr_n_samples: n_distr counts or NULL);
+ * gnn != NULL: the graph index with these parameters */
+static mtfhost_tracker *nn_create(int am, int ssm, int resx, int resy, int n_samples, int max_iters, double epsilon, int n_distr,
+	const double *ssm_sigma, const double *ssm_mean, const int *distr_n_samples, unsigned long long seed, int device, int n_channels, const GNNParams *gnn) {
 	try {
 		if (n_distr < 1 || !ssm_sigma) throw utils::InvalidArgument("mtfhost_nn_create: n_distr must be positive");
 		std::unique_ptr<mtfhost_tracker> t(new mtfhost_tracker());   /* (a constructor below may throw: nothing leaks) */
@@ -199,9 +200,31 @@ mtfhost_tracker *mtfhost_nn_create(int am, int ssm, int resx, int resy, int n_sa
 			if (ssm_mean) p.ssm_mean.emplace_back(ssm_mean + 8 * i, ssm_mean + 8 * i + t->pair->S);
 		}
 		if (distr_n_samples) p.distr_n_samples.assign(distr_n_samples, distr_n_samples + n_distr);
+		if (gnn) { p.index_type = NNParams::GNN; p.gnn = *gnn; }
 		t->sm.reset(new hip::NN(t->am, t->ssm, p));
 		return t.release();
 	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+mtfhost_tracker *mtfhost_nn_create(int am, int ssm, int resx, int resy, int n_samples, int max_iters, double epsilon, int n_distr,
+	const double *ssm_sigma, const double *ssm_mean, const int *distr_n_samples, unsigned long long seed, int device, int n_channels) {
+	return nn_create(am, ssm, resx, resy, n_samples, max_iters, epsilon, n_distr, ssm_sigma, ssm_mean, distr_n_samples, seed, device, n_channels, nullptr);
+}
+/* the same with NNParams::index_type = GNN and the GNNParams given */
+mtfhost_tracker *mtfhost_nn_create_gnn(int am, int ssm, int resx, int resy, int n_samples, int max_iters, double epsilon, int n_distr,
+	const double *ssm_sigma, const double *ssm_mean, const int *distr_n_samples, unsigned long long seed, int device, int n_channels,
+	int gnn_degree, int gnn_max_steps, int gnn_random_start, unsigned long long gnn_seed, int gnn_start_node) {
+	GNNParams g;
+	g.degree = gnn_degree; g.max_steps = gnn_max_steps; g.random_start = gnn_random_start != 0; g.seed = gnn_seed; g.start_node = gnn_start_node;
+	return nn_create(am, ssm, resx, resy, n_samples, max_iters, epsilon, n_distr, ssm_sigma, ssm_mean, distr_n_samples, seed, device, n_channels, &g);
+}
+/* start node and step count of every iteration's walk of the last update() of an mtfhost_nn_create_gnn tracker -> entries written */
+int mtfhost_nn_walks(mtfhost_tracker *t, int *start_nodes, int *n_steps, int max_rows) {
+	hip::NN *nn = t ? dynamic_cast<hip::NN *>(t->sm.get()) : nullptr;
+	if (!nn || !start_nodes || !n_steps) { g_err = "mtfhost_nn_walks: not an NN tracker"; return -1; }
+	const int rows = std::min((int)nn->getWalkStarts().size(), max_rows);
+	std::memcpy(start_nodes, nn->getWalkStarts().data(), sizeof(int) * (size_t)rows);
+	std::memcpy(n_steps, nn->getWalkSteps().data(), sizeof(int) * (size_t)rows);
+	return rows;
 }
 /* best_idx, best_dist, update_norm of the iterations of the last update() of an mtfhost_nn_create tracker: up to max_rows rows -> rows written */
 int mtfhost_nn_log(mtfhost_tracker *t, double *log, int max_rows) {

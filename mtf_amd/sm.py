@@ -1007,7 +1007,9 @@ class NNDataset:
 
 
 class NNTracker:
-    """nt::NN (SM/src/NT/NN.cc) with the exhaustive index, dataset and search resident on the device: `initialize` builds the dataset at the
+    """nt::NN (SM/src/NT/NN.cc) with the exhaustive index (index="exact", the default) or the reference's graph index gnn::GNN (index="gnn",
+    gnn_params: the keywords of _lib.gnn_desc -- the reference's GNNParams -- plus start_node; SM/src/NT/GNN.cc), dataset and search
+    resident on the device: `initialize` builds the dataset at the
     template (NN.cc:85-113, mtfhip_nn_build: nothing comes to the host), `update` is NN::update (NN.cc:236-277) in one C-ABI call
     (mtfhip_nn_update: per iteration the patch's distance feature, the exact search, compositionalUpdate with the winner's perturbation,
     all enqueued back to back).  max_iters / epsilon: NNParams (SM/src/NNParams.cc:6-7).  SSD and NCC, single- and multi-channel.
@@ -1016,15 +1018,23 @@ class NNTracker:
 
     def __init__(self, ctx, am=L.AM_SSD, ssm=L.SSM_HOMOGRAPHY, resx=50, resy=50, n_samples=1000,
                  ssm_sigma=(0.01, 0.01, 2.0, 0.01, 0.01, 2.0, 1e-5, 1e-5), ssm_mean=None, distr_n_samples=None, max_iters=1, epsilon=0.01,
-                 seed=0, am_params=None):
+                 seed=0, am_params=None, index="exact", gnn_params=None):
         self._h = None
         _refuse_low_order("NNTracker", ssm)
+        if index not in ("exact", "gnn"):
+            raise ValueError("NNTracker: index must be 'exact' or 'gnn'")
+        self.index, self.gnn_params = index, dict(gnn_params or {})
         self.ds = NNDataset(ctx, am, ssm, resx, resy, n_samples, ssm_sigma, ssm_mean, seed, am_params, distr_n_samples)
         self.batch = self.ds.batch
         self.n, self.S = self.ds.n, self.ds.S
         self.max_iters, self.epsilon = int(max_iters), float(epsilon)
         self._h = self.batch.nn_create(self.n)
         self.n_iters, self.log = 0, np.zeros((0, 3))
+        self.walk_starts, self.walk_steps = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        if index == "gnn":
+            self.batch.nn_set_index(self._h, "gnn")
+            if "start_node" in self.gnn_params:
+                self.batch.nn_gnn_set_start(self._h, self.gnn_params["start_node"])
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1043,22 +1053,38 @@ class NNTracker:
         self.batch.set_corners(np.asarray(corners, dtype=np.float64).reshape(1, 2, 4))
         self.batch.initialize_pix_vals()
 
-    def initialize(self, corners, features=None, perturbations=None, features_dev_ptr=None, perturbations_dev_ptr=None):
-        """NN::initialize (NN.cc:85-113): the template at `corners` and the dataset -- built on the device (several distributions: consecutive
-        row blocks seeded seed + k, as NNDataset.initialize), or the given one"""
+    def initialize(self, corners, features=None, perturbations=None, features_dev_ptr=None, perturbations_dev_ptr=None, graph=None):
+        """NN::initialize (NN.cc:85-124): the template at `corners` and the dataset -- built on the device (several distributions: consecutive
+        row blocks seeded seed + k, as NNDataset.initialize), or the given one --, and with index="gnn" the graph behind it (buildGraph,
+        NN.cc:110-124; or the given `graph`)"""
         self._template(corners)
         if features is not None or features_dev_ptr is not None:
-            self.set_dataset(features, perturbations, features_dev_ptr, perturbations_dev_ptr)
+            self.set_dataset(features, perturbations, features_dev_ptr, perturbations_dev_ptr, graph=graph)
             return
         d = self.ds
         self.batch.nn_build(self._h, [self.batch.nn_desc(cnt, d.sigmas[k], d.means[k], d.seed + k) for k, cnt in enumerate(d.distr_n_samples)])
+        self._graph(graph)
 
-    def set_dataset(self, features=None, perturbations=None, features_dev_ptr=None, perturbations_dev_ptr=None):
+    def _graph(self, graph=None):
+        if self.index != "gnn":
+            return
+        if graph is not None:
+            self.batch.nn_gnn_set_graph(self._h, graph, self.gnn_params)
+        else:
+            self.batch.nn_gnn_build(self._h, self.gnn_params)
+
+    def set_dataset(self, features=None, perturbations=None, features_dev_ptr=None, perturbations_dev_ptr=None, graph=None):
+        """a dataset made elsewhere; with index="gnn" the graph is rebuilt over it, or taken from `graph` (n_samples, degree)"""
         if features_dev_ptr is not None:
             self.batch.nn_set_dataset_dev(self._h, features_dev_ptr, perturbations_dev_ptr)
         else:
             self.batch.nn_set_dataset(self._h, np.asarray(features, dtype=np.float64).reshape(self.n, -1),
                                       np.asarray(perturbations, dtype=np.float64).reshape(self.n, self.S))
+        self._graph(graph)
+
+    def get_graph(self):
+        """the graph (n_samples, effective degree) int32 read back: the reference's saveGraph (GNN.cc:206-221) without the file"""
+        return self.batch.nn_gnn_get_graph(self._h, self.n)
 
     def get_dataset(self):
         """(features (n, feat_size), perturbations (n, S)) read back: the reference's saveDataset (NN.cc:222-234) without the file"""
@@ -1070,6 +1096,8 @@ class NNTracker:
 
     def update(self):
         corners, self.n_iters, self.log = self.batch.nn_update(self._h, self.max_iters, self.epsilon)
+        if self.index == "gnn":   # per iteration: where the walk started and how many steps it took
+            self.walk_starts, self.walk_steps = self.batch.nn_gnn_last_walks(self._h, self.n_iters)
         return corners
 
     def set_region(self, corners):

@@ -56,7 +56,17 @@ typedef enum mtfhip_status {
  * overlapping sub-region, blended with per-pixel weights, after a sampling (LRSCV::updatePixVals, LRSCV.cc:224-261); single channel,
  * first-order Hessians, the per-function entry points and the fused init_template / iterate / track / track_region
  * (mtfhip_batch_set_lrscv below) */
-enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6 };
+/* MTFHIP_AM_SPSS: Sum of Pixelwise Structural Similarity (AM/src/SPSS.cc), f = sum (2 I0 It + c) / (I0^2 + It^2 + c) over the raw pixel
+ * values, c = (255 k)^2 (mtfhip_batch_set_spss below; no pix_mapper).  Its first-order Hessians are per-pixel WEIGHTED Gram matrices and
+ * df_dI0 is not -df_dIt (the reference's df_dI0 carries c (It - 2 I0), SPSS.cc:135-138, and is kept).  Served: single channel, homography
+ * and affine, every first-order per-function AppearanceModel entry point (df_dI0 / df_dIt readable through mtfhip_batch_read), and
+ * mtfhip_batch_init_template / _set_region / _iterate / _track / _track_region with ESM, FCLK and ICLK, chained or not, materialize 0 / 1,
+ * with or without Levenberg-Marquardt, both arithmetic modes, on the two-launch loop.  Everything else returns
+ * MTFHIP_ERR_NOT_IMPLEMENTED with its reason in mtfhip_last_error(): n_channels 3 and the three low-order SSMs (at mtfhip_batch_create),
+ * sec_ord_hess and every second-order entry point, MTFHIP_SM_FALK / _IALK, ESM hess_type 4 (SumOfStd) and ICLK hess_type 1 (CurrentSelf)
+ * on the fused entry points (the per-function ones serve them), update_model, the grid entry points, score_candidates /
+ * sample_candidates, the particle filter and the NN / GNN entry points. */
+enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6, MTFHIP_AM_SPSS = 7 };
 /* MTFHIP_SSM_SIMILITUDE / _ISOMETRY / _TRANSLATION: the low-order rigid models (SSM/src/Similitude.cc, Isometry.cc, Translation.cc), states
  * [tx, ty, a, b] (warp [[1 + a, -b, tx], [b, 1 + a, ty]]), [tx, ty, theta] (warp [[cos, -sin, tx], [sin, cos, ty]]) and [tx, ty], S = 4 / 3 / 2.
  * Served: the StateSpaceModel entry points below (set_corners with normalized_init = 0, set_state, compositional_update, invert_state,
@@ -733,6 +743,11 @@ int mtfhip_batch_set_lrscv(mtfhip_batch *b, int n_sub_regions_x, int n_sub_regio
 /* the intensity maps of every target after its last map: B x (n_sub_regions_x n_sub_regions_y) x n_bins, sub-region idy n_x + idx
  * (map[b] = b before the first one) */
 int mtfhip_batch_lrscv_intensity_maps(mtfhip_batch *b, double *dst);
+
+/* ---- SPSS (MTFHIP_AM_SPSS) ---- */
+/* SPSSParams k (SPSS.cc:13-23; shipped spss_k 0.01): c = (k (PIX_MAX - PIX_MIN))^2 = (255 k)^2 (SPSS.cc:37-38).  k <= 0 selects the default
+ * 0.01.  Call before init_template / initialize_similarity (MTFHIP_ERR_LOGIC afterwards: the constant self Hessian is a function of c). */
+int mtfhip_batch_set_spss(mtfhip_batch *b, double k);
 
 /* ---- ssm.estimateWarpFromPts: the robust fit of the grid SSM to point pairs ---- */
 /* SSMEstimatorParams (SSM/include/mtf/SSM/SSMEstimatorParams.h:11-25; defaults SSMEstimatorParams.cc:5-13; the shipped values

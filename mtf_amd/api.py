@@ -232,7 +232,7 @@ class Batch:
     """B independent targets (AM + SSM pairs) sharing the context's current image."""
 
     def __init__(self, ctx, am=AM_SSD, ssm=SSM_HOMOGRAPHY, resx=50, resy=50, n_targets=1, grad_eps=1e-8,
-                 likelihood_alpha=1.0, mi_n_bins=8, mi_pre_seed=10.0, mi_pou=0, hess_eps=1.0, n_channels=1):
+                 likelihood_alpha=1.0, mi_n_bins=8, mi_pre_seed=10.0, mi_pou=0, hess_eps=1.0, n_channels=1, spss_k=None):
         self.ctx = ctx
         self.desc = PatchDesc(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, hess_eps,
                               n_channels)
@@ -244,6 +244,8 @@ class Batch:
         self.NP = resx * resy            # sample points (ImageBase::getNPix)
         self.N = self.NP * n_channels    # rows of every per-pixel AM array (getPatchSize); == NP for single channel
         self.S = L.ssm_state_size(ssm)
+        if spss_k is not None:           # SPSSParams k of an AM_SPSS batch (am_params of the trackers)
+            self.set_spss(spss_k)
 
     def close(self):
         if self._h:
@@ -551,6 +553,10 @@ class Batch:
         out = np.empty((self.B, nb))
         L.check(L.lib().mtfhip_batch_scv_intensity_map(self._h, _p(out)))
         return out
+
+    def set_spss(self, k=0.01):
+        """SPSSParams k of an AM_SPSS batch, before init_template: c = (255 k)^2; k <= 0 selects the shipped 0.01 (mtfhip_batch_set_spss)"""
+        L.check(L.lib().mtfhip_batch_set_spss(self._h, float(k)))
 
     def set_rscv(self, use_bspl=0, weighted_mapping=0, mapped_gradient=0):
         """RSCVParams use_bspl, weighted_mapping, mapped_gradient of an AM_RSCV batch, before init_template; the defaults are the

@@ -42,6 +42,7 @@ int mtfhip_am_update_model(mtfhip_batch *b, const double *pts, double learning_r
 	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: RSCV is not available on this entry point (the template update would have to refresh its code plane)");
 	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LSCV is not available on this entry point (the template update would have to refresh I0_orig)");
 	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LRSCV is not available on this entry point (the template update would have to refresh its code plane)");
+	TRY(spss_refuse(b, "updateModel", " has no online template update on the device path"));
 	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: appearance model %d", b->desc.am);
 	TRY(single_channel(b, "update_model"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "update_model before initializePixVals");
@@ -337,7 +338,7 @@ static int mi_grad(mtfhip_batch *b, int curr) {
 
 /* ------------------------------------------------------------------ AppearanceModel */
 static int am_supported(mtfhip_batch *b, const char *fn) {
-	if (ssd_like(b) || b->desc.am == MTFHIP_AM_NCC || b->desc.am == MTFHIP_AM_MI) return MTFHIP_OK;
+	if (ssd_like(b) || b->desc.am == MTFHIP_AM_NCC || b->desc.am == MTFHIP_AM_MI || spss_am(b)) return MTFHIP_OK;
 	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s :: appearance model %d is not available on the device path yet", fn, b->desc.am);
 }
 
@@ -356,6 +357,11 @@ int mtfhip_am_initialize_similarity(mtfhip_batch *b) {
 	}
 	if (b->init_sim) return MTFHIP_OK;
 	HIP_TRY(hipMemsetAsync(b->buf[MTFHIP_BUF_DF_DI0], 0, sizeof(double) * b->N * b->B, b->ctx->stream));
+	if (spss_am(b)) {   /* SPSS::initializeSimilarity SPSS.cc:94-100: It = I0, f_vec = 1, f = patch_size */
+		for (auto &h : b->th) h.f = (double)b->N;
+		b->init_sim = true;
+		return MTFHIP_OK;
+	}
 	for (auto &h : b->th) h.f = 0;
 	b->init_sim = true;
 	return MTFHIP_OK;
@@ -376,8 +382,8 @@ int mtfhip_am_initialize_grad(mtfhip_batch *b) {
 		b->init_grad = true;
 		return MTFHIP_OK;
 	}
-	if (b->desc.am == MTFHIP_AM_NCC) {
-		/* NCC::initializeGrad NCC.cc:97-122: gradient vectors start at zero */
+	if (b->desc.am == MTFHIP_AM_NCC || spss_am(b)) {
+		/* NCC::initializeGrad NCC.cc:97-122, SPSS::initializeGrad SPSS.cc:104-114: gradient vectors start at zero */
 		if (!b->init_grad) {
 			HIP_TRY(hipMemsetAsync(b->buf[MTFHIP_BUF_DF_DI0], 0, sizeof(double) * b->N * b->B, b->ctx->stream));
 			HIP_TRY(hipMemsetAsync(b->buf[MTFHIP_BUF_DF_DIT], 0, sizeof(double) * b->N * b->B, b->ctx->stream));
@@ -419,6 +425,7 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 		if (!prereq_only) TRY(mi_read_f(b));
 		return MTFHIP_OK;
 	}
+	if (spss_am(b)) return spss_update_similarity(b, prereq_only);
 	/* SCV::updateSimilarity (SCV.cc:194-230): the intensity map from It and I0_orig, I0 re-mapped, then SSDBase::updateSimilarity */
 	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 1, b->ctx->stream));
 	/* LSCV::updateSimilarity (LSCV.cc:263-304): unless once_per_frame and not the first iteration, the localized re-map of I0 */
@@ -438,6 +445,7 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 static int do_update_curr_grad(mtfhip_batch *b) {
 	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 1); stale_clear(b, false, true); return rc; }
 	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 1);
+	if (spss_am(b)) return spss_update_grad(b, 1);
 	if (b->lz.df0_stale) TRY(ensure_one(b, false));
 	TimedScope ts(b->ctx, "negate");
 	launch_negate(b->buf[MTFHIP_BUF_DF_DI0], b->buf[MTFHIP_BUF_DF_DIT], (size_t)b->N * b->B, b->ctx->stream);
@@ -467,6 +475,7 @@ int mtfhip_am_update_init_grad(mtfhip_batch *b) {
 	FLUSH(b);
 	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 0); stale_clear(b, true, false); return rc; }
 	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 0);
+	if (spss_am(b)) return spss_update_grad(b, 0);
 	return MTFHIP_OK;
 }
 int mtfhip_am_get_similarity(mtfhip_batch *b, double *f) {
@@ -482,7 +491,8 @@ int mtfhip_am_get_likelihood(mtfhip_batch *b, double *l) {
 	FLUSH_AM(b);
 	for (int t = 0; t < b->B; ++t) {
 		double f = b->th[t].f;
-		if (ssd_like(b)) l[t] = std::exp(-b->desc.likelihood_alpha * std::sqrt(-f / (double)b->N));
+		if (spss_am(b)) l[t] = std::exp(b->desc.likelihood_alpha * (f - (double)b->N));   /* SPSS::getLikelihood SPSS.cc:46-48 */
+		else if (ssd_like(b)) l[t] = std::exp(-b->desc.likelihood_alpha * std::sqrt(-f / (double)b->N));
 		else { double d = (1.0 / f) - 1; l[t] = std::exp(-b->desc.likelihood_alpha * d * d); }
 	}
 	return MTFHIP_OK;
@@ -874,6 +884,7 @@ int mtfhip_am_cmpt_init_hessian(mtfhip_batch *b, int j0_buf, double *H) {
 	TRY(j_ready(b, j0_buf, "cmptInitHessian"));
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, j0_buf, 0, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, j0_buf, 0, H);
+	if (spss_am(b)) return spss_hessian(b, j0_buf, SPSS_W_INIT, H);
 	return gram_to_host(b, j0_buf, H, -1.0, false);
 }
 int mtfhip_am_cmpt_curr_hessian(mtfhip_batch *b, int jt_buf, double *H) {
@@ -883,6 +894,7 @@ int mtfhip_am_cmpt_curr_hessian(mtfhip_batch *b, int jt_buf, double *H) {
 	TRY(j_ready(b, jt_buf, "cmptCurrHessian"));
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 1, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 1, H);
+	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_CURR, H);
 	return gram_to_host(b, jt_buf, H, -1.0, false);
 }
 int mtfhip_am_cmpt_self_hessian(mtfhip_batch *b, int jt_buf, double *H) {
@@ -892,6 +904,7 @@ int mtfhip_am_cmpt_self_hessian(mtfhip_batch *b, int jt_buf, double *H) {
 	TRY(j_ready(b, jt_buf, "cmptSelfHessian"));
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 2, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 2, H);
+	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_SELF, H);
 	return gram_to_host(b, jt_buf, H, -1.0, false);
 }
 int mtfhip_am_cmpt_sum_of_hessians(mtfhip_batch *b, int j0_buf, int jt_buf, double *H) {
@@ -904,6 +917,7 @@ int mtfhip_am_cmpt_sum_of_hessians(mtfhip_batch *b, int j0_buf, int jt_buf, doub
 		/* generic AppearanceModel::cmptSumOfHessians AppearanceModel.h:196-208 */
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
 		if (b->desc.am == MTFHIP_AM_NCC) { TRY(ncc_hessian(b, j0_buf, 0, H0.data())); TRY(ncc_hessian(b, jt_buf, 1, H)); }
+		else if (spss_am(b)) { TRY(spss_hessian(b, j0_buf, SPSS_W_INIT, H0.data())); TRY(spss_hessian(b, jt_buf, SPSS_W_CURR, H)); }
 		else { TRY(mi_hessian(b, j0_buf, 0, H0.data())); TRY(mi_hessian(b, jt_buf, 1, H)); }
 		for (size_t i = 0; i < H0.size(); ++i) H[i] += H0[i];
 		return MTFHIP_OK;
@@ -1052,6 +1066,7 @@ static int add_second_order(mtfhip_batch *b, int d2a, int d2b, const double *dev
 int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_init_hessian (second order)", 1));
+	TRY(spss_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_init_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_init_hessian(b, j0_buf, H));
@@ -1061,6 +1076,7 @@ int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double
 int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_curr_hessian (second order)", 1));
+	TRY(spss_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_curr_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_curr_hessian(b, jt_buf, H));
@@ -1070,6 +1086,7 @@ int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_self_hessian (second order)", 1));
+	TRY(spss_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_self_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_self_hessian (second order): NULL argument");
@@ -1087,6 +1104,7 @@ int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 int mtfhip_am_cmpt_sum_of_hessians2(mtfhip_batch *b, int j0_buf, int jt_buf, int d20_buf, int d2t_buf, double *H) {
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_sum_of_hessians (second order)", 1));
+	TRY(spss_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_sum_of_hessians (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_sum_of_hessians (second order): NULL argument");

@@ -75,6 +75,7 @@ int mtfhip_score_candidates_dev(mtfhip_batch *b, const double *dev_states, int C
 	FLUSH_AM(b);   /* (every candidate warps the template grid itself: CURR_PTS are not read) */
 	if (!b || !dev_states) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "score_candidates"));
+	TRY(spss_refuse(b, "score_candidates", " is not available on this entry point"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	TRY(refuse_intensity_mapped(b, "score_candidates", " candidates are not available"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "score_candidates before the template was initialised");
@@ -87,6 +88,7 @@ int mtfhip_score_candidates(mtfhip_batch *b, const double *states, int C, double
 	FLUSH(b);
 	if (!b || !states) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "score_candidates"));
+	TRY(spss_refuse(b, "score_candidates", " is not available on this entry point"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	size_t need = (size_t)C * (b->S + 2);
 	if (need > b->cand_capacity) {
@@ -109,6 +111,7 @@ int mtfhip_sample_candidates_dev(mtfhip_batch *b, const double *dev_states, int 
 	FLUSH(b);
 	if (!b || !dev_states || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "sample_candidates"));
+	TRY(spss_refuse(b, "sample_candidates", " is not available on this entry point"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: MI distance features (5 x N B-spline rows) are not available");
 	TRY(refuse_intensity_mapped(b, "sample_candidates", " distance features are not available"));
@@ -123,6 +126,7 @@ int mtfhip_sample_candidates(mtfhip_batch *b, const double *states, int C, doubl
 	FLUSH(b);
 	if (!b || !states || !features) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "sample_candidates"));
+	TRY(spss_refuse(b, "sample_candidates", " is not available on this entry point"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	double *d_states = nullptr, *d_feat = nullptr;
 	HIP_TRY(hipMalloc(&d_states, sizeof(double) * C * b->S));
@@ -149,6 +153,7 @@ int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *d
 	FLUSH(b);
 	if (!b || !d || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
 	TRY(lowdof_refuse(b, "nn_dataset"));
+	TRY(spss_refuse(b, "nn_dataset", " is not available on this entry point"));
 	TRY(refuse_intensity_mapped(b, "nn_dataset", " is not available on the NN dataset"));
 	if (d->n_samples <= 0 || row_lo < 0 || row_count < 0 || row_lo + row_count > d->n_samples)
 		return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: rows [%d, %d) of %d samples", row_lo, row_lo + row_count, d->n_samples);
@@ -190,6 +195,7 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 int mtfhip_nn_dataset(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *perturbations_in, double *perturbations_out, double *features) {
 	if (!b || !d || !features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
 	TRY(lowdof_refuse(b, "nn_dataset"));
+	TRY(spss_refuse(b, "nn_dataset", " is not available on this entry point"));
 	if (d->n_samples <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: n_samples must be positive");
 	int F = 0;
 	TRY(mtfhip_nn_feature_size(b, &F));

@@ -366,7 +366,9 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	/* the fused kernel addresses a target's arrays with 32-bit byte offsets (ld_off / st_off): 8 columns of N doubles */
 	if ((double)d->resx * d->resy * 3.0 >= (double)(1u << 26)) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: %dx%d sample points per target exceed the 2^26-row limit", d->resx, d->resy);
 	if (d->grad_eps <= 0 || d->hess_eps < 0) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: grad_eps must be positive (got %g)", d->grad_eps);
-	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_SPSS) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am == MTFHIP_AM_SPSS && d->n_channels == 3)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "SPSS with n_channels 3 (MCSPSS) is not available on the device path (single channel only)");
 	if (d->am == MTFHIP_AM_LRSCV && (d->mi_n_bins > kLscvMaxBins || d->mi_n_bins == 1))
 		return fail(MTFHIP_ERR_INVALID_ARG, "LRSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kLscvMaxBins);
 	if (d->am == MTFHIP_AM_LRSCV && d->n_channels == 3)
@@ -391,7 +393,7 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	/* Similitude / Isometry / Translation: SSD and NCC, single channel (mtfhip.h) -- refused here, before any kernel could read a six- or
 	 * eight-wide state of theirs */
 	if (ssm_lowdof(d->ssm) && d->am != MTFHIP_AM_SSD && d->am != MTFHIP_AM_NCC)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model is served with SSD and NCC only (MI and the SCV family are not available with it)", ssm_name(d->ssm));
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model is served with SSD and NCC only (MI, the SCV family and SPSS are not available with it)", ssm_name(d->ssm));
 	if (ssm_lowdof(d->ssm) && d->n_channels == 3)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model with n_channels 3 is not available (single channel only)", ssm_name(d->ssm));
 	HIP_TRY(hipSetDevice(c->device));

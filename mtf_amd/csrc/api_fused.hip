@@ -37,6 +37,15 @@ int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn) {
 		 * initialize / setRegion).  Eight bins (the weights are read from the 8-bin gradient-factor tables). */
 		return MTFHIP_OK;
 	}
+	if (spss_am(b)) {
+		/* SPSS: first-order Hessians; the pass fills ONE weighted Gram matrix per row (kernels_fused_spss.hip), and ESM's SumOfStd is the mean
+		 * of two with different weights and rows (cmptInitHessian(J0) + cmptCurrHessian(Jt), AppearanceModel.h:194-206) */
+		if (sm->sec_ord_hess) return spss_refuse(b, fn, " with second-order Hessians is not available on the device path (first-order only)");
+		if (sm->sm == MTFHIP_SM_ESM && sm->hess_type == 4)
+			return spss_refuse(b, fn, " with ESM hess_type SumOfStd needs two weighted Gram matrices in one pass and is not available on the fused entry points "
+				"(cmpt_sum_of_hessians serves it)");
+		return MTFHIP_OK;
+	}
 	TRY(scv_refuse(b, fn, sm->sec_ord_hess));   /* (SCV: SSD on the re-mapped template, first order) */
 	if (!ssd_like(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: unknown appearance model", fn);
 	return MTFHIP_OK;
@@ -98,6 +107,10 @@ static int init_self_hessian(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *
 		TRY(mtfhip_ssm_cmpt_pix_hessian(b, b->d0_variant, MTFHIP_BUF_D2I0_DX2, MTFHIP_BUF_DI0_DX, MTFHIP_BUF_D2I0_DP2));
 		return mtfhip_am_cmpt_self_hessian2(b, MTFHIP_BUF_J0, MTFHIP_BUF_D2I0_DP2, H0);
 	}
+	/* SPSS: the constant Hessian of InitialSelf is cmptSelfHessian at It = I0 (SPSS.cc:91-101, :221-225).  At initialize the It buffer holds I0;
+	 * a setRegion that refreshes H0 comes behind a loop whose last pass may or may not have materialised It, so the weight is taken from I0
+	 * itself: the same H0 whatever the loop wrote */
+	if (spss_am(b)) { FLUSH_AM(b); return spss_hessian(b, MTFHIP_BUF_J0, SPSS_W_SELF0, H0); }
 	return mtfhip_am_cmpt_self_hessian(b, MTFHIP_BUF_J0, H0);
 }
 /* A low-order SSM's template in affine coordinates (mtfhip_batch::lo_ssm), behind the interface's own N x S Jacobian: the affine rows of dI0_dx
@@ -352,6 +365,7 @@ int assemble_rows(mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, int
 	for (int t = 0; t < b->B; ++t) {
 		double ft, *gt = g + (size_t)t * b->S, *Ht = H + (size_t)t * S2;
 		if (ncc) TRY(ncc_assemble(b, sm, hess_mean, b->h_acc + (size_t)t * NCC_ACC_COUNT, b->th[t], &ft, gt, Ht));
+		else if (spss_am(b)) { spss_assemble(b, sm, b->h_acc + (size_t)t * ACC_COUNT, b->th[t].h0, &ft, gt, Ht); b->th[t].f = ft; }
 		else { assemble(b, sm, b->h_acc + (size_t)t * ACC_COUNT, b->th[t].h0, &ft, gt, Ht); b->th[t].f = ft; }
 		if (so) for (int k = 0; k < S2; ++k) Ht[k] += so_scale * so[(size_t)t * S2 + k];
 		if (f) f[t] = ft;
@@ -440,7 +454,8 @@ static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, do
 	int nblk = fused_blocks_per_target(b->N, b->B);
 	{
 		TimedScope ts(b->ctx, "fused_lk");
-		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream, &rm, &lm);
+		const SpssArgs sp = spss_am(b) ? spss_args(b, sm) : SpssArgs{};
+		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream, &rm, &lm, spss_am(b) ? &sp : nullptr);
 	}
 	b->it_valid = fa.materialize;
 	b->dit_valid = fa.materialize && fa.mode != 2;

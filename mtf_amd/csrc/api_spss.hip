@@ -1,0 +1,107 @@
+/*
+ * api_spss.hip -- the Sum of Pixelwise Structural Similarity appearance model's own state (AM/src/SPSS.cc): its parameter k, what a fused
+ * launch reads for a search method, the host-side assembly of a fused pass's row, and the per-function similarity, gradients and Hessians
+ * (C-ABI implementation, include/mtfhip.h; the kernels: kernels_spss.hip, kernels_fused_spss.hip; no CPU fallback: HIP kernels or an error)
+ */
+#include "mtfhip_api_internal.h"
+
+int spss_refuse(const mtfhip_batch *b, const char *fn, const char *what) {
+	if (!b || !spss_am(b)) return MTFHIP_OK;
+	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SPSS%s (served: the first-order per-function AppearanceModel entry points and init_template / set_region / "
+		"iterate / track / track_region with ESM, FCLK and ICLK)", fn, what);
+}
+
+/* the weight of the Gram matrix the pass accumulates and the row of its current Jacobian, by search method and Hessian type (NT/FCLK.cc:262-283,
+ * NT/ESM.cc:298-377, NT/ICLK.cc:204-252): the self types weight Jt by cmptSelfHessian's factor, the Std types by cmptCurrHessian's (ESM Original:
+ * over the mean row, FusedArgs::hess_mean) or, for ICLK, J0 by cmptInitHessian's; InitialSelf reads the constant H0 and ignores the sum */
+SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
+	SpssArgs sp;
+	sp.c = b->spss_c;
+	const int ht = sm->hess_type;
+	if (sm->sm == MTFHIP_SM_ICLK) sp.weight = ht == 2 ? SPSS_W_INIT : SPSS_W_SELF;
+	else if (sm->sm == MTFHIP_SM_FCLK) sp.weight = ht == 2 ? SPSS_W_CURR : SPSS_W_SELF;
+	else sp.weight = ht >= 3 ? SPSS_W_CURR : SPSS_W_SELF;
+	sp.g_mean = (sm->sm == MTFHIP_SM_ESM && sm->jac_type == 0) ? 1 : 0;
+	return sp;
+}
+
+/* one target's reduced SPSS row -> f, g and H of the search method before damping (the device twin: finish_track_body's SPSS) */
+void spss_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H) {
+	const int S = b->S;
+	if (f) *f = acc[ACC_RR];
+	for (int s = 0; s < S; ++s) {
+		if (sm->sm == MTFHIP_SM_ICLK) g[s] = acc[ACC_G2 + s];
+		else if (sm->sm == MTFHIP_SM_ESM && sm->jac_type != 0) g[s] = 0.5 * (acc[ACC_G + s] - acc[ACC_G2 + s]);
+		else g[s] = acc[ACC_G + s];
+	}
+	const bool use_h0 = sm->hess_type == 0;
+	const bool sum_h0 = sm->sm == MTFHIP_SM_ESM && sm->hess_type == 2;
+	int k = 0;
+	for (int a = 0; a < 8; ++a)
+		for (int c = a; c < 8; ++c) {
+			if (a < S && c < S) {
+				double v = use_h0 ? h0[c * S + a] : acc[ACC_H + k];
+				if (sum_h0) v = (v + h0[c * S + a]) * 0.5;
+				H[c * S + a] = v; H[a * S + c] = v;
+			}
+			++k;
+		}
+}
+
+int spss_update_similarity(mtfhip_batch *b, int prereq_only) {
+	/* (f_vec, f_vec_den and It_sqr are functions of I0 and It: every kernel that needs them recomputes them, so prereq_only has nothing to store) */
+	if (prereq_only) return MTFHIP_OK;
+	const int nblk = simple_blocks_per_target(b->N);
+	{
+		TimedScope ts(b->ctx, "spss_similarity");
+		launch_spss_similarity(b->view(), b->spss_c, b->d_partials, nblk, b->ctx->stream);
+	}
+	TRY(read_acc(b, nblk));
+	for (int t = 0; t < b->B; ++t) b->th[t].f = b->h_acc[(size_t)t * ACC_COUNT + ACC_RR];
+	return MTFHIP_OK;
+}
+int spss_update_grad(mtfhip_batch *b, int curr) {
+	TimedScope ts(b->ctx, "spss_grad");
+	launch_spss_grad(b->view(), b->spss_c, curr, b->buf[curr ? MTFHIP_BUF_DF_DIT : MTFHIP_BUF_DF_DI0], b->ctx->stream);
+	return MTFHIP_OK;
+}
+int spss_hessian(mtfhip_batch *b, int j_buf, int weight, double *H) {
+	const int nblk = simple_blocks_per_target(b->N), S = b->S;
+	{
+		TimedScope ts(b->ctx, "spss_hessian");
+		launch_spss_hessian(b->view(), b->spss_c, weight, b->buf[j_buf], b->d_partials, nblk, b->ctx->stream);
+	}
+	TRY(read_acc(b, nblk));
+	for (int t = 0; t < b->B; ++t) {
+		const double *src = b->h_acc + (size_t)t * ACC_COUNT + ACC_H;
+		double *Ht = H + (size_t)t * S * S;
+		int k = 0;
+		for (int a = 0; a < 8; ++a)
+			for (int c = a; c < 8; ++c) {
+				if (a < S && c < S) { Ht[c * S + a] = src[k]; Ht[a * S + c] = src[k]; }
+				++k;
+			}
+	}
+	return MTFHIP_OK;
+}
+
+extern "C" {
+
+int mtfhip_batch_set_spss(mtfhip_batch *b, double k) {
+	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "set_spss: NULL batch");
+	if (!spss_am(b)) return fail(MTFHIP_ERR_INVALID_ARG, "set_spss: the batch's appearance model is %d, not SPSS", b->desc.am);
+	if (b->init_pix_vals || b->init_sim)
+		return fail(MTFHIP_ERR_LOGIC, "set_spss: k is fixed once the template is initialised (call it before init_template / initialize_similarity)");
+	if (!std::isfinite(k)) return fail(MTFHIP_ERR_INVALID_ARG, "set_spss: k is not a finite number");
+	const double kk = k > 0 ? k : 0.01;
+	/* SPSS.cc:37-38: c = k (PIX_MAX - PIX_MIN); c *= c */
+	double c = kk * (255.0 - 0.0);
+	c *= c;
+	/* c keeps f_vec_den = I0^2 + It^2 + c away from zero on black pixels: a k whose c is not a normal number would divide by zero there */
+	if (!std::isnormal(c)) return fail(MTFHIP_ERR_INVALID_ARG, "set_spss: k = %g gives c = (255 k)^2 = %g, which is not a normal number", kk, c);
+	b->spss_k = kk;
+	b->spss_c = c;
+	return MTFHIP_OK;
+}
+
+} /* extern "C" */

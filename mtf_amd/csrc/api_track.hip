@@ -91,7 +91,8 @@ static int iclk_one_launch_max_pix() {
 bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	/* (SCV re-maps its template, RSCV rebuilds its map between the passes: they take the fused launch + finish per pass) */
 	/* (a low-order SSM takes the two-launch loop, whose finish projects the affine system: the one-launch kernels solve what they accumulate) */
-	return b->C == 1 && !b->lo_ssm && !intensity_mapped(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
+	/* (SPSS: the one-launch kernels accumulate SSD's or NCC's sums) */
+	return b->C == 1 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
 		b->N <= iclk_one_launch_max_pix();
 }
 
@@ -212,6 +213,7 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 	if (b->C != 1) return false;   /* (no multi-channel instantiation of the persistent kernel) */
 	if (b->lo_ssm) return false;   /* (the low-order SSMs are served by the two-launch loop only) */
 	if (intensity_mapped(b)) return false;   /* (the template re-map / the current map runs between the passes) */
+	if (spss_am(b)) return false;   /* (SPSS is served by the two-launch loop only: fused_select) */
 	if (b->B > 8) return false;   /* a batch is better served by its own decomposition (eight workgroups per target) */
 	if (sm->max_iters < 2) return false;
 	int nblk, rows;
@@ -454,7 +456,7 @@ static bool track_takes_step(const mtfhip_batch *b, const FusedArgs &fa, int so_
 	const char *e_st = std::getenv("MTFHIP_STEP");   /* (read per call: the tests flip it) */
 	const char *e_mx = std::getenv("MTFHIP_STEP_MAX_TARGETS");
 	const int max_t = e_mx ? std::atoi(e_mx) : 8;
-	return (e_st && e_st[0] == '1') && so_term < 0 && !b->lo_ssm && !intensity_mapped(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
+	return (e_st && e_st[0] == '1') && so_term < 0 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
 }
 /* one pass of one chunk on its queue: the intensity re-maps, the pixel pass (lean: the non-materialising one), the second-order pass, the finish */
 struct FinishCtl { PhaseCtl pc; HostPublish pub; int prio; };
@@ -476,7 +478,8 @@ static int track_chunk_pass(mtfhip_batch *b, const mtfhip_sm_desc *sm, const Fus
 	if (b->desc.am == MTFHIP_AM_LRSCV && (!b->lscv_once || it == 0)) TRY(lrscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &lm));
 	{
 		TimedScope tsc(b->ctx, "fused_lk", r.s);
-		launch_fused_ssd(r.bc, b->ctx->img, lean ? r.fl : r.fc, r.part, r.nblk_c, r.s, &rm, &lm);
+		const SpssArgs sp = spss_am(b) ? spss_args(b, sm) : SpssArgs{};
+		launch_fused_ssd(r.bc, b->ctx->img, lean ? r.fl : r.fc, r.part, r.nblk_c, r.s, &rm, &lm, spss_am(b) ? &sp : nullptr);
 	}
 	if (cx.so_term >= 0) {
 		TimedScope tsc(b->ctx, "second_order", r.s);
@@ -689,7 +692,7 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 		/* tolerance mode + a definite first-order system: the register-resident finish (finish_track_fast_body) */
 		const char *e = std::getenv("MTFHIP_FAST_FINISH");   /* (read per call: the tests compare the two bodies in one process) */
 		const bool enabled = !(e && e[0] == '0');
-		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && !ncc && !mi && cx.so_term < 0) ? 1 : 0;
+		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && !ncc && !mi && !spss_am(b) && cx.so_term < 0) ? 1 : 0;   /* (SPSS: k_finish_track_spss) */
 		/* a low-order SSM: the projection lives in finish_track_body alone (the register-resident body would index its rows at run time);
 		 * its materialising loop keeps every target's last warp for the Jacobian written behind the loop (track_core) */
 		if (b->lo_ssm) { ts.fast_finish = 0; ts.keep_last = (fa.materialize && fa.mode != 2) ? 1 : 0; ts.lo_ssm = b->lo_ssm; ts.SS = ssm_state_size(b->lo_ssm); }

@@ -2,7 +2,7 @@
  * kernels_fused.hip -- the fused Lucas-Kanade iteration (SSD and NCC) and the device-side solve + update
  * (one of the translation units of libmtfhip.so; conventions and the shared device helpers: mtfhip_device.h)
  */
-#include "mtfhip_finish_device.h"
+#include "mtfhip_finish_kernel.h"
 #include "mtfhip_fused_device.h"
 #include "mtfhip_grid_device.h"
 
@@ -23,55 +23,7 @@ __global__ __launch_bounds__(kBlock, MTFHIP_FAST_WAVES) void k_fused_fast(BatchV
 }
 
 
-/* stand-alone finish: one wave per target */
-/* pc (two-queue loop): the queues run best half a period apart -- one's fill / drain / solve under the other's streaming (48-49 us per
- * step of 64 x 200 x 200, the two pixel passes starting 23-25 us apart) -- but started together, or on some boxes by themselves, they
- * stay close to lockstep (55-56 us).  Each queue's solve stamps the wall clock when it ends, and ends no sooner than `frac` of its own
- * last period after the other queue's stamp: a queue that runs too close behind the other is held back until it is not. */
-/* ts.finish_prio: the waves of this launch raise their issue priority once, at entry (a kernel argument: a scalar branch around one
- * s_setprio, no per-segment flips) and drop it again in front of the phase spin, which sleeps.
- * pub.host (the chunked loop's fused delivery, api_track.hip): a target's wave hands the target's warp, state, corners and iteration count to
- * the host exactly once -- in the pass that stops it, or in the last pass the host enqueues (ts.last_pass) if it is still active then -- with
- * the hand-over of publish_target; the arrivals of all passes and both queues count to pub.B, the last one raises the host's flag.  pub_t0:
- * the launch's first target in the batch (bv and ts are the chunk's views). */
-template <bool LO>
-__device__ __forceinline__ void finish_track_kernel(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
-	const double *partials, int nblk, const PhaseCtl &pc, const HostPublish &pub, int pub_t0) {
-	if (ts.finish_prio) __builtin_amdgcn_s_setprio(3);
-	const int t = blockIdx.x;
-	__shared__ int s_stopped;
-	if (pub.host && threadIdx.x == 0) __hip_atomic_store(&s_stopped, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-	if constexpr (LO) finish_track_body<false, false, true>(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
-	else if (ts.fast_finish) finish_track_fast_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
-	else finish_track_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
-	if (pub.host && threadIdx.x < 64) {
-		/* the first wave alone: its lane 0 cleared and set the flag (1: active at entry, 3: stopped by this pass), and everything the bodies leave
-		 * for the host is stored by lanes of this wave -- the warp's entry q by lane q; the state by lane 0 (finish_track_body) or entry q by
-		 * lane q (the fast body); the corners' entries 2q and 2q + 1 by lane q < 4 (finish_track_body) or entry q by lane q; the iteration
-		 * count by lane 0.  Lane q reads entry q back, so some entries cross lanes: that is in order at wavefront scope (the stores are
-		 * issued before the loads of the same wave, to the same addresses), which is all this needs -- no barrier and no wait for the stores
-		 * on the passes that deliver nothing */
-		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-		const int ran = __hip_atomic_load(&s_stopped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-		if (ran == 3 || (ran && ts.last_pass)) {
-			const int lane = threadIdx.x;
-			const double wq = lane < 9 ? bv.warps[9 * t + lane] : 0.0, sq = lane < 8 ? bv.states[8 * t + lane] : 0.0, cq = lane < 8 ? ts.corners[8 * t + lane] : 0.0;
-			publish_target(pub, pub_t0 + t, wq, sq, cq, __hip_atomic_load(ts.n_iters + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT), pub.B);
-		}
-	}
-	if (ts.finish_prio) __builtin_amdgcn_s_setprio(0);
-	if (pc.mine && blockIdx.x == 0 && threadIdx.x == 0) {
-		const unsigned long long prev = ld_coh(pc.mine), other = ld_coh(pc.other);
-		unsigned long long now = wall_clock64();   /* 100 MHz */
-		if (prev && other && now > prev && now - prev < 50000ull) {   /* (a period of less than 500 us: the queue is in its stride) */
-			const unsigned long long min_lag = (unsigned long long)((double)(now - prev) * pc.frac);
-			while (now > other && now - other < min_lag) { __builtin_amdgcn_s_sleep(8); now = wall_clock64(); }
-		}
-		st_coh(pc.mine, now);
-	}
-}
-
-
+/* stand-alone finish: one wave per target (finish_track_kernel, mtfhip_finish_kernel.h) */
 __global__ __launch_bounds__(256) void k_finish_track(BatchView bv, mtfhip_sm_desc sm, TrackState ts,
 	const double *partials, int nblk, PhaseCtl pc, HostPublish pub, int pub_t0) {
 	finish_track_kernel<false>(bv, sm, ts, partials, nblk, pc, pub, pub_t0);
@@ -82,7 +34,6 @@ __global__ __launch_bounds__(256) void k_finish_track_lo(BatchView bv, mtfhip_sm
 	const double *partials, int nblk, PhaseCtl pc, HostPublish pub, int pub_t0) {
 	finish_track_kernel<true>(bv, sm, ts, partials, nblk, pc, pub, pub_t0);
 }
-
 
 /* MI device-side loop: g and H of the fused MI passes (mi_H = [B][64] H column-major | [B][16] unused here | [B][64] second H of
  * SumOfStd; gpart = the gradient pass's block rows [B][ng][16]) laid out as the reduced row the finish reads for SSD --
@@ -117,7 +68,7 @@ __global__ __launch_bounds__(64) void k_finish_track_mi(BatchView bv, mtfhip_sm_
 
 /* the unit's instantiations and the one of a launch: fused_select / fused_visit (mtfhip_fused_dispatch.h) */
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	hipStream_t st, const RscvMap *rm, const LrscvMap *lm) {
+	hipStream_t st, const RscvMap *rm, const LrscvMap *lm, const SpssArgs *sp) {
 	/* (the API enqueues pass 1 of RSCV / LRSCV in front and hands its maps over.  RSCV: no map, no launch; LRSCV without one -- a later
 	 * pass of a frame under once_per_frame -- is an SSD pass on the raw patch, LRSCV.cc:234-235) */
 	const bool mapped = bv.am == MTFHIP_AM_RSCV ? (rm && rm->map) : (bv.am == MTFHIP_AM_LRSCV && lm && lm->map);
@@ -125,6 +76,11 @@ void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &f
 	if (!k.served) return;
 	if (k.am == MTFHIP_AM_RSCV) { launch_fused_rscv(bv, im, fa, partials, nblk, *rm, st); return; }
 	if (k.am == MTFHIP_AM_LRSCV) { launch_fused_lrscv(bv, im, fa, partials, nblk, *lm, st); return; }
+	if (k.am == MTFHIP_AM_SPSS) {   /* (the API hands its constant and what the search method reads: a launch without them is an error) */
+		if (sp) launch_fused_spss(bv, im, fa, partials, nblk, *sp, st);
+		else note_launch_error(hipErrorInvalidValue, __FILE__, __LINE__);
+		return;
+	}
 	if (k.mc) { launch_fused_mc(bv, im, fa, partials, nblk, st); return; }   /* MCSSD / MCNCC */
 	const dim3 g = grid2(nblk, bv.B);
 	const bool launched = fused_visit<FusedUnit<FUSED_ROUTE_LOOP, false, MTFHIP_AM_SSD, MTFHIP_AM_NCC>>(k, [&](auto AM, auto SSM, auto CH, auto MD, auto MAT, auto FAST) {
@@ -143,7 +99,8 @@ void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const Tr
 	int nblk, hipStream_t st, PhaseCtl pc, const HostPublish &pub, int pub_t0) {
 	/* NCC rows are 72 wide: two waves load them, the first one solves; many block rows (a single large target): 240 lanes sum them */
 	const dim3 block(nblk > 8 ? 256 : (bv.am == MTFHIP_AM_NCC ? 128 : 64));
-	if (ts.lo_ssm) MTFHIP_LAUNCH(k_finish_track_lo, dim3(bv.B), block, 0, st, bv, sm, ts, partials, nblk, pc, pub, pub_t0);
+	if (bv.am == MTFHIP_AM_SPSS) launch_finish_track_spss(bv, sm, ts, partials, nblk, st, pc, pub, pub_t0, block);   /* (kernels_fused_spss.hip) */
+	else if (ts.lo_ssm) MTFHIP_LAUNCH(k_finish_track_lo, dim3(bv.B), block, 0, st, bv, sm, ts, partials, nblk, pc, pub, pub_t0);
 	else MTFHIP_LAUNCH(k_finish_track, dim3(bv.B), block, 0, st, bv, sm, ts, partials, nblk, pc, pub, pub_t0);
 }
 

@@ -293,6 +293,8 @@ struct mtfhip_batch {
 	int scv_hist = 0, scv_linear = 0, scv_mapped_grad = 0, scv_nb = 0;
 	double *d_scv_i0 = nullptr, *d_scv_part = nullptr, *d_scv_map = nullptr;
 	unsigned short *d_scv_code = nullptr;
+	/* SPSS (am = MTFHIP_AM_SPSS): SPSSParams k and c = (k (PIX_MAX - PIX_MIN))^2 (SPSS.cc:37-38) */
+	double spss_k = 0.01, spss_c = (0.01 * 255.0) * (0.01 * 255.0);
 	/* RSCV (am = MTFHIP_AM_RSCV): RSCVParams weighted_mapping, n_bins; the template's code plane ((int)I0), pass-1 rows and arrival
 	 * counters, the intensity maps, and It_orig of the per-function route (kernels_rscv.hip) */
 	int rscv_linear = 0, rscv_nb = 0;
@@ -549,6 +551,16 @@ static inline bool intensity_mapped(const mtfhip_batch *b) {
 static inline const char *intensity_mapped_name(const mtfhip_batch *b) {
 	return b->desc.am == MTFHIP_AM_SCV ? "SCV" : (b->desc.am == MTFHIP_AM_RSCV ? "RSCV" : (b->desc.am == MTFHIP_AM_LSCV ? "LSCV" : "LRSCV"));
 }
+/* SPSS: a model of its own -- no SSD branch serves it, and of the fused routes only the two-launch loop does (fused_select) */
+static inline bool spss_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SPSS; }
+/* api_spss.hip.  spss_refuse: "<fn>: SPSS<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for an SPSS batch, MTFHIP_OK otherwise; spss_args: what a fused
+ * launch for the search method sm reads beside FusedArgs; the per-function updateSimilarity, update*Grad and Hessians (weight: SPSS_W_*) */
+int spss_refuse(const mtfhip_batch *b, const char *fn, const char *what);
+mtfhip::SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
+int spss_update_similarity(mtfhip_batch *b, int prereq_only);
+int spss_update_grad(mtfhip_batch *b, int curr);
+int spss_hessian(mtfhip_batch *b, int j_buf, int weight, double *H);
+void spss_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H);
 /* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
 int scv_capture(mtfhip_batch *b);
 int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);

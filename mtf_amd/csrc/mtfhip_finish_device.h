@@ -42,7 +42,13 @@ __device__ unsigned long long g_fin_trace[16];
 /* LO (k_finish_track_lo, kernels_fused.hip): the finish of a low-order SSM's batch (TrackState::lo_ssm) -- the projection of the affine-coordinate
  * system and the model's own update.  A template parameter, not a run-time branch: the kernels of homography and affine batches are
  * compiled without any of it (the Isometry's cos / sin / atan2 alone would raise their register and scratch demand). */
-template <bool COH = false, bool ADDITIVE = false, bool LO = false>
+/* SPSS (k_finish_track_spss, kernels_fused_spss.hip): the reduced row is an SPSS pass's (kernels_fused_spss.hip) -- ACC_RR = f itself (a sum of scores
+ * that Levenberg-Marquardt maximises as it stands), ACC_H the WEIGHTED Gram matrix, i.e. the Hessian with its sign, ACC_G = sum df_dIt row
+ * and ACC_G2 = sum df_dI0 J0 row, from which the search method's Jacobian is cmptCurrJacobian (FCLK; ESM jac_type Original, over the mean
+ * row), cmptInitJacobian (ICLK) or half the difference (ESM DiffOfJacs, AppearanceModel.h:161-164, NT/ESM.cc:309).  ICLK's Std Hessian
+ * is not constant (cmptInitHessian weights J0 J0^T by a function of It, SPSS.cc:160-165) and comes from the row; the curr / init weights
+ * change sign, so every non-self system is solved with pivoting. */
+template <bool COH = false, bool ADDITIVE = false, bool LO = false, bool SPSS = false>
 __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
 	const double *partials, int nblk, int t, int *stop_flag = nullptr) {
 	auto LD = [](const double *p) -> double { if constexpr (COH) return ld_coh(p); else return *p; };
@@ -145,7 +151,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	int lm_iter_id = n_it_prev;   /* (LM keeps its own counter) */
 	bool undo = false;
 	if (lmp) {
-		const double f_now = ts.f_ext ? LD(ts.f_ext + t) : (ncc ? 0.0 : -acc_s[ACC_RR] / 2);
+		const double f_now = ts.f_ext ? LD(ts.f_ext + t) : (ncc ? 0.0 : (SPSS ? acc_s[ACC_RR] : -acc_s[ACC_RR] / 2));
 		const double prev_f = LD(lmp + 0);
 		lm_delta = LD(lmp + 1);
 		const bool state_reset = LD(lmp + 2) != 0.0;
@@ -168,7 +174,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 			else { ST(lmp + 2, 0.0); if (!state_reset) ST(lmp + 0, f_use); }
 		}
 	}
-	const bool use_h0 = (sm.hess_type == 0) || (sm.sm == MTFHIP_SM_ICLK && !ts.h_from_acc);
+	const bool use_h0 = (sm.hess_type == 0) || (!SPSS && sm.sm == MTFHIP_SM_ICLK && !ts.h_from_acc);
 	const bool sum_h0 = (sm.sm == MTFHIP_SM_ESM) && (sm.hess_type == 2 || (sm.hess_type == 4 && !ts.h_from_acc));   /* (MI's SumOfStd arrives summed) */
 	const double gscale = (sm.sm == MTFHIP_SM_ESM) ? 0.5 : 1.0;
 	/* NCC from its moments (ncc_assemble in api_ncc_moments.hip is the host twin; formulas and citations there) */
@@ -208,7 +214,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		}
 		/* (the constant Hessian as entry (r, c), not from a triangle: MI's initial self Hessian with its second-order part is not
 		 * symmetric in the homography's last two rows / columns; every other one is, and reads the same numbers) */
-		double v = use_h0 ? h0s[c * S + r] : -acc_s[ACC_H + kk];
+		double v = use_h0 ? h0s[c * S + r] : (SPSS ? acc_s[ACC_H + kk] : -acc_s[ACC_H + kk]);
 		if (sum_h0) v = (v + h0s[c * S + r]) * 0.5;
 		/* sec_ord_hess: + sum_p df_dI[p] d2I_dp2[:, p] (SSDBase.cc:313-415); the homography blocks are not symmetric in their
 		 * last two rows / columns (Homography.cc:421,613,796), so the entry is taken as (r, c), not from a triangle */
@@ -216,6 +222,11 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		return v;
 	};
 	auto g_entry = [&](int s) -> double {
+		if constexpr (SPSS) {
+			if (sm.sm == MTFHIP_SM_ICLK) return acc_s[ACC_G2 + s];
+			if (sm.sm == MTFHIP_SM_ESM && sm.jac_type != 0) return 0.5 * (acc_s[ACC_G + s] - acc_s[ACC_G2 + s]);
+			return acc_s[ACC_G + s];
+		}
 		if (!ncc) return gscale * acc_s[ACC_G + s];
 		auto cj = [&](int which) { return n_u0(which, s) - n_f * n_ut(which, s); };
 		auto ij = [&](int which) { return (n_b / n_c) * (n_ut(which, s) - n_f * n_u0(which, s)); };
@@ -232,7 +243,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	 * a flat template's zero pivot leaves its unknown at zero), but NCC's Std / SumOfStd and MI's Hessians can be indefinite away
 	 * from convergence, where the reference's colPivHouseholderQr (NT/FCLK.cc:298) does not care either.  (A row-per-lane
 	 * elimination in registers with v_readlane broadcasts was measured slower than this LDS form: 8.9 k against 6.9 k clocks.) */
-	const bool pivoting = ncc || ts.h_from_acc || ts.h_extra != nullptr;   /* (the search and the row swap are two barriers and eight LDS reads per step: skipped for SSD) */
+	const bool pivoting = SPSS || ncc || ts.h_from_acc || ts.h_extra != nullptr;   /* (the search and the row swap are two barriers and eight LDS reads per step: skipped for SSD) */
 	/* The low-order SSMs: J_S = J_aff M with M constant, 6 x SS, at most two +-1 entries per column (Translation.h:45-63,
 	 * Isometry.cc:115-135,162-185, Similitude.cc:163-210) --
 	 *   Translation [Ja0, Ja1]    Isometry [Ja0, Ja1, Ja4 - Ja3]    Similitude [Ja0, Ja1, Ja2 + Ja5, Ja4 - Ja3]
@@ -284,7 +295,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 			trec[8 * i + j] = (i < SS && j < SS) ? hij : 0.0;
 			if (j == 0) trec[64 + i] = gi;
 			if (lane == 0) {
-				trec[88] = ts.f_ext ? LD(ts.f_ext + t) : (ncc ? n_f : -acc_s[ACC_RR] / 2);
+				trec[88] = ts.f_ext ? LD(ts.f_ext + t) : (ncc ? n_f : (SPSS ? acc_s[ACC_RR] : -acc_s[ACC_RR] / 2));
 				trec[90] = undo ? 1.0 : 0.0; trec[91] = lm_delta; trec[92] = 1.0;
 			}
 		}

@@ -149,14 +149,37 @@ __device__ __forceinline__ double lrscv_blend(const double *m, const LrscvMap &l
 /* AM = MTFHIP_AM_LRSCV (kernels_fused_lrscv.hip): RSCV's structure with the localized blend.  The prologue copies the target's maps (at
  * most 64 KB less the kernel's static arrays, launch_fused_lrscv) into the dynamic LDS; every sample It_orig is replaced by
  * lrscv_blend right after it is taken, reading the pixel's weights from the batch's [R][N] table. */
+/* AM = MTFHIP_AM_SPSS (kernels_fused_spss.hip): the row's outer product enters the Hessian with the pixel's weight w -- acc[ACC_H ..] +=
+ * w rw rw^T, upper triangle; w rw[a] is formed once per a (8 products more than the plain Gram matrix) */
+template <int S>
+__device__ __forceinline__ void spss_gram(double *acc, double w, const double *rw) {
+	int k = 0;
+#pragma unroll
+	for (int a = 0; a < 8; ++a) {
+		const double wa = a < S ? w * rw[a] : 0.0;
+#pragma unroll
+		for (int b = a; b < 8; ++b) {
+			if (a < S && b < S) acc[k] = fma(wa, rw[b], acc[k]);
+			++k;
+		}
+	}
+}
 /* COHROW: the workgroup's partial row leaves as write-through stores (the persistent loop, and the one-launch-per-pass kernel of
  * kernels_step.hip whose last-arriving workgroup reads every row in the same launch) */
-template <int AM, int SSM, bool CHAINED, int MODE, bool MAT, bool FAST = false, bool PERSIST = false, bool MC = false, bool COHROW = PERSIST>
+/* X: the arguments of a model beyond the maps -- one SpssArgs for AM = MTFHIP_AM_SPSS (deduced from the call), none otherwise: the other
+ * models' instantiations keep the signature they had */
+__device__ __forceinline__ const SpssArgs *spss_args_ptr() { return nullptr; }
+__device__ __forceinline__ const SpssArgs *spss_args_ptr(const SpssArgs &a) { return &a; }
+template <int AM, int SSM, bool CHAINED, int MODE, bool MAT, bool FAST = false, bool PERSIST = false, bool MC = false, bool COHROW = PERSIST,
+	class... X>
 __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	const RscvMap &rm = RscvMap{}, const LrscvMap &lm = LrscvMap{}) {
+	const RscvMap &rm = RscvMap{}, const LrscvMap &lm = LrscvMap{}, const X &...x) {
 	constexpr int S = (SSM == MTFHIP_SSM_HOMOGRAPHY) ? 8 : 6;
 	constexpr bool NCC = AM == MTFHIP_AM_NCC;
-	constexpr int K = NCC ? NCC_ACC_COUNT : 48;
+	constexpr bool SPSS = AM == MTFHIP_AM_SPSS;
+	[[maybe_unused]] auto spx = [&]() -> const SpssArgs & { return *spss_args_ptr(x...); };
+	static_assert(sizeof...(X) == (SPSS ? 1 : 0), "SPSS takes its SpssArgs, the other models nothing more");
+	constexpr int K = NCC ? NCC_ACC_COUNT : (SPSS ? (int)ACC_COUNT : 48);   /* (SPSS fills the second gemv, ACC_G2, as well) */
 	constexpr int ROW_LEN = NCC ? NCC_ACC_COUNT : ACC_COUNT;
 	__shared__ double lds[4 * K];
 	/* NCC + ESM carries 71 accumulators (142 VGPRs) and every instantiation of it sat at the 256-register limit with reloads inside the
@@ -259,6 +282,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 	static_assert(!(RSCV && (GR_OK || NCC || PERSIST || MC || COHROW)), "RSCV: single channel, one launch per pass, no grid rebuild");
 	constexpr bool LRSCV = AM == MTFHIP_AM_LRSCV;
 	static_assert(!(LRSCV && (GR_OK || NCC || PERSIST || MC || COHROW)), "LRSCV: single channel, one launch per pass, no grid rebuild");
+	static_assert(!(SPSS && (GR_OK || PERSIST || MC || COHROW)), "SPSS: single channel, one launch per pass, no grid rebuild");
 	/* (uniform per workgroup; every thread of the workgroup gets here, nothing before it returns) */
 	auto fill_map = [&]() {
 		if constexpr (RSCV) {
@@ -496,7 +520,37 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 		if constexpr (RSCV) it = rscv_map_val(reinterpret_cast<const double *>(grid_tab), rm.nb, rm.linear, it);
 		if constexpr (LRSCV) it = lrscv_blend(reinterpret_cast<const double *>(grid_tab), lm, lm.wts + i, N, it);
 		const double r = it - cur.i0;
-		if constexpr (NCC) {
+		/* SPSS: the pixel's score f_vec, the two gradient entries and the weight of its outer product in the Hessian the search method asked
+		 * for (SpssArgs::weight), SPSS.cc:116-225 with a = I0, b = It.  Replay: the reference's expressions and IEEE divisions in its order;
+		 * FAST: one refined reciprocal of f_vec_den (and one of 2 It^2 + c for the self weight), reused */
+		double s_dt = 0.0, s_d0 = 0.0, s_w = 0.0;
+		if constexpr (SPSS) {
+			const double a = cur.i0, b = it, c = spx().c;
+			const double a2 = a * a, b2 = b * b;
+			const double den = (a2 + b2) + c;
+			double fv;
+			if constexpr (FAST) {
+				const double rden = rcp_fast(den);
+				fv = fma(2 * a, b, c) * rden;
+				if constexpr (MODE != 2) s_dt = 2 * fma(-fv, b, a) * rden;
+				if (MODE != 0 || spx().weight == SPSS_W_INIT) s_d0 = 2 * fma(b, b2 - a2, c * (b - 2 * a)) * (rden * rden);
+				if (spx().weight == SPSS_W_SELF) s_w = -2 * rcp_fast(fma(2.0, b2, c));
+				else if (spx().weight == SPSS_W_CURR) s_w = -2 * fma(3 * s_dt, b, fv) * rden;
+				else s_w = -2 * fma(a, s_d0, fv) * rden;
+			} else {
+				fv = (2 * a * b + c) / den;
+				if constexpr (MODE != 2) s_dt = 2 * (a - fv * b) / den;
+				if (MODE != 0 || spx().weight == SPSS_W_INIT) s_d0 = 2 * (b * (b2 - a2) + c * (b - 2 * a)) / (den * den);
+				if (spx().weight == SPSS_W_SELF) s_w = -2 / (2 * b2 + c);
+				else if (spx().weight == SPSS_W_CURR) s_w = -2 * (fv + 3 * s_dt * b) / den;
+				else s_w = -2 * (fv + a * s_d0) / den;
+			}
+			acc[ACC_RR] += fv;
+			if constexpr (MAT) {   /* df_dIt / df_dI0 beside It, where the search method updates them (NT/FCLK.cc:220, NT/ESM.cc:247-251, NT/ICLK.cc:197) */
+				if constexpr (MODE != 2) st_off<double>(bv.buf[MTFHIP_BUF_DF_DIT] + (size_t)t * N, o8, s_dt);
+				if constexpr (MODE != 0) st_off<double>(bv.buf[MTFHIP_BUF_DF_DI0] + (size_t)t * N, o8, s_d0);
+			}
+		} else if constexpr (NCC) {
 			acc[NCC_IT] += it; acc[NCC_IT2] = fma(it, it, acc[NCC_IT2]); acc[NCC_I0IT] = fma(cur.i0, it, acc[NCC_I0IT]);
 		} else {
 			acc[44] = fma(r, r, acc[44]);
@@ -529,8 +583,10 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 				for (int s = 0; s < S; ++s) {
 					if constexpr (PARK_ITJ0) park_add(8 + s, it * r0[s]);
 					else if constexpr (NCC) acc[NCC_ITJ0 + s] = fma(it, r0[s], acc[NCC_ITJ0 + s]);
+					else if constexpr (SPSS) acc[ACC_G2 + s] = fma(s_d0, r0[s], acc[ACC_G2 + s]);
 					else acc[36 + s] = fma(MODE == 1 ? -r : r, r0[s], acc[36 + s]);
 				}
+				if constexpr (SPSS && MODE == 2) { if (spx().weight == SPSS_W_INIT) spss_gram<S>(acc, s_w, r0); }   /* cmptInitHessian(J0), NT/ICLK.cc Std */
 			}
 			if constexpr (MODE != 2) {
 				double Ix, Iy;
@@ -554,6 +610,10 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 						acc[NCC_ITJ + s] = fma(it, row[s], acc[NCC_ITJ + s]);
 						if constexpr (PARK_I0J) park_add(s, cur.i0 * row[s]);
 						else acc[NCC_I0J + s] = fma(cur.i0, row[s], acc[NCC_I0J + s]);
+					} else if constexpr (SPSS) {
+						/* cmptCurrJacobian over Jt, or over the mean Jacobian (ESM jac_type Original) */
+						if constexpr (MODE == 1) acc[ACC_G + s] = fma(s_dt, spx().g_mean ? 0.5 * (r0[s] + row[s]) : row[s], acc[ACC_G + s]);
+						else acc[ACC_G + s] = fma(s_dt, row[s], acc[ACC_G + s]);
 					} else {
 						acc[36 + s] = fma(-r, row[s], acc[36 + s]);
 					}
@@ -567,6 +627,8 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 						}
 					}
 				}
+				if constexpr (SPSS) spss_gram<S>(acc, s_w, row);
+				else {
 				int k = 0;
 #pragma unroll
 				for (int a = 0; a < 8; ++a)
@@ -575,6 +637,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 						if (a < S && b < S) acc[k] = fma(row[a], row[b], acc[k]);
 						++k;
 					}
+				}
 			}
 			return;
 		}
@@ -670,6 +733,27 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 					for (int s = 0; s < S; ++s) row[s] = (r0[s] + row[s]) / 2.0;
 				}
 			}
+		} else if constexpr (SPSS) {
+			if constexpr (MODE == 1) {
+				/* cmptCurrJacobian over the mean Jacobian (jac_type Original, NT/ESM.cc:304) or over Jt; mean_pix_jacobian as NT/ESM.cc:239 forms it */
+#pragma unroll
+				for (int s = 0; s < S; ++s) acc[ACC_G + s] = fma(s_dt, spx().g_mean ? (r0[s] + row[s]) / 2.0 : row[s], acc[ACC_G + s]);
+			} else if constexpr (MODE == 0) {
+#pragma unroll
+				for (int s = 0; s < S; ++s) acc[ACC_G + s] = fma(s_dt, row[s], acc[ACC_G + s]);
+			}
+			if constexpr (MODE != 0) {
+#pragma unroll
+				for (int s = 0; s < S; ++s) acc[ACC_G2 + s] = fma(s_d0, r0[s], acc[ACC_G2 + s]);
+			}
+			if constexpr (MODE == 1) {
+				if (fa.hess_mean) {
+#pragma unroll
+					for (int s = 0; s < S; ++s) row[s] = (r0[s] + row[s]) / 2.0;
+				}
+			}
+			if constexpr (MODE == 2) { if (spx().weight == SPSS_W_INIT) spss_gram<S>(acc, s_w, r0); }   /* cmptInitHessian(J0), NT/ICLK.cc Std */
+			else spss_gram<S>(acc, s_w, row);
 		} else if constexpr (MODE == 0) {
 			const double v = -r;
 #pragma unroll
@@ -686,7 +770,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 #pragma unroll
 			for (int s = 0; s < S; ++s) acc[36 + s] = fma(r, r0[s], acc[36 + s]);
 		}
-		if constexpr (MODE != 2) {
+		if constexpr (MODE != 2 && !SPSS) {
 #ifndef MTFHIP_EXPERIMENT_NOACC
 			int k = 0;
 #pragma unroll

@@ -5,7 +5,7 @@
  *
  * fused_select() is the one place that knows how the runtime choice -- appearance model, channels, state-space model, search method's
  * mode, chained warp, materialising or lean, replay or tolerance arithmetic -- becomes the key {AM, SSM, CHAINED, MODE, MAT, FAST} of a
- * kernel, and which choices each of the three routes serves.  The six translation units that instantiate fused_lk_body keep their
+ * kernel, and which choices each of the three routes serves.  The seven translation units that instantiate fused_lk_body keep their
  * __global__ wrappers and call fused_visit() with a generic lambda that names the wrapper; rscv_it_kind, grid_regen_kernel and
  * track_step_available are read off the same key.  A new appearance model adds its line to fused_select() and a unit with its wrappers.
  */
@@ -31,7 +31,7 @@ enum { RSCV_IT_REPLAY = 0, RSCV_IT_FAST_ICLK = 1, RSCV_IT_FAST_CHAINED = 2, RSCV
 /* the template arguments of one instantiation; mc: the multi-channel body (MC = true, kernels_fused_mc.hip); served = false: the route
  * has no kernel for the input, and the other fields say nothing */
 struct FusedKey {
-	int am, ssm, mode;     /* MTFHIP_AM_SSD / _NCC / _RSCV / _LRSCV ; MTFHIP_SSM_* ; 0 FCLK, 1 ESM, 2 ICLK */
+	int am, ssm, mode;     /* MTFHIP_AM_SSD / _NCC / _RSCV / _LRSCV / _SPSS ; MTFHIP_SSM_* ; 0 FCLK, 1 ESM, 2 ICLK */
 	bool chained, mat, fast, mc, served;
 };
 constexpr bool operator==(const FusedKey &a, const FusedKey &b) {
@@ -52,6 +52,8 @@ constexpr FusedKey fused_select(int route, int am, int channels, int ssm, int mo
 	case MTFHIP_AM_NCC: k.am = MTFHIP_AM_NCC; break;
 	case MTFHIP_AM_RSCV: if (!mapped) return k; k.am = MTFHIP_AM_RSCV; break;
 	case MTFHIP_AM_LRSCV: k.am = mapped ? MTFHIP_AM_LRSCV : MTFHIP_AM_SSD; break;
+	/* SPSS (kernels_fused_spss.hip): single channel, the two-launch loop only (`plain` below keeps it off the one-launch routes) */
+	case MTFHIP_AM_SPSS: if (channels != 1) return k; k.am = MTFHIP_AM_SPSS; break;
 	default: return k;
 	}
 	/* the mapping kernels take every row as a pixel of one plane; MCSSD / MCNCC are SSD / NCC with the multi-channel body */

@@ -331,6 +331,16 @@ struct LrscvMap {
 	int nb = 0, R = 0, affine = 0, linear = 0;
 };
 
+/* SPSS (am = MTFHIP_AM_SPSS): what the fused pass needs beside FusedArgs, an extra argument behind the fused kernels' own -- c = (255 k)^2
+ * (SPSS.cc:37-38); weight: the per-pixel weight of the Gram matrix in ACC_H (SPSS_W_*: cmptSelfHessian SPSS.cc:221-225, cmptCurrHessian
+ * :191-196, cmptInitHessian :160-165), taken over Jt (FCLK, ESM), Jm (ESM with FusedArgs::hess_mean) or J0 (ICLK); g_mean: ACC_G is
+ * sum df_dIt Jm (ESM jac_type Original, NT/ESM.cc:246-249) instead of sum df_dIt Jt */
+enum { SPSS_W_SELF = 0, SPSS_W_CURR = 1, SPSS_W_INIT = 2, SPSS_W_SELF0 = 3 };   /* SELF0 (per-function kernel only): the self weight at It = I0 */
+struct SpssArgs {
+	double c = 6.5025;
+	int weight = SPSS_W_SELF, g_mean = 0;
+};
+
 /* one-time probe: does the kernel-argument segment hold (BatchView, ImgView, FusedArgs) where fused_lk_body's inline-warp path reads them? */
 bool kernarg_layout_verified(hipStream_t st);
 void launch_queue_delay(double microseconds, hipStream_t st);
@@ -510,7 +520,17 @@ void launch_publish_host(const void *src, void *dst_host, size_t bytes, int *cou
 /* the fused LK iteration for SSD (and RSCV: bv.am == MTFHIP_AM_RSCV takes the RSCV instantiations, which need rm; LRSCV: with lm and its
  * maps the LRSCV instantiations, without them -- a later pass of a frame under once_per_frame -- the SSD ones on the raw patch) */
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials,
-	int nblk, hipStream_t st, const RscvMap *rm = nullptr, const LrscvMap *lm = nullptr);
+	int nblk, hipStream_t st, const RscvMap *rm = nullptr, const LrscvMap *lm = nullptr, const SpssArgs *sp = nullptr);
+/* kernels_fused_spss.hip: the SPSS instantiations of the fused body (replay and tolerance mode); and the finish that reads their rows,
+ * k_finish_track_spss (launch_finish_track takes it for bv.am == MTFHIP_AM_SPSS) */
+void launch_fused_spss(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const SpssArgs &sp,
+	hipStream_t st);
+/* kernels_spss.hip, the per-function entry points (SPSS.cc:116-225): f_vec summed into ACC_RR of the block rows (updateSimilarity); df_dIt
+ * (curr = 1, updateCurrGrad) or df_dI0 (updateInitGrad) into `out`; the weighted Gram matrix sum w J J^T of a pixel Jacobian into ACC_H,
+ * w = SPSS_W_* with df_dIt / df_dI0 read from their buffers as the reference reads its members */
+void launch_spss_similarity(const BatchView &bv, double c, double *partials, int nblk, hipStream_t st);
+void launch_spss_grad(const BatchView &bv, double c, int curr, double *out, hipStream_t st);
+void launch_spss_hessian(const BatchView &bv, double c, int weight, const double *J, double *partials, int nblk, hipStream_t st);
 /* kernels_fused_lrscv.hip: the LRSCV instantiations of the fused body (replay and tolerance mode) */
 void launch_fused_lrscv(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const LrscvMap &lm,
 	hipStream_t st);
@@ -628,6 +648,9 @@ void launch_finish_track(const BatchView &bv, const mtfhip_sm_desc &sm, const Tr
  * (every pointer may be NULL) */
 struct LoopWords { int *zero_i; int n_zero_i; unsigned long long *phase; double *lm; int n_lm; double lm_delta_init; int *count; };
 void launch_track_prologue(const void *src_host, void *dst, size_t bytes, size_t skip_off, size_t skip_len, const LoopWords &lw, hipStream_t st);
+/* kernels_fused_spss.hip: the finish over an SPSS pass's rows (launch_finish_track hands it bv.am == MTFHIP_AM_SPSS with its own block size) */
+void launch_finish_track_spss(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials, int nblk,
+	hipStream_t st, PhaseCtl pc, const HostPublish &pub, int pub_t0, dim3 block);
 
 /* ---- the additive search methods nt::FALK / nt::IALK (kernels_alk.hip) ---- */
 struct AlkArgs {

@@ -52,6 +52,7 @@ struct HipPair {
 		bool weighted_mapping);                                                /* mtfhip_batch_set_lscv (am = MTFHIP_AM_LSCV) */
 	void setLRSCV(int sub_regions_x, int sub_regions_y, int spacing_x, int spacing_y, bool affine_mapping, bool once_per_frame,
 		bool weighted_mapping);                                                /* mtfhip_batch_set_lrscv (am = MTFHIP_AM_LRSCV) */
+	void setSPSS(double k);                                                    /* mtfhip_batch_set_spss (am = MTFHIP_AM_SPSS) */
 	int hessianBuffer(const MatrixXd &D, bool may_register);
 };
 
@@ -91,6 +92,11 @@ struct HipLRSCVParams {
 	bool affine_mapping = false; bool once_per_frame = false; int n_bins = 256; double pre_seed = 0;
 	bool weighted_mapping = false; bool show_subregions = false; bool debug_mode = false;
 };
+/* SPSSParams (AM/include/mtf/AM/SPSS.h), the reference's field names; k: the shipped spss_k (Config/modules.cfg), c = (255 k)^2.  A
+ * pix_mapper (an ImageBase the pixel values are taken through) is not available on the device path: SPSS reads the raw samples. */
+struct HipSPSSParams {
+	double k = 0.01;
+};
 struct HipLink {
 	int am = MTFHIP_AM_SSD, ssm = MTFHIP_SSM_HOMOGRAPHY, resx = 50, resy = 50;   /* AMParams / SSMParams: resx, resy */
 	double grad_eps = 1e-8, likelihood_alpha = 1.0;                           /* AMParams::grad_eps; SSDParams / NCCParams / MIParams::likelihood_alpha */
@@ -99,6 +105,7 @@ struct HipLink {
 	HipRSCVParams rscv;                                                        /* am = MTFHIP_AM_RSCV ("rscv") */
 	HipLSCVParams lscv;                                                        /* am = MTFHIP_AM_LSCV ("lscv") */
 	HipLRSCVParams lrscv;                                                      /* am = MTFHIP_AM_LRSCV ("lrscv", "lrsc") */
+	HipSPSSParams spss;                                                        /* am = MTFHIP_AM_SPSS ("spss") */
 	int device = 0; void *stream = nullptr;
 	std::shared_ptr<HipPair> pair(int n_channels = 1) {
 		if (!p && am == MTFHIP_AM_SCV) {
@@ -120,6 +127,10 @@ struct HipLink {
 			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, lrscv.n_bins, lrscv.pre_seed, 0, device, stream, n_channels);
 			p->setLRSCV(lrscv.sub_regions_x, lrscv.sub_regions_y, lrscv.spacing_x, lrscv.spacing_y, lrscv.affine_mapping, lrscv.once_per_frame,
 				lrscv.weighted_mapping);
+		}
+		if (!p && am == MTFHIP_AM_SPSS) {
+			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, 0, 0.0, 0, device, stream, n_channels);
+			p->setSPSS(spss.k);
 		}
 		if (!p) p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, device, stream, n_channels);
 		else if (n_channels > 1 && n_channels != p->n_channels)   /* (SearchMethod<AM, SSM> constructs the AM first: it fixes the channel count) */
@@ -227,6 +238,32 @@ private:
 	const double *ptsArg(const PtsT &pts) const;
 	const double *gradPtsArg(const GradPtsT &pts) const;
 	static void colMajorToHost(MatrixXd &H, const double *src, int S);
+};
+
+/* The reference's names for the SPSS model (AM/include/mtf/AM/SPSS.h): SPSSParams {k} -- with the HipLink every device parameter block
+ * carries in place of the AMParams base -- and class SPSS with its ParamType, params and c = (k (PIX_MAX - PIX_MIN))^2 (SPSS.cc:37-38).  A caller that
+ * wrote `SPSS(&spss_params)` constructs this one: the HipAM of an MTFHIP_AM_SPSS pair whose k is the block's.  No pix_mapper (not available on
+ * the device path). */
+struct SPSSParams : HipAMParams {
+	double k = 0.01;
+	SPSSParams() = default;
+	SPSSParams(std::shared_ptr<HipLink> link_, double k_) : k(k_) { link = link_; }
+};
+class SPSS : public HipAM {
+public:
+	typedef SPSSParams ParamType;
+	explicit SPSS(const ParamType *spss_params, int _n_channels = 1) : HipAM(linked(spss_params), _n_channels), params(*spss_params),
+		c((params.k > 0 ? params.k : 0.01) * 255.0 * ((params.k > 0 ? params.k : 0.01) * 255.0)) {}
+	const ParamType params;
+	const double c;
+private:
+	/* the link's appearance model and k are the block's, set before the pair is created (a pair that exists keeps what it was created with) */
+	static const HipAMParams *linked(const ParamType *sp) {
+		if (!sp || !sp->link) throw utils::InvalidArgument("SPSS :: the parameter block carries no HipLink (the AM and the SSM of a tracker share one)");
+		sp->link->am = MTFHIP_AM_SPSS;
+		sp->link->spss.k = sp->k;
+		return sp;
+	}
 };
 
 class HipSSM : public StateSpaceModel {

@@ -195,6 +195,21 @@ def hess_border_points(h, w, n=272):
     return np.stack([np.resize(np.array(xs), n), np.resize(np.array(ys), n)])
 
 
+def dp_ulp_sensitivity(oracle, rec):
+    """How far the reference's own update moves when every entry of its own H and g moves by one ulp (eight seeded sign patterns, the
+    largest relative change of colpiv_qr_solve's dp): the least any other order of the same sums can do to it.  (The sums themselves move
+    by more than one ulp under a reordering -- about sqrt(N) -- so this under-states the reference's order sensitivity and the bound built
+    on it is the stricter one.)"""
+    H, g = rec["H"], rec["g"]
+    worst = 0.0
+    for seed in range(8):
+        rng = np.random.default_rng(seed)
+        Hp = H * (1.0 + rng.choice([-1.0, 1.0], size=H.shape) * 2.0 ** -52)
+        gp = g * (1.0 + rng.choice([-1.0, 1.0], size=g.shape) * 2.0 ** -52)
+        worst = max(worst, rel(-oracle.colpiv_qr_solve(Hp, gp), rec["dp"]))
+    return worst
+
+
 def long_double_solve(A, b):
     """A x = b by Gaussian elimination with complete pivoting in numpy.longdouble (the extended-precision yardstick the device's and the
     reference's solves are both measured against); None where a pivot vanishes"""

@@ -24,6 +24,7 @@ from mtf_amd import _lib as L
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import lk_seam_cases as K   # noqa: E402
+from lk_seam_cases import dp_ulp_sensitivity as _dp_ulp_sensitivity   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -61,21 +62,6 @@ def _check(f, g, H, rec, am, tol_f, tol_H, tol_g, what):
     assert eH < tol_H, what
     assert eg < tol_g, what
     return dict(f=ef, H=eH, g=eg)
-
-
-def _dp_ulp_sensitivity(oracle, rec):
-    """How far the reference's own update moves when every entry of its own H and g moves by one ulp (eight seeded sign patterns, the
-    largest relative change of colpiv_qr_solve's dp): the least any other order of the same sums can do to it.  (The sums themselves move
-    by more than one ulp under a reordering -- about sqrt(N) -- so this under-states the reference's order sensitivity and the bound built
-    on it is the stricter one.)"""
-    H, g = rec["H"], rec["g"]
-    worst = 0.0
-    for seed in range(8):
-        rng = np.random.default_rng(seed)
-        Hp = H * (1.0 + rng.choice([-1.0, 1.0], size=H.shape) * 2.0 ** -52)
-        gp = g * (1.0 + rng.choice([-1.0, 1.0], size=g.shape) * 2.0 ** -52)
-        worst = max(worst, K.rel(-oracle.colpiv_qr_solve(Hp, gp), rec["dp"]))
-    return worst
 
 
 # ================================================================================================ Part A

@@ -793,6 +793,39 @@ int mtfhip_ssm_estimate_from_pts_dev(mtfhip_ctx *ctx, int ssm, const mtfhip_est_
 	const int *host_n_pts, int max_pts, const float *dev_in_pts, const float *dev_out_pts, int *dev_subsets, int subsets_given, int n_hyp,
 	unsigned long long seed, double *dev_state_update, unsigned char *dev_mask, int *dev_info, double *dev_stats);
 
+/* ---- am.estimateOpticalFlow: the translation-only NCC flow of GridTrackerFlow (AM/src/NCC.cc:412-526) ---- */
+enum { MTFHIP_FLOW_MAX_WIN = 1024 };        /* samples of a search window, win_w * win_h */
+enum { MTFHIP_FLOW_TRACE_STRIDE = 8 };      /* doubles per (point, pass) of the trace */
+enum { MTFHIP_FLOW_NONFINITE = 0, MTFHIP_FLOW_CONVERGED = 1, MTFHIP_FLOW_MAX_ITERS = 2 };   /* status */
+typedef struct mtfhip_flow_desc {
+	int win_w, win_h;     /* search_window_x / _y (GridTrackerFlowParams.h:6-17: 10 x 10); each >= 2, win_w * win_h <= MTFHIP_FLOW_MAX_WIN */
+	int max_iters;        /* default 30 */
+	double epsilon;       /* term_eps: a point stops after the pass whose squared step is below it; default 0.01 */
+	int const_grad;       /* use_const_grad: the gradient is taken from the previous image once instead of from the current one per pass */
+	double grad_eps;      /* step of the central differences, the AM's grad_eps: 1e-8 */
+	int math_mode;        /* MTFHIP_MATH_REPLAY / MTFHIP_MATH_FAST */
+} mtfhip_flow_desc;
+/* NCC::estimateOpticalFlow for n_pts points in ONE launch (a workgroup per point): the win_w x win_h lattice of a point -- LinSpaced over
+ * [x - w / 2, x + w / 2], step w / (w - 1) -- is sampled from the context's PREVIOUS image (mtfhip_image_keep_prev) for the template and,
+ * per pass, from the CURRENT image; raw pixel values (no norm_mult / norm_add), bilinear with the constant border 128.  A pass solves the
+ * 2 x 2 Gauss-Newton system of the NCC, adds the step to the point in float32 and to every lattice coordinate in double, and stops the
+ * point once the squared step is below epsilon (after the update) or after max_iters passes.
+ *   prev_pts / curr_pts: n_pts x 2 floats (cv::Point2f); n_iters[p]: passes run; status[p]: MTFHIP_FLOW_*.
+ *   A non-finite step (a window that is flat in either image: the reference goes on with NaN coordinates, which is undefined behaviour) stops
+ *   the point at that pass: curr_pts[p] = NaN, status 0.  A non-finite prev_pts[p] likewise, with n_iters 0.
+ * Errors, all before any launch: no previous image MTFHIP_ERR_LOGIC; previous and current image of different shapes, win_w or win_h < 2,
+ * n_pts <= 0, max_iters <= 0, an unknown math_mode, NULL arguments MTFHIP_ERR_INVALID_ARG; a multi-channel image (the reference serves
+ * CV_32FC1 only, NCC.cc:416-420) and windows of more than MTFHIP_FLOW_MAX_WIN samples MTFHIP_ERR_NOT_IMPLEMENTED. */
+int mtfhip_ncc_estimate_optical_flow(mtfhip_ctx *ctx, const mtfhip_flow_desc *desc, int n_pts, const float *prev_pts, float *curr_pts,
+	int *n_iters, int *status);
+/* the same on device pointers, only enqueued on the context's stream (no copy, no synchronisation) */
+int mtfhip_ncc_estimate_optical_flow_dev(mtfhip_ctx *ctx, const mtfhip_flow_desc *desc, int n_pts, const float *dev_prev_pts,
+	float *dev_curr_pts, int *dev_n_iters, int *dev_status);
+/* the debugging form: also trace[n_pts][trace_cap][MTFHIP_FLOW_TRACE_STRIDE] (host), per point and pass opt_flow[2], f, df_dx[2],
+ * d2f_dx2 (0,0), (0,1), (1,1); passes a point did not run are zero.  trace_cap >= max_iters. */
+int mtfhip_ncc_estimate_optical_flow_trace(mtfhip_ctx *ctx, const mtfhip_flow_desc *desc, int n_pts, const float *prev_pts, float *curr_pts,
+	int *n_iters, int *status, double *trace, int trace_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,22 @@ def est_n_hyp(p):
     return 1
 
 
+class FlowDesc(C.Structure):
+    """mtfhip_flow_desc: NCC::estimateOpticalFlow's arguments (AM/src/NCC.cc:412-414; defaults GridTrackerFlowParams.h:6-17)"""
+    _fields_ = [("win_w", C.c_int), ("win_h", C.c_int), ("max_iters", C.c_int), ("epsilon", C.c_double), ("const_grad", C.c_int),
+                ("grad_eps", C.c_double), ("math_mode", C.c_int)]
+
+
+FLOW_MAX_WIN, FLOW_TRACE_STRIDE = 1024, 8
+FLOW_NONFINITE, FLOW_CONVERGED, FLOW_MAX_ITERS = 0, 1, 2
+
+
+def flow_desc(win=(10, 10), max_iters=30, epsilon=0.01, const_grad=False, grad_eps=1e-8, math=MATH_FAST):
+    """win: (width, height) of the search window, or one number for both"""
+    w, h = (win, win) if isinstance(win, int) else (win[0], win[1])
+    return FlowDesc(int(w), int(h), int(max_iters), float(epsilon), int(bool(const_grad)), float(grad_eps), int(math))
+
+
 class NnDesc(C.Structure):
     """mtfhip_nn_desc: NN::generateDataset's parameters (SM/src/NT/NN.cc:56-84, 131-191)"""
     _fields_ = [("n_samples", C.c_int), ("additive_update", C.c_int), ("sigma", C.c_double * 8), ("mean", C.c_double * 8), ("seed", C.c_ulonglong)]
@@ -180,6 +196,7 @@ SYMBOLS = [
     "mtfhip_nn_get_dataset_dev", "mtfhip_nn_search", "mtfhip_nn_search_dev", "mtfhip_nn_update",
     "mtfhip_nn_gnn_build", "mtfhip_nn_gnn_get_graph", "mtfhip_nn_gnn_set_graph", "mtfhip_nn_gnn_search", "mtfhip_nn_gnn_search_dev",
     "mtfhip_nn_set_index", "mtfhip_nn_gnn_set_start", "mtfhip_nn_gnn_get_start", "mtfhip_nn_gnn_last_walks",
+    "mtfhip_ncc_estimate_optical_flow", "mtfhip_ncc_estimate_optical_flow_dev", "mtfhip_ncc_estimate_optical_flow_trace",
 ]
 
 
@@ -296,6 +313,9 @@ def lib():
         L.mtfhip_nn_set_index.argtypes = [C.c_void_p, C.c_int]
         L.mtfhip_nn_gnn_set_start.argtypes = [C.c_void_p, C.c_int]
         L.mtfhip_nn_gnn_get_start.argtypes = [C.c_void_p, C.c_void_p]
+        for fn in ("mtfhip_ncc_estimate_optical_flow", "mtfhip_ncc_estimate_optical_flow_dev"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.mtfhip_ncc_estimate_optical_flow_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         _lib = L
     return _lib
 

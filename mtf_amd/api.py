@@ -209,6 +209,26 @@ class Context:
                          float(stats[s, 0]), float(stats[s, 1]), used[s].copy() if used is not None else None) for s in range(S)]
         return res[0] if single else res
 
+    def estimate_optical_flow(self, prev_pts, win=(10, 10), max_iters=30, epsilon=0.01, const_grad=False, math=L.MATH_FAST, grad_eps=1e-8,
+                              trace=False):
+        """am.estimateOpticalFlow of NCC (AM/src/NCC.cc:412-526) on the device (mtfhip_ncc_estimate_optical_flow): the translation-only NCC
+        flow of every point of prev_pts (n, 2) from the context's previous image (keep_prev) to the current one, on a win = (width, height)
+        lattice, all points in one launch.  Returns curr_pts (n, 2) float32, n_iters (n,), status (n,): 1 stopped by epsilon, 2 ran
+        max_iters, 0 a non-finite step (curr_pts NaN).  trace=True: also (n, max_iters, 8) per pass opt_flow[2], f, df_dx[2],
+        d2f_dx2 (0,0), (0,1), (1,1), zero for the passes a point did not run."""
+        d = L.flow_desc(win, max_iters, epsilon, const_grad, grad_eps, math)
+        pp = np.ascontiguousarray(np.asarray(prev_pts, dtype=np.float32).reshape(-1, 2))
+        n = len(pp)
+        cp = np.zeros((n, 2), dtype=np.float32)
+        ni, st = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        if not trace:
+            L.check(L.lib().mtfhip_ncc_estimate_optical_flow(self._h, C.byref(d), n, _p(pp), _p(cp), _p(ni), _p(st)))
+            return cp, ni, st
+        cap = max(int(max_iters), 1)
+        tr = np.zeros((max(n, 1), cap, L.FLOW_TRACE_STRIDE))
+        L.check(L.lib().mtfhip_ncc_estimate_optical_flow_trace(self._h, C.byref(d), n, _p(pp), _p(cp), _p(ni), _p(st), _p(tr), cap))
+        return cp, ni, st, tr[:n]
+
     def timing(self, on=True):
         """on: False/0 off, True/1 every launch, n > 1 every n-th launch of a kernel family"""
         L.check(L.lib().mtfhip_timing_enable(self._h, int(on)))

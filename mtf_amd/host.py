@@ -74,6 +74,13 @@ def lib():
         H.mtfhost_grid_call.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         H.mtfhost_grid_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         H.mtfhost_grid_set_est_params.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_ulonglong]
+        H.mtfhost_grid_flow_create.restype = C.c_void_p
+        H.mtfhost_grid_flow_create.argtypes = [C.c_int] * 5 + [C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]
+        H.mtfhost_grid_flow_destroy.argtypes = [C.c_void_p]
+        H.mtfhost_grid_flow_set_estimator.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        H.mtfhost_grid_flow_call.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        H.mtfhost_grid_flow_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        H.mtfhost_grid_flow_set_est_params.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_ulonglong]
         H.mtfhost_nn_create.restype = C.c_void_p
         H.mtfhost_nn_create.argtypes = [C.c_int] * 6 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
         H.mtfhost_nn_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -483,6 +490,109 @@ class CppGridTracker:
         fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         _check(fn(self._h, int(what), int(n_frames), c.ctypes.data_as(C.c_void_p), C.byref(us)))
         return us.value
+
+
+def am_optical_flow(am, frame0, frame1, prev_pts, win=(10, 10), max_iters=30, epsilon=0.01, const_grad=False, math=_lib.MATH_FAST, device=0):
+    """HipAM::estimateOpticalFlow of appearance model `am` from frame0 (kept as the previous image) to frame1 -> curr_pts, n_iters, status;
+    every model but NCC raises HostError (FunctonNotImplemented)"""
+    assert all(f.dtype == np.float32 and f.flags["C_CONTIGUOUS"] and f.ndim == 2 for f in (frame0, frame1)) and frame0.shape == frame1.shape
+    pp = np.ascontiguousarray(np.asarray(prev_pts, dtype=np.float32).reshape(-1, 2))
+    n = len(pp)
+    cp, ni, st = np.zeros((n, 2), dtype=np.float32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    fn = lib().mtfhost_am_optical_flow
+    fn.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
+    _check(fn(int(am), int(device), frame0.ctypes.data_as(C.c_void_p), frame1.ctypes.data_as(C.c_void_p), frame0.shape[0], frame0.shape[1], frame0.shape[1],
+              int(win[0]), int(win[1]), int(max_iters), float(epsilon), int(bool(const_grad)), int(math), n, pp.ctypes.data_as(C.c_void_p),
+              cp.ctypes.data_as(C.c_void_p), ni.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p)))
+    return cp, ni, st
+
+
+class CppGridTrackerFlow:
+    """mtf::hip::GridFlow (mtf_amd/host/DeviceGridFlow.h): nt::GridTrackerFlow with the reference's parameter block -- the grid's points
+    tracked by the device optical flow (NCC::estimateOpticalFlow), the grid SSM fitted to them.  estimator(prev_pts (n, 2), curr_pts (n, 2))
+    -> state update replaces the built-in least-squares fit; est_params (_lib.est_params(...)) selects the device estimator instead."""
+
+    def __init__(self, grid_size=10, search_window=10, max_iters=30, epsilon=0.01, use_const_grad=0, pyramid_levels=0, min_eig_thresh=1e-4,
+                 grid_ssm=_lib.SSM_HOMOGRAPHY, estimator=None, est_params=None, est_seed=1, grid_size_y=None, search_window_y=None,
+                 math=_lib.MATH_FAST, device=0):
+        _refuse_low_order("CppGridTrackerFlow", grid_ssm)
+        gy, wy = grid_size_y or grid_size, search_window_y or search_window
+        h = lib().mtfhost_grid_flow_create(grid_size, gy, search_window, wy, max_iters, float(epsilon), int(bool(use_const_grad)), int(pyramid_levels),
+                                           float(min_eig_thresh), grid_ssm, int(math), device)
+        if not h:
+            raise HostError(lib().mtfhost_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+        self.n, self.S = grid_size * gy, _lib.ssm_state_size(grid_ssm)
+        self._img, self._cb = None, None
+        if est_params is not None:
+            p = est_params
+            _check(lib().mtfhost_grid_flow_set_est_params(self._h, p.method, p.ransac_reproj_thresh, p.n_model_pts, p.refine, p.max_iters,
+                                                          p.max_subset_attempts, p.confidence, p.lm_max_iters, int(est_seed)))
+        elif estimator is not None:
+            S = self.S
+
+            def cb(_user, cnt, prev, curr, out):
+                a = np.ctypeslib.as_array(prev, shape=(cnt, 2)).astype(np.float64)
+                b = np.ctypeslib.as_array(curr, shape=(cnt, 2)).astype(np.float64)
+                upd = np.asarray(estimator(a, b), dtype=np.float64)
+                for i in range(S):
+                    out[i] = upd[i]
+            self._cb = _GRID_EST(cb)
+            _check(lib().mtfhost_grid_flow_set_estimator(self._h, C.cast(self._cb, C.c_void_p), None))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and not sys.is_finalizing():
+            lib().mtfhost_grid_flow_destroy(self._h)
+            self._h = None
+
+    def set_image(self, img):
+        assert img.dtype == np.float32 and img.flags["C_CONTIGUOUS"] and img.ndim == 2
+        self._img = img
+        _check(lib().mtfhost_grid_flow_call(self._h, 0, None, img.ctypes.data_as(C.c_void_p), img.shape[0], img.shape[1], img.shape[1]))
+
+    def _corners_call(self, what, corners):
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float64).reshape(2, 4).T.ravel())
+        _check(lib().mtfhost_grid_flow_call(self._h, what, c.ctypes.data_as(C.c_void_p), None, 0, 0, 0))
+
+    def initialize(self, corners):
+        self._corners_call(1, corners)
+
+    def set_region(self, corners):
+        self._corners_call(3, corners)
+
+    def update(self):
+        _check(lib().mtfhost_grid_flow_call(self._h, 2, None, None, 0, 0, 0))
+        return self.get_region()
+
+    def _get(self, what, size):
+        out = np.empty(size)
+        _check(lib().mtfhost_grid_flow_get(self._h, what, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def get_region(self):
+        return self._get(0, 8).reshape(4, 2).T.copy()
+
+    def prev_pts(self):
+        return self._get(1, 2 * self.n).reshape(self.n, 2).astype(np.float32)
+
+    def curr_pts(self):
+        return self._get(2, 2 * self.n).reshape(self.n, 2).astype(np.float32)
+
+    def ssm_update(self):
+        return self._get(3, self.S)
+
+    def n_iters(self):
+        return self._get(4, self.n).astype(np.int32)
+
+    def status(self):
+        return self._get(5, self.n).astype(np.int32)
+
+    def pix_mask(self):
+        return self._get(6, self.n).astype(np.uint8)
+
+    @property
+    def est_ok(self):
+        return bool(self._get(7, 1)[0])
 
 
 GridTracker = CppGridTracker   # mtf::hip::Grid under the name the Python driver (sm.GridTracker) uses

@@ -123,6 +123,7 @@ private:
 	std::vector<GridPt> est_in, est_out;
 	void estimate(const std::vector<GridPt> &in_pts, const std::vector<GridPt> &out_pts);
 	void resetTrackers(bool reinit);
+	friend class GridFlow;   /* (DeviceGridFlow.h: the same default fit) */
 	static void leastSquaresFit(int ssm, VectorXd &state_update, const std::vector<GridPt> &in_pts, const std::vector<GridPt> &out_pts);
 };
 

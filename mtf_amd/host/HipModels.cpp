@@ -194,6 +194,17 @@ void HipAM::updateDistFeat(double *feat_addr) {
 void HipAM::updateModel(const PtsT &pts) {
 	HipPair::check(mtfhip_am_update_model(p->b, ptsArg(pts), learning_rate));
 }
+void HipAM::keepPrevImg() { HipPair::check(mtfhip_image_keep_prev(p->ctx)); }
+void HipAM::estimateOpticalFlow(std::vector<EstPt> &curr_pts, const std::vector<EstPt> &prev_pts, int win_w, int win_h, unsigned int n_pts, int max_iters,
+	double term_eps, bool const_grad, int math_mode, std::vector<int> *n_iters, std::vector<int> *status) const {
+	if (p->am != MTFHIP_AM_NCC) throw utils::FunctonNotImplemented("estimateOpticalFlow :: Not implemented Yet");   /* AppearanceModel.h:221-226 */
+	if (curr_pts.size() != n_pts || prev_pts.size() != n_pts) throw utils::InvalidArgument("NCC::estimateOpticalFlow :: curr_pts and prev_pts must hold n_pts points");
+	const mtfhip_flow_desc fd{win_w, win_h, max_iters, term_eps, const_grad ? 1 : 0, p->grad_eps, math_mode};
+	std::vector<int> it(n_pts), st(n_pts);
+	HipPair::check(mtfhip_ncc_estimate_optical_flow(p->ctx, &fd, (int)n_pts, n_pts ? &prev_pts[0].x : nullptr, n_pts ? &curr_pts[0].x : nullptr, it.data(), st.data()));
+	if (n_iters) *n_iters = it;
+	if (status) *status = st;
+}
 
 void HipAM::cmptInitJacobian(RowVectorXd &g, const MatrixXd &J0) {
 	HipPair::check(mtfhip_am_cmpt_init_jacobian(p->b, p->jacobianBuffer(J0, false), g.data()));

@@ -191,6 +191,13 @@ public:
 	 * Config/parameters.h:200), outside [0, 1] = running average */
 	void updateModel(const PtsT &curr_pts) override;
 	void setLearningRate(double lr) { learning_rate = lr; }
+	/* NCC::estimateOpticalFlow (AM/src/NCC.cc:412-526; AppearanceModel.h:221-226 throws FunctonNotImplemented for every other model, and so
+	 * does this): the translation-only NCC flow of prev_pts on a win_w x win_h lattice, all points in one launch (mtfhip_ncc_estimate_optical_flow).
+	 * prev_img is not an argument: it is the frame keepPrevImg() kept on the device (prev_img = curr_img.clone() without the copy).
+	 * A point whose step is not finite comes back as NaN; n_iters / status (may be NULL): passes run and MTFHIP_FLOW_* per point. */
+	void estimateOpticalFlow(std::vector<EstPt> &curr_pts, const std::vector<EstPt> &prev_pts, int win_w, int win_h, unsigned int n_pts, int max_iters,
+		double term_eps, bool const_grad, int math_mode = MTFHIP_MATH_FAST, std::vector<int> *n_iters = nullptr, std::vector<int> *status = nullptr) const;
+	void keepPrevImg();
 	/* NN / FLANN distance feature of the patch at the SSM's current state: SSD = the pixel values (SSDBase.h:116-125), NCC =
 	 * centred and normalised (NCC.cc:530-537); computed on the device (mtfhip_sample_candidates), MI has none here */
 	void initializeDistFeat() override { dist_feat.resize((int)p->N); }

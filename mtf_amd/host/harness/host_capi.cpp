@@ -15,6 +15,7 @@
 #include "../DevicePF.h"
 #include "../DeviceNN.h"
 #include "../DeviceGrid.h"
+#include "../DeviceGridFlow.h"
 #include "SearchMethods.h"
 #include "PF.h"
 #include "TemplatedSM.h"
@@ -462,6 +463,101 @@ int mtfhost_grid_get(mtfhost_grid *h, int what, double *dst) {
 		return 0;
 	} catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
+}
+
+/* ---- mtf::hip::GridFlow (DeviceGridFlow.h): nt::GridTrackerFlow, the optical-flow grid tracker ---- */
+struct mtfhost_grid_flow { std::unique_ptr<hip::GridFlow> g; };
+extern "C" {
+mtfhost_grid_flow *mtfhost_grid_flow_create(int grid_size_x, int grid_size_y, int search_window_x, int search_window_y, int max_iters, double epsilon,
+	int use_const_grad, int pyramid_levels, double min_eig_thresh, int grid_ssm, int math_mode, int device) {
+	try {
+		GridTrackerFlowParams gp;
+		gp.grid_size_x = grid_size_x; gp.grid_size_y = grid_size_y; gp.search_window_x = search_window_x; gp.search_window_y = search_window_y;
+		gp.max_iters = max_iters; gp.epsilon = epsilon; gp.use_const_grad = use_const_grad != 0; gp.pyramid_levels = pyramid_levels; gp.min_eig_thresh = min_eig_thresh;
+		std::unique_ptr<mtfhost_grid_flow> h(new mtfhost_grid_flow());
+		h->g.reset(new hip::GridFlow(gp, grid_ssm, math_mode, device));
+		return h.release();
+	} catch (const utils::Exception &e) { g_err = std::string(e.type()) + ": " + e.what(); return nullptr; }
+	catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+void mtfhost_grid_flow_destroy(mtfhost_grid_flow *h) { delete h; }
+int mtfhost_grid_flow_set_estimator(mtfhost_grid_flow *h, mtfhost_grid_estimator est, void *user) {
+	if (!h) { g_err = "NULL grid"; return -1; }
+	if (!est) return 0;
+	h->g->setEstimator([est, user](VectorXd &u, const std::vector<GridPt> &a, const std::vector<GridPt> &c) {
+		std::vector<float> fa(2 * a.size()), fc(2 * c.size());
+		for (size_t i = 0; i < a.size(); ++i) { fa[2 * i] = a[i].x; fa[2 * i + 1] = a[i].y; fc[2 * i] = c[i].x; fc[2 * i + 1] = c[i].y; }
+		est(user, (int)a.size(), fa.data(), fc.data(), u.data());
+	});
+	return 0;
+}
+int mtfhost_grid_flow_set_est_params(mtfhost_grid_flow *h, int method, double ransac_reproj_thresh, int n_model_pts, int refine, int max_iters,
+	int max_subset_attempts, double confidence, int lm_max_iters, unsigned long long seed) {
+	try {
+		if (!h) { g_err = "NULL grid"; return -1; }
+		if (method < 0 || method > 2) { g_err = "Invalid estimation method specified"; return -1; }
+		const SSMEstimatorParams ep(static_cast<SSMEstimatorParams::EstType>(method), ransac_reproj_thresh, n_model_pts, refine != 0, max_iters, max_subset_attempts,
+			false, confidence, lm_max_iters);
+		h->g->setEstimatorParams(ep, seed);
+		return 0;
+	} catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+/* what: 0 setImage(img) 1 initialize(corners) 2 update() 3 setRegion(corners) */
+int mtfhost_grid_flow_call(mtfhost_grid_flow *h, int what, const double *corners, const float *img, int rows, int cols, int step) {
+	try {
+		CornersT c;
+		if (corners) std::memcpy(c.data(), corners, sizeof(double) * 8);
+		switch (what) {
+		case 0: h->g->setImage(ImageView{img, rows, cols, step}); break;
+		case 1: h->g->initialize(c); break;
+		case 2: h->g->update(); break;
+		case 3: h->g->setRegion(c); break;
+		default: g_err = "mtfhost_grid_flow_call: unknown selector"; return -1;
+		}
+		return 0;
+	} catch (const utils::Exception &e) { g_err = std::string(e.type()) + ": " + e.what(); return -1; }
+	catch (const std::exception &e) { g_err = e.what(); return -2; }
+}
+/* what: 0 region (8) 1 prev_pts (n x 2) 2 curr_pts (n x 2) 3 ssm_update (S) 4 passes per point (n) 5 status per point (n) 6 pix_mask (n) 7 estimator ok (1) */
+int mtfhost_grid_flow_get(mtfhost_grid_flow *h, int what, double *dst) {
+	try {
+		hip::GridFlow &g = *h->g;
+		switch (what) {
+		case 0: std::memcpy(dst, g.getRegion().data(), sizeof(double) * 8); break;
+		case 1: for (size_t i = 0; i < g.getPrevPts().size(); ++i) { dst[2 * i] = g.getPrevPts()[i].x; dst[2 * i + 1] = g.getPrevPts()[i].y; } break;
+		case 2: for (size_t i = 0; i < g.getCurrPts().size(); ++i) { dst[2 * i] = g.getCurrPts()[i].x; dst[2 * i + 1] = g.getCurrPts()[i].y; } break;
+		case 3: std::memcpy(dst, g.getSSMUpdate().data(), sizeof(double) * g.getSSMUpdate().size()); break;
+		case 4: for (size_t i = 0; i < g.getIters().size(); ++i) dst[i] = g.getIters()[i]; break;
+		case 5: for (size_t i = 0; i < g.getStatus().size(); ++i) dst[i] = g.getStatus()[i]; break;
+		case 6: for (size_t i = 0; i < g.getPixMask().size(); ++i) dst[i] = g.getPixMask()[i]; break;
+		case 7: dst[0] = g.estimatorOk() ? 1 : 0; break;
+		default: g_err = "mtfhost_grid_flow_get: unknown selector"; return -1;
+		}
+		return 0;
+	} catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+}
+
+/* HipAM::estimateOpticalFlow (NCC.cc:412-526) of appearance model `am`: setCurrImg(frame0), keepPrevImg(), setCurrImg(frame1), the flow of n_pts points.
+ * Every model but NCC throws FunctonNotImplemented (-1, the type in the message). */
+extern "C" int mtfhost_am_optical_flow(int am, int device, const float *frame0, const float *frame1, int rows, int cols, int step, int win_w, int win_h,
+	int max_iters, double epsilon, int const_grad, int math_mode, int n_pts, const float *prev_pts, float *curr_pts, int *n_iters, int *status) {
+	try {
+		auto link = std::make_shared<hip::HipLink>();
+		link->am = am; link->ssm = MTFHIP_SSM_HOMOGRAPHY; link->resx = 10; link->resy = 10; link->device = device;
+		hip::HipAM::ParamType amp; amp.link = link;
+		hip::HipAM a(&amp);
+		a.setCurrImg(ImageView{frame0, rows, cols, step});
+		a.keepPrevImg();
+		a.setCurrImg(ImageView{frame1, rows, cols, step});
+		std::vector<EstPt> pp(n_pts), cp(n_pts);
+		for (int i = 0; i < n_pts; ++i) { pp[i].x = prev_pts[2 * i]; pp[i].y = prev_pts[2 * i + 1]; }
+		std::vector<int> it, st;
+		a.estimateOpticalFlow(cp, pp, win_w, win_h, (unsigned int)n_pts, max_iters, epsilon, const_grad != 0, math_mode, &it, &st);
+		for (int i = 0; i < n_pts; ++i) { curr_pts[2 * i] = cp[i].x; curr_pts[2 * i + 1] = cp[i].y; n_iters[i] = it[i]; status[i] = st[i]; }
+		return 0;
+	} catch (const utils::Exception &e) { g_err = std::string(e.type()) + ": " + e.what(); return -1; }
+	catch (const std::exception &e) { g_err = e.what(); return -2; }
 }
 
 /* the same for the templated ESM<HipAM, HipSSM> (sm = 0) and ICLK<HipAM, HipSSM> (sm = 2): initialize on frame0, update() on frame1; then --

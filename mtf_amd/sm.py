@@ -580,6 +580,148 @@ class GridTracker:
         return self.tracker.n_iters
 
 
+class GridTrackerFlow:
+    """nt::GridTrackerFlow (SM/src/NT/GridTrackerFlow.cc:74-126; `grid_sm flow`): the grid_size x grid_size points of the grid SSM are
+    tracked from the previous frame to the current one by NCC::estimateOpticalFlow (AM/src/NCC.cc:412-526, Context.estimate_optical_flow:
+    one launch for all points) on a search_window lattice, the grid SSM is fitted to prev_pts -> curr_pts (ssm.estimateWarpFromPts) and the
+    region warped by the fit.  The points drift: after a frame prev_pts = curr_pts, they are put back on the grid by set_region only.
+    Parameter names and defaults are GridTrackerFlowParams' (GridTrackerFlowParams.h:6-17).  pyramid_levels and min_eig_thresh are carried
+    and ignored, as in the reference, which prints them and never reads them (there is no pyramid).  grid_ssm: homography or affine.
+    With est_params (_lib.est_params) the device estimator follows the flow on the context's stream without a host round trip in between
+    (`pix_mask`, `est_ok` after every update; frame f draws from est_seed + f); without it `estimator(prev_pts, curr_pts) -> state update`
+    is pluggable, default an all-points least-squares fit.  A point whose flow is not finite (its window is flat in either frame) makes
+    update() raise LogicError with the tracker's state unchanged -- the reference's callers treat a non-finite state as a lost tracker."""
+
+    def __init__(self, ctx, grid_size=10, search_window=10, max_iters=30, epsilon=0.01, use_const_grad=0, pyramid_levels=0, min_eig_thresh=1e-4,
+                 grid_ssm=L.SSM_HOMOGRAPHY, estimator=None, est_params=None, est_seed=1, grid_size_y=None, search_window_y=None, math=L.MATH_FAST):
+        _refuse_low_order("GridTrackerFlow", grid_ssm)
+        if grid_ssm not in (L.SSM_HOMOGRAPHY, L.SSM_AFFINE):
+            raise L.InvalidArgument(-1, "GridTrackerFlow: unknown state space model %r" % (grid_ssm,))
+        self.ctx = ctx
+        self.pyramid_levels, self.min_eig_thresh = pyramid_levels, min_eig_thresh      # unused (GridTrackerFlow.cc:20-22 prints them)
+        self.win = (int(search_window), int(search_window_y or search_window))
+        self.max_iters, self.epsilon, self.use_const_grad, self.math = int(max_iters), float(epsilon), int(bool(use_const_grad)), int(math)
+        # the grid SSM's points alone: a GridDesc whose sampling resolution is the grid's (neither an extra row nor patches)
+        self.gd = L.GridDesc(int(grid_size), int(grid_size_y or grid_size), 1, 1, 0, 0, 0)
+        self.n = self.gd.grid_size_x * self.gd.grid_size_y
+        self.grid_ssm = grid_ssm
+        self.est_params, self.est_seed = est_params, int(est_seed)
+        self.estimator = estimator if estimator is not None else least_squares_estimator(grid_ssm)
+        self.region = None
+        self.prev_pts = np.zeros((self.n, 2), dtype=np.float32)
+        self.curr_pts = np.zeros((self.n, 2), dtype=np.float32)
+        self.ssm_update = np.zeros(L.ssm_state_size(grid_ssm))
+        self.n_iters = np.zeros(self.n, dtype=np.int32)
+        self.status = np.zeros(self.n, dtype=np.int32)
+        self.pix_mask = np.ones(self.n, dtype=np.uint8)       # GridTrackerFlow.cc:57-58
+        self.est_ok = self.est_result = None
+        self._dev = None
+
+    def grid_pts(self, region_corners):
+        """ssm.getPts() of the grid SSM laid over the region: (n, 2), row-major"""
+        import ctypes as C
+        r = np.ascontiguousarray(np.asarray(region_corners, dtype=np.float64).reshape(2, 4).T)
+        pts, pcs = np.empty((self.n, 2)), np.empty((self.n, 4, 2))
+        L.check(L.lib().mtfhip_grid_layout(C.byref(self.gd), r.ctypes.data, pts.ctypes.data, pcs.ctypes.data))
+        return pts
+
+    # GridTrackerFlow::initialize :74-86
+    def initialize(self, region_corners):
+        self.set_region(region_corners)
+        self.ctx.keep_prev()             # am->getCurrImg().copyTo(prev_img) :82
+
+    # GridTrackerFlow::setRegion :119-126
+    def set_region(self, region_corners):
+        self.region = np.asarray(region_corners, dtype=np.float64).reshape(2, 4).copy()
+        self.prev_pts[...] = self.grid_pts(self.region).astype(np.float32)
+
+    def get_region(self):
+        return self.region.copy()
+
+    def _flow_desc(self):
+        return L.flow_desc(self.win, self.max_iters, self.epsilon, self.use_const_grad, 1e-8, self.math)
+
+    def _check_finite(self, curr, status):
+        bad = np.flatnonzero((status == L.FLOW_NONFINITE) | ~np.isfinite(curr).all(axis=1))
+        if len(bad):
+            p = int(bad[0])
+            raise L.LogicError(-3, "GridTrackerFlow: the optical flow of point %d (%.3f, %.3f) is not finite (pass %d): %d of %d points lost"
+                               % (p, self.prev_pts[p, 0], self.prev_pts[p, 1], int(self.n_iters[p]), len(bad), self.n))
+
+    def _update_chained(self):
+        """the flow's and the estimator's device-pointer forms back to back on the context's stream: one upload (the points, the point count
+        and the subset rows' -1 fill), two launches, one download, one wait.  The arrays live in one device buffer with a pinned host
+        mirror (torch is the allocator and the copy engine only)."""
+        import ctypes as C
+        import torch
+        p, n = self.est_params, self.n
+        n_hyp, mp = max(int(L.est_n_hyp(p)), 1), p.n_model_pts
+        d = self._dev
+        if d is None or d["n_sub"] != n_hyp * mp:
+            a16 = lambda v: (v + 15) & ~15
+            o = {}
+            o["prev"] = 0
+            o["npts"] = a16(o["prev"] + 8 * n)
+            o["sub"] = a16(o["npts"] + 4)
+            o["curr"] = a16(o["sub"] + 4 * n_hyp * mp)          # [0, curr): uploaded; [curr, end): downloaded
+            o["iters"] = a16(o["curr"] + 8 * n)
+            o["status"] = a16(o["iters"] + 4 * n)
+            o["upd"] = a16(o["status"] + 4 * n)
+            o["stats"] = a16(o["upd"] + 64)
+            o["info"] = a16(o["stats"] + 16)
+            o["mask"] = a16(o["info"] + 16)
+            o["end"] = a16(o["mask"] + n)
+            dev = torch.device("cuda", self.ctx.device)
+            host = torch.zeros(o["end"], dtype=torch.uint8).pin_memory()
+            hb = host.numpy()
+            view = lambda key, dtype, count: hb[o[key]:o[key] + count * np.dtype(dtype).itemsize].view(dtype)
+            d = self._dev = dict(o=o, n_sub=n_hyp * mp, host=host, buf=torch.empty(o["end"], dtype=torch.uint8, device=dev),
+                                 stream=torch.cuda.ExternalStream(self.ctx.stream, device=dev) if self.ctx.stream else torch.cuda.default_stream(dev),
+                                 prev=view("prev", np.float32, 2 * n).reshape(n, 2), curr=view("curr", np.float32, 2 * n).reshape(n, 2),
+                                 iters=view("iters", np.int32, n), status=view("status", np.int32, n), upd=view("upd", np.float64, 8),
+                                 info=view("info", np.int32, 4), mask=view("mask", np.uint8, n), host_n=np.array([n], dtype=np.int32))
+            view("npts", np.int32, 1)[0] = n
+            view("sub", np.int32, n_hyp * mp)[...] = -1          # (the estimator fills the rows it draws; -1 tells the others)
+        o, base = d["o"], d["buf"].data_ptr()
+        ptr = lambda key: C.c_void_p(base + o[key])
+        d["prev"][...] = self.prev_pts
+        fd = self._flow_desc()
+        with torch.cuda.stream(d["stream"]):
+            d["buf"][:o["curr"]].copy_(d["host"][:o["curr"]], non_blocking=True)
+            L.check(L.lib().mtfhip_ncc_estimate_optical_flow_dev(self.ctx._h, C.byref(fd), n, ptr("prev"), ptr("curr"), ptr("iters"), ptr("status")))
+            L.check(L.lib().mtfhip_ssm_estimate_from_pts_dev(self.ctx._h, int(self.grid_ssm), C.byref(p), 1, ptr("npts"), d["host_n"].ctypes.data, n,
+                                                             ptr("prev"), ptr("curr"), ptr("sub"), 0, n_hyp, self.est_seed, ptr("upd"), ptr("mask"),
+                                                             ptr("info"), ptr("stats")))
+            d["host"][o["curr"]:].copy_(d["buf"][o["curr"]:], non_blocking=True)
+        self.ctx.synchronize()
+        return (d["curr"].copy(), d["iters"].copy(), d["status"].copy(), d["upd"][:L.ssm_state_size(self.grid_ssm)].copy(), d["mask"].copy(),
+                bool(d["info"][0]))
+
+    # GridTrackerFlow::update :88-105
+    def update(self):
+        """one frame: the flow of every point, the fit of the grid SSM, the region warped by it.  Returns the region's corners (2 x 4)."""
+        if self.region is None:
+            raise RuntimeError("GridTrackerFlow.update before initialize")
+        if self.est_params is not None:
+            curr, self.n_iters, self.status, upd, mask, ok = self._update_chained()
+            self._check_finite(curr, self.status)      # (the fit of a lost frame is dropped with it)
+            self.est_seed += 1
+            self.pix_mask, self.est_ok = mask, ok
+        else:
+            curr, self.n_iters, self.status = self.ctx.estimate_optical_flow(self.prev_pts, self.win, self.max_iters, self.epsilon,
+                                                                             self.use_const_grad, self.math)
+            self._check_finite(curr, self.status)
+            upd = np.asarray(self.estimator(self.prev_pts.astype(np.float64), curr.astype(np.float64)), dtype=np.float64)
+        self.curr_pts[...] = curr
+        self.ssm_update = upd
+        from .api import apply_warp_to_pts
+        # ssm.applyWarpToCorners(opt_warped_corners, ssm.getCorners(), ssm_update); ssm.setCorners(opt_warped_corners) :93-95
+        self.region = apply_warp_to_pts(self.grid_ssm, self.region, upd)
+        self.prev_pts[...] = self.curr_pts         # :97-100 (not put back on the grid)
+        self.ctx.keep_prev()                       # am->getCurrImg().copyTo(prev_img) :102
+        return self.region.copy()
+
+
 class Comm:
     """A communicator of the C-ABI collective (mtfhip_comm_*: RCCL directly, no torch).  rank 0 calls Comm.unique_id() and hands
     the 128 bytes to the other ranks over whatever channel the host program has; `torch_bootstrap` does it with a

@@ -56,7 +56,7 @@ int alk_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	 * nothing stale is left behind for a later search method that skips its own init_template) */
 	TRY(store_h0(b, H0.data(), false));
 	if (b->desc.am == MTFHIP_AM_NCC) {
-		if (!b->d_ncc_tm) HIP_TRY(hipMalloc(&b->d_ncc_tm, sizeof(double) * 52 * (size_t)b->B));
+		HIP_TRY(b->d_ncc_tm.reserve(52 * (size_t)b->B));
 		HIP_TRY(hipMemsetAsync(b->d_ncc_tm, 0, sizeof(double) * 52 * (size_t)b->B, b->ctx->stream));
 	}
 	HIP_TRY(hipStreamSynchronize(b->ctx->stream));   /* (store_h0's staging) */

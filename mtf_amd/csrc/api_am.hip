@@ -509,7 +509,7 @@ void stale_clear(mtfhip_batch *b, bool df0, bool dft) {
 	if (!L.df0_sh && !L.dft_sh) L.shadow_valid = false;
 }
 static void swap_shadow(mtfhip_batch *b) {
-	std::swap(b->buf[MTFHIP_BUF_IT], b->d_it_shadow);
+	b->buf[MTFHIP_BUF_IT].swap(b->d_it_shadow);
 	if (b->desc.am == MTFHIP_AM_NCC)
 		for (int t = 0; t < b->B; ++t) {
 			TargetHost &h = b->th[t]; mtfhip_batch::Lazy::NccSave &v = b->lz.ncc_shadow[t];
@@ -557,10 +557,10 @@ int protect_stale(mtfhip_batch *b, bool w0, bool wt) {
 		if (L.df0_sh) TRY(ensure_one(b, false));
 		if (L.dft_sh) TRY(ensure_one(b, true));
 	}
-	if (!b->d_it_shadow) HIP_TRY(hipMalloc(&b->d_it_shadow, sizeof(double) * b->per_target[MTFHIP_BUF_IT] * b->B));
+	HIP_TRY(b->d_it_shadow.reserve(b->per_target[MTFHIP_BUF_IT] * b->B));
 	L.ncc_shadow.resize(b->B);
 	for (int t = 0; t < b->B; ++t) { const TargetHost &h = b->th[t]; L.ncc_shadow[t] = {h.It_mean, h.a, h.b, h.f}; }
-	std::swap(b->buf[MTFHIP_BUF_IT], b->d_it_shadow);   /* the launch fills the other buffer; th keeps the current scalars */
+	b->buf[MTFHIP_BUF_IT].swap(b->d_it_shadow);   /* the launch fills the other buffer; th keeps the current scalars */
 	L.shadow_valid = true;
 	if (cur0) L.df0_sh = true;
 	if (curt) L.dft_sh = true;
@@ -1095,7 +1095,7 @@ int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 	if (b->desc.am == MTFHIP_AM_SSD) return MTFHIP_OK;
 	/* MI: weight = sum_r curr_hist_grad(r) * sum_t curr_hist_mat(t) * self_grad_factor(r, t)  (MI.cc:710-723);
 	 * the self table was filled by the first-order call above */
-	if (!b->d_d2_w) HIP_TRY(hipMalloc(&b->d_d2_w, sizeof(double) * (size_t)b->N * b->B));
+	HIP_TRY(b->d_d2_w.reserve((size_t)b->N * b->B));
 	launch_mi_grad(b->view(), b->desc.mi_n_bins, b->mi_hist_norm, b->buf[MTFHIP_BUF_IT], b->buf[MTFHIP_BUF_IT], b->d_mi_tb, MI_T_SELF,
 		b->d_d2_w, b->ctx->stream);
 	return add_second_order(b, d2_buf, -1, b->d_d2_w, H);

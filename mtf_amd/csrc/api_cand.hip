@@ -40,12 +40,9 @@ int score_block_dev(mtfhip_batch *b, const double *dev_states, int lo, int cnt, 
 		if (!b->init_sim) return fail(MTFHIP_ERR_LOGIC, "score_candidates before initializeSimilarity");
 		const int nblk = 1;
 		const size_t need = (size_t)std::max(cnt, 1) * nblk * b->mi_row_len;
-		if (need > b->cand_mi_capacity) {
+		if (need > b->d_cand_mi.capacity()) {
 			HIP_TRY(hipStreamSynchronize(st));
-			if (b->d_cand_mi) (void)hipFree(b->d_cand_mi);
-			b->d_cand_mi = nullptr;
-			HIP_TRY(hipMalloc(&b->d_cand_mi, sizeof(double) * need));
-			b->cand_mi_capacity = need;
+			HIP_TRY(b->d_cand_mi.reserve(need));
 		}
 		MiFastPlan fp;
 		fp.nb = b->desc.mi_n_bins;
@@ -91,12 +88,7 @@ int mtfhip_score_candidates(mtfhip_batch *b, const double *states, int C, double
 	TRY(spss_refuse(b, "score_candidates", " is not available on this entry point"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	size_t need = (size_t)C * (b->S + 2);
-	if (need > b->cand_capacity) {
-		if (b->d_cand) HIP_TRY(hipFree(b->d_cand));
-		b->d_cand = nullptr;
-		HIP_TRY(hipMalloc(&b->d_cand, sizeof(double) * need));
-		b->cand_capacity = need;
-	}
+	HIP_TRY(b->d_cand.reserve(need));
 	double *d_states = b->d_cand, *d_lik = b->d_cand + (size_t)C * b->S, *d_sim = d_lik + C;
 	HIP_TRY(hipMemcpyAsync(d_states, states, sizeof(double) * C * b->S, hipMemcpyHostToDevice, b->ctx->stream));
 	TRY(mtfhip_score_candidates_dev(b, d_states, C, d_lik, d_sim));
@@ -128,16 +120,14 @@ int mtfhip_sample_candidates(mtfhip_batch *b, const double *states, int C, doubl
 	TRY(lowdof_refuse(b, "sample_candidates"));
 	TRY(spss_refuse(b, "sample_candidates", " is not available on this entry point"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
-	double *d_states = nullptr, *d_feat = nullptr;
-	HIP_TRY(hipMalloc(&d_states, sizeof(double) * C * b->S));
-	if (hipMalloc(&d_feat, sizeof(double) * (size_t)C * b->N) != hipSuccess) { (void)hipFree(d_states); return fail(MTFHIP_ERR_HIP, "hipMalloc of the %d x %d feature matrix failed", C, b->N); }
-	int rc = MTFHIP_OK;
-	if (hipMemcpyAsync(d_states, states, sizeof(double) * C * b->S, hipMemcpyHostToDevice, b->ctx->stream) != hipSuccess) rc = fail(MTFHIP_ERR_HIP, "state upload failed");
-	if (rc == MTFHIP_OK) rc = mtfhip_sample_candidates_dev(b, d_states, C, d_feat);
-	if (rc == MTFHIP_OK && hipMemcpyAsync(features, d_feat, sizeof(double) * (size_t)C * b->N, hipMemcpyDeviceToHost, b->ctx->stream) != hipSuccess) rc = fail(MTFHIP_ERR_HIP, "feature read-back failed");
-	if (hipStreamSynchronize(b->ctx->stream) != hipSuccess && rc == MTFHIP_OK) rc = fail(MTFHIP_ERR_HIP, "stream synchronisation failed");
-	(void)hipFree(d_states); (void)hipFree(d_feat);
-	return rc;
+	Dev<double> d_states, d_feat;   /* (released on every return; the release waits for what is in flight) */
+	HIP_TRY(d_states.reserve((size_t)C * b->S));
+	if (d_feat.reserve((size_t)C * b->N) != hipSuccess) return fail(MTFHIP_ERR_HIP, "device allocation of the %d x %d feature matrix failed", C, b->N);
+	HIP_TRY(hipMemcpyAsync(d_states, states, sizeof(double) * C * b->S, hipMemcpyHostToDevice, b->ctx->stream));
+	TRY(mtfhip_sample_candidates_dev(b, d_states, C, d_feat));
+	HIP_TRY(hipMemcpyAsync(features, d_feat, sizeof(double) * (size_t)C * b->N, hipMemcpyDeviceToHost, b->ctx->stream));
+	HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+	return MTFHIP_OK;
 }
 
 /* NN::generateDataset (SM/src/NT/NN.cc:131-191) */
@@ -174,12 +164,10 @@ int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *d
 	/* tolerance mode: the samples' warps go through a scratch array (k_nn_warps -> k_nn_rows), grown to the largest launch so far */
 	double *warps = nullptr;
 	if (nn_two_launch_ok(b->view_raw(), b->ctx->img, b->math_mode == MTFHIP_MATH_FAST)) {
-		const size_t need = nn_warps_bytes(row_count);
-		if (need > b->nn_warps_cap) {
+		const size_t need = nn_warps_bytes(row_count) / sizeof(double);
+		if (need > b->d_nn_warps.capacity()) {
 			HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-			if (b->d_nn_warps) { (void)hipFree(b->d_nn_warps); b->d_nn_warps = nullptr; b->nn_warps_cap = 0; }
-			HIP_TRY(hipMalloc(&b->d_nn_warps, need));
-			b->nn_warps_cap = need;
+			HIP_TRY(b->d_nn_warps.reserve(need));
 		}
 		warps = b->d_nn_warps;
 	}
@@ -200,18 +188,16 @@ int mtfhip_nn_dataset(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *pe
 	int F = 0;
 	TRY(mtfhip_nn_feature_size(b, &F));
 	const size_t C = (size_t)d->n_samples;
-	double *d_p = nullptr, *d_feat = nullptr;
-	HIP_TRY(hipMalloc(&d_p, sizeof(double) * C * b->S));
-	if (hipMalloc(&d_feat, sizeof(double) * C * F) != hipSuccess) { (void)hipFree(d_p); return fail(MTFHIP_ERR_HIP, "hipMalloc of the %d x %d feature matrix failed", d->n_samples, F); }
-	int rc = MTFHIP_OK;
+	Dev<double> d_p, d_feat;   /* (released on every return; the release waits for what is in flight) */
+	HIP_TRY(d_p.reserve(C * b->S));
+	if (d_feat.reserve(C * F) != hipSuccess) return fail(MTFHIP_ERR_HIP, "device allocation of the %d x %d feature matrix failed", d->n_samples, F);
 	hipStream_t st = b->ctx->stream;
-	if (perturbations_in && hipMemcpyAsync(d_p, perturbations_in, sizeof(double) * C * b->S, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(MTFHIP_ERR_HIP, "perturbation upload failed");
-	if (rc == MTFHIP_OK) rc = mtfhip_nn_dataset_dev(b, d, perturbations_in ? d_p : nullptr, d_p, d_feat, 0, d->n_samples);
-	if (rc == MTFHIP_OK && perturbations_out && hipMemcpyAsync(perturbations_out, d_p, sizeof(double) * C * b->S, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MTFHIP_ERR_HIP, "perturbation read-back failed");
-	if (rc == MTFHIP_OK && hipMemcpyAsync(features, d_feat, sizeof(double) * C * F, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MTFHIP_ERR_HIP, "feature read-back failed");
-	if (hipStreamSynchronize(st) != hipSuccess && rc == MTFHIP_OK) rc = fail(MTFHIP_ERR_HIP, "stream synchronisation failed");
-	(void)hipFree(d_p); (void)hipFree(d_feat);
-	return rc;
+	if (perturbations_in) HIP_TRY(hipMemcpyAsync(d_p, perturbations_in, sizeof(double) * C * b->S, hipMemcpyHostToDevice, st));
+	TRY(mtfhip_nn_dataset_dev(b, d, perturbations_in ? d_p.get() : nullptr, d_p, d_feat, 0, d->n_samples));
+	if (perturbations_out) HIP_TRY(hipMemcpyAsync(perturbations_out, d_p, sizeof(double) * C * b->S, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(features, d_feat, sizeof(double) * C * F, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return MTFHIP_OK;
 }
 
 } /* extern "C" */

@@ -52,11 +52,10 @@ int mtfhip_ctx_create(int device, void *hip_stream, mtfhip_ctx **out) {
 	mtfhip_ctx *c = new mtfhip_ctx();
 	c->device = device;
 	if (hipDeviceGetAttribute(&c->n_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); c->n_cus = 0; }
-	if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
+	if (hip_stream) c->stream.borrow((hipStream_t)hip_stream);
 	else {
-		hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-		if (e != hipSuccess) { delete c; return fail(MTFHIP_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-		c->own_stream = true;
+		hipError_t e = c->stream.create(hipStreamNonBlocking);
+		if (e != hipSuccess) { delete c; return fail(MTFHIP_ERR_HIP, "stream creation failed: %s", hipGetErrorString(e)); }
 	}
 	*out = c;
 	return MTFHIP_OK;
@@ -69,27 +68,9 @@ void mtfhip_ctx_destroy(mtfhip_ctx *c) {
 	try {
 		(void)hipSetDevice(c->device);
 		(void)hipStreamSynchronize(c->stream);
-		for (auto &kv : c->timers)
-			for (auto &p : kv.second.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-		for (auto e : c->free_events) (void)hipEventDestroy(e);
-		if (c->img_owned) (void)hipFree(c->img_owned);
-		if (c->prev_owned) (void)hipFree(c->prev_owned);
-		if (c->pair_owned) (void)hipFree(c->pair_owned);
-		if (c->raw) (void)hipFree(c->raw);
-		if (c->tmp_a) (void)hipFree(c->tmp_a);
-		if (c->tmp_b) (void)hipFree(c->tmp_b);
-		for (int q = 0; q < 3; ++q) {
-			if (c->extra_streams[q]) (void)hipStreamDestroy(c->extra_streams[q]);
-			if (c->ev_join[q]) (void)hipEventDestroy(c->ev_join[q]);
-		}
-		if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-		if (c->d_phase) (void)hipFree(c->d_phase);
-		if (c->est_ws) (void)hipFree(c->est_ws);
-		if (c->ev_ref) (void)hipEventDestroy(c->ev_ref);
-		if (c->own_stream) (void)hipStreamDestroy(c->stream);
+		delete c;   /* the members release what they own, in reverse order of declaration: the own stream after everything that ran on it */
 	} catch (...) {
 	}
-	delete c;
 }
 
 int mtfhip_ctx_synchronize(mtfhip_ctx *c) {
@@ -115,12 +96,7 @@ int mtfhip_image_upload_mc(mtfhip_ctx *c, const float *host_img, int height, int
 	const int logical_width = width;
 	width *= channels;   /* floats per row */
 	size_t need = (size_t)height * width;
-	if (need > c->img_capacity) {
-		if (c->img_owned) HIP_TRY(hipFree(c->img_owned));
-		c->img_owned = nullptr;
-		HIP_TRY(hipMalloc(&c->img_owned, need * sizeof(float)));
-		c->img_capacity = need;
-	}
+	HIP_TRY(c->img_owned.reserve(need));
 	HIP_TRY(hipMemcpy2DAsync(c->img_owned, (size_t)width * sizeof(float), host_img, (size_t)row_stride * sizeof(float),
 		(size_t)width * sizeof(float), (size_t)height, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream)); /* the caller may overwrite its buffer right after (TrackerBase.h:22-26) */
@@ -150,11 +126,9 @@ const float *ensure_pair_image(mtfhip_ctx *c) {
 	if (n * 8 >= 4294967296ull || im.w < 2 || im.h < 2) return nullptr;   /* (32-bit byte offsets into the pair image) */
 	if (c->pair_serial == c->img_serial && c->pair_owned) return c->pair_owned;
 	if (hipSetDevice(c->device) != hipSuccess) return nullptr;
-	if (2 * n > c->pair_capacity) {
-		if (c->pair_owned) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->pair_owned); }
-		c->pair_owned = nullptr; c->pair_capacity = 0;
-		if (hipMalloc(&c->pair_owned, 2 * n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-		c->pair_capacity = 2 * n;
+	if (2 * n > c->pair_owned.capacity()) {
+		if (c->pair_owned) (void)hipStreamSynchronize(c->stream);
+		if (c->pair_owned.reserve(2 * n) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
 	}
 	launch_pair_image(im, c->pair_owned, c->stream);
 	c->pair_serial = c->img_serial;
@@ -182,19 +156,13 @@ int mtfhip_image_keep_prev(mtfhip_ctx *c) {
 	if (c->img.data == c->prev.data) { c->prev = c->img; return MTFHIP_OK; }   /* kept already, no frame since */
 	if (c->img.data == c->img_owned) {
 		/* the context's own buffer: it becomes the previous frame's and the next upload / pre-processing pass fills the other one */
-		std::swap(c->img_owned, c->prev_owned);
-		std::swap(c->img_capacity, c->prev_capacity);
+		c->img_owned.swap(c->prev_owned);
 		c->prev = c->img;
 		return MTFHIP_OK;
 	}
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t row = (size_t)c->img.w * c->img.channels, need = row * c->img.h;
-	if (need > c->prev_capacity) {
-		if (c->prev_owned) HIP_TRY(hipFree(c->prev_owned));
-		c->prev_owned = nullptr; c->prev_capacity = 0;
-		HIP_TRY(hipMalloc(&c->prev_owned, need * sizeof(float)));
-		c->prev_capacity = need;
-	}
+	HIP_TRY(c->prev_owned.reserve(need));
 	HIP_TRY(hipMemcpy2DAsync(c->prev_owned, row * sizeof(float), c->img.data, (size_t)c->img.stride * sizeof(float), row * sizeof(float), (size_t)c->img.h,
 		hipMemcpyDeviceToDevice, c->stream));
 	/* a clone: the caller writes its next frame into the same buffer right after, on a stream of its own (as after mtfhip_image_upload) */
@@ -215,24 +183,12 @@ int mtfhip_image_swap_prev(mtfhip_ctx *c) {
 
 /* ------------------------------------------------------------------ pre-processing / pyramid */
 static int ensure_image(mtfhip_ctx *c, int rows, int cols) {
-	const size_t need = (size_t)rows * cols;
-	if (need > c->img_capacity) {
-		if (c->img_owned) HIP_TRY(hipFree(c->img_owned));
-		c->img_owned = nullptr;
-		HIP_TRY(hipMalloc(&c->img_owned, need * sizeof(float)));
-		c->img_capacity = need;
-	}
+	HIP_TRY(c->img_owned.reserve((size_t)rows * cols));
 	return MTFHIP_OK;
 }
 static int ensure_tmp(mtfhip_ctx *c, size_t need) {
-	if (need > c->tmp_capacity) {
-		if (c->tmp_a) HIP_TRY(hipFree(c->tmp_a));
-		if (c->tmp_b) HIP_TRY(hipFree(c->tmp_b));
-		c->tmp_a = c->tmp_b = nullptr;
-		HIP_TRY(hipMalloc(&c->tmp_a, need * sizeof(float)));
-		HIP_TRY(hipMalloc(&c->tmp_b, need * sizeof(float)));
-		c->tmp_capacity = need;
-	}
+	HIP_TRY(c->tmp_a.reserve(need));
+	HIP_TRY(c->tmp_b.reserve(need));
 	return MTFHIP_OK;
 }
 /* cv::getGaussianKernel(ksize, sigma, CV_32F) for sigma > 0: exp(-x^2 / (2 sigma^2)) rounded to float, normalised by the
@@ -271,12 +227,7 @@ int mtfhip_image_preprocess_ex(mtfhip_ctx *c, const void *host_raw, int rows, in
 	if (orows <= 0 || ocols <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "image_preprocess: resize_factor %g leaves no pixels", resize_factor);
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t raw_bytes = px * cols * rows;
-	if (raw_bytes > c->raw_capacity) {
-		if (c->raw) HIP_TRY(hipFree(c->raw));
-		c->raw = nullptr;
-		HIP_TRY(hipMalloc(&c->raw, raw_bytes));
-		c->raw_capacity = raw_bytes;
-	}
+	HIP_TRY(c->raw.reserve(raw_bytes));
 	TRY(ensure_image(c, std::max(rows, orows), std::max(cols, ocols)));
 	TRY(ensure_tmp(c, (size_t)rows * cols + 512));   /* (+ the 256-bin histogram and the look-up table of hist_eq behind tmp_b) */
 	HIP_TRY(hipMemcpy2DAsync(c->raw, px * cols, host_raw, (size_t)row_stride_bytes, px * cols, (size_t)rows, hipMemcpyHostToDevice, c->stream));
@@ -438,7 +389,7 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	size_t per[MTFHIP_BUF_COUNT] = {N, N, 2 * N, 2 * N, N, N, N * S, N * S, N * S, 2 * NP, 2 * NP, 8 * NP, NP, NP, 2 * NP, 2 * NP,
 		4 * N, 4 * N, 16 * NP, S * S * N, S * S * N, S * S * N};
 	b->hess_eps = d->hess_eps > 0 ? d->hess_eps : 1.0; /* HESS_EPS, AM/include/mtf/AM/ImageBase.h:9 */
-	for (int i = 0; i < MTFHIP_BUF_COUNT; ++i) { b->per_target[i] = per[i]; b->buf[i] = nullptr; }
+	for (int i = 0; i < MTFHIP_BUF_COUNT; ++i) b->per_target[i] = per[i];
 	b->th.resize(n_targets);
 	for (auto &h : b->th) { std::memset(&h, 0, sizeof(h)); h.warp = m3_identity(); }
 	b->nblk_max = simple_blocks_per_target(b->N);
@@ -453,52 +404,51 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		const size_t Bt = (size_t)n_targets, d = sizeof(double);
 		b->slab_dbl_bytes = 54 * Bt * d;
 		b->slab_bytes = b->slab_dbl_bytes + 2 * sizeof(int) * Bt;
-		if (hipMalloc(&b->d_slab, b->slab_bytes) != hipSuccess || hipHostMalloc(&b->h_stage_a, b->slab_bytes) != hipSuccess ||
-			hipHostMalloc(&b->h_stage_b, b->slab_bytes) != hipSuccess || hipEventCreateWithFlags(&b->ev_a, hipEventDisableTiming) != hipSuccess ||
-			hipEventCreateWithFlags(&b->ev_b, hipEventDisableTiming) != hipSuccess ||
-			hipHostMalloc(&b->h_wstage[0], 17 * Bt * d) != hipSuccess || hipHostMalloc(&b->h_wstage[1], 17 * Bt * d) != hipSuccess ||
-			hipEventCreateWithFlags(&b->ev_w[0], hipEventDisableTiming) != hipSuccess ||
-			hipEventCreateWithFlags(&b->ev_w[1], hipEventDisableTiming) != hipSuccess)
+		if (b->d_slab.reserve(b->slab_bytes) != hipSuccess || b->h_stage_a.reserve(b->slab_bytes) != hipSuccess ||
+			b->h_stage_b.reserve(b->slab_bytes) != hipSuccess || b->ev_a.create(hipEventDisableTiming) != hipSuccess ||
+			b->ev_b.create(hipEventDisableTiming) != hipSuccess ||
+			b->h_wstage[0].reserve(17 * Bt) != hipSuccess || b->h_wstage[1].reserve(17 * Bt) != hipSuccess ||
+			b->ev_w[0].create(hipEventDisableTiming) != hipSuccess || b->ev_w[1].create(hipEventDisableTiming) != hipSuccess)
 			return cleanup(fail(MTFHIP_ERR_HIP, "allocation of the per-target state slab failed"));
-		double *p = reinterpret_cast<double *>(b->d_slab);
+		double *p = reinterpret_cast<double *>(b->d_slab.get());
 		b->d_warps = p; b->d_states = p + 9 * Bt; b->d_corners = p + 17 * Bt; b->d_init_corners_hm = p + 25 * Bt;
 		b->d_ncc = p + 37 * Bt; b->d_w0 = p + 45 * Bt;
 		b->d_active = reinterpret_cast<int *>(b->d_slab + b->slab_dbl_bytes); b->d_iters = b->d_active + Bt;
 		(void)hipMemsetAsync(b->d_slab, 0, b->slab_bytes, c->stream);
 	}
-#define ALLOC(ptr, bytes) do { if (hipMalloc(&(ptr), (bytes)) != hipSuccess) return cleanup(fail(MTFHIP_ERR_HIP, "hipMalloc(%zu) failed", (size_t)(bytes))); } while (0)
-	ALLOC(b->d_partials, sizeof(double) * kAccRowMax * b->nblk_max * n_targets);
-	ALLOC(b->d_acc, sizeof(double) * kAccRowMax * n_targets);
-	ALLOC(b->d_scratch_pts, sizeof(double) * 18 * NP * n_targets); /* largest upload: pts (2 NP) + hess_pts (16 NP) */
-	ALLOC(b->d_h0, sizeof(double) * 64 * n_targets);
-	ALLOC(b->d_h0inv, sizeof(double) * 64 * n_targets);
-	ALLOC(b->d_colmean, sizeof(double) * 8 * n_targets);
+#define ALLOC(buf, n) do { if ((buf).reserve(n) != hipSuccess) return cleanup(fail(MTFHIP_ERR_HIP, "device allocation of %zu doubles failed", (size_t)(n))); } while (0)
+	ALLOC(b->d_partials, (size_t)kAccRowMax * b->nblk_max * n_targets);
+	ALLOC(b->d_acc, (size_t)kAccRowMax * n_targets);
+	ALLOC(b->d_scratch_pts, (size_t)18 * NP * n_targets); /* largest upload: pts (2 NP) + hess_pts (16 NP) */
+	ALLOC(b->d_h0, (size_t)64 * n_targets);
+	ALLOC(b->d_h0inv, (size_t)64 * n_targets);
+	ALLOC(b->d_colmean, (size_t)8 * n_targets);
 	if (d->am == MTFHIP_AM_MI) {
 		const int nb = d->mi_n_bins;
 		b->mi_row_len = std::max(std::max(nb + 2 * nb * nb, 36 + nb * nb * b->S), nb <= 10 ? mi_fast_row_len(nb) : 0);   /* widest of the MI partial rows (fused passes incl.) */
 		/* hist_norm_mult = 1 / (patch_size + hist_pre_seed * n_bins), hist_pre_seed = n_bins * pre_seed (MI.cc:97,104) */
 		b->mi_hist_norm = 1.0 / ((double)b->N + (nb * d->mi_pre_seed) * nb);
-		ALLOC(b->d_mi_tb, sizeof(double) * MI_SIZE * n_targets);
-		ALLOC(b->d_mi_part, sizeof(double) * (size_t)b->mi_row_len * b->nblk_max * n_targets);
-		ALLOC(b->d_mi_f, sizeof(double) * n_targets);
-		ALLOC(b->d_mi_red, sizeof(double) * (size_t)b->mi_row_len * n_targets);
-		ALLOC(b->d_mi_H, sizeof(double) * (64 + 16 + 64) * n_targets);   /* [B][64] Hessians, [B][16] Jacobian sums of the fused pass, [B][64] second Hessian (SumOfStd) */
+		ALLOC(b->d_mi_tb, (size_t)MI_SIZE * n_targets);
+		ALLOC(b->d_mi_part, (size_t)b->mi_row_len * b->nblk_max * n_targets);
+		ALLOC(b->d_mi_f, (size_t)n_targets);
+		ALLOC(b->d_mi_red, (size_t)b->mi_row_len * n_targets);
+		ALLOC(b->d_mi_H, (size_t)(64 + 16 + 64) * n_targets);   /* [B][64] Hessians, [B][16] Jacobian sums of the fused pass, [B][64] second Hessian (SumOfStd) */
 		(void)hipMemsetAsync(b->d_mi_tb, 0, sizeof(double) * MI_SIZE * n_targets, c->stream);
 	}
 #undef ALLOC
-	if (hipHostMalloc(&b->h_acc, sizeof(double) * kAccRowMax * n_targets, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-		return cleanup(fail(MTFHIP_ERR_HIP, "hipHostMalloc failed"));
+	if (b->h_acc.reserve((size_t)kAccRowMax * n_targets) != hipSuccess)
+		return cleanup(fail(MTFHIP_ERR_HIP, "allocation of the pinned result rows failed"));
 	{
 		const char *zc = std::getenv("MTFHIP_ZERO_COPY");
 		void *dp = nullptr, *fp = nullptr;
 		if (!(zc && zc[0] == '0') && hipHostGetDevicePointer(&dp, b->h_acc, 0) == hipSuccess &&
-			hipHostMalloc(&b->h_flag, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
-			hipHostGetDevicePointer(&fp, b->h_flag, 0) == hipSuccess && hipMalloc(&b->d_fin_count, sizeof(int)) == hipSuccess) {
+			b->h_flag.reserve(1) == hipSuccess &&
+			hipHostGetDevicePointer(&fp, b->h_flag, 0) == hipSuccess && b->d_fin_count.reserve(1) == hipSuccess) {
 			*b->h_flag = 0;
 			(void)hipMemsetAsync(b->d_fin_count, 0, sizeof(int), c->stream);
 			b->h_acc_dev = static_cast<double *>(dp); b->h_flag_dev = static_cast<unsigned long long *>(fp);
 			void *pp = nullptr;
-			if (hipHostMalloc(&b->h_pub, b->slab_bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
+			if (b->h_pub.reserve(b->slab_bytes) == hipSuccess &&
 				hipHostGetDevicePointer(&pp, b->h_pub, 0) == hipSuccess) b->h_pub_dev = static_cast<char *>(pp);
 			else (void)hipGetLastError();
 			void *sp = nullptr;
@@ -537,35 +487,9 @@ void mtfhip_batch_destroy(mtfhip_batch *b) {
 		reg.erase(std::remove(reg.begin(), reg.end(), b), reg.end());
 		(void)hipSetDevice(b->ctx->device);
 		(void)hipStreamSynchronize(b->ctx->stream);
-		for (int i = 0; i < MTFHIP_BUF_COUNT; ++i)
-			if (b->buf[i]) (void)hipFree(b->buf[i]);
-		void *ptrs[] = {b->d_slab, b->d_partials, b->d_acc, b->d_scratch_pts, b->d_h0,
-			b->d_cand, b->d_colmean, b->d_mi_tb, b->d_mi_part,
-			b->d_mi_f, b->d_mi_H, b->d_h0inv, b->d_d2_part, b->d_d2_out, b->d_d2_w, b->d_it_shadow, b->d_ncc_tm, b->d_mi_red, b->d_lm, b->d_persist, b->d_last_ws, b->d_need_mat, b->d_trace, b->d_cand_mi, b->d_mi_poly, b->d_nn_warps, b->d_fb, b->d_scv_i0, b->d_scv_code, b->d_scv_part, b->d_scv_map,
-			b->d_rscv_code, b->d_rscv_part, b->d_rscv_arrive, b->d_rscv_map, b->d_rscv_it, b->d_lscv_i0, b->d_lscv_code, b->d_lscv_cell, b->d_lscv_crng,
-			b->d_lscv_w, b->d_lscv_tot, b->d_lscv_arrive, b->d_lscv_map, b->d_lscv_aff};
-		for (void *p : ptrs)
-			if (p) (void)hipFree(p);
-		for (double *p : b->pass_j)
-			if (p) (void)hipFree(p);
-		if (b->h_fb) (void)hipHostFree(b->h_fb);
-		if (b->h_init_rec) (void)hipHostFree(b->h_init_rec);
-		if (b->h_init_flag) (void)hipHostFree(b->h_init_flag);
-		if (b->h_acc) (void)hipHostFree(b->h_acc);
-		if (b->h_flag) (void)hipHostFree(b->h_flag);
-		if (b->h_pub) (void)hipHostFree(b->h_pub);
-		if (b->d_fin_count) (void)hipFree(b->d_fin_count);
-		if (b->h_stage_a) (void)hipHostFree(b->h_stage_a);
-		if (b->h_stage_b) (void)hipHostFree(b->h_stage_b);
-		if (b->ev_a) (void)hipEventDestroy(b->ev_a);
-		if (b->ev_b) (void)hipEventDestroy(b->ev_b);
-		for (int k = 0; k < 2; ++k) {
-			if (b->h_wstage[k]) (void)hipHostFree(b->h_wstage[k]);
-			if (b->ev_w[k]) (void)hipEventDestroy(b->ev_w[k]);
-		}
+		delete b;   /* the members release what they own */
 	} catch (...) {
 	}
-	delete b;
 }
 
 int mtfhip_batch_n_targets(const mtfhip_batch *b) { return b ? b->B : 0; }
@@ -640,7 +564,7 @@ void set_corners_finish_deferred(mtfhip_batch *b) {
 		b->deferred_patches.resize(8 * Bt);
 		if (mtfhip_grid_layout(&b->deferred_gdesc, b->deferred_region, nullptr, b->deferred_patches.data()) == MTFHIP_OK) {
 			b->deferred_corners = b->deferred_patches.data();
-			std::memcpy(reinterpret_cast<double *>(b->h_stage_a) + 17 * Bt, b->deferred_patches.data(), sizeof(double) * 8 * Bt);   /* the slab's corners */
+			std::memcpy(reinterpret_cast<double *>(b->h_stage_a.get()) + 17 * Bt, b->deferred_patches.data(), sizeof(double) * 8 * Bt);   /* the slab's corners */
 			if (b->deferred_template_check && b->j0_is_template && b->template_corners.size() == 8 * Bt &&
 				std::memcmp(b->template_corners.data(), b->deferred_patches.data(), sizeof(double) * 8 * Bt) == 0)
 				b->j0_template_corners_epoch = b->corners_epoch;   /* (set_region_core's test, with the corners it did not have yet) */
@@ -650,7 +574,7 @@ void set_corners_finish_deferred(mtfhip_batch *b) {
 	const double *corners = b->deferred_corners;
 	if (!corners) return;
 	b->deferred_corners = nullptr;
-	double *sp = reinterpret_cast<double *>(b->h_stage_a);
+	double *sp = reinterpret_cast<double *>(b->h_stage_a.get());
 	double *s_w = sp, *s_s = sp + 9 * Bt, *s_ic = sp + 25 * Bt, *s_w0 = sp + 45 * Bt;
 	int *s_act = reinterpret_cast<int *>(b->h_stage_a + b->slab_dbl_bytes), *s_it = s_act + Bt;
 	static const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -692,7 +616,7 @@ int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, boo
 	 * AND the staged slab (w | s | corners | init_corners_hm | NCC scalars | w0 | flags: the layout of fill_stage) */
 	if (b->stage_a_busy) HIP_TRY(hipEventSynchronize(b->ev_a));
 	const size_t Bt = (size_t)b->B;
-	double *sp = reinterpret_cast<double *>(b->h_stage_a);
+	double *sp = reinterpret_cast<double *>(b->h_stage_a.get());
 	double *s_w = sp, *s_s = sp + 9 * Bt, *s_cr = sp + 17 * Bt, *s_ic = sp + 25 * Bt, *s_nc = sp + 37 * Bt, *s_w0 = sp + 45 * Bt;
 	int *s_act = reinterpret_cast<int *>(b->h_stage_a + b->slab_dbl_bytes), *s_it = s_act + Bt;
 	static const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -1184,7 +1108,7 @@ int mtfhip_timing_enable(mtfhip_ctx *c, int on) {
 }
 static void drain(mtfhip_ctx *c) {
 	(void)hipStreamSynchronize(c->stream);
-	for (hipStream_t s : c->extra_streams) if (s) (void)hipStreamSynchronize(s);
+	for (const Stream &s : c->extra_streams) if (s) (void)hipStreamSynchronize(s);
 	for (auto &kv : c->timers) {
 		for (auto &p : kv.second.pending) {
 			float ms = 0, t0 = 0;
@@ -1193,8 +1117,8 @@ static void drain(mtfhip_ctx *c) {
 				if (c->ev_ref && hipEventElapsedTime(&t0, c->ev_ref, p.first) == hipSuccess) kv.second.spans.emplace_back((double)t0, (double)t0 + ms);
 				else (void)hipGetLastError();
 			}
-			c->free_events.push_back(p.first);
-			c->free_events.push_back(p.second);
+			c->free_events.push_back(std::move(p.first));
+			c->free_events.push_back(std::move(p.second));
 		}
 		kv.second.pending.clear();
 	}
@@ -1203,7 +1127,7 @@ int mtfhip_timing_reset(mtfhip_ctx *c) {
 	if (!c) return fail(MTFHIP_ERR_INVALID_ARG, "timing_reset: NULL ctx");
 	drain(c);
 	for (auto &kv : c->timers) { kv.second.total_ms = 0; kv.second.n = 0; kv.second.launches = 0; kv.second.spans.clear(); }
-	if (!c->ev_ref && hipEventCreate(&c->ev_ref) != hipSuccess) { (void)hipGetLastError(); c->ev_ref = nullptr; }
+	if (!c->ev_ref && c->ev_ref.create() != hipSuccess) (void)hipGetLastError();
 	if (c->ev_ref) { (void)hipEventRecord(c->ev_ref, c->stream); (void)hipStreamSynchronize(c->stream); }
 	return MTFHIP_OK;
 }

@@ -66,12 +66,9 @@ int mtfhip_ssm_estimate_from_pts(mtfhip_ctx *c, int ssm, const mtfhip_est_params
 		o_sub = align16(o_out + sizeof(float) * 2 * S * max_pts), o_upd = align16(o_sub + sizeof(int) * S * n_hyp * mp), o_stats = align16(o_upd + sizeof(double) * 8 * S),
 		o_info = align16(o_stats + sizeof(double) * 2 * S), o_mask = align16(o_info + sizeof(int) * 4 * S), total = align16(o_mask + S * max_pts);
 	HIP_TRY(hipSetDevice(c->device));
-	if (c->est_ws_capacity < total) {
+	if (c->est_ws.capacity() < total) {
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (c->est_ws) HIP_TRY(hipFree(c->est_ws));
-		c->est_ws = nullptr; c->est_ws_capacity = 0;
-		HIP_TRY(hipMalloc(&c->est_ws, total));
-		c->est_ws_capacity = total;
+		HIP_TRY(c->est_ws.reserve(total));
 	}
 	std::vector<unsigned char> up(subsets ? o_upd : o_sub, 0), down(total - o_sub);
 	std::memcpy(up.data() + o_n, n_pts, sizeof(int) * S);

@@ -47,12 +47,9 @@ static int flow_host(const char *fn, mtfhip_ctx *c, const mtfhip_flow_desc *d, i
 		o_st = flow_align16(o_n + sizeof(int) * P), o_tr = flow_align16(o_st + sizeof(int) * P),
 		total = flow_align16(o_tr + (want_trace ? sizeof(double) * P * trace_cap * kFlowTraceStride : 0));
 	HIP_TRY(hipSetDevice(c->device));
-	if (c->est_ws_capacity < total) {
+	if (c->est_ws.capacity() < total) {
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (c->est_ws) HIP_TRY(hipFree(c->est_ws));
-		c->est_ws = nullptr; c->est_ws_capacity = 0;
-		HIP_TRY(hipMalloc(&c->est_ws, total));
-		c->est_ws_capacity = total;
+		HIP_TRY(c->est_ws.reserve(total));
 	}
 	hipStream_t st = c->stream;
 	HIP_TRY(hipMemcpyAsync(c->est_ws + o_prev, prev_pts, sizeof(float) * 2 * P, hipMemcpyHostToDevice, st));

@@ -149,14 +149,14 @@ int init_template_fused(mtfhip_batch *b, const mtfhip_sm_desc *sm, const RegionI
 	const bool ncc = b->desc.am == MTFHIP_AM_NCC;
 	TRY(need_image(b));
 	for (int id : {MTFHIP_BUF_I0, MTFHIP_BUF_IT, MTFHIP_BUF_DI0_DX, MTFHIP_BUF_DIT_DX, MTFHIP_BUF_J0, MTFHIP_BUF_DF_DI0, MTFHIP_BUF_DF_DIT}) TRY(ensure_buf(b, id));
-	if (!b->h_init_rec) {
-		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_init_rec), sizeof(double) * kInitRec * (size_t)b->B, hipHostMallocMapped));
+	if (!b->h_init_flag_dev) {   /* (the last of the record's four words to be set: while it is null a failed call is simply repeated) */
+		HIP_TRY(b->h_init_rec.reserve(kInitRec * (size_t)b->B));
 		HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->h_init_rec_dev), b->h_init_rec, 0));
-		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_init_flag), sizeof(unsigned long long), hipHostMallocMapped));
+		HIP_TRY(b->h_init_flag.reserve(1));
 		*b->h_init_flag = 0;
 		HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->h_init_flag_dev), b->h_init_flag, 0));
 	}
-	if (ncc && !b->d_ncc_tm) HIP_TRY(hipMalloc(&b->d_ncc_tm, sizeof(double) * 52 * (size_t)b->B));
+	if (ncc) HIP_TRY(b->d_ncc_tm.reserve(52 * (size_t)b->B));
 	++b->frame_count;   /* ImageBase.cc:74 */
 	const unsigned long long seq = ++b->init_seq;
 	{
@@ -534,7 +534,7 @@ int lazy_try_similarity(mtfhip_batch *b) {
 		for (int t = 0; t < b->B; ++t) ncc_refresh_mirrors(b, b->th[t], b->h_acc + (size_t)t * NCC_ACC_COUNT);
 		b->ncc_host_newer = true;
 		if (!L.no_cache) {   /* sum It J0 and the scalars: enough for cmptInitJacobian / cmptInitHessian of this IT */
-			L.ncc_M.assign(b->h_acc, b->h_acc + (size_t)NCC_ACC_COUNT * b->B);
+			L.ncc_M.assign(b->h_acc.get(), b->h_acc + (size_t)NCC_ACC_COUNT * b->B);
 			L.ncc_M_mean = false; L.ncc_M_it = L.ver[MTFHIP_BUF_IT]; L.ncc_M_jt = L.ncc_M_jm = -1;
 		}
 		return MTFHIP_OK;

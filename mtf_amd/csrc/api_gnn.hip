@@ -32,35 +32,35 @@ int gnn_check_desc(const mtfhip_nn *nn, const mtfhip_gnn_desc *d, const char *fn
 int gnn_ensure_ctl(mtfhip_nn *nn) {
 	NnGraph &g = nn->g;
 	if (g.d_count) return MTFHIP_OK;
-	hipStream_t st = nn->b->ctx->stream;
-	HIP_TRY(hipMalloc(&g.d_count, 16));
+	HIP_TRY(g.d_count.reserve(2));
 	g.d_start = reinterpret_cast<int *>(g.d_count + 1);
-	HIP_TRY(hipMemsetAsync(g.d_count, 0, 16, st));
+	const hipError_t e = hipMemsetAsync(g.d_count, 0, 16, nn->b->ctx->stream);
+	if (e != hipSuccess) { g.d_count.reset(); g.d_start = nullptr; }   /* (not zeroed is not there: the next call starts over) */
+	HIP_TRY(e);
 	return MTFHIP_OK;
 }
 int gnn_ensure_graph(mtfhip_nn *nn, int degree) {
 	NnGraph &g = nn->g;
 	const size_t want = (size_t)nn->n * (size_t)(degree > 0 ? degree : 1);
-	if (want > g.graph_cap) {
+	if (want > g.d_graph.capacity()) {
 		HIP_TRY(hipStreamSynchronize(nn->b->ctx->stream));
-		(void)hipFree(g.d_graph); g.d_graph = nullptr; g.graph_cap = 0;
-		HIP_TRY(hipMalloc(&g.d_graph, sizeof(int) * want));
-		g.graph_cap = want;
+		HIP_TRY(g.d_graph.reserve(want));
 	}
 	return MTFHIP_OK;
 }
 int gnn_ensure_walks(mtfhip_nn *nn, int Q) {
 	NnGraph &g = nn->g;
-	const int part = Q * g.nper;
-	if (Q <= g.walks_cap && part <= g.part_cap) return MTFHIP_OK;
+	const size_t nq = (size_t)Q, part = nq * g.nper;
+	if (nq <= g.d_walks.capacity() && part <= g.d_part.capacity() && nq <= g.d_tickets.capacity()) return MTFHIP_OK;
 	HIP_TRY(hipStreamSynchronize(nn->b->ctx->stream));
-	(void)hipFree(g.d_walks); (void)hipFree(g.d_part); (void)hipFree(g.d_tickets);
-	g.d_walks = nullptr; g.d_part = nullptr; g.d_tickets = nullptr; g.walks_cap = 0; g.part_cap = 0;
-	HIP_TRY(hipMalloc(&g.d_walks, sizeof(GnnWalk) * (size_t)Q));
-	HIP_TRY(hipMalloc(&g.d_part, sizeof(NnBest) * (size_t)part));
-	HIP_TRY(hipMalloc(&g.d_tickets, sizeof(unsigned) * (size_t)Q));
-	HIP_TRY(hipMemsetAsync(g.d_tickets, 0, sizeof(unsigned) * (size_t)Q, nn->b->ctx->stream));
-	g.walks_cap = Q; g.part_cap = part;
+	HIP_TRY(g.d_walks.reserve(nq));
+	HIP_TRY(g.d_part.reserve(part));
+	if (nq > g.d_tickets.capacity()) {   /* the tickets return to zero behind every walk: zeroed once, when they are allocated */
+		HIP_TRY(g.d_tickets.reserve(nq));
+		const hipError_t e = hipMemsetAsync(g.d_tickets, 0, sizeof(unsigned) * nq, nn->b->ctx->stream);
+		if (e != hipSuccess) g.d_tickets.reset();   /* (not zeroed is not there: the next call starts over) */
+		HIP_TRY(e);
+	}
 	return MTFHIP_OK;
 }
 void gnn_adopt(mtfhip_nn *nn, const mtfhip_gnn_desc *d, int degree) {
@@ -80,12 +80,6 @@ void gnn_enqueue_walks(mtfhip_nn *nn, const double *dev_queries, int Q, const in
 }
 } // namespace
 
-void gnn_free(mtfhip_nn *nn) {
-	NnGraph &g = nn->g;
-	(void)hipFree(g.d_graph); (void)hipFree(g.d_count); (void)hipFree(g.d_walks); (void)hipFree(g.d_part); (void)hipFree(g.d_tickets);
-	(void)hipFree(g.d_q); (void)hipFree(g.d_starts); (void)hipFree(g.d_idx); (void)hipFree(g.d_steps); (void)hipFree(g.d_dist);
-	g = NnGraph();
-}
 int gnn_need_graph(const mtfhip_nn *nn, const char *fn) {
 	if (!nn->g.valid) return fail(MTFHIP_ERR_LOGIC, "%s with the GNN index before nn_gnn_build / nn_gnn_set_graph (a new dataset invalidates the graph)", fn);
 	return MTFHIP_OK;
@@ -130,9 +124,9 @@ int mtfhip_nn_gnn_build(mtfhip_nn *nn, const mtfhip_gnn_desc *d) {
 		if (P < 1) P = 1;
 		if (P > (size_t)nn->n) P = (size_t)nn->n;
 		if (P > 65535u * (size_t)kGnnTile) P = 65535u * (size_t)kGnnTile;
-		double *scratch = nullptr;
-		if (hipMalloc(&scratch, sizeof(double) * P * (size_t)nn->n) != hipSuccess)
-			return fail(MTFHIP_ERR_HIP, "nn_gnn_build: hipMalloc of the %zu x %d distance panel failed", P, nn->n);
+		Dev<double> scratch;
+		if (scratch.reserve(P * (size_t)nn->n) != hipSuccess)
+			return fail(MTFHIP_ERR_HIP, "nn_gnn_build: device allocation of the %zu x %d distance panel failed", P, nn->n);
 		hipStream_t st = nn->b->ctx->stream;
 		{
 			TimedScope ts(nn->b->ctx, "gnn_build");
@@ -142,9 +136,7 @@ int mtfhip_nn_gnn_build(mtfhip_nn *nn, const mtfhip_gnn_desc *d) {
 				launch_gnn_select(scratch, nn->n, (int)lo, rows, degree, nn->g.d_graph, st);
 			}
 		}
-		const hipError_t e = hipStreamSynchronize(st);
-		(void)hipFree(scratch);
-		HIP_TRY(e);
+		HIP_TRY(hipStreamSynchronize(st));
 		TRY(launch_error_pending());
 	}
 	gnn_adopt(nn, d, degree);
@@ -211,20 +203,18 @@ int mtfhip_nn_gnn_search(mtfhip_nn *nn, const double *queries, int n_queries, co
 				return fail(MTFHIP_ERR_INVALID_ARG, "nn_gnn_search: start node %d of query %d is not a row of the %d", start_nodes[q], q, nn->n);
 	NnGraph &g = nn->g;
 	hipStream_t st = nn->b->ctx->stream;
-	if (n_queries > g.q_cap) {
-		HIP_TRY(hipStreamSynchronize(st));
-		(void)hipFree(g.d_q); (void)hipFree(g.d_starts); (void)hipFree(g.d_idx); (void)hipFree(g.d_steps); (void)hipFree(g.d_dist);
-		g.d_q = nullptr; g.d_starts = nullptr; g.d_idx = nullptr; g.d_steps = nullptr; g.d_dist = nullptr; g.q_cap = 0;
-		HIP_TRY(hipMalloc(&g.d_q, sizeof(double) * (size_t)n_queries * nn->F));
-		HIP_TRY(hipMalloc(&g.d_starts, sizeof(int) * (size_t)n_queries));
-		HIP_TRY(hipMalloc(&g.d_idx, sizeof(int) * (size_t)n_queries));
-		HIP_TRY(hipMalloc(&g.d_steps, sizeof(int) * (size_t)n_queries));
-		HIP_TRY(hipMalloc(&g.d_dist, sizeof(double) * (size_t)n_queries));
-		g.q_cap = n_queries;
-	}
+	const size_t Q = (size_t)n_queries;
+	/* (every member is asked: one that a failed grow left empty is allocated again whatever the others hold) */
+	if (Q * nn->F > g.d_q.capacity() || Q > g.d_starts.capacity() || Q > g.d_idx.capacity() || Q > g.d_steps.capacity() || Q > g.d_dist.capacity())
+		HIP_TRY(hipStreamSynchronize(st));   /* what is about to be released may still be read */
+	HIP_TRY(g.d_q.reserve(Q * nn->F));
+	HIP_TRY(g.d_starts.reserve(Q));
+	HIP_TRY(g.d_idx.reserve(Q));
+	HIP_TRY(g.d_steps.reserve(Q));
+	HIP_TRY(g.d_dist.reserve(Q));
 	HIP_TRY(hipMemcpyAsync(g.d_q, queries, sizeof(double) * (size_t)n_queries * nn->F, hipMemcpyHostToDevice, st));
 	if (start_nodes) HIP_TRY(hipMemcpyAsync(g.d_starts, start_nodes, sizeof(int) * (size_t)n_queries, hipMemcpyHostToDevice, st));
-	TRY(mtfhip_nn_gnn_search_dev(nn, g.d_q, n_queries, start_nodes ? g.d_starts : nullptr, g.d_idx, g.d_dist, g.d_steps));
+	TRY(mtfhip_nn_gnn_search_dev(nn, g.d_q, n_queries, start_nodes ? g.d_starts.get() : nullptr, g.d_idx, g.d_dist, g.d_steps));
 	HIP_TRY(hipMemcpyAsync(idx, g.d_idx, sizeof(int) * (size_t)n_queries, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(dist, g.d_dist, sizeof(double) * (size_t)n_queries, hipMemcpyDeviceToHost, st));
 	if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, g.d_steps, sizeof(int) * (size_t)n_queries, hipMemcpyDeviceToHost, st));

@@ -226,10 +226,10 @@ int mtfhip_grid_frame_fb(mtfhip_batch *b, const mtfhip_sm_desc *sm, const mtfhip
 			c->prev.channels == c->img.channels;
 		if (fused) {
 			const size_t B = (size_t)b->B;
-			if (!b->h_fb) {
-				HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_fb), sizeof(double) * 9 * B, hipHostMallocMapped));
+			if (!b->d_fb) {   /* (the last of the three to arrive: while it is null a failed call is simply repeated) */
+				HIP_TRY(b->h_fb.reserve(9 * B));
 				HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->h_fb_dev), b->h_fb, 0));
-				HIP_TRY(hipMalloc(&b->d_fb, sizeof(double) * 9 * B));
+				HIP_TRY(b->d_fb.reserve(9 * B));
 			}
 			b->fb_fused_req = true; b->fb_fused_reinit = fb->fb_reinit != 0;
 			const int rc = mtfhip_grid_frame(b, sm, g, nullptr, n_iters, corners, cen.data());

@@ -19,10 +19,8 @@ int lrscv_capture(mtfhip_batch *b) {
 	TRY(lscv_geometry(b, (size_t)kLscvLdsBudget - kLrscvFusedStaticLds));
 	const size_t B = (size_t)b->B, N = (size_t)b->N;
 	hipStream_t st = b->ctx->stream;
-	if (!b->d_rscv_code) {
-		HIP_TRY(hipMalloc(&b->d_rscv_code, N * B));
-		HIP_TRY(hipMalloc(&b->d_rscv_it, sizeof(double) * N * B));
-	}
+	HIP_TRY(b->d_rscv_it.reserve(N * B));
+	HIP_TRY(b->d_rscv_code.reserve(N * B));   /* (last: lrscv_update_pix_vals and lrscv_enqueue take it for "captured") */
 	/* LRSCV::initializePixVals, first call: It = I0 (LRSCV.cc:208-210) */
 	HIP_TRY(hipMemcpyAsync(b->d_rscv_it, b->buf[MTFHIP_BUF_I0], sizeof(double) * N * B, hipMemcpyDeviceToDevice, st));
 	/* the template's columns of the joint histograms: (int)I0 */

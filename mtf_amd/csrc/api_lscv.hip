@@ -62,17 +62,20 @@ int lscv_geometry(mtfhip_batch *b, size_t map_lds_budget) {
 	if ((double)(nb - 1) * (double)N >= 4294967296.0)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "init_template: %s with %zu sample points at %zu bins could overflow its u32 histogram sums", am, N, nb);
 	hipStream_t st = b->ctx->stream;
-	if (!b->d_lscv_cell) {
-		HIP_TRY(hipMalloc(&b->d_lscv_cell, sizeof(unsigned short) * N));
-		HIP_TRY(hipMalloc(&b->d_lscv_crng, sizeof(int) * 2 * (nx + ny)));
-		HIP_TRY(hipMalloc(&b->d_lscv_w, sizeof(double) * (size_t)R * N));
-		HIP_TRY(hipMalloc(&b->d_lscv_tot, sizeof(unsigned) * 2 * ncell * nb * B));
-		HIP_TRY(hipMalloc(&b->d_lscv_arrive, sizeof(unsigned) * B));
-		HIP_TRY(hipMalloc(&b->d_lscv_map, sizeof(double) * (size_t)R * nb * B));
-		HIP_TRY(hipMalloc(&b->d_lscv_aff, sizeof(double) * 2 * (size_t)R * B));
+	/* (d_lscv_cell, which set_lscv / set_lrscv take for "the geometry is fixed", arrives last: while it is null a failed call is simply
+	 * repeated, and the sums and counters are zeroed once the whole group is there) */
+	const bool first = !b->d_lscv_cell;
+	HIP_TRY(b->d_lscv_crng.reserve(2 * (size_t)(nx + ny)));
+	HIP_TRY(b->d_lscv_w.reserve((size_t)R * N));
+	HIP_TRY(b->d_lscv_tot.reserve(2 * ncell * nb * B));
+	HIP_TRY(b->d_lscv_arrive.reserve(B));
+	HIP_TRY(b->d_lscv_map.reserve((size_t)R * nb * B));
+	HIP_TRY(b->d_lscv_aff.reserve(2 * (size_t)R * B));
+	if (first) {
 		HIP_TRY(hipMemsetAsync(b->d_lscv_tot, 0, sizeof(unsigned) * 2 * ncell * nb * B, st));
 		HIP_TRY(hipMemsetAsync(b->d_lscv_arrive, 0, sizeof(unsigned) * B, st));
 	}
+	HIP_TRY(b->d_lscv_cell.reserve(N));
 	b->lscv_ncx = ncx; b->lscv_ncell = (int)ncell;
 	/* pixel i at (i % resx, i / resx): its cell, and sub_region_wts (LSCV.cc:170-197), computed as the reference does -- the centre
 	 * (start + end) / 2.0, the difference truncated toward zero, 1 / (1 + dx^2 + dy^2), each row divided by its sum taken idy outer,
@@ -114,10 +117,8 @@ int lscv_capture(mtfhip_batch *b) {
 	TRY(lscv_geometry(b, (size_t)kLscvLdsBudget));
 	const size_t B = (size_t)b->B, N = (size_t)b->N;
 	hipStream_t st = b->ctx->stream;
-	if (!b->d_lscv_i0) {
-		HIP_TRY(hipMalloc(&b->d_lscv_i0, sizeof(double) * N * B));
-		HIP_TRY(hipMalloc(&b->d_lscv_code, sizeof(unsigned short) * N * B));
-	}
+	HIP_TRY(b->d_lscv_code.reserve(N * B));
+	HIP_TRY(b->d_lscv_i0.reserve(N * B));   /* (last: lscv_enqueue takes it for "captured") */
 	/* I0_orig = I0 (LSCV.cc:232) and its bins */
 	HIP_TRY(hipMemcpyAsync(b->d_lscv_i0, b->buf[MTFHIP_BUF_I0], sizeof(double) * N * B, hipMemcpyDeviceToDevice, st));
 	launch_scv_codes(b->N, b->B, b->lscv_nb, b->d_lscv_i0, b->d_lscv_code, st);

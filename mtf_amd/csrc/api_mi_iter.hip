@@ -135,7 +135,7 @@ static int mi_enqueue_fast(mtfhip_batch *b, const mtfhip_sm_desc *sm, const MiPl
 	const int nblk = mi_blocks(b);
 	hipStream_t st = b->ctx->stream;
 	MiFastPlan fp = mi_fast_plan(b, pl, active, sm);
-	if (!b->d_mi_poly) HIP_TRY(hipMalloc(&b->d_mi_poly, sizeof(double) * (size_t)mi_poly_size(b->desc.mi_n_bins) * b->B));
+	HIP_TRY(b->d_mi_poly.reserve((size_t)mi_poly_size(b->desc.mi_n_bins) * b->B));
 	fp.poly = b->d_mi_poly;
 	const BatchView bv = b->view();
 	/* pass 1 holds 45.7 KB of LDS per workgroup: THREE workgroups per CU, so mi_blocks' ~4 per CU ran as one full round and a second one

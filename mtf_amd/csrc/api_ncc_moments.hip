@@ -120,7 +120,7 @@ int ncc_template_moments(mtfhip_batch *b) {
 	TRY(read_acc(b, nblk));
 	for (int t = 0; t < b->B; ++t) std::memcpy(b->th[t].ncc_gram0, b->h_acc + (size_t)t * ACC_COUNT + ACC_H, sizeof(double) * 36);
 	/* device copy for the device-side finish (k_finish_track) */
-	if (!b->d_ncc_tm) HIP_TRY(hipMalloc(&b->d_ncc_tm, sizeof(double) * 52 * (size_t)b->B));
+	HIP_TRY(b->d_ncc_tm.reserve(52 * (size_t)b->B));
 	std::vector<double> tm((size_t)52 * b->B);
 	for (int t = 0; t < b->B; ++t) {
 		std::memcpy(&tm[52 * (size_t)t], b->th[t].ncc_sj0, sizeof(double) * 8);
@@ -157,7 +157,7 @@ int ncc_lazy_outputs(mtfhip_batch *b, int trig, int j_a, bool hess_mean, double 
 	}
 	b->ncc_host_newer = true;
 	if (!L.no_cache) {
-		L.ncc_M.assign(b->h_acc, b->h_acc + (size_t)NCC_ACC_COUNT * b->B);
+		L.ncc_M.assign(b->h_acc.get(), b->h_acc + (size_t)NCC_ACC_COUNT * b->B);
 		L.ncc_M_mean = hess_mean;
 		L.ncc_M_it = L.ver[MTFHIP_BUF_IT]; L.ncc_M_jt = L.ver[MTFHIP_BUF_JT]; L.ncc_M_jm = L.ver[MTFHIP_BUF_JM];
 	}

@@ -6,18 +6,17 @@
 #include "mtfhip_nn_handle.h"
 
 static int nn_ensure_partials(mtfhip_nn *nn, int Q) {
-	if (Q <= nn->part_q) return MTFHIP_OK;
+	const size_t need = (size_t)Q * nn->nblk;
+	if (need <= nn->d_part.capacity()) return MTFHIP_OK;
 	HIP_TRY(hipStreamSynchronize(nn->b->ctx->stream));
-	if (nn->d_part) { (void)hipFree(nn->d_part); nn->d_part = nullptr; nn->part_q = 0; }
-	HIP_TRY(hipMalloc(&nn->d_part, sizeof(NnBest) * (size_t)Q * nn->nblk));
-	nn->part_q = Q;
+	HIP_TRY(nn->d_part.reserve(need));
 	return MTFHIP_OK;
 }
 static int nn_ensure_state(mtfhip_nn *nn, int max_iters) {
 	if (nn->d_state && max_iters <= nn->log_cap) return MTFHIP_OK;
 	HIP_TRY(hipStreamSynchronize(nn->b->ctx->stream));
-	if (nn->d_state) { (void)hipFree(nn->d_state); nn->d_state = nullptr; nn->log_cap = 0; }
-	HIP_TRY(hipMalloc(&nn->d_state, sizeof(double) * (size_t)(kNnStateDoubles + 1 + 4 * (size_t)max_iters)));
+	nn->d_state.reset(); nn->log_cap = 0;   /* (log_cap is the block's layout, not only its size: nn_walk_log) */
+	HIP_TRY(nn->d_state.reserve(kNnStateDoubles + 1 + 4 * (size_t)max_iters));
 	nn->log_cap = max_iters;
 	return MTFHIP_OK;
 }
@@ -55,10 +54,10 @@ int mtfhip_nn_create(mtfhip_batch *b, int n_samples, mtfhip_nn **out) {
 	nn->resident = nn_search_resident(nn->ncc, F);
 	nn->nblk = nn_search_blocks(n_samples, nn->resident);
 	auto cleanup = [&](int rc) { (void)mtfhip_nn_destroy(nn); return rc; };
-	if (hipMalloc(&nn->d_feat, sizeof(double) * (size_t)n_samples * F) != hipSuccess)
-		return cleanup(fail(MTFHIP_ERR_HIP, "nn_create: hipMalloc of the %d x %d feature matrix failed", n_samples, F));
-	if (hipMalloc(&nn->d_perts, sizeof(double) * (size_t)n_samples * nn->S) != hipSuccess || hipMalloc(&nn->d_query, sizeof(double) * (size_t)F) != hipSuccess)
-		return cleanup(fail(MTFHIP_ERR_HIP, "nn_create: hipMalloc failed"));
+	if (nn->d_feat.reserve((size_t)n_samples * F) != hipSuccess)
+		return cleanup(fail(MTFHIP_ERR_HIP, "nn_create: device allocation of the %d x %d feature matrix failed", n_samples, F));
+	if (nn->d_perts.reserve((size_t)n_samples * nn->S) != hipSuccess || nn->d_query.reserve((size_t)F) != hipSuccess)
+		return cleanup(fail(MTFHIP_ERR_HIP, "nn_create: device allocation failed"));
 	int rc = nn_ensure_partials(nn, 1);
 	if (rc == MTFHIP_OK) rc = nn_ensure_state(nn, 8);
 	if (rc != MTFHIP_OK) return cleanup(rc);
@@ -68,11 +67,11 @@ int mtfhip_nn_create(mtfhip_batch *b, int n_samples, mtfhip_nn **out) {
 
 int mtfhip_nn_destroy(mtfhip_nn *nn) {
 	if (!nn) return fail(MTFHIP_ERR_INVALID_ARG, "nn_destroy: NULL handle");
-	if (hipSetDevice(nn->device) == hipSuccess) (void)hipDeviceSynchronize();
-	(void)hipFree(nn->d_feat); (void)hipFree(nn->d_perts); (void)hipFree(nn->d_part); (void)hipFree(nn->d_query); (void)hipFree(nn->d_state);
-	(void)hipFree(nn->d_q); (void)hipFree(nn->d_idx); (void)hipFree(nn->d_dist);
-	gnn_free(nn);
-	delete nn;
+	try {
+		if (hipSetDevice(nn->device) == hipSuccess) (void)hipDeviceSynchronize();
+		delete nn;   /* the members, the graph index's included, release what they own */
+	} catch (...) {
+	}
 	return MTFHIP_OK;
 }
 
@@ -159,15 +158,13 @@ int mtfhip_nn_search(mtfhip_nn *nn, const double *queries, int n_queries, int *i
 	if (!queries || !idx || !dist) return fail(MTFHIP_ERR_INVALID_ARG, "nn_search: NULL argument");
 	TRY(nn_need_dataset(nn, "nn_search"));
 	hipStream_t st = nn->b->ctx->stream;
-	if (n_queries > nn->q_cap) {
-		HIP_TRY(hipStreamSynchronize(st));
-		(void)hipFree(nn->d_q); (void)hipFree(nn->d_idx); (void)hipFree(nn->d_dist);
-		nn->d_q = nullptr; nn->d_idx = nullptr; nn->d_dist = nullptr; nn->q_cap = 0;
-		HIP_TRY(hipMalloc(&nn->d_q, sizeof(double) * (size_t)n_queries * nn->F));
-		HIP_TRY(hipMalloc(&nn->d_idx, sizeof(int) * (size_t)n_queries));
-		HIP_TRY(hipMalloc(&nn->d_dist, sizeof(double) * (size_t)n_queries));
-		nn->q_cap = n_queries;
-	}
+	const size_t Q = (size_t)n_queries;
+	/* (every member is asked: one that a failed grow left empty is allocated again whatever the others hold) */
+	if (Q * nn->F > nn->d_q.capacity() || Q > nn->d_idx.capacity() || Q > nn->d_dist.capacity())
+		HIP_TRY(hipStreamSynchronize(st));   /* what is about to be released may still be read */
+	HIP_TRY(nn->d_q.reserve(Q * nn->F));
+	HIP_TRY(nn->d_idx.reserve(Q));
+	HIP_TRY(nn->d_dist.reserve(Q));
 	HIP_TRY(hipMemcpyAsync(nn->d_q, queries, sizeof(double) * (size_t)n_queries * nn->F, hipMemcpyHostToDevice, st));
 	TRY(mtfhip_nn_search_dev(nn, nn->d_q, n_queries, nn->d_idx, nn->d_dist));
 	HIP_TRY(hipMemcpyAsync(idx, nn->d_idx, sizeof(int) * (size_t)n_queries, hipMemcpyDeviceToHost, st));

@@ -98,40 +98,40 @@ struct mtfhip_pf {
 	unsigned prop_iter = 0;
 	long prop_corners_epoch = -1;
 	int pc = 0;
-	size_t wts_capacity = 0;
-	double *d_st = nullptr, *d_ar = nullptr;                                   /* the current (resampled) set */
-	double *d_prop[2] = {nullptr, nullptr}, *d_prop_ar[2] = {nullptr, nullptr}; /* proposals: this iteration's | the next one's */
-	double *d_wts = nullptr, *d_cum = nullptr, *d_chunk = nullptr, *d_out = nullptr, *d_normals = nullptr, *d_uniforms = nullptr;
-	double *d_parts = nullptr, *d_gparts = nullptr;   /* per-workgroup rows of the selection pass and their per-group folds */
+	Dev<double> d_st, d_ar;                 /* the current (resampled) set */
+	Dev<double> d_prop[2], d_prop_ar[2];    /* proposals: this iteration's | the next one's */
+	Dev<double> d_wts, d_cum, d_chunk, d_out, d_normals, d_uniforms;
+	Dev<double> d_parts, d_gparts;   /* per-workgroup rows of the selection pass and their per-group folds */
 	/* perturbations drawn ahead (PfSelectPlan): buffer q holds those of iteration pert_iter[q] (-1: none) for the template corners of
 	 * pert_epoch[q] and the sampler of pert_gen[q]; the selection pass of iteration t reads buffer (t + 1) & 1 and fills t & 1 with t + 2's */
-	double *d_pert[2] = {nullptr, nullptr};
+	Dev<double> d_pert[2];
 	long pert_iter[2] = {-1, -1}, pert_epoch[2] = {-1, -1};
 	unsigned pert_gen[2] = {0, 0}, sampler_gen = 0;
-	int *d_ids = nullptr, *d_counters = nullptr;
+	Dev<int> d_ids, d_counters;
 	/* residual resampling (PF.cc:538-582): sort keys in / out, particle order in / out, copies, their starts, hipCUB's scratch */
-	double *d_res_keys = nullptr;
-	int *d_res_idx = nullptr;
-	void *d_res_tmp = nullptr; size_t res_tmp_bytes = 0;
+	Dev<double> d_res_keys;
+	Dev<int> d_res_idx;
+	Dev<unsigned char> d_res_tmp;
 	double prev_corners[8];
 	/* several sampler distributions + adaptive resampling (PF.cc:240-269, 345-390): d_distr = sigma [8][8] | mean [8][8] | running sums
 	 * of the distribution weights [8] | the weights [8]; the particles' distribution ids; the scan's per-chunk statistics; its verdict
 	 * "this iteration resamples"; the next iteration's distribution draws when the caller hands them in */
 	int n_distr = 1;
-	double *d_distr = nullptr, *d_scan_stats = nullptr, *d_distr_u = nullptr;
-	int *d_distr_ids = nullptr, *d_resample_flag = nullptr;
+	Dev<double> d_distr, d_scan_stats, d_distr_u;
+	Dev<int> d_distr_ids, d_resample_flag;
 	std::vector<double> distr_u_next;
 	/* the peer-store exchange (mtfhip_pf_set_exchange; PfPeerPush / PfPeerWait in mtfhip_internal.h).  mailbox: header (counters[kPfMaxPeers] |
 	 * the storing launch's own arrival counter | seed | n | cap) | wts[2][cap] doubles; base[q]: rank q's mailbox as this process addresses it (own rank: mailbox; RCCL ranks: an IPC mapping;
 	 * loopback ranks: the pointer itself) */
 	struct Peer {
 		bool on = false;
-		void *mailbox = nullptr;
+		Owned<unsigned char, FineGrainedMem> mailbox;
 		size_t cap = 0;
-		void *base[kPfMaxPeers] = {};
+		void *base[kPfMaxPeers] = {};   /* views: our mailbox, the IPC mappings of the others' (closed by mtfhip_pf_destroy) or their pointers */
 		bool mapped[kPfMaxPeers] = {};
 		unsigned long long epoch = 0, expected[kPfMaxPeers] = {};
-		int *h_err = nullptr, *h_err_dev = nullptr;
+		Pinned<int, hipHostMallocMapped> h_err;
+		int *h_err_dev = nullptr;   /* a view: h_err's device address */
 		/* a FIXED-SIZE header in front of the two weight vectors -- counters[kPfMaxPeers] | the storing launch's own arrival counter | the
 		 * filter's seed | its particle count | its vector capacity -- so that a rank can read what a peer was created with BEFORE it
 		 * addresses anything whose position depends on it (r04 advisor: ranks created with different n_particles / capacities stored
@@ -139,7 +139,8 @@ struct mtfhip_pf {
 		static constexpr int kHeadWords = (kPfMaxPeers + 4 + 15) & ~15;   /* whole 128-byte lines: the vectors stay line aligned */
 		double *wts(int q, int parity) const { return static_cast<double *>(base[q]) + kHeadWords + (size_t)parity * cap; }
 		unsigned long long *counters(int q) const { return static_cast<unsigned long long *>(base[q]); }
-		unsigned long long *seed_slot(int q) const { return counters(q) + kPfMaxPeers + 1; }   /* seed | n_particles | cap */
+		static unsigned long long *seed_slot_of(void *mailbox_base) { return static_cast<unsigned long long *>(mailbox_base) + kPfMaxPeers + 1; }
+		unsigned long long *seed_slot(int q) const { return seed_slot_of(base[q]); }   /* seed | n_particles | cap */
 	} peer;
 	/* the weights of the last iteration: the mailbox vector of the last exchange, or d_wts */
 	double *last_wts() const { return peer.on && peer.epoch ? peer.wts(comm->rank, (int)(peer.epoch & 1)) : d_wts; }
@@ -255,15 +256,6 @@ int mtfhip_allgather_scores(mtfhip_comm *c, const double *dev_send, int count, d
 }
 
 /* ------------------------------------------------------------------ the particle filter */
-static void pf_free(mtfhip_pf *pf) {
-	void *ptrs[] = {pf->d_st, pf->d_ar, pf->d_prop[0], pf->d_prop[1], pf->d_prop_ar[0], pf->d_prop_ar[1], pf->d_wts, pf->d_cum, pf->d_chunk, pf->d_out,
-		pf->d_normals, pf->d_uniforms, pf->d_ids, pf->d_parts, pf->d_gparts, pf->d_counters, pf->d_res_keys, pf->d_res_idx, pf->d_res_tmp,
-		pf->d_distr, pf->d_scan_stats, pf->d_distr_u, pf->d_distr_ids, pf->d_resample_flag, pf->d_pert[0], pf->d_pert[1]};
-	for (void *p : ptrs) if (p) (void)hipFree(p);
-	for (int q = 0; q < kPfMaxPeers; ++q) if (pf->peer.mapped[q]) (void)hipIpcCloseMemHandle(pf->peer.base[q]);
-	if (pf->peer.mailbox) (void)hipFree(pf->peer.mailbox);
-	if (pf->peer.h_err) (void)hipHostFree(pf->peer.h_err);
-}
 /* which sampler the (SSM, update type, dynamic model, sampling switches) combination selects -- and which combinations the
  * reference itself refuses */
 static int pf_pick_sampler(const mtfhip_batch *b, const mtfhip_pf_desc *d, int *sampler, int *nz) {
@@ -302,38 +294,34 @@ int mtfhip_pf_create(mtfhip_batch *b, const mtfhip_pf_desc *d, mtfhip_pf **out) 
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "pf_create: MI particles are scored with up to 10 bins (multi-channel: 8)");
 	int sampler = 0, nz = 0;
 	TRY(pf_pick_sampler(b, d, &sampler, &nz));
-	mtfhip_pf *pf = new mtfhip_pf;
+	std::unique_ptr<mtfhip_pf> pf(new mtfhip_pf);   /* (a return below releases whatever the filter holds by then) */
 	pf->b = b; pf->d = *d; pf->n = d->n_particles; pf->S = b->S; pf->sampler = sampler; pf->nz = nz;
 	{ const char *e = std::getenv("MTFHIP_PF_LOOKAHEAD"); pf->lookahead_enabled = !(e && e[0] == '0'); }
 	{ const char *e = std::getenv("MTFHIP_PF_LOCAL"); pf->local_enabled = !(e && e[0] == '0'); }
 	{ const char *e = std::getenv("MTFHIP_PF_SKIP_ESTIMATE"); pf->skip_unread_estimates = !(e && e[0] == '0'); }
 	{ const char *e = std::getenv("MTFHIP_PF_PERT_AHEAD"); pf->pert_ahead_enabled = !(e && e[0] == '0'); }
 	const size_t nS = (size_t)pf->n * pf->S, n = (size_t)pf->n, npad = pf_round_chunk(n), nch = npad / (size_t)pf_chunk();
-	bool okm = true;
-	auto A = [&](auto &p, size_t bytes) { if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) okm = false; };
-	A(pf->d_st, sizeof(double) * nS); A(pf->d_ar, sizeof(double) * nS);
-	for (int k = 0; k < 2; ++k) { A(pf->d_prop[k], sizeof(double) * nS); A(pf->d_prop_ar[k], sizeof(double) * nS); }
-	for (int k = 0; k < 2; ++k) A(pf->d_pert[k], sizeof(double) * 8 * n);
-	A(pf->d_wts, sizeof(double) * npad); pf->wts_capacity = npad;
-	A(pf->d_cum, sizeof(double) * npad); A(pf->d_chunk, sizeof(double) * (2 + 16) * nch);   /* chunk totals | their prefix | sub-block sums */
+	HIP_TRY(pf->d_st.reserve(nS)); HIP_TRY(pf->d_ar.reserve(nS));
+	for (int k = 0; k < 2; ++k) { HIP_TRY(pf->d_prop[k].reserve(nS)); HIP_TRY(pf->d_prop_ar[k].reserve(nS)); }
+	for (int k = 0; k < 2; ++k) HIP_TRY(pf->d_pert[k].reserve(8 * n));
+	HIP_TRY(pf->d_wts.reserve(npad));
+	HIP_TRY(pf->d_cum.reserve(npad)); HIP_TRY(pf->d_chunk.reserve((2 + 16) * nch));   /* chunk totals | their prefix | sub-block sums */
 	const size_t nblk = (n + 255) / 256, ngrp = (nblk + 63) / 64;
-	A(pf->d_out, sizeof(double) * 32); A(pf->d_parts, sizeof(double) * pf_parts_per_block() * nblk); A(pf->d_gparts, sizeof(double) * pf_parts_per_block() * ngrp);
-	A(pf->d_normals, sizeof(double) * n * 10); A(pf->d_uniforms, sizeof(double) * n); A(pf->d_ids, sizeof(int) * n); A(pf->d_counters, sizeof(int) * (2 + ngrp));
-	if (okm && hipMemsetAsync(pf->d_counters, 0, sizeof(int) * (2 + ngrp), b->ctx->stream) != hipSuccess) okm = false;
+	HIP_TRY(pf->d_out.reserve(32)); HIP_TRY(pf->d_parts.reserve(pf_parts_per_block() * nblk)); HIP_TRY(pf->d_gparts.reserve(pf_parts_per_block() * ngrp));
+	HIP_TRY(pf->d_normals.reserve(n * 10)); HIP_TRY(pf->d_uniforms.reserve(n)); HIP_TRY(pf->d_ids.reserve(n)); HIP_TRY(pf->d_counters.reserve(2 + ngrp));
+	HIP_TRY(hipMemsetAsync(pf->d_counters, 0, sizeof(int) * (2 + ngrp), b->ctx->stream));
 	if (d->resampling_type == 3) {
-		A(pf->d_res_keys, sizeof(double) * 2 * n); A(pf->d_res_idx, sizeof(int) * 4 * n);   /* keys in | out ; idx in | order | copies | starts */
+		HIP_TRY(pf->d_res_keys.reserve(2 * n)); HIP_TRY(pf->d_res_idx.reserve(4 * n));   /* keys in | out ; idx in | order | copies | starts */
 		size_t t1 = 0, t2 = 0;
 		(void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, t1, (const double *)nullptr, (double *)nullptr, (const int *)nullptr, (int *)nullptr, (int)n);
 		(void)hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (const int *)nullptr, (int *)nullptr, (int)n);
-		pf->res_tmp_bytes = std::max(t1, t2) + 256;
-		A(pf->d_res_tmp, pf->res_tmp_bytes);
+		HIP_TRY(pf->d_res_tmp.reserve(std::max(t1, t2) + 256));
 	}
-	if (okm && hipMemsetAsync(pf->d_out, 0, sizeof(double) * 32, b->ctx->stream) != hipSuccess) okm = false;
+	HIP_TRY(hipMemsetAsync(pf->d_out, 0, sizeof(double) * 32, b->ctx->stream));
 	if (d->adaptive_resampling_thresh > 0 && d->adaptive_resampling_thresh <= 1) {   /* PF.cc:114-118 */
-		A(pf->d_scan_stats, sizeof(double) * 17 * nch); A(pf->d_resample_flag, sizeof(int));
+		HIP_TRY(pf->d_scan_stats.reserve(17 * nch)); HIP_TRY(pf->d_resample_flag.reserve(1));
 	}
-	if (!okm) { pf_free(pf); delete pf; return fail(MTFHIP_ERR_HIP, "pf_create: hipMalloc failed"); }
-	*out = pf;
+	*out = pf.release();
 	return MTFHIP_OK;
 }
 /* PFParams::processDistributions + nt::PF's state_sigma / state_mean (PFParams.cc:101-170, PF.cc:55-56, 96-97): n_distr sampler
@@ -348,12 +336,12 @@ int mtfhip_pf_set_distributions(mtfhip_pf *pf, int n_distr, const double *sigma,
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "pf_set_distributions: several distributions need update_distr_wts (the reference divides by a zero weight sum without it, PF.cc:241-257)");
 	hipStream_t st = pf->b->ctx->stream;
 	const size_t n = (size_t)pf->n, nch = pf_round_chunk(n) / (size_t)pf_chunk();
-	if (!pf->d_distr) HIP_TRY(hipMalloc(&pf->d_distr, sizeof(double) * (64 + 64 + 8 + 8)));
+	HIP_TRY(pf->d_distr.reserve(64 + 64 + 8 + 8));
 	if (n_distr > 1) {
-		if (!pf->d_scan_stats) HIP_TRY(hipMalloc(&pf->d_scan_stats, sizeof(double) * 17 * nch));
-		if (!pf->d_resample_flag) HIP_TRY(hipMalloc(&pf->d_resample_flag, sizeof(int)));
-		if (!pf->d_distr_ids) HIP_TRY(hipMalloc(&pf->d_distr_ids, sizeof(int) * n));
-		if (!pf->d_distr_u) HIP_TRY(hipMalloc(&pf->d_distr_u, sizeof(double) * n));
+		HIP_TRY(pf->d_scan_stats.reserve(17 * nch));
+		HIP_TRY(pf->d_resample_flag.reserve(1));
+		HIP_TRY(pf->d_distr_ids.reserve(n));
+		HIP_TRY(pf->d_distr_u.reserve(n));
 	}
 	double h[144];
 	std::memset(h, 0, sizeof(h));
@@ -398,8 +386,11 @@ int mtfhip_pf_get_distributions(mtfhip_pf *pf, double *wts, int *ids, int *resam
 }
 void mtfhip_pf_destroy(mtfhip_pf *pf) {
 	if (!pf) return;
-	pf_free(pf);
-	delete pf;
+	try {
+		for (int q = 0; q < kPfMaxPeers; ++q) if (pf->peer.mapped[q]) (void)hipIpcCloseMemHandle(pf->peer.base[q]);   /* (the others' mailboxes: mappings, not allocations of ours) */
+		delete pf;   /* the members release what they own */
+	} catch (...) {
+	}
 }
 /* shard the scoring over the communicator: rank r scores particles [r m, (r + 1) m), m = ceil(n / R), and one in-place all-gather
  * distributes the weights; proposals and resampling are replicated (identical draws and identical weights on every rank) */
@@ -412,11 +403,9 @@ int mtfhip_pf_set_comm(mtfhip_pf *pf, mtfhip_comm *c) {
 		int lo, cnt, m;
 		pf_shard(pf->n, c->world, c->rank, &lo, &cnt, &m);
 		const size_t need = std::max(pf_round_chunk((size_t)pf->n), (size_t)m * c->world);
-		if (need > pf->wts_capacity) {
+		if (need > pf->d_wts.capacity()) {
 			HIP_TRY(hipStreamSynchronize(pf->b->ctx->stream));
-			(void)hipFree(pf->d_wts); pf->d_wts = nullptr;
-			HIP_TRY(hipMalloc(&pf->d_wts, sizeof(double) * need));
-			pf->wts_capacity = need;
+			HIP_TRY(pf->d_wts.reserve(need));
 		}
 		/* Every rank scores a block of ITS OWN proposals and resamples from the gathered weights: the design relies on the ranks
 		 * drawing identical proposals, i.e. on one Philox key.  One 8-byte all-gather at set-up makes a mismatch an error instead of a
@@ -466,17 +455,20 @@ static int pf_peer_alloc(mtfhip_pf *pf) {
 	hipStream_t st = pf->b->ctx->stream;
 	int lo, cnt, m;
 	pf_shard(pf->n, c->world, c->rank, &lo, &cnt, &m);
-	pr.cap = (std::max(pf->wts_capacity, (size_t)m * c->world) + 1) & ~(size_t)1;
-	const size_t bytes = sizeof(double) * 2 * pr.cap + sizeof(unsigned long long) * mtfhip_pf::Peer::kHeadWords;
-	HIP_TRY(hipExtMallocWithFlags(&pr.mailbox, bytes, hipDeviceMallocFinegrained));
-	HIP_TRY(hipMemsetAsync(pr.mailbox, 0, bytes, st));
-	pr.base[c->rank] = pr.mailbox;
-	const unsigned long long ident[3] = {pf->d.seed, (unsigned long long)pf->n, (unsigned long long)pr.cap};
-	HIP_TRY(hipMemcpyAsync(pr.seed_slot(c->rank), ident, sizeof(ident), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&pr.h_err), sizeof(int), hipHostMallocMapped));
+	/* (h_err first and pr.mailbox, which everything else takes for "set up", last: while it is null a failed call is simply repeated) */
+	HIP_TRY(pr.h_err.reserve(1));
 	*pr.h_err = 0;
 	HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&pr.h_err_dev), pr.h_err, 0));
+	pr.cap = (std::max(pf->d_wts.capacity(), (size_t)m * c->world) + 1) & ~(size_t)1;
+	const size_t bytes = sizeof(double) * 2 * pr.cap + sizeof(unsigned long long) * mtfhip_pf::Peer::kHeadWords;
+	decltype(pr.mailbox) box;
+	HIP_TRY(box.reserve(bytes));
+	HIP_TRY(hipMemsetAsync(box, 0, bytes, st));
+	const unsigned long long ident[3] = {pf->d.seed, (unsigned long long)pf->n, (unsigned long long)pr.cap};
+	HIP_TRY(hipMemcpyAsync(mtfhip_pf::Peer::seed_slot_of(box.get()), ident, sizeof(ident), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipStreamSynchronize(st));   /* the counters are zero and the seed is in place before anybody can learn where they are */
+	pr.mailbox = std::move(box);
+	pr.base[c->rank] = pr.mailbox;
 	return MTFHIP_OK;
 }
 /* every base[] is in place: the ranks must have been created with one seed (identical proposals: see mtfhip_pf_set_comm) */
@@ -550,16 +542,13 @@ int mtfhip_pf_set_exchange(mtfhip_pf *pf, int mode) {
 	static_assert(sizeof(hipIpcMemHandle_t) % sizeof(double) == 0, "the handle travels as doubles over the weight all-gather");
 	constexpr int hw = (int)(sizeof(hipIpcMemHandle_t) / sizeof(double));
 	HIP_TRY(hipIpcGetMemHandle(&mine, pr.mailbox));
-	double *d_h = nullptr;
-	HIP_TRY(hipMalloc(&d_h, sizeof(hipIpcMemHandle_t) * (size_t)c->world));
+	Dev<double> d_h;
+	HIP_TRY(d_h.reserve((size_t)hw * c->world));
 	std::vector<hipIpcMemHandle_t> all((size_t)c->world);
-	int rc = MTFHIP_OK;
-	if (hipMemcpyAsync(d_h + (size_t)c->rank * hw, &mine, sizeof(mine), hipMemcpyHostToDevice, st) != hipSuccess) rc = MTFHIP_ERR_HIP;
-	if (rc == MTFHIP_OK) rc = mtfhip_allgather_scores(c, d_h + (size_t)c->rank * hw, hw, d_h, st);
-	if (rc == MTFHIP_OK && hipMemcpyAsync(all.data(), d_h, sizeof(hipIpcMemHandle_t) * (size_t)c->world, hipMemcpyDeviceToHost, st) != hipSuccess) rc = MTFHIP_ERR_HIP;
-	if (rc == MTFHIP_OK && hipStreamSynchronize(st) != hipSuccess) rc = MTFHIP_ERR_HIP;
-	(void)hipFree(d_h);
-	if (rc != MTFHIP_OK) return fail(rc, "pf_set_exchange: the exchange of the mailbox handles failed");
+	HIP_TRY(hipMemcpyAsync(d_h + (size_t)c->rank * hw, &mine, sizeof(mine), hipMemcpyHostToDevice, st));
+	TRY(mtfhip_allgather_scores(c, d_h + (size_t)c->rank * hw, hw, d_h, st));
+	HIP_TRY(hipMemcpyAsync(all.data(), d_h, sizeof(hipIpcMemHandle_t) * (size_t)c->world, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
 	return mtfhip_pf_exchange_connect(pf, all.data());
 }
 /* ProjectiveBase::setSampler (ProjectiveBase.cc:208-215) */
@@ -633,7 +622,7 @@ static int pf_residual_sources(mtfhip_pf *pf, PfBuffers &bf, size_t nch, hipStre
 	const double *total = bf.chunk_incl + (nch - 1);   /* particle_cum_wts[n - 1] */
 	launch_pf_residual_prep(n, total, bf.wts, keys_in, idx_in, bf.resample_flag, st);
 	if (n > 1) {
-		size_t tb = pf->res_tmp_bytes;
+		size_t tb = pf->d_res_tmp.capacity();
 		/* std::sort(idx, idx + n - 1, wts[a] > wts[b]): the last index is not part of the range */
 		if (hipcub::DeviceRadixSort::SortPairsDescending(pf->d_res_tmp, tb, (const double *)keys_in, keys_out, (const int *)idx_in, order, n - 1, 0, 64, st) != hipSuccess)
 			return fail(MTFHIP_ERR_HIP, "pf_iteration: radix sort of the particle weights failed");
@@ -641,7 +630,7 @@ static int pf_residual_sources(mtfhip_pf *pf, PfBuffers &bf, size_t nch, hipStre
 	HIP_TRY(hipMemcpyAsync(order + (n - 1), idx_in + (n - 1), sizeof(int), hipMemcpyDeviceToDevice, st));
 	launch_pf_residual_copies(n, bf.wts, order, copies, st);
 	{
-		size_t tb = pf->res_tmp_bytes;
+		size_t tb = pf->d_res_tmp.capacity();
 		if (hipcub::DeviceScan::ExclusiveSum(pf->d_res_tmp, tb, (const int *)copies, starts, n, st) != hipSuccess)
 			return fail(MTFHIP_ERR_HIP, "pf_iteration: scan of the copy counts failed");
 	}
@@ -814,7 +803,7 @@ static int pf_collect_estimate(mtfhip_pf *pf, unsigned long long pub_seq, double
 		HIP_TRY(hipMemcpyAsync(out, pf->d_out, sizeof(out), hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
 	}
-	if (pf->peer.on && pf->peer.h_err && __atomic_load_n(pf->peer.h_err, __ATOMIC_ACQUIRE) != 0)
+	if (pf->peer.on && pf->peer.h_err && __atomic_load_n(pf->peer.h_err.get(), __ATOMIC_ACQUIRE) != 0)
 		return fail(MTFHIP_ERR_HIP, "pf_iteration: rank %d gave up waiting for another rank's weights (peer-store exchange): the estimate is not valid", pf->comm ? pf->comm->rank : 0);
 	if (pf->d.mean_type == 2) TRY(mtfhip_ssm_set_corners(b, out + 10));
 	else TRY(mtfhip_ssm_set_state(b, out));

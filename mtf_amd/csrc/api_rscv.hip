@@ -12,16 +12,19 @@
 int rscv_capture(mtfhip_batch *b) {
 	const size_t B = (size_t)b->B, N = (size_t)b->N, nb = (size_t)b->rscv_nb;
 	hipStream_t st = b->ctx->stream;
-	if (!b->d_rscv_code) {
-		HIP_TRY(hipMalloc(&b->d_rscv_code, N * B));
-		HIP_TRY(hipMalloc(&b->d_rscv_part, sizeof(unsigned) * (size_t)rscv_hist_blocks(b->N) * 2 * nb * B));
-		HIP_TRY(hipMalloc(&b->d_rscv_arrive, sizeof(unsigned) * B));
-		HIP_TRY(hipMalloc(&b->d_rscv_map, sizeof(double) * nb * B));
-		HIP_TRY(hipMalloc(&b->d_rscv_it, sizeof(double) * N * B));
+	/* (d_rscv_code, which everything else takes for "captured", arrives last: while it is null a failed call is simply repeated, and what
+	 * belongs to the first call runs once the whole group is there) */
+	const bool first = !b->d_rscv_code;
+	HIP_TRY(b->d_rscv_part.reserve((size_t)rscv_hist_blocks(b->N) * 2 * nb * B));
+	HIP_TRY(b->d_rscv_arrive.reserve(B));
+	HIP_TRY(b->d_rscv_map.reserve(nb * B));
+	HIP_TRY(b->d_rscv_it.reserve(N * B));
+	if (first) {
 		HIP_TRY(hipMemsetAsync(b->d_rscv_arrive, 0, sizeof(unsigned) * B, st));
 		/* RSCV::initializePixVals, first call: It = I0, It_orig = It (RSCV.cc:158-162) */
 		HIP_TRY(hipMemcpyAsync(b->d_rscv_it, b->buf[MTFHIP_BUF_I0], sizeof(double) * N * B, hipMemcpyDeviceToDevice, st));
 	}
+	HIP_TRY(b->d_rscv_code.reserve(N * B));
 	/* the template's columns of the joint histogram: (int)I0 */
 	launch_rscv_codes(b->N, b->B, b->rscv_nb, b->buf[MTFHIP_BUF_I0], b->d_rscv_code, st);
 	/* before the first updatePixVals the map is the identity of the bins (what the empty-bin rule gives) */

@@ -11,12 +11,11 @@
 int scv_capture(mtfhip_batch *b) {
 	const size_t B = (size_t)b->B, N = (size_t)b->N, nb = (size_t)b->scv_nb;
 	hipStream_t st = b->ctx->stream;
-	if (!b->d_scv_i0) {
-		HIP_TRY(hipMalloc(&b->d_scv_i0, sizeof(double) * N * B));
-		HIP_TRY(hipMalloc(&b->d_scv_code, sizeof(unsigned short) * N * B));
-		HIP_TRY(hipMalloc(&b->d_scv_part, sizeof(double) * (size_t)scv_hist_blocks(b->N) * 2 * nb * B));
-		HIP_TRY(hipMalloc(&b->d_scv_map, sizeof(double) * nb * B));
-	}
+	/* (d_scv_i0, which scv_enqueue takes for "captured", arrives last: while it is null a failed call is simply repeated) */
+	HIP_TRY(b->d_scv_code.reserve(N * B));
+	HIP_TRY(b->d_scv_part.reserve((size_t)scv_hist_blocks(b->N) * 2 * nb * B));
+	HIP_TRY(b->d_scv_map.reserve(nb * B));
+	HIP_TRY(b->d_scv_i0.reserve(N * B));
 	/* I0_orig = I0 (SCV.cc:166) */
 	HIP_TRY(hipMemcpyAsync(b->d_scv_i0, b->buf[MTFHIP_BUF_I0], sizeof(double) * N * B, hipMemcpyDeviceToDevice, st));
 	launch_scv_codes(b->N, b->B, b->scv_nb, b->d_scv_i0, b->d_scv_code, st);

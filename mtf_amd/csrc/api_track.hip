@@ -29,7 +29,7 @@ int loop_upload_slab(mtfhip_batch *b, hipStream_t st, bool keep_ncc, const LoopW
 }
 /* per-target LM state: prev_similarity 0, leven_marq_delta = lm_delta_init, no pending reset, iteration 0 */
 int loop_lm_state(mtfhip_batch *b, const mtfhip_sm_desc *sm, hipStream_t st, double **lm) {
-	if (!b->d_lm) HIP_TRY(hipMalloc(&b->d_lm, sizeof(double) * kLmStride * (size_t)b->B));
+	HIP_TRY(b->d_lm.reserve(kLmStride * (size_t)b->B));
 	std::vector<double> lm0((size_t)kLmStride * b->B, 0.0);
 	for (int t = 0; t < b->B; ++t) lm0[(size_t)kLmStride * t + 1] = sm->lm_delta_init;
 	HIP_TRY(hipMemcpyAsync(b->d_lm, lm0.data(), sizeof(double) * lm0.size(), hipMemcpyHostToDevice, st));
@@ -194,8 +194,10 @@ static void persist_decomposition(const mtfhip_batch *b, int &nblk, int &rows) {
 /* the arrival / barrier words of the persistent and the one-launch-per-pass kernels: zero between launches */
 static int ensure_persist_words(mtfhip_batch *b, hipStream_t st) {
 	if (b->d_persist) return MTFHIP_OK;
-	HIP_TRY(hipMalloc(&b->d_persist, 2 * sizeof(int) * (size_t)b->B));
-	HIP_TRY(hipMemsetAsync(b->d_persist, 0, 2 * sizeof(int) * (size_t)b->B, st));
+	HIP_TRY(b->d_persist.reserve(2 * (size_t)b->B));
+	const hipError_t e = hipMemsetAsync(b->d_persist, 0, 2 * sizeof(int) * (size_t)b->B, st);
+	if (e != hipSuccess) b->d_persist.reset();   /* (not zeroed is not there: the next call starts over) */
+	HIP_TRY(e);
 	return MTFHIP_OK;
 }
 static unsigned long long persist_timeout_ticks() {   /* 100 MHz ticks; MTFHIP_PERSIST_TIMEOUT_US for tests (default 20 ms) */
@@ -360,7 +362,7 @@ static int track_loop_persist(mtfhip_batch *b, const mtfhip_sm_desc *sm, const F
 	persist_decomposition(b, nblk_p, rows_p);
 	FusedArgs fp = fa;
 	fp.rows_per_block = rows_p;
-	PersistState ps{b->d_persist, reinterpret_cast<unsigned *>(b->d_persist) + b->B, b->persist_gen, persist_timeout_ticks()};
+	PersistState ps{b->d_persist, reinterpret_cast<unsigned *>(b->d_persist.get()) + b->B, b->persist_gen, persist_timeout_ticks()};
 	b->persist_gen += (unsigned)cx.max_passes + 1u;
 	TimedScope tsc(b->ctx, "track_persist");
 	launch_track_persist(b->view(), b->ctx->img, fp, *sm, ts, b->d_partials, nblk_p, ps, cx.max_passes, st);
@@ -423,15 +425,15 @@ static double track_phase_frac() {
 	return e_ph ? std::atof(e_ph) : 0.35;
 }
 static void track_phase_words(mtfhip_ctx *c) {
-	if (!c->d_phase && hipMalloc(&c->d_phase, sizeof(unsigned long long) * 4) != hipSuccess) { (void)hipGetLastError(); c->d_phase = nullptr; }
+	if (c->d_phase.reserve(4) != hipSuccess) (void)hipGetLastError();
 }
 static int track_open_queues(mtfhip_batch *b, int n_streams, double &phase_frac) {
 	mtfhip_ctx *c = b->ctx;
 	if (n_streams >= 2) {
-		if (!c->ev_fork && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); n_streams = 1; }
+		if (!c->ev_fork && c->ev_fork.create(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); n_streams = 1; }
 		for (int q = 0; q + 1 < n_streams; ++q)
-			if (!c->extra_streams[q] && (hipStreamCreateWithFlags(&c->extra_streams[q], hipStreamNonBlocking) != hipSuccess ||
-				hipEventCreateWithFlags(&c->ev_join[q], hipEventDisableTiming) != hipSuccess)) { (void)hipGetLastError(); n_streams = 1; break; }
+			if (!(c->extra_streams[q] && c->ev_join[q]) && (c->extra_streams[q].create(hipStreamNonBlocking) != hipSuccess ||
+				c->ev_join[q].create(hipEventDisableTiming) != hipSuccess)) { (void)hipGetLastError(); n_streams = 1; break; }
 	}
 	phase_frac = track_phase_frac();
 	if (n_streams == 2 && phase_frac > 0) {
@@ -524,8 +526,8 @@ static int track_loop_chunked(mtfhip_batch *b, const mtfhip_sm_desc *sm, const F
 	/* deferred materialisation (track_defers_materialisation): the passes before the last run the lean kernel */
 	const bool defer = track_defers_materialisation(b, sm, fa, cx.so_term, cx.resume, use_step);
 	if (defer || ts.keep_last) {
-		if (!b->d_last_ws) HIP_TRY(hipMalloc(&b->d_last_ws, sizeof(double) * 17 * (size_t)b->B));
-		if (!b->d_need_mat) HIP_TRY(hipMalloc(&b->d_need_mat, sizeof(int) * (size_t)b->B));
+		HIP_TRY(b->d_last_ws.reserve(17 * (size_t)b->B));
+		HIP_TRY(b->d_need_mat.reserve((size_t)b->B));
 		if (!cx.words_ready) HIP_TRY(hipMemsetAsync(b->d_need_mat, 0, sizeof(int) * (size_t)b->B, st));
 	}
 	/* the later queue's start-up delay: a quarter of the period of the pass kind that runs.  Materialising passes are store-bound (130 B per pixel
@@ -655,10 +657,10 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 		/* (the flags only for a call that can defer -- the one-launch-per-pass form, decided with the queues, may still turn it down: the
 		 * flags are then zeroed for nothing; the stamps only where two queues will use them; words that exist from earlier calls cost nothing) */
 		if (track_defers_materialisation(b, sm, fa, cx.so_term, resume, false)) {
-			if (!b->d_last_ws) HIP_TRY(hipMalloc(&b->d_last_ws, sizeof(double) * 17 * (size_t)b->B));
-			if (!b->d_need_mat) HIP_TRY(hipMalloc(&b->d_need_mat, sizeof(int) * (size_t)b->B));
+			HIP_TRY(b->d_last_ws.reserve(17 * (size_t)b->B));
+			HIP_TRY(b->d_need_mat.reserve((size_t)b->B));
 		}
-		if (sm->leven_marq && !b->d_lm) HIP_TRY(hipMalloc(&b->d_lm, sizeof(double) * kLmStride * (size_t)b->B));
+		if (sm->leven_marq) HIP_TRY(b->d_lm.reserve(kLmStride * (size_t)b->B));
 		if (track_queues(b, fa) == 2 && track_phase_frac() > 0) track_phase_words(b->ctx);
 		lw = LoopWords{b->d_need_mat, b->d_need_mat ? b->B : 0, b->ctx->d_phase, sm->leven_marq ? b->d_lm : nullptr, b->B, sm->lm_delta_init, b->d_fin_count};
 		cx.words_ready = true;
@@ -734,10 +736,10 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 int mtfhip_batch_track_trace(mtfhip_batch *b, int max_passes) {
 	if (!b || max_passes < 0) return fail(MTFHIP_ERR_INVALID_ARG, "track_trace: invalid argument");
 	HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-	if (b->d_trace) { (void)hipFree(b->d_trace); b->d_trace = nullptr; }
-	b->trace_cap = max_passes;
+	b->d_trace.reset(); b->trace_cap = 0;
 	if (max_passes > 0) {
-		HIP_TRY(hipMalloc(&b->d_trace, sizeof(double) * kTraceStride * (size_t)max_passes * b->B));
+		HIP_TRY(b->d_trace.reserve(kTraceStride * (size_t)max_passes * b->B));
+		b->trace_cap = max_passes;
 		HIP_TRY(hipMemsetAsync(b->d_trace, 0, sizeof(double) * kTraceStride * (size_t)max_passes * b->B, b->ctx->stream));
 	}
 	return MTFHIP_OK;

@@ -124,17 +124,16 @@ bool kernarg_layout_verified(hipStream_t st) {
 	static int state = -1;   /* -1 not asked, 0 no, 1 yes */
 	if (state >= 0) return state == 1;
 	state = 0;
-	double *d_out = nullptr;
-	if (hipMalloc(&d_out, sizeof(double) * 18) != hipSuccess) { (void)hipGetLastError(); return false; }
+	Dev<double> d_out;
+	if (d_out.reserve(18) != hipSuccess) { (void)hipGetLastError(); return false; }
 	BatchView bv{}; ImgView im{}; FusedArgs fa{};
 	bv.B = 1; im.w = 2; fa.mode = 3; fa.inline_warp = 1;
 	for (int q = 0; q < 9; ++q) fa.iw[q] = 0.5 + 1.25 * q;
 	for (int q = 0; q < 8; ++q) fa.is[q] = -3.0 - 0.75 * q;
 	double h[18] = {0};
-	hipLaunchKernelGGL(k_kernarg_probe, dim3(1), dim3(64), 0, st, bv, im, fa, d_out);
+	hipLaunchKernelGGL(k_kernarg_probe, dim3(1), dim3(64), 0, st, bv, im, fa, d_out.get());
 	bool ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, st) == hipSuccess &&
 		hipStreamSynchronize(st) == hipSuccess;
-	(void)hipFree(d_out);
 	for (int q = 0; ok && q < 9; ++q) ok = h[q] == fa.iw[q];
 	for (int q = 0; ok && q < 8; ++q) ok = h[9 + q] == fa.is[q];
 	state = ok ? 1 : 0;

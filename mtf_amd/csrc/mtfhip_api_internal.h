@@ -148,7 +148,7 @@ static bool rect_to_quad(double lo_x, double lo_y, double hi_x, double hi_y, con
 
 /* ------------------------------------------------------------------ handles */
 struct Timer {
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+	std::vector<std::pair<Event, Event>> pending;
 	double total_ms = 0;
 	int n = 0;
 	long launches = 0;
@@ -159,43 +159,40 @@ struct Timer {
 
 struct mtfhip_ctx {
 	int device = 0;
-	hipStream_t stream = nullptr;
-	bool own_stream = false;
+	Stream stream;   /* the caller's (borrowed) or the library's own */
 	/* second queue of the device-side loop (track_loop_chunked: two chunks of independent targets in flight, one's solve + update under the
 	 * other's pixel pass); created on first use, ordered against `stream` by the two events */
-	hipStream_t extra_streams[3] = {nullptr, nullptr, nullptr};
-	hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-	unsigned long long *d_phase = nullptr;   /* [4] wall-clock stamps of the queues' last solve (PhaseCtl) */
-	ImgView img{nullptr, 0, 0, 0};
-	float *img_owned = nullptr;
-	size_t img_capacity = 0;
+	Stream extra_streams[3];
+	Event ev_fork, ev_join[3];
+	Dev<unsigned long long> d_phase;   /* [4] wall-clock stamps of the queues' last solve (PhaseCtl) */
+	ImgView img{nullptr, 0, 0, 0};   /* img, prev: views -- into img_owned / prev_owned, or of a borrowed image */
+	Dev<float> img_owned;
 	/* the previous frame (GridTracker's prev_img = curr_img.clone(), SM/src/GridTracker.cc:241-243, 266): mtfhip_image_keep_prev.  An image
 	 * the context owns is kept by exchanging the two owned buffers (the next upload fills the other one: no copy); a borrowed one is copied. */
 	ImgView prev{nullptr, 0, 0, 0};
-	float *prev_owned = nullptr;
-	size_t prev_capacity = 0;
-	unsigned char *raw = nullptr; size_t raw_capacity = 0;      /* staging of the raw frame (pre-processing) */
-	float *tmp_a = nullptr, *tmp_b = nullptr; size_t tmp_capacity = 0; /* gray / row-pass intermediates */
+	Dev<float> prev_owned;
+	Dev<unsigned char> raw;      /* staging of the raw frame (pre-processing) */
+	Dev<float> tmp_a, tmp_b;     /* gray / row-pass intermediates */
 	/* The current image with every texel next to the one BELOW it -- pair[2 (y W + x)] = I[y][x], pair[2 (y W + x) + 1] = I[y + 1][x] -- so that
 	 * the four texels of a bilinear cell are 16 contiguous bytes: ONE gather per sample instead of two for the kernels that sit on the vector
 	 * memory path (the candidate scorer; r06 -- the NN rows kernel gained nothing from it).  Built on demand (ensure_pair_image) for images the context owns (an uploaded or derived
 	 * image cannot change behind the library's back; a borrowed one can), rebuilt when img_serial has moved. */
-	float *pair_owned = nullptr; size_t pair_capacity = 0;
+	Dev<float> pair_owned;
 	unsigned long long img_serial = 1, pair_serial = 0, pair_demand_serial = 0;
 	size_t pair_demand = 0;   /* candidates scored on the current image so far without the copy (pair_image_if_it_pays) */
 	int n_cus = 0;   /* compute units: the persistent loop needs its whole grid resident */
 	bool timing = false;
 	int timing_stride = 1;   /* events are recorded around every timing_stride-th launch of a family */
 	std::map<std::string, Timer> timers;
-	hipEvent_t ev_ref = nullptr;   /* recorded by timing_reset: origin of Timer::spans */
-	std::vector<hipEvent_t> free_events;
+	Event ev_ref;   /* recorded by timing_reset: origin of Timer::spans */
+	std::vector<Event> free_events;
 	std::vector<struct mtfhip_batch *> batches;   /* live batches: deferred work is flushed before the image changes */
-	unsigned char *est_ws = nullptr; size_t est_ws_capacity = 0;   /* mtfhip_ssm_estimate_from_pts: device staging of its arguments and results */
+	Dev<unsigned char> est_ws;   /* mtfhip_ssm_estimate_from_pts: device staging of its arguments and results */
 };
 
 struct TimedScope {
 	mtfhip_ctx *ctx;
-	hipEvent_t a = nullptr, b = nullptr;
+	Event a, b;
 	Timer *tm = nullptr;
 	hipStream_t on;
 	TimedScope(mtfhip_ctx *c, const char *family, hipStream_t stream = nullptr) : ctx(c), on(stream ? stream : c->stream) {
@@ -204,9 +201,9 @@ struct TimedScope {
 		if ((cand->launches++ % ctx->timing_stride) != 0) return;
 		tm = cand;
 		auto get = [&]() {
-			hipEvent_t e;
-			if (!ctx->free_events.empty()) { e = ctx->free_events.back(); ctx->free_events.pop_back(); }
-			else (void)hipEventCreate(&e);
+			Event e;
+			if (!ctx->free_events.empty()) { e = std::move(ctx->free_events.back()); ctx->free_events.pop_back(); }
+			else (void)e.create();
 			return e;
 		};
 		a = get(); b = get();
@@ -215,7 +212,7 @@ struct TimedScope {
 	~TimedScope() {
 		if (!tm) return;
 		(void)hipEventRecord(b, on);
-		tm->pending.emplace_back(a, b);
+		tm->pending.emplace_back(std::move(a), std::move(b));
 	}
 };
 
@@ -248,27 +245,32 @@ struct mtfhip_batch {
 	 * desc.ssm are the model's own and the three buffers the interface's N x S arrays. */
 	int lo_ssm = 0;
 	bool pass_mode = false;
-	double *pass_j[3] = {nullptr, nullptr, nullptr};
+	Dev<double> pass_j[3];
 	size_t pass_j_per_target[3] = {0, 0, 0};
 	double norm_mult = 1, norm_add = 0;
-	double *buf[MTFHIP_BUF_COUNT];
+	/* Every Dev<>, Pinned<> and Event member owns what it names and releases it with the batch.  The raw pointers are VIEWS: d_warps,
+	 * d_states, d_corners, d_init_corners_hm, d_ncc, d_w0, d_active and d_iters point into d_slab, and every *_dev is the device address of
+	 * the pinned buffer it is named after. */
+	Dev<double> buf[MTFHIP_BUF_COUNT];
 	size_t per_target[MTFHIP_BUF_COUNT];
-	double *d_warps = nullptr, *d_states = nullptr;
-	double *d_partials = nullptr, *d_acc = nullptr, *d_scratch_pts = nullptr, *d_w0 = nullptr;
-	double *d_h0 = nullptr, *d_corners = nullptr, *d_init_corners_hm = nullptr, *d_cand = nullptr;
-	double *d_ncc = nullptr, *d_colmean = nullptr; /* [B][8] NCC scalars / column means */
+	double *d_warps = nullptr, *d_states = nullptr, *d_w0 = nullptr, *d_corners = nullptr, *d_init_corners_hm = nullptr;   /* views into d_slab */
+	double *d_ncc = nullptr;   /* [B][8] NCC scalars: a view into d_slab */
+	Dev<double> d_partials, d_acc, d_scratch_pts, d_h0, d_cand;
+	Dev<double> d_colmean; /* [B][8] column means */
 	/* MI: per-target table block, block partial rows, similarity and Hessian outputs */
-	double *d_mi_tb = nullptr, *d_mi_part = nullptr, *d_mi_f = nullptr, *d_mi_H = nullptr;
-	double *d_mi_poly = nullptr;   /* [B][mi_poly_size()], allocated by the first recompute iteration */
+	Dev<double> d_mi_tb, d_mi_part, d_mi_f, d_mi_H;
+	Dev<double> d_mi_poly;   /* [B][mi_poly_size()], allocated by the first recompute iteration */
 	/* the fused template initialisation (kernels_init.hip, init_template's ICLK fast path): its small results arrive in this pinned
 	 * record (kInitRec doubles per target) behind init_flag; init_mirror_seq != 0: the host mirrors (th[].h0, NCC scalars and template
 	 * moments) are older than the device copies until pull_init_mirrors() has folded the record in (lazy_flush does) */
-	double *h_init_rec = nullptr, *h_init_rec_dev = nullptr;
-	unsigned long long *h_init_flag = nullptr, *h_init_flag_dev = nullptr, init_seq = 0, init_mirror_seq = 0;
+	Pinned<double, hipHostMallocMapped> h_init_rec;
+	double *h_init_rec_dev = nullptr;
+	Pinned<unsigned long long, hipHostMallocMapped> h_init_flag;
+	unsigned long long *h_init_flag_dev = nullptr, init_seq = 0, init_mirror_seq = 0;
 	bool init_rec_device = false;   /* the pending record was NOT published to pinned memory (grid re-initialisations, r05): pull_init_mirrors copies d_h0 / d_ncc / d_ncc_tm instead */
-	double *d_mi_red = nullptr;   /* [B][mi_row_len] block rows summed (the Hessian assembly then reads one row per target) */
-	double *d_h0inv = nullptr; /* [B][64] inverse of the constant Hessian (one-launch ICLK) */
-	double *d_d2_part = nullptr, *d_d2_out = nullptr, *d_d2_w = nullptr; /* second-order term: block rows, [B][64] sums, MI self weights */
+	Dev<double> d_mi_red;   /* [B][mi_row_len] block rows summed (the Hessian assembly then reads one row per target) */
+	Dev<double> d_h0inv; /* [B][64] inverse of the constant Hessian (one-launch ICLK) */
+	Dev<double> d_d2_part, d_d2_out, d_d2_w; /* second-order term: block rows, [B][64] sums, MI self weights */
 	double hess_eps = 1.0;
 	/* MTFHIP_MATH_*: arithmetic of the non-materialising kernels (include/mtfhip.h) */
 	int math_mode = (std::getenv("MTFHIP_MATH") && (std::getenv("MTFHIP_MATH")[0] == 'r' || std::getenv("MTFHIP_MATH")[0] == '0')) ? MTFHIP_MATH_REPLAY : MTFHIP_MATH_FAST;
@@ -291,16 +293,16 @@ struct mtfhip_batch {
 	/* SCV (am = MTFHIP_AM_SCV): SCVParams hist_type / weighted_mapping / mapped_gradient, n_bins; the original template (I0_orig, the
 	 * normalised samples of initializePixVals) and its code plane, pass-1 rows and the intensity maps (kernels_scv.hip) */
 	int scv_hist = 0, scv_linear = 0, scv_mapped_grad = 0, scv_nb = 0;
-	double *d_scv_i0 = nullptr, *d_scv_part = nullptr, *d_scv_map = nullptr;
-	unsigned short *d_scv_code = nullptr;
+	Dev<double> d_scv_i0, d_scv_part, d_scv_map;
+	Dev<unsigned short> d_scv_code;
 	/* SPSS (am = MTFHIP_AM_SPSS): SPSSParams k and c = (k (PIX_MAX - PIX_MIN))^2 (SPSS.cc:37-38) */
 	double spss_k = 0.01, spss_c = (0.01 * 255.0) * (0.01 * 255.0);
 	/* RSCV (am = MTFHIP_AM_RSCV): RSCVParams weighted_mapping, n_bins; the template's code plane ((int)I0), pass-1 rows and arrival
 	 * counters, the intensity maps, and It_orig of the per-function route (kernels_rscv.hip) */
 	int rscv_linear = 0, rscv_nb = 0;
-	unsigned char *d_rscv_code = nullptr;
-	unsigned *d_rscv_part = nullptr, *d_rscv_arrive = nullptr;
-	double *d_rscv_map = nullptr, *d_rscv_it = nullptr;
+	Dev<unsigned char> d_rscv_code;
+	Dev<unsigned> d_rscv_part, d_rscv_arrive;
+	Dev<double> d_rscv_map, d_rscv_it;
 	/* (LRSCV, am = MTFHIP_AM_LRSCV, uses RSCV's code plane and It_orig buffer, and LSCV's configuration, first-iteration flag, geometry,
 	 * sums, arrival counters, maps and affine parameters: api_lrscv.hip) */
 	/* LSCV (am = MTFHIP_AM_LSCV): LSCVParams n_sub_regions_x / _y, spacing_x / _y, affine_mapping, once_per_frame, weighted_mapping,
@@ -309,47 +311,49 @@ struct mtfhip_batch {
 	 * (kernels_lscv.hip) */
 	int lscv_nx = 3, lscv_ny = 3, lscv_sx = 10, lscv_sy = 10, lscv_affine = 0, lscv_once = 0, lscv_linear = 0, lscv_nb = 0;
 	int lscv_first_iter = 0, lscv_ncx = 0, lscv_ncell = 0;
-	double *d_lscv_i0 = nullptr, *d_lscv_w = nullptr, *d_lscv_map = nullptr, *d_lscv_aff = nullptr;
-	unsigned short *d_lscv_code = nullptr, *d_lscv_cell = nullptr;
-	int *d_lscv_crng = nullptr;
-	unsigned *d_lscv_tot = nullptr, *d_lscv_arrive = nullptr;
-	size_t cand_capacity = 0;
-	double *d_cand_mi = nullptr; size_t cand_mi_capacity = 0;   /* MI candidate scoring: histogram rows per candidate */
-	int *d_active = nullptr, *d_iters = nullptr;
+	Dev<double> d_lscv_i0, d_lscv_w, d_lscv_map, d_lscv_aff;
+	Dev<unsigned short> d_lscv_code, d_lscv_cell;
+	Dev<int> d_lscv_crng;
+	Dev<unsigned> d_lscv_tot, d_lscv_arrive;
+	Dev<double> d_cand_mi;   /* MI candidate scoring: histogram rows per candidate */
+	int *d_active = nullptr, *d_iters = nullptr;   /* views into d_slab */
 	/* The small per-target state lives in ONE device allocation (warps | states | corners | init_corners_hm | ncc | w0 |
 	 * active | iters) mirrored by two pinned staging buffers, so that set_corners and track each move it with a single
 	 * copy (a grid frame used to cost 14 small copies and 4 stream syncs around a 100 us kernel). */
-	char *d_slab = nullptr, *h_stage_a = nullptr, *h_stage_b = nullptr;
-	hipEvent_t ev_a = nullptr, ev_b = nullptr;
+	Dev<char> d_slab;
+	Pinned<char> h_stage_a, h_stage_b;
+	Event ev_a, ev_b;
 	/* k_track_persist: barrier words, the generation counter the host advances per launch; persist_ok is cleared for good when a
 	 * launch could not keep its workgroups resident (the two-launch loop finishes the call and serves the later ones) */
-	int *d_persist = nullptr;
+	Dev<int> d_persist;
 	/* deferred materialisation of the device-side loop (track_loop_chunked): warp [B][9] | state [B][8] of the last pass of a target that stopped
 	 * behind a non-materialising pass, and the per-target flags of the trailing materialising launch */
-	double *d_last_ws = nullptr;
-	int *d_need_mat = nullptr;
+	Dev<double> d_last_ws;
+	Dev<int> d_need_mat;
 	unsigned persist_gen = 0;
 	bool persist_ok = true;
 	bool stage_a_busy = false;   /* ev_a guards an upload from h_stage_a that may still be in flight */
 	/* warp + state of every target after setState / compositionalUpdate: one copy from a pinned double buffer, no sync */
-	double *h_wstage[2] = {nullptr, nullptr};
-	hipEvent_t ev_w[2] = {nullptr, nullptr};
+	Pinned<double> h_wstage[2];
+	Event ev_w[2];
 	int wflip = 0;
 	/* CURR_PTS / CURR_HXY / CURR_Z lag behind the warp: only the un-fused kernels read them, so k_apply_warp runs when
 	 * one of those is about to be launched (lazy_flush) or the arrays are read, not after every update */
 	bool pts_stale = false;
-	double *d_it_shadow = nullptr;
-	double *d_ncc_tm = nullptr;   /* [B][52] NCC template moments for the device-side finish */
+	Dev<double> d_it_shadow;
+	Dev<double> d_ncc_tm;   /* [B][52] NCC template moments for the device-side finish */
 	/* the one-launch forward-backward frame (k_grid_fb): requested by mtfhip_grid_frame_fb around its track call */
 	/* set by a fused grid re-initialisation (grid_reinit_fused: identity warps, zero states, corners = the templates' corners on host AND device),
 	 * cleared by whatever changes the mirrors' warps / states / corners next (set_corners_core, apply_states) and consumed by the next track_core:
 	 * its one-launch kernel then starts from init_corners_hm and the slab is not uploaded (TrackState::fresh_reset) */
 	bool fresh_reinit = false;
 	bool fb_fused_req = false, fb_fused_reinit = true;
-	double *h_fb = nullptr, *h_fb_dev = nullptr, *d_fb = nullptr;   /* [B][9] the backward pass's corners | iteration count: pinned host copy, device copy */
-	double *d_nn_warps = nullptr; size_t nn_warps_cap = 0;   /* NN dataset, tolerance mode: the samples' warps between k_nn_warps and k_nn_rows */
-	double *d_lm = nullptr;       /* [B][kLmStride] Levenberg-Marquardt state of the device-side loop */
-	double *d_trace = nullptr; int trace_cap = 0;   /* [B][trace_cap][kTraceStride] debug trace of the device-side loop, or NULL */
+	Pinned<double, hipHostMallocMapped> h_fb;
+	double *h_fb_dev = nullptr;
+	Dev<double> d_fb;   /* [B][9] the backward pass's corners | iteration count: pinned host copy, device copy */
+	Dev<double> d_nn_warps;   /* NN dataset, tolerance mode: the samples' warps between k_nn_warps and k_nn_rows */
+	Dev<double> d_lm;       /* [B][kLmStride] Levenberg-Marquardt state of the device-side loop */
+	Dev<double> d_trace; int trace_cap = 0;   /* [B][trace_cap][kTraceStride] debug trace of the device-side loop, or NULL */
 	/* NCC: a fused iteration updated the scalars (It_mean, a, b, f) on the host only; the un-fused kernels read d_ncc */
 	bool ncc_host_newer = false;
 	/* mtfhip_grid_frame behind a fused re-initialisation (reset-every-frame mode): the loop kernel is ENQUEUED behind k_template_init instead
@@ -357,15 +361,17 @@ struct mtfhip_batch {
 	 * pending while this is set, and the slab upload of the call leaves the device's NCC scalars (the kernel's own) alone */
 	bool hold_init_pull = false;
 	size_t slab_bytes = 0, slab_dbl_bytes = 0;
-	double *h_acc = nullptr; /* pinned */
+	Pinned<double, hipHostMallocMapped | hipHostMallocCoherent> h_acc;
 	/* Zero-copy read-back of the reduced rows: h_acc is host-coherent pinned memory the reduction kernel writes directly
 	 * (h_acc_dev = its device address) followed by a sequence number in h_flag; the host spins on the flag instead of
 	 * paying a copy command plus a stream synchronisation per iteration (MTFHIP_ZERO_COPY=0: copy + sync) */
 	double *h_acc_dev = nullptr;
-	unsigned long long *h_flag = nullptr, *h_flag_dev = nullptr, acc_seq = 0;
+	Pinned<unsigned long long, hipHostMallocMapped | hipHostMallocCoherent> h_flag;
+	unsigned long long *h_flag_dev = nullptr, acc_seq = 0;
 	char *h_stage_a_dev = nullptr, *h_stage_b_dev = nullptr;   /* device addresses of the staging buffers when kernels may read them (k_ingest_host), else NULL */
-	char *h_pub = nullptr, *h_pub_dev = nullptr;   /* host-coherent mirror of the state slab, written by k_publish_host (track's read-back) */
-	int *d_fin_count = nullptr;
+	Pinned<char, hipHostMallocMapped | hipHostMallocCoherent> h_pub;
+	char *h_pub_dev = nullptr;   /* host-coherent mirror of the state slab, written by k_publish_host (track's read-back) */
+	Dev<int> d_fin_count;
 	int nblk_max;
 	int unit_z = 1;
 	/* INIT_PTS is the lattice set_corners (or the grid kernel's region mode) laid out INSIDE init_corners: what lets the candidate scorer
@@ -450,16 +456,15 @@ struct mtfhip_batch {
 
 static int ensure_buf(mtfhip_batch *b, int id) {
 	if (b->buf[id]) return MTFHIP_OK;
-	HIP_TRY(hipMalloc(&b->buf[id], sizeof(double) * b->per_target[id] * b->B));
+	HIP_TRY(b->buf[id].reserve(b->per_target[id] * b->B));
 	HIP_TRY(hipMemsetAsync(b->buf[id], 0, sizeof(double) * b->per_target[id] * b->B, b->ctx->stream));
 	return MTFHIP_OK;
 }
 
 /* the second-order term's block rows and [B][64] sums (k_second_order_ssd, k_weighted_plane_sum), allocated by the first call that needs them */
 static int ensure_second_order_scratch(mtfhip_batch *b) {
-	if (b->d_d2_part) return MTFHIP_OK;
-	HIP_TRY(hipMalloc(&b->d_d2_part, sizeof(double) * 64 * (size_t)simple_blocks_per_target(b->N) * b->B));
-	HIP_TRY(hipMalloc(&b->d_d2_out, sizeof(double) * 64 * (size_t)b->B));
+	HIP_TRY(b->d_d2_part.reserve(64 * (size_t)simple_blocks_per_target(b->N) * b->B));
+	HIP_TRY(b->d_d2_out.reserve(64 * (size_t)b->B));
 	return MTFHIP_OK;
 }
 
@@ -474,7 +479,7 @@ struct PassMode {
 	PassMode &operator=(const PassMode &) = delete;
 	void flip() {
 		static const int ids[3] = {MTFHIP_BUF_J0, MTFHIP_BUF_JT, MTFHIP_BUF_JM};
-		for (int k = 0; k < 3; ++k) { std::swap(b->buf[ids[k]], b->pass_j[k]); std::swap(b->per_target[ids[k]], b->pass_j_per_target[k]); }
+		for (int k = 0; k < 3; ++k) { b->buf[ids[k]].swap(b->pass_j[k]); std::swap(b->per_target[ids[k]], b->pass_j_per_target[k]); }
 		b->pass_mode = !b->pass_mode;
 		b->S = b->pass_mode ? 6 : ssm_state_size(b->lo_ssm);
 		b->desc.ssm = b->pass_mode ? (int)MTFHIP_SSM_AFFINE : b->lo_ssm;
@@ -635,7 +640,7 @@ static int wait_host_flag(mtfhip_batch *b, unsigned long long seq) {
 	const auto t0 = std::chrono::steady_clock::now();
 	bool yielding = false;
 	for (unsigned spins = 0;; ++spins) {
-		if (__atomic_load_n(b->h_flag, __ATOMIC_ACQUIRE) == seq) return MTFHIP_OK;
+		if (__atomic_load_n(b->h_flag.get(), __ATOMIC_ACQUIRE) == seq) return MTFHIP_OK;
 		if (yielding) std::this_thread::yield(); else cpu_relax();
 		if ((spins & 0x3ff) == 0x3ff || yielding) {
 			const auto dt = std::chrono::steady_clock::now() - t0;
@@ -645,7 +650,7 @@ static int wait_host_flag(mtfhip_batch *b, unsigned long long seq) {
 	}
 	/* the kernel did not report in: let the runtime tell why */
 	HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-	if (__atomic_load_n(b->h_flag, __ATOMIC_ACQUIRE) == seq) return MTFHIP_OK;
+	if (__atomic_load_n(b->h_flag.get(), __ATOMIC_ACQUIRE) == seq) return MTFHIP_OK;
 	return fail(MTFHIP_ERR_HIP, "device results were not delivered to host memory");
 }
 /* fold the record of a fused template initialisation into the host mirrors (see mtfhip_batch::init_mirror_seq) */
@@ -682,13 +687,13 @@ static int pull_init_mirrors(mtfhip_batch *b) {
 	const auto t0 = std::chrono::steady_clock::now();
 	bool ok = false;
 	for (unsigned spins = 0;; ++spins) {
-		if (__atomic_load_n(b->h_init_flag, __ATOMIC_ACQUIRE) == seq) { ok = true; break; }
+		if (__atomic_load_n(b->h_init_flag.get(), __ATOMIC_ACQUIRE) == seq) { ok = true; break; }
 		cpu_relax();
 		if ((spins & 0x3ff) == 0x3ff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
 	}
 	if (!ok) {
 		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-		if (__atomic_load_n(b->h_init_flag, __ATOMIC_ACQUIRE) != seq) return fail(MTFHIP_ERR_HIP, "the template initialisation's results were not delivered to host memory");
+		if (__atomic_load_n(b->h_init_flag.get(), __ATOMIC_ACQUIRE) != seq) return fail(MTFHIP_ERR_HIP, "the template initialisation's results were not delivered to host memory");
 	}
 	const bool ncc = b->desc.am == MTFHIP_AM_NCC;
 	for (int t = 0; t < b->B; ++t) {

@@ -9,8 +9,39 @@
 #include <hip/hip_runtime.h>
 #include "../../include/mtfhip.h"
 #include "mtfhip_fused_dispatch.h"
+#include "mtfhip_owned.h"
 
 namespace mtfhip {
+
+/* The policies of the owner types (mtfhip_owned.h).  These are the library's only calls that obtain or release device memory, pinned host
+ * memory, events and streams: a handle's member is an owner built on them, or a documented view. */
+struct DeviceMem {
+	static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+	static void release(void *p) { (void)hipFree(p); }
+};
+template <unsigned Flags = hipHostMallocDefault> struct PinnedMem {
+	static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, Flags); }
+	static void release(void *p) { (void)hipHostFree(p); }
+};
+struct FineGrainedMem {   /* device memory other devices' kernels may store into while ours polls it (the particle filter's mailbox) */
+	static hipError_t alloc(void **p, size_t bytes) { return hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained); }
+	static void release(void *p) { (void)hipFree(p); }
+};
+struct EventApi {
+	typedef hipEvent_t handle;
+	static hipError_t create(hipEvent_t *e) { return hipEventCreate(e); }
+	static hipError_t create(hipEvent_t *e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
+	static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+};
+struct StreamApi {
+	typedef hipStream_t handle;
+	static hipError_t create(hipStream_t *s, unsigned flags) { return hipStreamCreateWithFlags(s, flags); }
+	static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+};
+template <class T> using Dev = Owned<T, DeviceMem>;
+template <class T, unsigned Flags = hipHostMallocDefault> using Pinned = Owned<T, PinnedMem<Flags>>;
+typedef OwnedHandle<EventApi> Event;
+typedef OwnedHandle<StreamApi> Stream;
 
 struct ImgView {
 	const float *data;

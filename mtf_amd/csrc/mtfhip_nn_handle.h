@@ -17,12 +17,12 @@ struct NnGraph {
 	bool valid = false;                       /* a graph of the CURRENT dataset is resident */
 	mtfhip_gnn_desc desc{};                   /* as given; `degree` below is the effective one */
 	int degree = 0, nper = 1;                 /* neighbours per node | workgroups of a step launch per walk */
-	int *d_graph = nullptr; size_t graph_cap = 0;           /* [n][degree] */
-	unsigned long long *d_count = nullptr;    /* device: searches begun (what random_start's draws are keyed by), then the start node (an int) */
-	int *d_start = nullptr;
-	GnnWalk *d_walks = nullptr; NnBest *d_part = nullptr; unsigned *d_tickets = nullptr; int walks_cap = 0, part_cap = 0;
+	Dev<int> d_graph;                         /* [n][degree] */
+	Dev<unsigned long long> d_count;          /* [2] device: searches begun (what random_start's draws are keyed by), then the start node (an int) */
+	int *d_start = nullptr;                   /* a view: the second word of d_count */
+	Dev<GnnWalk> d_walks; Dev<NnBest> d_part; Dev<unsigned> d_tickets;
 	std::vector<int> last_walks;                            /* of the last update(): start, steps per iteration run */
-	double *d_q = nullptr; int *d_starts = nullptr, *d_idx = nullptr, *d_steps = nullptr; double *d_dist = nullptr; int q_cap = 0;   /* staging of the host form of the search */
+	Dev<double> d_q, d_dist; Dev<int> d_starts, d_idx, d_steps;   /* staging of the host form of the search */
 };
 
 struct mtfhip_nn {
@@ -31,20 +31,19 @@ struct mtfhip_nn {
 	int n = 0, F = 0, S = 0, ncc = 0;
 	bool host_stepped = false, have_dataset = false;
 	int resident = 0, nblk = 0;           /* workgroups of a search launch */
-	double *d_feat = nullptr, *d_perts = nullptr;
-	NnBest *d_part = nullptr; int part_q = 0;   /* [part_q][nblk] */
-	double *d_query = nullptr;            /* the tracker's query feature, feat_size */
+	Dev<double> d_feat, d_perts;
+	Dev<NnBest> d_part;                   /* [queries][nblk] */
+	Dev<double> d_query;                  /* the tracker's query feature, feat_size */
 	/* W | corners | init_corners_hm | zero perturbation | pad, then ctl (done, n_iters: two ints in one double's place), then the log
 	 * (log_cap x 3), then the GNN walks' log (log_cap x two ints: start node, steps): one read-back brings all of it */
-	double *d_state = nullptr; int log_cap = 0;
-	double *d_q = nullptr; int *d_idx = nullptr; double *d_dist = nullptr; int q_cap = 0;   /* staging of the host form of the search */
+	Dev<double> d_state; int log_cap = 0;
+	Dev<double> d_q, d_dist; Dev<int> d_idx;   /* staging of the host form of the search */
 	NnGraph g;
 };
 
 static inline int *nn_walk_log(const mtfhip_nn *nn) { return reinterpret_cast<int *>(nn->d_state + kNnStateDoubles + 1 + 3 * (size_t)nn->log_cap); }
 
 /* api_gnn.hip, for mtfhip_nn_update and the handle's life cycle */
-void gnn_free(mtfhip_nn *nn);
 int gnn_need_graph(const mtfhip_nn *nn, const char *fn);    /* MTFHIP_ERR_LOGIC without a valid graph */
 int gnn_prepare_update(mtfhip_nn *nn, int max_iters);       /* the walk's buffers, before the first launch of an update */
 /* iteration `it` of NN::update with the graph index: the walk from the handle's start node for nn->d_query, its result as the one partial

@@ -56,8 +56,8 @@ int alk_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	 * nothing stale is left behind for a later search method that skips its own init_template) */
 	TRY(store_h0(b, H0.data(), false));
 	if (b->desc.am == MTFHIP_AM_NCC) {
-		HIP_TRY(b->d_ncc_tm.reserve(52 * (size_t)b->B));
-		HIP_TRY(hipMemsetAsync(b->d_ncc_tm, 0, sizeof(double) * 52 * (size_t)b->B, b->ctx->stream));
+		HIP_TRY(b->d_ncc_tm.reserve(NCC_TM_COUNT * (size_t)b->B));
+		HIP_TRY(hipMemsetAsync(b->d_ncc_tm, 0, sizeof(double) * NCC_TM_COUNT * (size_t)b->B, b->ctx->stream));
 	}
 	HIP_TRY(hipStreamSynchronize(b->ctx->stream));   /* (store_h0's staging) */
 	b->j0_is_template = false;   /* (J0, where it exists, is the cmptPixJacobian form: the compositional kernels' rebuild does not apply) */

@@ -156,7 +156,7 @@ int init_template_fused(mtfhip_batch *b, const mtfhip_sm_desc *sm, const RegionI
 		*b->h_init_flag = 0;
 		HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->h_init_flag_dev), b->h_init_flag, 0));
 	}
-	if (ncc) HIP_TRY(b->d_ncc_tm.reserve(52 * (size_t)b->B));
+	if (ncc) HIP_TRY(b->d_ncc_tm.reserve(NCC_TM_COUNT * (size_t)b->B));
 	++b->frame_count;   /* ImageBase.cc:74 */
 	const unsigned long long seq = ++b->init_seq;
 	{
@@ -336,71 +336,35 @@ int second_order_term(const mtfhip_sm_desc *sm, int am) {
 	}
 }
 
-/* turns one target's reduced accumulators into the SM's g and H (before LM damping):
- * NT/FCLK.cc:260-288 ; NT/ESM.cc:298-377 with SSDBase.cc:169-191,287-311 ; NT/ICLK.cc:206-251 */
-void assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0,
-	double *f, double *g, double *H) {
-	const int S = b->S;
-	if (f) *f = -acc[ACC_RR] / 2;
-	const double gscale = sm->sm == MTFHIP_SM_ESM ? 0.5 : 1.0;
-	for (int s = 0; s < S; ++s) g[s] = gscale * acc[ACC_G + s];
-	const bool use_h0 = (sm->hess_type == 0) || (sm->sm == MTFHIP_SM_ICLK);
-	const bool sum_h0 = (sm->sm == MTFHIP_SM_ESM) && (sm->hess_type == 2 || sm->hess_type == 4);
-	int k = 0;
-	for (int a = 0; a < 8; ++a)
-		for (int c = a; c < 8; ++c) {
-			if (a < S && c < S) {
-				double v = use_h0 ? h0[c * S + a] : -acc[ACC_H + k];
-				if (sum_h0) v = (v + h0[c * S + a]) * 0.5;
-				H[c * S + a] = v; H[a * S + c] = v;
-			}
-			++k;
-		}
-}
-/* the reduced rows of a fused SSD / NCC pass -> every target's f, g and H (before damping); so: [B][S x S] second-order sums (x so_scale) or NULL */
+/* the reduced rows of a fused pass -> every target's f, g and H of the search method before damping: loops over the entries of mtfhip_sm_system.h,
+ * the statement the device-side finish reads as well (NT/FCLK.cc:260-288 ; NT/ESM.cc:298-377 with SSDBase.cc:169-191,287-311 ; NT/ICLK.cc:206-251).
+ * so: [B][S x S] second-order sums (x so_scale) or NULL */
 int assemble_rows(mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, int nblk, const double *so, double so_scale, double *f, double *g, double *H) {
-	const bool ncc = b->desc.am == MTFHIP_AM_NCC;
-	const int S2 = b->S * b->S;
-	TRY(read_rows(b, nblk, ncc ? NCC_ACC_COUNT : ACC_COUNT));
+	const bool ncc = b->desc.am == MTFHIP_AM_NCC, spss = spss_am(b);
+	const int S = b->S, S2 = S * S, RL = ncc ? NCC_ACC_COUNT : ACC_COUNT;
+	TRY(read_rows(b, nblk, RL));
+	if (ncc && !ncc_has_gram(ncc_h_which(*sm), hess_mean)) return fail(MTFHIP_ERR_LOGIC, "fused NCC: the Gram matrix this Hessian needs was not accumulated");
 	for (int t = 0; t < b->B; ++t) {
-		double ft, *gt = g + (size_t)t * b->S, *Ht = H + (size_t)t * S2;
-		if (ncc) TRY(ncc_assemble(b, sm, hess_mean, b->h_acc + (size_t)t * NCC_ACC_COUNT, b->th[t], &ft, gt, Ht));
-		else if (spss_am(b)) { spss_assemble(b, sm, b->h_acc + (size_t)t * ACC_COUNT, b->th[t].h0, &ft, gt, Ht); b->th[t].f = ft; }
-		else { assemble(b, sm, b->h_acc + (size_t)t * ACC_COUNT, b->th[t].h0, &ft, gt, Ht); b->th[t].f = ft; }
-		if (so) for (int k = 0; k < S2; ++k) Ht[k] += so_scale * so[(size_t)t * S2 + k];
-		if (f) f[t] = ft;
+		TargetHost &h = b->th[t];
+		const double *row = b->h_acc + (size_t)t * RL, *sot = so ? so + (size_t)t * S2 : nullptr;
+		double *gt = g + (size_t)t * S, *Ht = H + (size_t)t * S2;
+		if (ncc) ncc_refresh_mirrors(b, h, row); else h.f = ssd_f(spss, row);
+		NccSys q = NccSys();
+		if (ncc) q = ncc_host_sys(b, h, row);
+		if (f) f[t] = h.f;
+		for (int s = 0; s < S; ++s) gt[s] = ncc ? ncc_g(*sm, q, s) : ssd_g(*sm, spss, row, s);
+		for (int c = 0; c < S; ++c)
+			for (int r = 0; r < S; ++r) {
+				/* (ncc_h leaves ex out of InitialSelf and ESM's SumOfSelf: second_order_term is -1 for exactly those, so `so` is NULL there) */
+				const double ex = sot ? so_scale * sot[c * S + r] : 0.0;
+				if (ncc) Ht[c * S + r] = ncc_h(*sm, q, h.h0[(r < c ? c : r) * S + (r < c ? r : c)], ex, r, c);
+				else { double v = ssd_h(*sm, false, spss, row, h.h0, S, r, c); if (sot) v += ex; Ht[c * S + r] = v; }
+			}
 	}
 	if (ncc) b->ncc_host_newer = true;
 	return MTFHIP_OK;
 }
 
-/* A low-order SSM's pixel Jacobian is the affine one times a constant 6 x S matrix M with at most two +-1 entries per column
- * (Translation.h:45-63, Isometry.cc:115-135,162-185, Similitude.cc:163-210):
- *   Translation [Ja0, Ja1]    Isometry [Ja0, Ja1, Ja4 - Ja3]    Similitude [Ja0, Ja1, Ja2 + Ja5, Ja4 - Ja3]
- * and every g and H of the search methods is linear / bilinear in it: g_S = g_aff M, H_S = M^T H_aff M.  col k of M: rows a0 and (a1 >= 0)
- * a1 with sign s1.  The device twin is in finish_track_body. */
-static void lowdof_col(int lo_ssm, int k, int &a0, int &a1, double &s1) {
-	a0 = k; a1 = -1; s1 = 0.0;
-	if (k >= 2) { const bool sum = lo_ssm == MTFHIP_SSM_SIMILITUDE && k == 2; a0 = sum ? 2 : 4; a1 = sum ? 5 : 3; s1 = sum ? 1.0 : -1.0; }
-}
-/* g6 [6], H6 [6 x 6] column-major of one target -> g [SS], H [SS x SS] column-major */
-static void lowdof_project(int lo_ssm, const double *g6, const double *H6, double *g, double *H) {
-	const int SS = ssm_state_size(lo_ssm);
-	auto h6 = [&](int r, int c) { return H6[c * 6 + r]; };
-	for (int r = 0; r < SS; ++r) {
-		int r0, r1; double sr;
-		lowdof_col(lo_ssm, r, r0, r1, sr);
-		g[r] = g6[r0] + (r1 >= 0 ? sr * g6[r1] : 0.0);
-		for (int c = 0; c < SS; ++c) {
-			int c0, c1; double sc;
-			lowdof_col(lo_ssm, c, c0, c1, sc);
-			double v = h6(r0, c0);
-			if (c1 >= 0) v += sc * h6(r0, c1);
-			if (r1 >= 0) { v += sr * h6(r1, c0); if (c1 >= 0) v += sr * sc * h6(r1, c1); }
-			H[c * SS + r] = v;
-		}
-	}
-}
 static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
 int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H) {
 	TRY(lowdof_sm_refuse(b, sm, "iterate"));
@@ -421,7 +385,14 @@ int mtfhip_batch_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, d
 		TRY(iterate_core(b, sm, f, g6.data(), H6.data()));
 	}
 	const int SS = b->S;
-	for (int t = 0; t < b->B; ++t) lowdof_project(b->lo_ssm, &g6[(size_t)6 * t], &H6[(size_t)36 * t], g + (size_t)t * SS, H + (size_t)t * SS * SS);
+	/* g_S = g_aff M, H_S = M^T H_aff M (lowdof_g / lowdof_h, mtfhip_sm_system.h) over the column-major 6 x 6 of each target */
+	for (int t = 0; t < b->B; ++t) {
+		const double *gt6 = &g6[(size_t)6 * t], *Ht6 = &H6[(size_t)36 * t];
+		for (int c = 0; c < SS; ++c) {
+			g[(size_t)t * SS + c] = lowdof_g(b->lo_ssm, c, [&](int a) { return gt6[a]; });
+			for (int r = 0; r < SS; ++r) H[(size_t)t * SS * SS + c * SS + r] = lowdof_h(b->lo_ssm, r, c, [&](int rr, int cc) { return Ht6[cc * 6 + rr]; });
+		}
+	}
 	if (sm->materialize && sm->sm != MTFHIP_SM_ICLK) {
 		TRY(do_cmpt_pix_jacobian(b, sm->chained_warp ? MTFHIP_JAC_WARPED : MTFHIP_JAC_INIT, MTFHIP_BUF_DIT_DX, MTFHIP_BUF_JT));
 		if (sm->sm == MTFHIP_SM_ESM && (sm->jac_type == 0 || sm->hess_type == 3)) TRY(mtfhip_sm_mean_jacobian(b));   /* NT/ESM.cc:239-242 */

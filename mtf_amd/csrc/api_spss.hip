@@ -1,6 +1,6 @@
 /*
  * api_spss.hip -- the Sum of Pixelwise Structural Similarity appearance model's own state (AM/src/SPSS.cc): its parameter k, what a fused
- * launch reads for a search method, the host-side assembly of a fused pass's row, and the per-function similarity, gradients and Hessians
+ * launch reads for a search method (its row's f, g and H: the SPSS entries of mtfhip_sm_system.h), and the per-function similarity, gradients and Hessians
  * (C-ABI implementation, include/mtfhip.h; the kernels: kernels_spss.hip, kernels_fused_spss.hip; no CPU fallback: HIP kernels or an error)
  */
 #include "mtfhip_api_internal.h"
@@ -23,29 +23,6 @@ SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	else sp.weight = ht >= 3 ? SPSS_W_CURR : SPSS_W_SELF;
 	sp.g_mean = (sm->sm == MTFHIP_SM_ESM && sm->jac_type == 0) ? 1 : 0;
 	return sp;
-}
-
-/* one target's reduced SPSS row -> f, g and H of the search method before damping (the device twin: finish_track_body's SPSS) */
-void spss_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H) {
-	const int S = b->S;
-	if (f) *f = acc[ACC_RR];
-	for (int s = 0; s < S; ++s) {
-		if (sm->sm == MTFHIP_SM_ICLK) g[s] = acc[ACC_G2 + s];
-		else if (sm->sm == MTFHIP_SM_ESM && sm->jac_type != 0) g[s] = 0.5 * (acc[ACC_G + s] - acc[ACC_G2 + s]);
-		else g[s] = acc[ACC_G + s];
-	}
-	const bool use_h0 = sm->hess_type == 0;
-	const bool sum_h0 = sm->sm == MTFHIP_SM_ESM && sm->hess_type == 2;
-	int k = 0;
-	for (int a = 0; a < 8; ++a)
-		for (int c = a; c < 8; ++c) {
-			if (a < S && c < S) {
-				double v = use_h0 ? h0[c * S + a] : acc[ACC_H + k];
-				if (sum_h0) v = (v + h0[c * S + a]) * 0.5;
-				H[c * S + a] = v; H[a * S + c] = v;
-			}
-			++k;
-		}
 }
 
 int spss_update_similarity(mtfhip_batch *b, int prereq_only) {

@@ -259,7 +259,7 @@ __global__ __launch_bounds__(kBlock) void k_iclk_track(BatchView bv, ImgView im,
 	if constexpr (FAST) {
 		/* Tolerance mode: ONE workgroup-wide reduction per iteration instead of four (NCC) / two (SSD), and no serial section.
 		 * NCC's similarity and df_dI0 . J0 are functions of raw moments -- sum It, sum It^2, sum I0 It, sum It J0 plus the
-		 * template's constants sum J0, sum I0 J0 (the fused NCC kernel's algebra, api_fused.hip::ncc_assemble) -- so the two-pass
+		 * template's constants sum J0, sum I0 J0 (the algebra of mtfhip_sm_system.h's ncc_init_jac, here with reciprocals and FMAs) -- so the two-pass
 		 * mean / norm / gradient-mean chain of NCC.cc:124-194 collapses into one pass; SSD accumulates r^2 and r J0 together.
 		 * The S x S product with the pre-inverted Hessian, the inverse compositional update and the corner test are then
 		 * evaluated redundantly by every thread from the broadcast sums: no thread-0 section, no barrier behind it, the warp stays

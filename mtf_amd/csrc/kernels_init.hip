@@ -8,7 +8,8 @@
  * host, the template moments of the fused NCC path): 385 us per frame of 256 patches against 42 us for tracking them.  Here one
  * workgroup per patch samples the template, takes its finite-difference gradient, writes the steepest-descent rows, reduces the
  * moments everything else is a function of -- sum I0, |I0 - mean|^2, sum J0, sum I0 J0, Gram(J0) -- forms the constant self
- * Hessian (SSD: -J0^T J0, SSDBase.cc:268-285; NCC: NCC.cc:337-389 in raw moments, the algebra of api_fused.hip::ncc_assemble),
+ * Hessian (SSD: -J0^T J0, SSDBase.cc:268-285; NCC: NCC.cc:337-389 in raw moments, the algebra of mtfhip_sm_system.h's ncc_hess at
+ * It = I0 -- written out here because it multiplies by 1 / b^2 where ncc_hess divides: adopting the shared form would change H0's bits),
  * inverts it (scaled, partially pivoted Gauss-Jordan on one wave) and leaves the small results both in device memory (for the
  * tracking launches that follow) and in a pinned host record the library folds into its mirrors when somebody asks for them.
  * One of the translation units of libmtfhip.so.

@@ -228,7 +228,7 @@ struct TargetHost {
 	double I0_mean, It_mean, a, b, c, gmean;
 	double h0[64]; /* constant self Hessian of the template (column-major), set by init_template */
 	/* NCC, fused path: moments of the template's pixel Jacobian (constant while J0 is): sum J0, sum I0 J0, Gram(J0) */
-	double ncc_sj0[8], ncc_i0j0[8], ncc_gram0[36];
+	double ncc_tm[NCC_TM_COUNT];
 };
 
 struct mtfhip_batch;
@@ -565,7 +565,6 @@ mtfhip::SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int spss_update_similarity(mtfhip_batch *b, int prereq_only);
 int spss_update_grad(mtfhip_batch *b, int curr);
 int spss_hessian(mtfhip_batch *b, int j_buf, int weight, double *H);
-void spss_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H);
 /* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
 int scv_capture(mtfhip_batch *b);
 int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
@@ -662,22 +661,20 @@ static int pull_init_mirrors(mtfhip_batch *b) {
 		 * a synchronisation, paid by the rare caller that reads the mirrors behind a grid re-initialisation instead of by every frame */
 		static thread_local std::vector<double> h0v, ncv, tmv;
 		const size_t Bt = (size_t)b->B;
-		h0v.resize(64 * Bt); ncv.resize(8 * Bt); tmv.resize(52 * Bt);
+		h0v.resize(64 * Bt); ncv.resize(8 * Bt); tmv.resize(NCC_TM_COUNT * Bt);
 		HIP_TRY(hipMemcpyAsync(h0v.data(), b->d_h0, sizeof(double) * 64 * Bt, hipMemcpyDeviceToHost, b->ctx->stream));
 		if (ncc_am) {
 			HIP_TRY(hipMemcpyAsync(ncv.data(), b->d_ncc, sizeof(double) * 8 * Bt, hipMemcpyDeviceToHost, b->ctx->stream));
-			HIP_TRY(hipMemcpyAsync(tmv.data(), b->d_ncc_tm, sizeof(double) * 52 * Bt, hipMemcpyDeviceToHost, b->ctx->stream));
+			HIP_TRY(hipMemcpyAsync(tmv.data(), b->d_ncc_tm, sizeof(double) * NCC_TM_COUNT * Bt, hipMemcpyDeviceToHost, b->ctx->stream));
 		}
 		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
 		for (int t = 0; t < b->B; ++t) {
 			TargetHost &h = b->th[t];
 			std::memcpy(h.h0, &h0v[64 * (size_t)t], sizeof(double) * 64);
 			if (ncc_am) {
-				const double *r = &ncv[8 * (size_t)t], *m = &tmv[52 * (size_t)t];
+				const double *r = &ncv[8 * (size_t)t], *m = &tmv[NCC_TM_COUNT * (size_t)t];
 				h.I0_mean = r[0]; h.c = r[1]; h.It_mean = r[2]; h.b = r[3]; h.f = r[4]; h.gmean = r[5];
-				std::memcpy(h.ncc_sj0, m, sizeof(double) * 8);
-				std::memcpy(h.ncc_i0j0, m + 8, sizeof(double) * 8);
-				std::memcpy(h.ncc_gram0, m + 16, sizeof(double) * 36);
+				std::memcpy(h.ncc_tm, m, sizeof(double) * NCC_TM_COUNT);
 			}
 		}
 		b->init_mirror_seq = 0; b->init_rec_device = false;
@@ -702,9 +699,7 @@ static int pull_init_mirrors(mtfhip_batch *b) {
 		std::memcpy(h.h0, r, sizeof(double) * 64);
 		if (ncc) {
 			h.I0_mean = r[64]; h.c = r[65]; h.It_mean = r[66]; h.b = r[67]; h.f = r[68]; h.gmean = r[69];
-			std::memcpy(h.ncc_sj0, r + 72, sizeof(double) * 8);
-			std::memcpy(h.ncc_i0j0, r + 80, sizeof(double) * 8);
-			std::memcpy(h.ncc_gram0, r + 88, sizeof(double) * 36);
+			std::memcpy(h.ncc_tm, r + 72, sizeof(double) * NCC_TM_COUNT);
 		}
 	}
 	b->init_mirror_seq = 0;
@@ -832,14 +827,15 @@ int do_update_grad_pts(mtfhip_batch *b, double grad_eps);
 int gemv_to_host(mtfhip_batch *b, const double *v1, int j1, const double *v2, int j2, int sum_mode, double *g, int diff);
 int mi_blocks(const mtfhip_batch *b);
 int push_ncc(mtfhip_batch *b);
-/* api_ncc_moments.hip (ncc_assemble: one target's reduced row -> f, g and H before damping; ncc_refresh_mirrors: its scalars -> It_mean / b / a / f) */
+/* api_ncc_moments.hip (ncc_host_sys: one target's reduced row and template mirrors as the NCC system of mtfhip_sm_system.h; ncc_refresh_mirrors: its
+ * scalars -> It_mean / b / a / f) */
 int ncc_template_moments(mtfhip_batch *b);
 int ncc_lazy_outputs(mtfhip_batch *b, int trig, int j_a, bool hess_mean, double *g);
 int ncc_hessian_from_cache(mtfhip_batch *b, int j_buf, int kind, double *H);
-int ncc_assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, const double *M, TargetHost &h, double *f, double *g, double *H);
+static inline NccSys ncc_host_sys(const mtfhip_batch *b, const TargetHost &h, const double *M) { return ncc_sys(M, h.ncc_tm, h.I0_mean, h.c, (double)b->N); }
 void ncc_refresh_mirrors(const mtfhip_batch *b, TargetHost &h, const double *M);
-/* api_fused.hip (second_order_term: -1 for none; assemble: one target's reduced SSD row -> f, g and H; assemble_rows: every target of an SSD / NCC
- * pass; store_h0: th[].h0, d_h0 and d_h0inv from H0 [B][S x S] -- enqueued only: the caller synchronises the stream before it returns) */
+/* api_fused.hip (second_order_term: -1 for none; assemble_rows: every target's reduced row of an SSD-family / SPSS / NCC pass -> f, g and H;
+ * store_h0: th[].h0, d_h0 and d_h0inv from H0 [B][S x S] -- enqueued only: the caller synchronises the stream before it returns) */
 int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn);
 bool template_init_fused_ok(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int init_template_fused(mtfhip_batch *b, const mtfhip_sm_desc *sm, const mtfhip::RegionIngest *rg = nullptr, bool publish_host = true);
@@ -847,7 +843,6 @@ int set_region_core(mtfhip_batch *b, const double *corners, const mtfhip_sm_desc
 static inline bool region_refreshes(const mtfhip_sm_desc *sm) { return sm->sm == MTFHIP_SM_ESM || (sm->sm == MTFHIP_SM_FCLK && sm->hess_type == 0); }
 int fused_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm, FusedArgs &fa);
 int second_order_term(const mtfhip_sm_desc *sm, int am = MTFHIP_AM_SSD);
-void assemble(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *acc, const double *h0, double *f, double *g, double *H);
 int assemble_rows(mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, int nblk, const double *so, double so_scale, double *f, double *g, double *H);
 int store_h0(mtfhip_batch *b, const double *H0, bool with_inverse);
 /* api_mi_iter.hip.  What an MI iteration of the search method needs from the AM (NT/ESM.cc:315-377, NT/FCLK.cc:262-283, NT/ICLK.cc:204-252) */

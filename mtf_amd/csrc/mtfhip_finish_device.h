@@ -16,6 +16,105 @@ __device__ unsigned long long g_fin_trace[16];
 #define FIN_STAMP(k) do { } while (0)
 #endif
 
+/* ---- what the two finish bodies share beside the system itself (mtfhip_sm_system.h) ---- */
+/* COH (k_track_persist): everything the loop rewrites between passes -- partial rows, warp, state, corners, counters, flags, the
+ * Levenberg-Marquardt block -- is read and written with the coherent accessors of mtfhip_device.h (st_coh / ld_coh). */
+template <bool COH> __device__ __forceinline__ double fin_ld(const double *p) { if constexpr (COH) return ld_coh(p); else return *p; }
+template <bool COH> __device__ __forceinline__ int fin_ld(const int *p) { if constexpr (COH) return ld_coh(p); else return *p; }
+template <bool COH> __device__ __forceinline__ void fin_st(double *p, double v) { if constexpr (COH) st_coh(p, v); else *p = v; }
+template <bool COH> __device__ __forceinline__ void fin_st(int *p, int v) { if constexpr (COH) st_coh(p, v); else *p = v; }
+
+/* Fixed-order sum of the block rows of target t, column by column.  Up to eight rows (the batched decomposition) one lane per column sums
+ * them in one round trip; a single large target has 157: the rows are cut into three contiguous runs (multiples of eight rows) summed by
+ * three groups of 80 lanes and combined in run order -- 7 rounds instead of 20.  (Workgroups of fewer than 240 threads keep the single
+ * run.)  Two steps, so that the caller's other loads and its test of `active` sit between the requests and their use: fin_sum_runs
+ * returns the lane's column sum of a single run, or leaves the runs' sums in part_s; fin_sum_combine (a barrier for three runs) gives
+ * lane < RL its column. */
+__device__ __forceinline__ int fin_sum_n_runs(int nblk) { return (nblk > 8 && blockDim.x >= 240) ? 3 : 1; }
+template <bool COH>
+__device__ __forceinline__ double fin_sum_runs(const double *partials, int nblk, int RL, int t, double (*part_s)[80]) {
+	const int lane = threadIdx.x;
+	const int n_runs = fin_sum_n_runs(nblk);
+	const int run_len = n_runs == 1 ? nblk : ((nblk + 3 * 8 - 1) / (3 * 8)) * 8;
+	const int run = n_runs == 1 ? 0 : lane / 80, col = n_runs == 1 ? lane : lane % 80;
+	double v_acc = 0;
+	if (col < RL && run < n_runs) {
+		const int b0 = run * run_len, b1 = (b0 + run_len < nblk) ? b0 + run_len : nblk;
+		const double *p = partials + (size_t)t * nblk * RL + col;
+		auto ld = [&](size_t off) -> double { return fin_ld<COH>(p + off); };
+		/* eight block rows in flight per lane */
+		double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
+		int b = b0;
+		for (; b + 7 < b1; b += 8) {
+			s0 += ld((size_t)b * RL); s1 += ld((size_t)(b + 1) * RL);
+			s2 += ld((size_t)(b + 2) * RL); s3 += ld((size_t)(b + 3) * RL);
+			s4 += ld((size_t)(b + 4) * RL); s5 += ld((size_t)(b + 5) * RL);
+			s6 += ld((size_t)(b + 6) * RL); s7 += ld((size_t)(b + 7) * RL);
+		}
+		for (; b < b1; ++b) s0 += ld((size_t)b * RL);
+		const double v = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
+		if (n_runs == 1) v_acc = v; else part_s[run][col] = v;
+	}
+	return v_acc;
+}
+__device__ __forceinline__ double fin_sum_combine(int nblk, int RL, double v_acc, const double (*part_s)[80]) {
+	const int lane = threadIdx.x;
+	if (fin_sum_n_runs(nblk) > 1) {
+		__syncthreads();
+		if (lane < RL) v_acc = (part_s[0][lane] + part_s[1][lane]) + part_s[2][lane];
+	}
+	return v_acc;
+}
+
+/* the target stops iterating; behind a pass that did not materialise (TrackState::lean_pass) the warp and the state the pass ran at
+ * are kept for the trailing materialising launch */
+template <bool COH, bool LO>
+__device__ __forceinline__ void fin_stop_target(const TrackState &ts, int t, int *stop_flag, const double *w_old, const double *s_old) {
+	fin_st<COH>(ts.active + t, 0);
+	if (stop_flag) __hip_atomic_store(stop_flag, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+	if (ts.lean_pass || (LO && ts.keep_last)) {
+		for (int q = 0; q < 9; ++q) fin_st<COH>(ts.warp_last + 9 * t + q, w_old[q]);
+		for (int q = 0; q < 8; ++q) fin_st<COH>(ts.state_last + 8 * t + q, s_old[q]);
+		if (ts.lean_pass) fin_st<COH>(ts.need_mat + t, 1);
+	}
+}
+
+/* Levenberg-Marquardt: the accept / undo decision on the similarity f of this pass (NT/ESM.cc:186-232, NT/FCLK.cc:205-250,
+ * NT/ICLK.cc:181-199): a pure function of the block's words; returns undo and rescales delta */
+__device__ __forceinline__ bool fin_lm_decide(double f, double prev_f, double &delta, bool state_reset, int iter_id, double update) {
+	bool undo = false;
+	if (!state_reset) {
+		if (iter_id > 0) {
+			if (f < prev_f) { delta *= update; undo = true; }
+			else if (f > prev_f) delta /= update;
+		}
+	}
+	return undo;
+}
+/* ... and what one lane writes back of it */
+template <bool COH>
+__device__ __forceinline__ void fin_lm_store(double *lmp, double f, double delta, bool state_reset, bool undo) {
+	fin_st<COH>(lmp + 1, delta);
+	if (undo) fin_st<COH>(lmp + 2, 1.0);
+	else { fin_st<COH>(lmp + 2, 0.0); if (!state_reset) fin_st<COH>(lmp + 0, f); }
+}
+
+/* the close of a pass, one lane: count it, test convergence on the corner change, stop the target */
+template <bool COH, bool ADDITIVE, bool LO>
+__device__ __forceinline__ void fin_count_and_stop(const mtfhip_sm_desc &sm, const TrackState &ts, int t, int *stop_flag, double *lmp, double *trec,
+	int n_it_prev, int lm_iter_id, bool undo, double change, const double *w_old, const double *s_old) {
+	const int n_it = n_it_prev + 1;   /* passes done (the reference's iters_done) */
+	fin_st<COH>(ts.n_iters + t, n_it);
+	if (trec) trec[89] = (double)n_it_prev;
+	if (lmp) {
+		/* an undo pass skips the convergence test (`continue`); it consumes an iteration in the for loops of ESM and ICLK
+		 * (NT/ESM.cc:179, NT/ICLK.cc:169) but not in FCLK's while loop (NT/FCLK.cc:193-223) */
+		const int id = lm_iter_id + ((undo && sm.sm == MTFHIP_SM_FCLK && !ADDITIVE) ? 0 : 1);
+		fin_st<COH>(lmp + 3, (double)id);
+		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) fin_stop_target<COH, LO>(ts, t, stop_flag, w_old, s_old);
+	} else if (change < sm.epsilon || n_it >= sm.max_iters) fin_stop_target<COH, LO>(ts, t, stop_flag, w_old, s_old);
+}
+
 /* ===================================================================== */
 /* on-device solve + compositional update (batched drivers only)          */
 /* ===================================================================== */
@@ -30,8 +129,7 @@ __device__ unsigned long long g_fin_trace[16];
  *       (Homography.cc:73-92,109-114, Affine.cc:90-106,145-150, NT/FCLK.cc:314-339). */
 /* Body of the device-side finish, executed by the first wave of the calling workgroup (all threads of the workgroup
  * must call it: it contains workgroup barriers). */
-/* COH (k_track_persist): everything the loop rewrites between passes -- partial rows, warp, state, corners, counters, flags, the
- * Levenberg-Marquardt block -- is read and written with the coherent accessors of mtfhip_device.h (st_coh / ld_coh). */
+/* COH (k_track_persist): the coherent accessors, fin_ld / fin_st above. */
 /* ADDITIVE (k_alk_finish, kernels_alk.hip: nt::FALK / nt::IALK, NT/FALK.cc:229-246, NT/IALK.cc:180-194): the solved update is ADDED to the
  * state -- StateSpaceModel::additiveUpdate, ProjectiveBase.cc:51-55: curr_state += state_update, the warp rebuilt from the state
  * (getWarpFromState), the corners from the warp -- and a Levenberg-Marquardt undo adds its negative (NT/FALK.cc:156-158); the `continue`
@@ -51,26 +149,14 @@ __device__ unsigned long long g_fin_trace[16];
 template <bool COH = false, bool ADDITIVE = false, bool LO = false, bool SPSS = false>
 __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
 	const double *partials, int nblk, int t, int *stop_flag = nullptr) {
-	auto LD = [](const double *p) -> double { if constexpr (COH) return ld_coh(p); else return *p; };
-	auto LDI = [](const int *p) -> int { if constexpr (COH) return ld_coh(p); else return *p; };
-	auto ST = [](double *p, double v) { if constexpr (COH) st_coh(p, v); else *p = v; };
-	auto STI = [](int *p, int v) { if constexpr (COH) st_coh(p, v); else *p = v; };
-	/* the target stops iterating; behind a pass that did not materialise (TrackState::lean_pass) the warp and the state the pass ran at
-	 * are kept for the trailing materialising launch */
-	auto stop_target = [&](const double *w_old, const double *s_old) {
-		STI(ts.active + t, 0);
-		if (stop_flag) __hip_atomic_store(stop_flag, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-		if (ts.lean_pass || (LO && ts.keep_last)) {
-			for (int q = 0; q < 9; ++q) ST(ts.warp_last + 9 * t + q, w_old[q]);
-			for (int q = 0; q < 8; ++q) ST(ts.state_last + 8 * t + q, s_old[q]);
-			if (ts.lean_pass) STI(ts.need_mat + t, 1);
-		}
-	};
+	auto LD = [](const double *p) -> double { return fin_ld<COH>(p); };
+	auto LDI = [](const int *p) -> int { return fin_ld<COH>(p); };
+	auto ST = [](double *p, double v) { fin_st<COH>(p, v); };
 	FIN_STAMP(0);
 	__shared__ double acc_s[NCC_ACC_COUNT];   /* >= ACC_COUNT */
 	__shared__ double A[8][9];
 	__shared__ double dps[8];
-	__shared__ double h0s[64], Ws[9], crs[8], ics[12], tms[52], ncs[2], sos[8];
+	__shared__ double h0s[64], Ws[9], crs[8], ics[12], tms[NCC_TM_COUNT], ncs[2], sos[8];
 	const int lane = threadIdx.x;
 	const bool wv0 = lane < 64;
 	const int S = bv.S;
@@ -95,37 +181,12 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		if (lane < 8) v_cr = LD(ts.corners + 8 * t + lane);
 		if (lane < 12) v_ic = ts.init_corners_hm[12 * t + lane];
 		if (ncc) {
-			if (lane < 52) v_tm = ts.ncc_tm[(size_t)t * 52 + lane];
+			if (lane < NCC_TM_COUNT) v_tm = ts.ncc_tm[(size_t)t * NCC_TM_COUNT + lane];
 			if (lane < 2) v_nc = ts.ncc[(size_t)t * 8 + lane];
 		}
 	}
-	/* fixed-order sum of the block rows.  Up to eight rows (the batched decomposition) one lane per column sums them in one round
-	 * trip; a single large target has 157: the rows are cut into three contiguous runs (multiples of eight rows) summed by
-	 * three groups of 80 lanes and combined in run order -- 7 rounds instead of 20.  (Workgroups of fewer than 240 threads keep
-	 * the single run.) */
 	__shared__ double part_s[3][80];
-	const int n_runs = (nblk > 8 && blockDim.x >= 240) ? 3 : 1;
-	const int run_len = n_runs == 1 ? nblk : ((nblk + 3 * 8 - 1) / (3 * 8)) * 8;
-	{
-		const int run = n_runs == 1 ? 0 : lane / 80, col = n_runs == 1 ? lane : lane % 80;
-		if (col < RL && run < n_runs) {
-			const int b0 = run * run_len, b1 = (b0 + run_len < nblk) ? b0 + run_len : nblk;
-			const double *p = partials + (size_t)t * nblk * RL + col;
-			auto ld = [&](size_t off) -> double { return LD(p + off); };
-			/* eight block rows in flight per lane */
-			double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
-			int b = b0;
-			for (; b + 7 < b1; b += 8) {
-				s0 += ld((size_t)b * RL); s1 += ld((size_t)(b + 1) * RL);
-				s2 += ld((size_t)(b + 2) * RL); s3 += ld((size_t)(b + 3) * RL);
-				s4 += ld((size_t)(b + 4) * RL); s5 += ld((size_t)(b + 5) * RL);
-				s6 += ld((size_t)(b + 6) * RL); s7 += ld((size_t)(b + 7) * RL);
-			}
-			for (; b < b1; ++b) s0 += ld((size_t)b * RL);
-			const double v = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
-			if (n_runs == 1) v_acc = v; else part_s[run][col] = v;
-		}
-	}
+	v_acc = fin_sum_runs<COH>(partials, nblk, RL, t, part_s);
 	if (!act) return;
 	if (stop_flag && lane == 0) __hip_atomic_store(stop_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 	FIN_STAMP(1);
@@ -134,107 +195,44 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		if (lane < 9) Ws[lane] = v_w;
 		if (lane < 8) { crs[lane] = v_cr; sos[lane] = v_so; }
 		if (lane < 12) ics[lane] = v_ic;
-		if (lane < 52) tms[lane] = v_tm;
+		if (lane < NCC_TM_COUNT) tms[lane] = v_tm;
 		if (lane < 2) ncs[lane] = v_nc;
 	}
-	if (n_runs > 1) {
-		__syncthreads();
-		if (lane < RL) v_acc = (part_s[0][lane] + part_s[1][lane]) + part_s[2][lane];
-	}
+	v_acc = fin_sum_combine(nblk, RL, v_acc, part_s);
 	if (lane < RL) { acc_s[lane] = v_acc; ST(ts.acc + (size_t)t * RL + lane, v_acc); }
 	__syncthreads();
 	FIN_STAMP(2);
 	const int i = (lane >> 3) & 7, j = lane & 7;
+	/* the system of this pass: mtfhip_sm_system.h.  NCC's scalars once, from the reduced row and the template's constants */
+	NccSys nq = NccSys();
+	if (ncc) nq = ncc_sys(acc_s, tms, ncs[0], ncs[1], (double)bv.N);
+	const double f_row = ncc ? nq.f : ssd_f(SPSS, acc_s);
 	/* ---- Levenberg-Marquardt: the accept / undo test on the similarity of this pass (uniform over the workgroup) ---- */
 	double *lmp = ts.lm ? ts.lm + (size_t)t * kLmStride : nullptr;
 	double lm_delta = 0.0;
 	int lm_iter_id = n_it_prev;   /* (LM keeps its own counter) */
 	bool undo = false;
 	if (lmp) {
-		const double f_now = ts.f_ext ? LD(ts.f_ext + t) : (ncc ? 0.0 : (SPSS ? acc_s[ACC_RR] : -acc_s[ACC_RR] / 2));
+		const double f_use = ts.f_ext ? LD(ts.f_ext + t) : f_row;   /* (MI's similarity is not a function of the row) */
 		const double prev_f = LD(lmp + 0);
 		lm_delta = LD(lmp + 1);
 		const bool state_reset = LD(lmp + 2) != 0.0;
 		lm_iter_id = (int)LD(lmp + 3);
-		double f_use = f_now;
-		if (ncc) {
-			const double nN0 = (double)bv.N, mt0 = acc_s[NCC_IT] / nN0, b20 = acc_s[NCC_IT2] - nN0 * mt0 * mt0;
-			f_use = (acc_s[NCC_I0IT] - nN0 * ncs[0] * mt0) / (sqrt(b20) * ncs[1]);
-		}
-		if (!state_reset) {
-			if (lm_iter_id > 0) {
-				if (f_use < prev_f) { lm_delta *= sm.lm_delta_update; undo = true; }
-				else if (f_use > prev_f) lm_delta /= sm.lm_delta_update;
-			}
-		}
+		undo = fin_lm_decide(f_use, prev_f, lm_delta, state_reset, lm_iter_id, sm.lm_delta_update);
 		__syncthreads();   /* every thread has read the LM block before lane 0 rewrites it */
-		if (lane == 0) {
-			ST(lmp + 1, lm_delta);
-			if (undo) ST(lmp + 2, 1.0);
-			else { ST(lmp + 2, 0.0); if (!state_reset) ST(lmp + 0, f_use); }
-		}
+		if (lane == 0) fin_lm_store<COH>(lmp, f_use, lm_delta, state_reset, undo);
 	}
-	const bool use_h0 = (sm.hess_type == 0) || (!SPSS && sm.sm == MTFHIP_SM_ICLK && !ts.h_from_acc);
-	const bool sum_h0 = (sm.sm == MTFHIP_SM_ESM) && (sm.hess_type == 2 || (sm.hess_type == 4 && !ts.h_from_acc));   /* (MI's SumOfStd arrives summed) */
-	const double gscale = (sm.sm == MTFHIP_SM_ESM) ? 0.5 : 1.0;
-	/* NCC from its moments (ncc_assemble in api_ncc_moments.hip is the host twin; formulas and citations there) */
-	const double nN = (double)bv.N;
-	const double n_mt = ncc ? acc_s[NCC_IT] / nN : 0.0, n_m0 = ncs[0], n_c = ncc ? ncs[1] : 1.0;
-	const double n_b2 = ncc ? acc_s[NCC_IT2] - nN * n_mt * n_mt : 1.0, n_b = ncc ? sqrt(n_b2) : 1.0;
-	const double n_f = ncc ? (acc_s[NCC_I0IT] - nN * n_m0 * n_mt) / (n_b * n_c) : 0.0;
-	auto mom = [&](int which, int c0, int ct, int s) -> double {   /* which: 0 J0, 1 Jt, 2 their mean */
-		const double v0 = c0 >= 0 ? tms[c0 + s] : acc_s[NCC_ITJ0 + s], vt = acc_s[ct + s];
-		return which == 0 ? v0 : (which == 1 ? vt : (v0 + vt) / 2);
-	};
-	auto n_ut = [&](int which, int s) { return (mom(which, -1, NCC_ITJ, s) - n_mt * mom(which, 0, NCC_SJ, s)) / n_b2; };
-	auto n_u0 = [&](int which, int s) { return (mom(which, 8, NCC_I0J, s) - n_m0 * mom(which, 0, NCC_SJ, s)) / (n_b * n_c); };
-	auto n_hess = [&](int kind, int which, int r, int c, int kk) -> double {   /* kind: 0 init, 1 curr, 2 self */
-		const double gram = which == 0 ? tms[16 + kk] : acc_s[NCC_GRAM + kk];
-		const double G = -(gram - mom(which, 0, NCC_SJ, r) * mom(which, 0, NCC_SJ, c) / nN) / n_b2;
-		const double utr = n_ut(which, r), utc = n_ut(which, c);
-		if (kind == 2) return G + utr * utc;
-		const double u0r = n_u0(which, r), u0c = n_u0(which, c);
-		return n_f * G - utr * u0c - u0r * utc + 3 * (kind == 1 ? utr * utc : u0r * u0c);
-	};
+	/* entry (r, c) of H and entry s of g as the search method holds them, padded to 8 x 8: thin adapters over mtfhip_sm_system.h */
 	auto h_entry = [&](int r, int c) -> double {
 		if (r >= S || c >= S) return r == c ? -1.0 : 0.0;
-		const int a = r < c ? r : c, b2 = r < c ? c : r;
-		const int kk = a * 8 - (a * (a - 1)) / 2 + (b2 - a);
-		if (ncc) {
-			const int ht = sm.hess_type;
-			const double h0v = h0s[b2 * S + a];
-			/* sec_ord_hess (NCC.cc:391-410): the weighted pixel-Hessian sums of k_second_order_ssd's NCC form, entry (r, c) */
-			const double ex = ts.h_extra ? ts.h_extra_scale * ts.h_extra[(size_t)t * S * S + c * S + r] : 0.0;
-			if (ht == 0) return h0v;
-			if (sm.sm == MTFHIP_SM_ICLK) return n_hess(0, 0, r, c, kk) + ex;
-			if (sm.sm == MTFHIP_SM_FCLK || ht == 1 || ht == 5) return n_hess(ht == 1 ? 2 : 1, 1, r, c, kk) + ex;
-			if (ht == 2) return 0.5 * (n_hess(2, 1, r, c, kk) + h0v);
-			if (ht == 3) return n_hess(1, 2, r, c, kk) + ex;
-			return 0.5 * (n_hess(0, 0, r, c, kk) + n_hess(1, 1, r, c, kk)) + ex;
-		}
-		/* (the constant Hessian as entry (r, c), not from a triangle: MI's initial self Hessian with its second-order part is not
-		 * symmetric in the homography's last two rows / columns; every other one is, and reads the same numbers) */
-		double v = use_h0 ? h0s[c * S + r] : (SPSS ? acc_s[ACC_H + kk] : -acc_s[ACC_H + kk]);
-		if (sum_h0) v = (v + h0s[c * S + r]) * 0.5;
-		/* sec_ord_hess: + sum_p df_dI[p] d2I_dp2[:, p] (SSDBase.cc:313-415); the homography blocks are not symmetric in their
+		/* sec_ord_hess: + sum_p df_dI[p] d2I_dp2[:, p] (SSDBase.cc:313-415; NCC.cc:391-410); the homography blocks are not symmetric in their
 		 * last two rows / columns (Homography.cc:421,613,796), so the entry is taken as (r, c), not from a triangle */
+		if (ncc) return ncc_h(sm, nq, h0s[(r < c ? c : r) * S + (r < c ? r : c)], ts.h_extra ? ts.h_extra_scale * ts.h_extra[(size_t)t * S * S + c * S + r] : 0.0, r, c);
+		double v = ssd_h(sm, ts.h_from_acc != 0, SPSS, acc_s, h0s, S, r, c);
 		if (ts.h_extra) v += ts.h_extra_scale * ts.h_extra[(size_t)t * S * S + c * S + r];
 		return v;
 	};
-	auto g_entry = [&](int s) -> double {
-		if constexpr (SPSS) {
-			if (sm.sm == MTFHIP_SM_ICLK) return acc_s[ACC_G2 + s];
-			if (sm.sm == MTFHIP_SM_ESM && sm.jac_type != 0) return 0.5 * (acc_s[ACC_G + s] - acc_s[ACC_G2 + s]);
-			return acc_s[ACC_G + s];
-		}
-		if (!ncc) return gscale * acc_s[ACC_G + s];
-		auto cj = [&](int which) { return n_u0(which, s) - n_f * n_ut(which, s); };
-		auto ij = [&](int which) { return (n_b / n_c) * (n_ut(which, s) - n_f * n_u0(which, s)); };
-		if (sm.sm == MTFHIP_SM_FCLK) return cj(1);
-		if (sm.sm == MTFHIP_SM_ICLK) return ij(0);
-		if (sm.jac_type == 0) return cj(2);
-		return 0.5 * (cj(1) - ij(0));
-	};
+	auto g_entry = [&](int s) -> double { return (!SPSS && ncc) ? ncc_g(sm, nq, s) : ssd_g(sm, SPSS, acc_s, s); };
 	/* Symmetric diagonal equilibration by POWERS OF TWO: the products are exact, so the scaled elimination follows the unscaled
 	 * one bit for bit while its pivots stay near one (and a frexp / ldexp pair replaces the square root and the division of
 	 * 1 / sqrt|d|, a microsecond of dependent arithmetic on an idle workgroup). */
@@ -244,39 +242,10 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	 * from convergence, where the reference's colPivHouseholderQr (NT/FCLK.cc:298) does not care either.  (A row-per-lane
 	 * elimination in registers with v_readlane broadcasts was measured slower than this LDS form: 8.9 k against 6.9 k clocks.) */
 	const bool pivoting = SPSS || ncc || ts.h_from_acc || ts.h_extra != nullptr;   /* (the search and the row swap are two barriers and eight LDS reads per step: skipped for SSD) */
-	/* The low-order SSMs: J_S = J_aff M with M constant, 6 x SS, at most two +-1 entries per column (Translation.h:45-63,
-	 * Isometry.cc:115-135,162-185, Similitude.cc:163-210) --
-	 *   Translation [Ja0, Ja1]    Isometry [Ja0, Ja1, Ja4 - Ja3]    Similitude [Ja0, Ja1, Ja2 + Ja5, Ja4 - Ja3]
-	 * -- and every g and H above is linear / bilinear in the rows: g_S = g_aff M, H_S = M^T H_aff M, an entry of H_S a sum of at most four
-	 * of H_aff.  Taken here: behind h_entry / g_entry, in front of the Levenberg-Marquardt scaling (the reference damps the S x S Hessian),
-	 * the equilibration and the elimination; rows and columns >= SS are padded as above.  col k of M: rows a0 and (a1 >= 0) a1 with sign s1. */
-	auto lo_col = [&](int k, int &a0, int &a1, double &s1) {
-		a0 = k; a1 = -1; s1 = 0.0;
-		if (k >= 2) { const bool sum = lo == MTFHIP_SSM_SIMILITUDE && k == 2; a0 = sum ? 2 : 4; a1 = sum ? 5 : 3; s1 = sum ? 1.0 : -1.0; }
-	};
-	auto lo_h = [&](int r, int c) -> double {
-		if (r >= SS || c >= SS) return r == c ? -1.0 : 0.0;
-		int r0, r1, c0, c1; double sr, sc;
-		lo_col(r, r0, r1, sr); lo_col(c, c0, c1, sc);
-		/* (one copy of h_entry, not four: the loops stay loops) */
-		double v = 0.0;
-#pragma unroll 1
-		for (int u = 0; u < 2; ++u) {
-			const int ru = u ? r1 : r0;
-			if (ru < 0) continue;
-#pragma unroll 1
-			for (int w = 0; w < 2; ++w) {
-				const int cw = w ? c1 : c0;
-				if (cw >= 0) v += (u ? sr : 1.0) * (w ? sc : 1.0) * h_entry(ru, cw);
-			}
-		}
-		return v;
-	};
-	auto lo_g = [&](int s) -> double {
-		int a0, a1; double s1;
-		lo_col(s, a0, a1, s1);
-		return g_entry(a0) + (a1 >= 0 ? s1 * g_entry(a1) : 0.0);
-	};
+	/* The low-order SSMs: the SS x SS projection of the affine system (lowdof_h / lowdof_g, mtfhip_sm_system.h), taken here: behind h_entry /
+	 * g_entry, in front of the damping, the equilibration and the elimination; rows and columns >= SS are padded as above */
+	auto lo_h = [&](int r, int c) -> double { return (r >= SS || c >= SS) ? (r == c ? -1.0 : 0.0) : lowdof_h(lo, r, c, h_entry); };
+	auto lo_g = [&](int s) -> double { return lowdof_g(lo, s, g_entry); };
 	double hii, hjj, hij = 0.0, gi = 0.0;
 	if (lo) {
 		hii = lo_h(i, i); hjj = lo_h(j, j);
@@ -295,7 +264,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 			trec[8 * i + j] = (i < SS && j < SS) ? hij : 0.0;
 			if (j == 0) trec[64 + i] = gi;
 			if (lane == 0) {
-				trec[88] = ts.f_ext ? LD(ts.f_ext + t) : (ncc ? n_f : (SPSS ? acc_s[ACC_RR] : -acc_s[ACC_RR] / 2));
+				trec[88] = ts.f_ext ? LD(ts.f_ext + t) : f_row;
 				trec[90] = undo ? 1.0 : 0.0; trec[91] = lm_delta; trec[92] = 1.0;
 			}
 		}
@@ -469,16 +438,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		double ddx = crs[2 * q] - nxy[2 * q], ddy = crs[2 * q + 1] - nxy[2 * q + 1];
 		change += ddx * ddx + ddy * ddy;
 	}
-	const int n_it = n_it_prev + 1;   /* passes done (the reference's iters_done) */
-	STI(ts.n_iters + t, n_it);
-	if (trec) trec[89] = (double)n_it_prev;
-	if (lmp) {
-		/* an undo pass skips the convergence test (`continue`); it consumes an iteration in the for loops of ESM and ICLK
-		 * (NT/ESM.cc:179, NT/ICLK.cc:169) but not in FCLK's while loop (NT/FCLK.cc:193-223) */
-		const int id = lm_iter_id + ((undo && sm.sm == MTFHIP_SM_FCLK && !ADDITIVE) ? 0 : 1);
-		ST(lmp + 3, (double)id);
-		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) stop_target(Ws, sos);
-	} else if (change < sm.epsilon || n_it >= sm.max_iters) stop_target(Ws, sos);
+	fin_count_and_stop<COH, ADDITIVE, LO>(sm, ts, t, stop_flag, lmp, trec, n_it_prev, lm_iter_id, undo, change, Ws, sos);
 	FIN_STAMP(6);
 }
 
@@ -496,19 +456,9 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 template <bool COH = false>
 __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
 	const double *partials, int nblk, int t, int *stop_flag = nullptr) {
-	auto LD = [](const double *p) -> double { if constexpr (COH) return ld_coh(p); else return *p; };
-	auto LDI = [](const int *p) -> int { if constexpr (COH) return ld_coh(p); else return *p; };
-	auto ST = [](double *p, double v) { if constexpr (COH) st_coh(p, v); else *p = v; };
-	auto STI = [](int *p, int v) { if constexpr (COH) st_coh(p, v); else *p = v; };
-	auto stop_target = [&](const double *w_old, const double *s_old) {   /* (as finish_track_body's) */
-		STI(ts.active + t, 0);
-		if (stop_flag) __hip_atomic_store(stop_flag, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-		if (ts.lean_pass) {
-			for (int q = 0; q < 9; ++q) ST(ts.warp_last + 9 * t + q, w_old[q]);
-			for (int q = 0; q < 8; ++q) ST(ts.state_last + 8 * t + q, s_old[q]);
-			STI(ts.need_mat + t, 1);
-		}
-	};
+	auto LD = [](const double *p) -> double { return fin_ld<COH>(p); };
+	auto LDI = [](const int *p) -> int { return fin_ld<COH>(p); };
+	auto ST = [](double *p, double v) { fin_st<COH>(p, v); };
 	__shared__ double f_acc[ACC_COUNT], f_h0[64], f_w[9], f_cr[8], f_ic[12], f_lm[kLmStride + 1], f_part[3][80], f_so[8];
 	const int lane = threadIdx.x;
 	const bool wv0 = lane < 64;
@@ -529,28 +479,7 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 		if (lane < 8) v_cr = LD(ts.corners + 8 * t + lane);
 		if (lane < 12) v_ic = ts.init_corners_hm[12 * t + lane];
 	}
-	/* fixed-order sum of the block rows: the same runs and the same order as finish_track_body */
-	const int n_runs = (nblk > 8 && blockDim.x >= 240) ? 3 : 1;
-	const int run_len = n_runs == 1 ? nblk : ((nblk + 3 * 8 - 1) / (3 * 8)) * 8;
-	{
-		const int run = n_runs == 1 ? 0 : lane / 80, col = n_runs == 1 ? lane : lane % 80;
-		if (col < RL && run < n_runs) {
-			const int b0 = run * run_len, b1 = (b0 + run_len < nblk) ? b0 + run_len : nblk;
-			const double *p = partials + (size_t)t * nblk * RL + col;
-			auto ld = [&](size_t off) -> double { return LD(p + off); };
-			double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
-			int b = b0;
-			for (; b + 7 < b1; b += 8) {
-				s0 += ld((size_t)b * RL); s1 += ld((size_t)(b + 1) * RL);
-				s2 += ld((size_t)(b + 2) * RL); s3 += ld((size_t)(b + 3) * RL);
-				s4 += ld((size_t)(b + 4) * RL); s5 += ld((size_t)(b + 5) * RL);
-				s6 += ld((size_t)(b + 6) * RL); s7 += ld((size_t)(b + 7) * RL);
-			}
-			for (; b < b1; ++b) s0 += ld((size_t)b * RL);
-			const double v = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
-			if (n_runs == 1) v_acc = v; else f_part[run][col] = v;
-		}
-	}
+	v_acc = fin_sum_runs<COH>(partials, nblk, RL, t, f_part);
 	if (!act) return;
 	if (stop_flag && lane == 0) __hip_atomic_store(stop_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 	FIN_STAMP(1);
@@ -562,10 +491,7 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 		if (lane < kLmStride) f_lm[lane] = v_lm;
 		if (lane == 0) f_lm[kLmStride] = v_f;
 	}
-	if (n_runs > 1) {
-		__syncthreads();
-		if (lane < RL) v_acc = (f_part[0][lane] + f_part[1][lane]) + f_part[2][lane];
-	}
+	v_acc = fin_sum_combine(nblk, RL, v_acc, f_part);
 	if (lane < RL) { f_acc[lane] = v_acc; ST(ts.acc + (size_t)t * RL + lane, v_acc); }
 	__syncthreads();
 	if (!wv0) return;   /* the rest is wave 0's, without barriers */
@@ -574,25 +500,16 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 	double lm_delta = 0.0;
 	int lm_iter_id = n_it_prev;
 	bool undo = false;
-	const double f_now = ts.f_ext ? f_lm[kLmStride] : -f_acc[ACC_RR] / 2;
+	const double f_now = ts.f_ext ? f_lm[kLmStride] : ssd_f(false, f_acc);
 	if (lmp) {
 		const double prev_f = f_lm[0];
 		lm_delta = f_lm[1];
 		const bool state_reset = f_lm[2] != 0.0;
 		lm_iter_id = (int)f_lm[3];
-		if (!state_reset && lm_iter_id > 0) {
-			if (f_now < prev_f) { lm_delta *= sm.lm_delta_update; undo = true; }
-			else if (f_now > prev_f) lm_delta /= sm.lm_delta_update;
-		}
-		if (lane == 0) {
-			ST(lmp + 1, lm_delta);
-			if (undo) ST(lmp + 2, 1.0);
-			else { ST(lmp + 2, 0.0); if (!state_reset) ST(lmp + 0, f_now); }
-		}
+		undo = fin_lm_decide(f_now, prev_f, lm_delta, state_reset, lm_iter_id, sm.lm_delta_update);
+		if (lane == 0) fin_lm_store<COH>(lmp, f_now, lm_delta, state_reset, undo);
 	}
-	const bool use_h0 = (sm.hess_type == 0) || (sm.sm == MTFHIP_SM_ICLK);
-	const bool sum_h0 = (sm.sm == MTFHIP_SM_ESM) && (sm.hess_type == 2 || sm.hess_type == 4);
-	const double gscale = (sm.sm == MTFHIP_SM_ESM) ? 0.5 : 1.0;
+	/* (the SSD family's selection, mtfhip_sm_system.h: this body never serves SPSS rows, nor MI's -- h_from_acc is false by construction) */
 	/* ---- the system, lower triangle, in the registers of every lane ---- */
 	/* (every LDS operand is requested unconditionally and up front -- one wait; guarded reads were 36 round trips) */
 	double aH[36], aG[8], hI[36];
@@ -609,13 +526,10 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 	for (int r = 0; r < 8; ++r) {
 #pragma unroll
 		for (int c = 0; c <= r; ++c) {
-			const int kk = c * 8 - (c * (c - 1)) / 2 + (r - c);
-			const double h0v = hI[r * (r + 1) / 2 + c];
-			double v = use_h0 ? h0v : -aH[kk];
-			if (sum_h0) v = (v + h0v) * 0.5;
+			const double v = ssd_h_of(sm_use_h0(sm, false, false), sm_sum_h0(sm, false, false), false, aH[tri8(c, r)], hI[r * (r + 1) / 2 + c]);
 			M[r][c] = r < S ? v : (r == c ? -1.0 : 0.0);   /* (c <= r) */
 		}
-		y[r] = r < S ? gscale * aG[r] : 0.0;
+		y[r] = r < S ? ssd_g_of(sm, false, aG[r], 0.0) : 0.0;
 	}
 	FIN_STAMP(3);
 	double *trec = (ts.trace && n_it_prev < ts.trace_cap) ? ts.trace + ((size_t)t * ts.trace_cap + n_it_prev) * kTraceStride : nullptr;   /* debug trace */
@@ -731,15 +645,8 @@ __device__ __forceinline__ void finish_track_fast_body(const BatchView &bv, cons
 	if (trec) {
 #pragma unroll
 		for (int q = 0; q < 8; ++q) { trec[72 + q] = dp[q]; trec[80 + q] = Cr[q]; }
-		trec[89] = (double)n_it_prev;
 	}
-	const int n_it = n_it_prev + 1;
-	STI(ts.n_iters + t, n_it);
-	if (lmp) {
-		const int id = lm_iter_id + ((undo && sm.sm == MTFHIP_SM_FCLK) ? 0 : 1);
-		ST(lmp + 3, (double)id);
-		if ((!undo && change < sm.epsilon) || id >= sm.max_iters) stop_target(f_w, f_so);
-	} else if (change < sm.epsilon || n_it >= sm.max_iters) stop_target(f_w, f_so);
+	fin_count_and_stop<COH, false, false>(sm, ts, t, stop_flag, lmp, trec, n_it_prev, lm_iter_id, undo, change, f_w, f_so);
 	FIN_STAMP(6);
 }
 

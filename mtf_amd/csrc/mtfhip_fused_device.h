@@ -40,8 +40,6 @@ __device__ __forceinline__ bool in_cell(double x, double y, int lx, int ly) {
 	return (x >= 0) & (y >= 0) & ((int)x == lx) & ((int)y == ly) & ((x - lx) != 0) & ((y - ly) != 0);
 }
 
-/* index of (a, b), a <= b, in the upper-triangle order of the accumulator row (stride 8) */
-__host__ __device__ constexpr int tri8(int a, int b) { return a * 8 - (a * (a - 1)) / 2 + (b - a); }
 template <int S, int MODE>
 struct PixIn {
 	double2 p;
@@ -71,8 +69,8 @@ struct Tex {
  */
 
 /* AM = MTFHIP_AM_SSD: the residual-weighted sums above.  AM = MTFHIP_AM_NCC: the same pass accumulates the raw moments
- * NCC's similarity, Jacobians and first-order Hessians are functions of (NCC.cc:124-389 restated in ncc_from_moments,
- * api_ncc_moments.hip) -- Gram(row) | sum Jt | sum It Jt | sum I0 Jt | sum It J0 | sum It, It^2, I0 It -- so an NCC iteration
+ * NCC's similarity, Jacobians and first-order Hessians are functions of (NCC.cc:124-389 restated in raw moments,
+ * mtfhip_sm_system.h) -- Gram(row) | sum Jt | sum It Jt | sum I0 Jt | sum It J0 | sum It, It^2, I0 It -- so an NCC iteration
  * needs no second pass over the pixels for the means; the partial rows are NCC_ACC_COUNT wide. */
 /* FAST (lean launches only, MAT = false): tolerance-mode arithmetic -- one reciprocal per point, FMA-contracted warp / interpolant /
  * rows, and on the wave-uniform interior path the closed-form slope of the bilinear cell times the ROUNDED step the reference's 1e-8

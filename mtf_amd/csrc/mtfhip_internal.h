@@ -10,6 +10,7 @@
 #include "../../include/mtfhip.h"
 #include "mtfhip_fused_dispatch.h"
 #include "mtfhip_owned.h"
+#include "mtfhip_sm_system.h"
 
 namespace mtfhip {
 
@@ -65,25 +66,7 @@ struct BatchView {
 	double *states;       /* [B][8] curr_state */
 };
 
-/* accumulator slots produced by the reducing kernels, per target */
-enum {
-	ACC_H = 0,            /* 36: upper triangle of sum J_a J_b, row-major over (a<=b) with S=8 stride */
-	ACC_G = 36,           /* 8 : sum v_i * Jrow_i  (v = residual-type vector of the mode) */
-	ACC_RR = 44,          /* 1 : sum r^2 */
-	ACC_G2 = 45,          /* 8 : second gemv (ESM generic: df_dI0 * J0) */
-	ACC_COUNT = 56        /* padded so the halving butterfly divides evenly 3 times */
-};
-/* partial / reduced row of the fused NCC iteration: raw moments over the pixels of a target (J = the row the Hessian is
- * built from -- Jt, or the mean of J0 and Jt for ESM's Original Hessian; the g-type sums always use Jt and J0 themselves) */
-enum {
-	NCC_GRAM = 0,         /* 36: sum J_a J_b, upper triangle as ACC_H */
-	NCC_SJ = 36,          /* 8 : sum Jt */
-	NCC_ITJ = 44,         /* 8 : sum It Jt */
-	NCC_I0J = 52,         /* 8 : sum I0 Jt */
-	NCC_ITJ0 = 60,        /* 8 : sum It J0 */
-	NCC_IT = 68, NCC_IT2 = 69, NCC_I0IT = 70,
-	NCC_ACC_COUNT = 72    /* 72 -> 36 -> 18 -> 9 under the halving butterfly */
-};
+/* (the accumulator slots ACC_* / NCC_* of the reducing kernels and tri8: mtfhip_sm_system.h) */
 
 /* Every kernel launch of the library goes through this macro: the launch status (invalid configuration, missing code object,
  * out-of-resources ...) is read back at once and kept as a sticky error that the next C-ABI call which synchronises reports,

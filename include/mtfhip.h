@@ -66,7 +66,19 @@ typedef enum mtfhip_status {
  * sec_ord_hess and every second-order entry point, MTFHIP_SM_FALK / _IALK, ESM hess_type 4 (SumOfStd) and ICLK hess_type 1 (CurrentSelf)
  * on the fused entry points (the per-function ones serve them), update_model, the grid entry points, score_candidates /
  * sample_candidates, the particle filter and the NN / GNN entry points. */
-enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6, MTFHIP_AM_SPSS = 7 };
+/* MTFHIP_AM_SSIM: Structural Similarity (AM/src/SSIM.cc), f = (2 mt m0 + c1)(2 cov + c2) / ((mt^2 + m0^2 + c1)(vt + v0 + c2)) over the means,
+ * variances and covariance of the raw pixel values of the two patches, c1 = (255 k1)^2, c2 = (255 k2)^2 (mtfhip_batch_set_ssim below; no
+ * pix_mapper).  Everything SSIM.cc derives is a function of the raw moments an NCC pass reduces, so the fused entry points run NCC's kernels
+ * and a finish of their own.  The reference's expressions are kept: its integer quotient 2 / (patch_size - 1), its gradient
+ * vectors (not the derivatives of f), its cmptInitHessian / cmptCurrHessian, which are NOT symmetric.  What is state in the reference and
+ * not algebra is not kept: cmptSelfHessian does not overwrite c and d for later calls, and after initialize_similarity f = 1.  Served: single
+ * channel; homography, affine, Similitude, Isometry and Translation; every first-order per-function AppearanceModel entry point; and
+ * mtfhip_batch_init_template / _set_region / _iterate / _track / _track_region / _track_trace with ESM, FCLK and ICLK and every first-order
+ * hess_type they have for NCC, chained or not, materialize 0 / 1, with or without Levenberg-Marquardt, both arithmetic modes, on the
+ * two-launch loop.  Everything else returns MTFHIP_ERR_NOT_IMPLEMENTED with its reason in mtfhip_last_error(): n_channels 3 (at
+ * mtfhip_batch_create), sec_ord_hess and every second-order entry point, MTFHIP_SM_FALK / _IALK, update_model, the grid entry points,
+ * score_candidates / sample_candidates / nn_dataset, the particle filter and the NN / GNN entry points. */
+enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6, MTFHIP_AM_SPSS = 7, MTFHIP_AM_SSIM = 8 };
 /* MTFHIP_SSM_SIMILITUDE / _ISOMETRY / _TRANSLATION: the low-order rigid models (SSM/src/Similitude.cc, Isometry.cc, Translation.cc), states
  * [tx, ty, a, b] (warp [[1 + a, -b, tx], [b, 1 + a, ty]]), [tx, ty, theta] (warp [[cos, -sin, tx], [sin, cos, ty]]) and [tx, ty], S = 4 / 3 / 2.
  * Served: the StateSpaceModel entry points below (set_corners with normalized_init = 0, set_state, compositional_update, invert_state,
@@ -748,6 +760,12 @@ int mtfhip_batch_lrscv_intensity_maps(mtfhip_batch *b, double *dst);
 /* SPSSParams k (SPSS.cc:13-23; shipped spss_k 0.01): c = (k (PIX_MAX - PIX_MIN))^2 = (255 k)^2 (SPSS.cc:37-38).  k <= 0 selects the default
  * 0.01.  Call before init_template / initialize_similarity (MTFHIP_ERR_LOGIC afterwards: the constant self Hessian is a function of c). */
 int mtfhip_batch_set_spss(mtfhip_batch *b, double k);
+
+/* ---- SSIM (MTFHIP_AM_SSIM) ---- */
+/* SSIMParams k1, k2 (SSIM.cc:4-23; shipped ssim_k1 0.01, ssim_k2 0.03): c1 = (k1 (PIX_MAX - PIX_MIN))^2 = (255 k1)^2, c2 likewise
+ * (SSIM.cc:36-39).  A value <= 0 selects its default.  Call before init_template / initialize_similarity (MTFHIP_ERR_LOGIC afterwards: the
+ * constant self Hessian is a function of them). */
+int mtfhip_batch_set_ssim(mtfhip_batch *b, double k1, double k2);
 
 /* ---- ssm.estimateWarpFromPts: the robust fit of the grid SSM to point pairs ---- */
 /* SSMEstimatorParams (SSM/include/mtf/SSM/SSMEstimatorParams.h:11-25; defaults SSMEstimatorParams.cc:5-13; the shipped values

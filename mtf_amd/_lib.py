@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTFHIP_LIB", os.path.join(_HERE, "libmtfhip.so"))
 CSRC = os.path.join(_HERE, "csrc")
 
-AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV, AM_LRSCV, AM_SPSS = 0, 1, 2, 3, 4, 5, 6, 7
+AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV, AM_LRSCV, AM_SPSS, AM_SSIM = 0, 1, 2, 3, 4, 5, 6, 7, 8
 SCV_HIST_DIRAC, SCV_HIST_BILINEAR, SCV_HIST_BSPLINE = 0, 1, 2
 SSM_HOMOGRAPHY, SSM_AFFINE, SSM_SIMILITUDE, SSM_ISOMETRY, SSM_TRANSLATION = 0, 1, 2, 3, 4
 # state sizes (StateSpaceModel::getStateSize): Homography.cc:36, Affine.cc:47, Similitude.cc:63, Isometry.cc:52, Translation.cc:48
@@ -190,7 +190,7 @@ SYMBOLS = [
     "mtfhip_timing_enable", "mtfhip_timing_reset", "mtfhip_timing_get", "mtfhip_timing_get_busy", "mtfhip_ssm_estimate_state_sigma", "mtfhip_batch_track_queues", "mtfhip_batch_inline_warp",
     "mtfhip_batch_grid_regen", "mtfhip_batch_set_scv", "mtfhip_batch_scv_intensity_map", "mtfhip_batch_set_rscv",
     "mtfhip_batch_rscv_intensity_map", "mtfhip_batch_set_lscv", "mtfhip_batch_lscv_intensity_maps", "mtfhip_batch_set_first_iter",
-    "mtfhip_batch_first_iter", "mtfhip_batch_set_lrscv", "mtfhip_batch_lrscv_intensity_maps", "mtfhip_batch_set_spss",
+    "mtfhip_batch_first_iter", "mtfhip_batch_set_lrscv", "mtfhip_batch_lrscv_intensity_maps", "mtfhip_batch_set_spss", "mtfhip_batch_set_ssim",
     "mtfhip_ssm_estimate_from_pts", "mtfhip_ssm_estimate_from_pts_dev",
     "mtfhip_nn_create", "mtfhip_nn_destroy", "mtfhip_nn_build", "mtfhip_nn_set_dataset", "mtfhip_nn_set_dataset_dev", "mtfhip_nn_get_dataset",
     "mtfhip_nn_get_dataset_dev", "mtfhip_nn_search", "mtfhip_nn_search_dev", "mtfhip_nn_update",
@@ -288,6 +288,7 @@ def lib():
         L.mtfhip_batch_set_lrscv.argtypes = [C.c_void_p] + [C.c_int] * 7
         L.mtfhip_batch_lrscv_intensity_maps.argtypes = [C.c_void_p, C.c_void_p]
         L.mtfhip_batch_set_spss.argtypes = [C.c_void_p, C.c_double]
+        L.mtfhip_batch_set_ssim.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.mtfhip_ssm_estimate_state_sigma.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.mtfhip_pf_set_distributions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mtfhip_pf_set_distr_draws.argtypes = [C.c_void_p, C.c_void_p]

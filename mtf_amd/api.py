@@ -252,7 +252,7 @@ class Batch:
     """B independent targets (AM + SSM pairs) sharing the context's current image."""
 
     def __init__(self, ctx, am=AM_SSD, ssm=SSM_HOMOGRAPHY, resx=50, resy=50, n_targets=1, grad_eps=1e-8,
-                 likelihood_alpha=1.0, mi_n_bins=8, mi_pre_seed=10.0, mi_pou=0, hess_eps=1.0, n_channels=1, spss_k=None):
+                 likelihood_alpha=1.0, mi_n_bins=8, mi_pre_seed=10.0, mi_pou=0, hess_eps=1.0, n_channels=1, spss_k=None, ssim_k1=None, ssim_k2=None):
         self.ctx = ctx
         self.desc = PatchDesc(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, hess_eps,
                               n_channels)
@@ -266,6 +266,8 @@ class Batch:
         self.S = L.ssm_state_size(ssm)
         if spss_k is not None:           # SPSSParams k of an AM_SPSS batch (am_params of the trackers)
             self.set_spss(spss_k)
+        if ssim_k1 is not None or ssim_k2 is not None:   # SSIMParams k1, k2 of an AM_SSIM batch (am_params of the trackers)
+            self.set_ssim(0.0 if ssim_k1 is None else ssim_k1, 0.0 if ssim_k2 is None else ssim_k2)
 
     def close(self):
         if self._h:
@@ -577,6 +579,11 @@ class Batch:
     def set_spss(self, k=0.01):
         """SPSSParams k of an AM_SPSS batch, before init_template: c = (255 k)^2; k <= 0 selects the shipped 0.01 (mtfhip_batch_set_spss)"""
         L.check(L.lib().mtfhip_batch_set_spss(self._h, float(k)))
+
+    def set_ssim(self, k1=0.01, k2=0.03):
+        """SSIMParams k1, k2 of an AM_SSIM batch, before init_template: c1 = (255 k1)^2, c2 = (255 k2)^2; a value <= 0 selects its shipped default
+        0.01 / 0.03 (mtfhip_batch_set_ssim)"""
+        L.check(L.lib().mtfhip_batch_set_ssim(self._h, float(k1), float(k2)))
 
     def set_rscv(self, use_bspl=0, weighted_mapping=0, mapped_gradient=0):
         """RSCVParams use_bspl, weighted_mapping, mapped_gradient of an AM_RSCV batch, before init_template; the defaults are the

@@ -43,6 +43,7 @@ int mtfhip_am_update_model(mtfhip_batch *b, const double *pts, double learning_r
 	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LSCV is not available on this entry point (the template update would have to refresh I0_orig)");
 	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LRSCV is not available on this entry point (the template update would have to refresh its code plane)");
 	TRY(spss_refuse(b, "updateModel", " has no online template update on the device path"));
+	TRY(ssim_refuse(b, "updateModel", " has no online template update (SSIM.cc has none either)"));
 	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: appearance model %d", b->desc.am);
 	TRY(single_channel(b, "update_model"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "update_model before initializePixVals");
@@ -152,7 +153,7 @@ int push_ncc(mtfhip_batch *b) {
 	for (int t = 0; t < b->B; ++t) {
 		const TargetHost &h = b->th[t];
 		double *p = &s[8 * t];
-		p[0] = h.I0_mean; p[1] = h.c; p[2] = h.It_mean; p[3] = h.b; p[4] = h.f; p[5] = h.gmean;
+		p[0] = h.I0_mean; p[1] = h.c; p[2] = h.It_mean; p[3] = h.b; p[4] = h.f; p[5] = h.gmean; p[6] = h.i0_ss;
 	}
 	HIP_TRY(hipMemcpyAsync(b->d_ncc, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice, b->ctx->stream));
 	HIP_TRY(hipStreamSynchronize(b->ctx->stream));
@@ -182,8 +183,10 @@ static int ncc_initialize_similarity(mtfhip_batch *b) {
 	TRY(read_acc(b, nblk));
 	for (int t = 0; t < b->B; ++t) {
 		TargetHost &h = b->th[t];
-		h.c = std::sqrt(b->h_acc[(size_t)t * ACC_COUNT + ACC_G + 2]);
-		if (!b->init_sim) { h.f = 1; h.b = h.c; }
+		h.i0_ss = b->h_acc[(size_t)t * ACC_COUNT + ACC_G + 2];   /* (SSIM's init_pix_var is this over N - 1, SSIM.cc:58) */
+		h.c = std::sqrt(h.i0_ss);
+		/* (SSIM::initializeSimilarity SSIM.cc:66-72: curr_pix_var = cross_pix_var = init_pix_var, f = 1 -- the system at It = I0) */
+		if (!b->init_sim) { h.f = 1; h.b = h.c; if (ssim_am(b)) { h.it_ss = h.i0_ss; h.a = h.i0_ss; } }
 	}
 	b->init_sim = true;
 	return push_ncc(b);
@@ -338,7 +341,7 @@ static int mi_grad(mtfhip_batch *b, int curr) {
 
 /* ------------------------------------------------------------------ AppearanceModel */
 static int am_supported(mtfhip_batch *b, const char *fn) {
-	if (ssd_like(b) || b->desc.am == MTFHIP_AM_NCC || b->desc.am == MTFHIP_AM_MI || spss_am(b)) return MTFHIP_OK;
+	if (ssd_like(b) || b->desc.am == MTFHIP_AM_NCC || b->desc.am == MTFHIP_AM_MI || spss_am(b) || ssim_am(b)) return MTFHIP_OK;
 	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s :: appearance model %d is not available on the device path yet", fn, b->desc.am);
 }
 
@@ -346,7 +349,8 @@ int mtfhip_am_initialize_similarity(mtfhip_batch *b) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "initialize_similarity: NULL batch");
 	TRY(am_supported(b, "initializeSimilarity"));
-	if (b->desc.am == MTFHIP_AM_NCC) return ncc_initialize_similarity(b);
+	/* (SSIM::initializeSimilarity SSIM.cc:50-76 keeps the template's mean and centred sum of squares, as NCC's does, and f = 1) */
+	if (ncc_rows(b)) return ncc_initialize_similarity(b);
 	if (b->desc.am == MTFHIP_AM_MI) {
 		/* MI::initializeSimilarity MI.cc:207-287 */
 		const int first = b->init_sim ? 0 : 1;
@@ -382,8 +386,8 @@ int mtfhip_am_initialize_grad(mtfhip_batch *b) {
 		b->init_grad = true;
 		return MTFHIP_OK;
 	}
-	if (b->desc.am == MTFHIP_AM_NCC || spss_am(b)) {
-		/* NCC::initializeGrad NCC.cc:97-122, SPSS::initializeGrad SPSS.cc:104-114: gradient vectors start at zero */
+	if (b->desc.am == MTFHIP_AM_NCC || spss_am(b) || ssim_am(b)) {
+		/* NCC::initializeGrad NCC.cc:97-122, SPSS::initializeGrad SPSS.cc:104-114, SSIM::initializeGrad SSIM.cc:78-96: gradient vectors start at zero */
 		if (!b->init_grad) {
 			HIP_TRY(hipMemsetAsync(b->buf[MTFHIP_BUF_DF_DI0], 0, sizeof(double) * b->N * b->B, b->ctx->stream));
 			HIP_TRY(hipMemsetAsync(b->buf[MTFHIP_BUF_DF_DIT], 0, sizeof(double) * b->N * b->B, b->ctx->stream));
@@ -426,6 +430,7 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 		return MTFHIP_OK;
 	}
 	if (spss_am(b)) return spss_update_similarity(b, prereq_only);
+	if (ssim_am(b)) return ssim_update_similarity(b, prereq_only);
 	/* SCV::updateSimilarity (SCV.cc:194-230): the intensity map from It and I0_orig, I0 re-mapped, then SSDBase::updateSimilarity */
 	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 1, b->ctx->stream));
 	/* LSCV::updateSimilarity (LSCV.cc:263-304): unless once_per_frame and not the first iteration, the localized re-map of I0 */
@@ -446,6 +451,7 @@ static int do_update_curr_grad(mtfhip_batch *b) {
 	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 1); stale_clear(b, false, true); return rc; }
 	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 1);
 	if (spss_am(b)) return spss_update_grad(b, 1);
+	if (ssim_am(b)) return ssim_update_grad(b, 1);
 	if (b->lz.df0_stale) TRY(ensure_one(b, false));
 	TimedScope ts(b->ctx, "negate");
 	launch_negate(b->buf[MTFHIP_BUF_DF_DI0], b->buf[MTFHIP_BUF_DF_DIT], (size_t)b->N * b->B, b->ctx->stream);
@@ -476,6 +482,7 @@ int mtfhip_am_update_init_grad(mtfhip_batch *b) {
 	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 0); stale_clear(b, true, false); return rc; }
 	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 0);
 	if (spss_am(b)) return spss_update_grad(b, 0);
+	if (ssim_am(b)) return ssim_update_grad(b, 0);
 	return MTFHIP_OK;
 }
 int mtfhip_am_get_similarity(mtfhip_batch *b, double *f) {
@@ -493,6 +500,7 @@ int mtfhip_am_get_likelihood(mtfhip_batch *b, double *l) {
 		double f = b->th[t].f;
 		if (spss_am(b)) l[t] = std::exp(b->desc.likelihood_alpha * (f - (double)b->N));   /* SPSS::getLikelihood SPSS.cc:46-48 */
 		else if (ssd_like(b)) l[t] = std::exp(-b->desc.likelihood_alpha * std::sqrt(-f / (double)b->N));
+		else if (ssim_am(b)) l[t] = ssim_likelihood(f, b->desc.likelihood_alpha);   /* SSIM::getLikelihood SSIM.cc:45-48 */
 		else { double d = (1.0 / f) - 1; l[t] = std::exp(-b->desc.likelihood_alpha * d * d); }
 	}
 	return MTFHIP_OK;
@@ -885,6 +893,7 @@ int mtfhip_am_cmpt_init_hessian(mtfhip_batch *b, int j0_buf, double *H) {
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, j0_buf, 0, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, j0_buf, 0, H);
 	if (spss_am(b)) return spss_hessian(b, j0_buf, SPSS_W_INIT, H);
+	if (ssim_am(b)) return ssim_hessian(b, j0_buf, NCC_H_INIT, H);
 	return gram_to_host(b, j0_buf, H, -1.0, false);
 }
 int mtfhip_am_cmpt_curr_hessian(mtfhip_batch *b, int jt_buf, double *H) {
@@ -895,6 +904,7 @@ int mtfhip_am_cmpt_curr_hessian(mtfhip_batch *b, int jt_buf, double *H) {
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 1, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 1, H);
 	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_CURR, H);
+	if (ssim_am(b)) return ssim_hessian(b, jt_buf, NCC_H_CURR, H);
 	return gram_to_host(b, jt_buf, H, -1.0, false);
 }
 int mtfhip_am_cmpt_self_hessian(mtfhip_batch *b, int jt_buf, double *H) {
@@ -905,6 +915,7 @@ int mtfhip_am_cmpt_self_hessian(mtfhip_batch *b, int jt_buf, double *H) {
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 2, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 2, H);
 	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_SELF, H);
+	if (ssim_am(b)) return ssim_hessian(b, jt_buf, NCC_H_SELF, H);
 	return gram_to_host(b, jt_buf, H, -1.0, false);
 }
 int mtfhip_am_cmpt_sum_of_hessians(mtfhip_batch *b, int j0_buf, int jt_buf, double *H) {
@@ -918,6 +929,7 @@ int mtfhip_am_cmpt_sum_of_hessians(mtfhip_batch *b, int j0_buf, int jt_buf, doub
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
 		if (b->desc.am == MTFHIP_AM_NCC) { TRY(ncc_hessian(b, j0_buf, 0, H0.data())); TRY(ncc_hessian(b, jt_buf, 1, H)); }
 		else if (spss_am(b)) { TRY(spss_hessian(b, j0_buf, SPSS_W_INIT, H0.data())); TRY(spss_hessian(b, jt_buf, SPSS_W_CURR, H)); }
+		else if (ssim_am(b)) { TRY(ssim_hessian(b, j0_buf, NCC_H_INIT, H0.data())); TRY(ssim_hessian(b, jt_buf, NCC_H_CURR, H)); }
 		else { TRY(mi_hessian(b, j0_buf, 0, H0.data())); TRY(mi_hessian(b, jt_buf, 1, H)); }
 		for (size_t i = 0; i < H0.size(); ++i) H[i] += H0[i];
 		return MTFHIP_OK;
@@ -1067,6 +1079,7 @@ int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_init_hessian (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ssim_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_init_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_init_hessian(b, j0_buf, H));
@@ -1077,6 +1090,7 @@ int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_curr_hessian (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ssim_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_curr_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_curr_hessian(b, jt_buf, H));
@@ -1087,6 +1101,7 @@ int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_self_hessian (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ssim_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_self_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_self_hessian (second order): NULL argument");
@@ -1105,6 +1120,7 @@ int mtfhip_am_cmpt_sum_of_hessians2(mtfhip_batch *b, int j0_buf, int jt_buf, int
 	FLUSH_AM(b);
 	TRY(scv_refuse(b, "cmpt_sum_of_hessians (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ssim_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_sum_of_hessians (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_sum_of_hessians (second order): NULL argument");

@@ -317,7 +317,9 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	/* the fused kernel addresses a target's arrays with 32-bit byte offsets (ld_off / st_off): 8 columns of N doubles */
 	if ((double)d->resx * d->resy * 3.0 >= (double)(1u << 26)) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: %dx%d sample points per target exceed the 2^26-row limit", d->resx, d->resy);
 	if (d->grad_eps <= 0 || d->hess_eps < 0) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: grad_eps must be positive (got %g)", d->grad_eps);
-	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_SPSS) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_SSIM) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am == MTFHIP_AM_SSIM && d->n_channels == 3)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "SSIM with n_channels 3 (MCSSIM) is not available on the device path (single channel only)");
 	if (d->am == MTFHIP_AM_SPSS && d->n_channels == 3)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "SPSS with n_channels 3 (MCSPSS) is not available on the device path (single channel only)");
 	if (d->am == MTFHIP_AM_LRSCV && (d->mi_n_bins > kLscvMaxBins || d->mi_n_bins == 1))
@@ -341,10 +343,10 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		return fail(MTFHIP_ERR_INVALID_ARG, "MI::Too few bins %d specified to enforce partition of unity constraint", d->mi_n_bins);
 	if (!ssm_known(d->ssm)) return fail(MTFHIP_ERR_INVALID_ARG, "unknown state space model %d", d->ssm);
 	if (d->n_channels != 0 && d->n_channels != 1 && d->n_channels != 3) return fail(MTFHIP_ERR_INVALID_ARG, "n_channels %d (1 or 3 expected)", d->n_channels);
-	/* Similitude / Isometry / Translation: SSD and NCC, single channel (mtfhip.h) -- refused here, before any kernel could read a six- or
-	 * eight-wide state of theirs */
-	if (ssm_lowdof(d->ssm) && d->am != MTFHIP_AM_SSD && d->am != MTFHIP_AM_NCC)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model is served with SSD and NCC only (MI, the SCV family and SPSS are not available with it)", ssm_name(d->ssm));
+	/* Similitude / Isometry / Translation: SSD, NCC and SSIM (on NCC's affine pass), single channel (mtfhip.h) -- refused here, before any kernel
+	 * could read a six- or eight-wide state of theirs */
+	if (ssm_lowdof(d->ssm) && d->am != MTFHIP_AM_SSD && d->am != MTFHIP_AM_NCC && d->am != MTFHIP_AM_SSIM)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model is served with SSD, NCC and SSIM only (MI, the SCV family and SPSS are not available with it)", ssm_name(d->ssm));
 	if (ssm_lowdof(d->ssm) && d->n_channels == 3)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "batch_create: the %s state space model with n_channels 3 is not available (single channel only)", ssm_name(d->ssm));
 	HIP_TRY(hipSetDevice(c->device));
@@ -636,7 +638,7 @@ int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, boo
 		for (int t = 0; t < b->B; ++t) {
 			const TargetHost &h = b->th[t];
 			double *q8 = s_nc + 8 * t;
-			q8[0] = h.I0_mean; q8[1] = h.c; q8[2] = h.It_mean; q8[3] = h.b; q8[4] = h.f; q8[5] = h.gmean; q8[6] = q8[7] = 0;
+			q8[0] = h.I0_mean; q8[1] = h.c; q8[2] = h.It_mean; q8[3] = h.b; q8[4] = h.f; q8[5] = h.gmean; q8[6] = h.i0_ss; q8[7] = 0;
 		}
 		b->deferred_corners = layout_later ? nullptr : corners; b->deferred_for_track = for_track;
 		b->deferred_layout = layout_later;
@@ -671,7 +673,7 @@ int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, boo
 		std::memcpy(s_cr + 8 * t, corners + 8 * t, sizeof(double) * 8);
 		std::memcpy(s_ic + 12 * t, h.init_corners_hm, sizeof(double) * 12);
 		double *q8 = s_nc + 8 * t;
-		q8[0] = h.I0_mean; q8[1] = h.c; q8[2] = h.It_mean; q8[3] = h.b; q8[4] = h.f; q8[5] = h.gmean; q8[6] = q8[7] = 0;
+		q8[0] = h.I0_mean; q8[1] = h.c; q8[2] = h.It_mean; q8[3] = h.b; q8[4] = h.f; q8[5] = h.gmean; q8[6] = h.i0_ss; q8[7] = 0;
 		std::memcpy(s_w0 + 9 * t, W0.m, sizeof(double) * 9);
 		s_act[t] = for_track ? 1 : 0;
 		if (for_track) s_it[t] = 0;

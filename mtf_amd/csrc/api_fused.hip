@@ -46,6 +46,12 @@ int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn) {
 				"(cmpt_sum_of_hessians serves it)");
 		return MTFHIP_OK;
 	}
+	if (ssim_am(b)) {
+		/* SSIM: every first-order type NCC has, from the same rows (ssim_h, mtfhip_sm_system.h); its second-order Hessians weight the pixel
+		 * Hessian by df_dI (SSIM.cc:187-198, 256-268), which no pass accumulates for it */
+		if (sm->sec_ord_hess) return ssim_refuse(b, fn, " with second-order Hessians is not available on the device path (first-order only)");
+		return MTFHIP_OK;
+	}
 	TRY(scv_refuse(b, fn, sm->sec_ord_hess));   /* (SCV: SSD on the re-mapped template, first order) */
 	if (!ssd_like(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: unknown appearance model", fn);
 	return MTFHIP_OK;
@@ -111,6 +117,9 @@ static int init_self_hessian(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *
 	 * a setRegion that refreshes H0 comes behind a loop whose last pass may or may not have materialised It, so the weight is taken from I0
 	 * itself: the same H0 whatever the loop wrote */
 	if (spss_am(b)) { FLUSH_AM(b); return spss_hessian(b, MTFHIP_BUF_J0, SPSS_W_SELF0, H0); }
+	/* SSIM: cmptSelfHessian(J0) at It = I0 (SSIM.cc:270-287) is a function of the template's moments (every caller takes them in front: th[].ncc_tm
+	 * is current); no pixel pass of its own, and the same H0 whatever a loop left in the It buffer */
+	if (ssim_am(b)) return ssim_h0(b, H0);
 	return mtfhip_am_cmpt_self_hessian(b, MTFHIP_BUF_J0, H0);
 }
 /* A low-order SSM's template in affine coordinates (mtfhip_batch::lo_ssm), behind the interface's own N x S Jacobian: the affine rows of dI0_dx
@@ -119,13 +128,13 @@ static int init_self_hessian(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *
 static int lowdof_template(mtfhip_batch *b, const mtfhip_sm_desc *sm, int variant, bool with_h0) {
 	PassMode pm(b);
 	TRY(do_cmpt_pix_jacobian(b, variant, MTFHIP_BUF_DI0_DX, MTFHIP_BUF_J0));
+	if (ncc_rows(b)) TRY(ncc_template_moments(b));   /* (in front of H0: SSIM's is a function of them) */
 	if (with_h0) {
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
 		TRY(init_self_hessian(b, sm, H0.data()));
 		TRY(store_h0(b, H0.data(), true));
 		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
 	}
-	if (b->desc.am == MTFHIP_AM_NCC) TRY(ncc_template_moments(b));
 	return MTFHIP_OK;
 }
 /* nt::ICLK::initialize of small single-channel SSD / NCC patches in ONE launch (kernels_init.hip): the grid tracker re-initialises its
@@ -138,7 +147,7 @@ bool template_init_fused_ok(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	if (e && e[0] == '0') return false;
 	if (b->lo_ssm) return false;   /* (k_template_init writes the SSM's own rows and Hessian: the low-order models keep theirs in affine coordinates) */
 	const int am = b->desc.am;
-	if (am != MTFHIP_AM_SSD && am != MTFHIP_AM_NCC) return false;
+	if (am != MTFHIP_AM_SSD && am != MTFHIP_AM_NCC) return false;   /* (SSIM: k_template_init writes NCC's H0, not cmptSelfHessian of SSIM.cc) */
 	const bool const_h = sm->hess_type == 0 || (sm->hess_type == 2 && am == MTFHIP_AM_SSD);
 	return sm->sm == MTFHIP_SM_ICLK && const_h && sm->chained_warp && !sm->sec_ord_hess && b->C == 1 && b->N <= kTemplateInitMaxPix &&
 		b->h_flag_dev != nullptr && b->ctx->img.data != nullptr && b->ctx->img.channels == 1;
@@ -220,11 +229,11 @@ int mtfhip_batch_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	TRY(mtfhip_am_initialize_hess(b));
 	if (b->lo_ssm) TRY(lowdof_template(b, sm, sm->chained_warp ? MTFHIP_JAC_WARPED : MTFHIP_JAC_INIT, true));
 	else {
+		if (ncc_rows(b)) TRY(ncc_template_moments(b));   /* (in front of H0: SSIM's is a function of them) */
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
 		TRY(init_self_hessian(b, sm, H0.data()));
 		TRY(store_h0(b, H0.data(), true));
 		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-		if (b->desc.am == MTFHIP_AM_NCC) TRY(ncc_template_moments(b));
 	}
 	b->j0_is_template = true;
 	b->j0_template_corners_epoch = b->corners_epoch;
@@ -261,6 +270,8 @@ int set_region_core(mtfhip_batch *b, const double *corners, const mtfhip_sm_desc
 	}
 	TRY(mtfhip_ssm_cmpt_pix_jacobian(b, MTFHIP_JAC_INIT, MTFHIP_BUF_DI0_DX, MTFHIP_BUF_J0));
 	const bool need_h0 = sm->hess_type == 0 || (sm->sm == MTFHIP_SM_ESM && sm->hess_type == 2);
+	/* (the template moments in front of H0: SSIM's is a function of them; a low-order SSM's are taken over its affine rows, lowdof_template) */
+	if (ncc_rows(b) && !b->lo_ssm) TRY(ncc_template_moments(b));
 	if (b->lo_ssm) TRY(lowdof_template(b, sm, MTFHIP_JAC_INIT, need_h0));
 	else if (need_h0) {
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
@@ -269,7 +280,6 @@ int set_region_core(mtfhip_batch *b, const double *corners, const mtfhip_sm_desc
 		TRY(store_h0(b, H0.data(), true));
 		HIP_TRY(hipStreamSynchronize(b->ctx->stream));
 	}
-	if (b->desc.am == MTFHIP_AM_NCC && !b->lo_ssm) TRY(ncc_template_moments(b));   /* (a low-order SSM's: over its affine rows, lowdof_template) */
 	b->j0_is_template = true;
 	b->j0_template_corners_epoch = b->corners_epoch;
 	b->j0_variant = MTFHIP_JAC_INIT;
@@ -340,7 +350,7 @@ int second_order_term(const mtfhip_sm_desc *sm, int am) {
  * the statement the device-side finish reads as well (NT/FCLK.cc:260-288 ; NT/ESM.cc:298-377 with SSDBase.cc:169-191,287-311 ; NT/ICLK.cc:206-251).
  * so: [B][S x S] second-order sums (x so_scale) or NULL */
 int assemble_rows(mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, int nblk, const double *so, double so_scale, double *f, double *g, double *H) {
-	const bool ncc = b->desc.am == MTFHIP_AM_NCC, spss = spss_am(b);
+	const bool ncc = ncc_rows(b), spss = spss_am(b), ssim = ssim_am(b);   /* (ncc: the rows are NCC's moments -- NCC itself and SSIM) */
 	const int S = b->S, S2 = S * S, RL = ncc ? NCC_ACC_COUNT : ACC_COUNT;
 	TRY(read_rows(b, nblk, RL));
 	if (ncc && !ncc_has_gram(ncc_h_which(*sm), hess_mean)) return fail(MTFHIP_ERR_LOGIC, "fused NCC: the Gram matrix this Hessian needs was not accumulated");
@@ -348,6 +358,16 @@ int assemble_rows(mtfhip_batch *b, const mtfhip_sm_desc *sm, bool hess_mean, int
 		TargetHost &h = b->th[t];
 		const double *row = b->h_acc + (size_t)t * RL, *sot = so ? so + (size_t)t * S2 : nullptr;
 		double *gt = g + (size_t)t * S, *Ht = H + (size_t)t * S2;
+		if (ssim) {
+			/* SSIM over NCC's row: entry (r, c) of the constant Hessian and of the row's own, never a triangle (ssim_hess is not symmetric) */
+			const SsimSys sq = ssim_host_sys(b, h, row);
+			ssim_refresh_mirrors(h, sq, row);
+			if (f) f[t] = h.f;
+			for (int s = 0; s < S; ++s) gt[s] = ssim_g(*sm, sq, s);
+			for (int c = 0; c < S; ++c)
+				for (int r = 0; r < S; ++r) Ht[c * S + r] = ssim_h(*sm, sq, h.h0[c * S + r], r, c);
+			continue;
+		}
 		if (ncc) ncc_refresh_mirrors(b, h, row); else h.f = ssd_f(spss, row);
 		NccSys q = NccSys();
 		if (ncc) q = ncc_host_sys(b, h, row);
@@ -431,7 +451,7 @@ static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, do
 	b->it_valid = fa.materialize;
 	b->dit_valid = fa.materialize && fa.mode != 2;
 	b->jt_valid = fa.materialize && fa.mode != 2;
-	const bool ncc = b->desc.am == MTFHIP_AM_NCC;
+	const bool ncc = b->desc.am == MTFHIP_AM_NCC;   /* (the second-order pass's NCC form: SSIM's second-order types are refused, check_sm) */
 	const int term = second_order_term(sm);
 	const int S2 = b->S * b->S;
 	std::vector<double> so;

@@ -91,8 +91,8 @@ static int iclk_one_launch_max_pix() {
 bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	/* (SCV re-maps its template, RSCV rebuilds its map between the passes: they take the fused launch + finish per pass) */
 	/* (a low-order SSM takes the two-launch loop, whose finish projects the affine system: the one-launch kernels solve what they accumulate) */
-	/* (SPSS: the one-launch kernels accumulate SSD's or NCC's sums) */
-	return b->C == 1 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
+	/* (SPSS: the one-launch kernels accumulate SSD's or NCC's sums; SSIM: NCC's sums, but they solve NCC's system) */
+	return b->C == 1 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && !ssim_am(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
 		b->N <= iclk_one_launch_max_pix();
 }
 
@@ -216,6 +216,7 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 	if (b->lo_ssm) return false;   /* (the low-order SSMs are served by the two-launch loop only) */
 	if (intensity_mapped(b)) return false;   /* (the template re-map / the current map runs between the passes) */
 	if (spss_am(b)) return false;   /* (SPSS is served by the two-launch loop only: fused_select) */
+	if (ssim_am(b)) return false;   /* (SSIM: NCC's pass, but its own finish -- the two-launch loop only) */
 	if (b->B > 8) return false;   /* a batch is better served by its own decomposition (eight workgroups per target) */
 	if (sm->max_iters < 2) return false;
 	int nblk, rows;
@@ -374,7 +375,7 @@ static int track_loop_persist(mtfhip_batch *b, const mtfhip_sm_desc *sm, const F
 struct ChunkRun { BatchView bc; FusedArgs fc, fl; TrackState tc, tl; int nblk_c, t0, nt; double *part; hipStream_t s; bool done; };
 static void track_chunk_runs(mtfhip_batch *b, const FusedArgs &fa, const TrackState &ts, int chunk, int n_streams, bool defer, std::vector<ChunkRun> &runs) {
 	const BatchView bv = b->view();
-	const bool ncc = b->desc.am == MTFHIP_AM_NCC;
+	const bool ncc = ncc_rows(b);
 	const size_t RL = ncc ? NCC_ACC_COUNT : ACC_COUNT;   /* partial / reduced row length */
 	for (int t0 = 0; t0 < b->B; t0 += chunk) {
 		const int nt = std::min(chunk, b->B - t0);
@@ -458,7 +459,7 @@ static bool track_takes_step(const mtfhip_batch *b, const FusedArgs &fa, int so_
 	const char *e_st = std::getenv("MTFHIP_STEP");   /* (read per call: the tests flip it) */
 	const char *e_mx = std::getenv("MTFHIP_STEP_MAX_TARGETS");
 	const int max_t = e_mx ? std::atoi(e_mx) : 8;
-	return (e_st && e_st[0] == '1') && so_term < 0 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
+	return (e_st && e_st[0] == '1') && so_term < 0 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && !ssim_am(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
 }
 /* one pass of one chunk on its queue: the intensity re-maps, the pixel pass (lean: the non-materialising one), the second-order pass, the finish */
 struct FinishCtl { PhaseCtl pc; HostPublish pub; int prio; };
@@ -493,7 +494,9 @@ static int track_chunk_pass(mtfhip_batch *b, const mtfhip_sm_desc *sm, const Fus
 	TrackState tf = lean ? r.tl : r.tc;
 	tf.last_pass = it + 1 == cx.max_passes ? 1 : 0;
 	tf.finish_prio = fc.prio;
-	launch_finish_track(r.bc, *sm, tf, r.part, r.nblk_c, r.s, fc.pc, fc.pub, r.t0);
+	/* (SSIM: the finish that reads NCC's rows as SSIM does, with the model's constants -- kernels_ssim.hip) */
+	if (ssim_am(b)) launch_finish_track_ssim(r.bc, *sm, tf, r.part, r.nblk_c, r.s, fc.pc, fc.pub, r.t0, b->ssim_c1, b->ssim_c2);
+	else launch_finish_track(r.bc, *sm, tf, r.part, r.nblk_c, r.s, fc.pc, fc.pub, r.t0);
 	return MTFHIP_OK;
 }
 /* Targets are independent, so the loops commute: all passes of a chunk of targets (track_chunk) run before the next chunk starts, two
@@ -632,7 +635,7 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 	 * and two rejections never follow each other (the pass after an undo skips the test) */
 	TrackCtx cx{second_order_term(sm, b->desc.am), (sm->leven_marq && sm->sm == MTFHIP_SM_FCLK) ? 2 * sm->max_iters : sm->max_iters, 0, resume, region_mode};
 	hipStream_t st = b->ctx->stream;
-	const bool mi = b->desc.am == MTFHIP_AM_MI, ncc = b->desc.am == MTFHIP_AM_NCC;
+	const bool mi = b->desc.am == MTFHIP_AM_MI, ncc = ncc_rows(b);   /* (ncc: the pass reduces NCC's rows -- NCC itself and SSIM) */
 	/* (the one-launch grid kernel has no Levenberg-Marquardt: with it ICLK takes the fused launch + finish per pass) */
 	const bool one_launch = !mi && !sm->leven_marq && iclk_one_launch(b, sm) && cx.so_term < 0;
 	FusedArgs fa;
@@ -694,7 +697,7 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 		/* tolerance mode + a definite first-order system: the register-resident finish (finish_track_fast_body) */
 		const char *e = std::getenv("MTFHIP_FAST_FINISH");   /* (read per call: the tests compare the two bodies in one process) */
 		const bool enabled = !(e && e[0] == '0');
-		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && !ncc && !mi && !spss_am(b) && cx.so_term < 0) ? 1 : 0;   /* (SPSS: k_finish_track_spss) */
+		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && !ncc && !mi && !spss_am(b) && !ssim_am(b) && cx.so_term < 0) ? 1 : 0;   /* (SPSS: k_finish_track_spss; SSIM: k_finish_track_ssim) */
 		/* a low-order SSM: the projection lives in finish_track_body alone (the register-resident body would index its rows at run time);
 		 * its materialising loop keeps every target's last warp for the Jacobian written behind the loop (track_core) */
 		if (b->lo_ssm) { ts.fast_finish = 0; ts.keep_last = (fa.materialize && fa.mode != 2) ? 1 : 0; ts.lo_ssm = b->lo_ssm; ts.SS = ssm_state_size(b->lo_ssm); }

@@ -226,6 +226,8 @@ struct TargetHost {
 	double f;
 	/* NCC scalars (AM/src/NCC.cc members) */
 	double I0_mean, It_mean, a, b, c, gmean;
+	double i0_ss;   /* sum (I0 - I0_mean)^2 itself (c is its root): slot 6 of the device scalars, read by the SSIM finish */
+	double it_ss;   /* SSIM: sum (It - It_mean)^2 of the last similarity update (a holds sum (I0 - I0_mean)(It - It_mean), as for NCC) */
 	double h0[64]; /* constant self Hessian of the template (column-major), set by init_template */
 	/* NCC, fused path: moments of the template's pixel Jacobian (constant while J0 is): sum J0, sum I0 J0, Gram(J0) */
 	double ncc_tm[NCC_TM_COUNT];
@@ -297,6 +299,8 @@ struct mtfhip_batch {
 	Dev<unsigned short> d_scv_code;
 	/* SPSS (am = MTFHIP_AM_SPSS): SPSSParams k and c = (k (PIX_MAX - PIX_MIN))^2 (SPSS.cc:37-38) */
 	double spss_k = 0.01, spss_c = (0.01 * 255.0) * (0.01 * 255.0);
+	/* SSIM (am = MTFHIP_AM_SSIM): SSIMParams k1, k2 and c1 = (k1 (PIX_MAX - PIX_MIN))^2, c2 likewise (SSIM.cc:36-39) */
+	double ssim_k1 = 0.01, ssim_k2 = 0.03, ssim_c1 = (0.01 * 255.0) * (0.01 * 255.0), ssim_c2 = (0.03 * 255.0) * (0.03 * 255.0);
 	/* RSCV (am = MTFHIP_AM_RSCV): RSCVParams weighted_mapping, n_bins; the template's code plane ((int)I0), pass-1 rows and arrival
 	 * counters, the intensity maps, and It_orig of the per-function route (kernels_rscv.hip) */
 	int rscv_linear = 0, rscv_nb = 0;
@@ -520,7 +524,7 @@ static void fill_stage(const mtfhip_batch *b, char *stage, const double *w0 /* [
 		std::memcpy(cr + 8 * t, h.corners, sizeof(double) * 8);
 		std::memcpy(ic + 12 * t, h.init_corners_hm, sizeof(double) * 12);
 		double *q = nc + 8 * t;
-		q[0] = h.I0_mean; q[1] = h.c; q[2] = h.It_mean; q[3] = h.b; q[4] = h.f; q[5] = h.gmean; q[6] = q[7] = 0;
+		q[0] = h.I0_mean; q[1] = h.c; q[2] = h.It_mean; q[3] = h.b; q[4] = h.f; q[5] = h.gmean; q[6] = h.i0_ss; q[7] = 0;
 		if (w0) std::memcpy(pw0 + 9 * t, w0 + 9 * t, sizeof(double) * 9);
 		act[t] = active;
 		if (zero_iters) it[t] = 0;
@@ -565,6 +569,27 @@ mtfhip::SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int spss_update_similarity(mtfhip_batch *b, int prereq_only);
 int spss_update_grad(mtfhip_batch *b, int curr);
 int spss_hessian(mtfhip_batch *b, int j_buf, int weight, double *H);
+/* SSIM: every quantity of SSIM.cc is a function of the raw moments an NCC pass reduces (mtfhip_sm_system.h), so an SSIM batch launches NCC's
+ * pass kernels (fused_select) on the two-launch loop, and its own finish (kernels_ssim.hip) */
+static inline bool ssim_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SSIM; }
+/* THE predicate of "this batch's fused passes reduce NCC's rows": the 72-wide partial / reduced row, the template moments th[].ncc_tm and their
+ * upload d_ncc_tm, the per-target scalars d_ncc and their refresh.  (What solves NCC's own system -- the one-launch, step and persistent
+ * kernels, the fused template initialisation, the second-order pass, the deferred-fusion layer -- asks for MTFHIP_AM_NCC by name.) */
+static inline bool ncc_rows(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_NCC || ssim_am(b); }
+/* api_ssim.hip.  ssim_refuse: "<fn>: SSIM<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for an SSIM batch, MTFHIP_OK otherwise; ssim_h0: the constant self
+ * Hessian from the template's moments (th[].ncc_tm must be current); the per-function updateSimilarity, update*Grad and Hessians (kind: NCC_H_*) */
+int ssim_refuse(const mtfhip_batch *b, const char *fn, const char *what);
+int ssim_h0(const mtfhip_batch *b, double *H0);
+int ssim_update_similarity(mtfhip_batch *b, int prereq_only);
+int ssim_update_grad(mtfhip_batch *b, int curr);
+int ssim_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
+/* one target's reduced NCC row and template mirrors as the SSIM system of mtfhip_sm_system.h; and the host mirrors of SSIM.cc's members it leaves */
+static inline mtfhip::SsimSys ssim_host_sys(const mtfhip_batch *b, const TargetHost &h, const double *M) {
+	return mtfhip::ssim_sys(M, h.ncc_tm, h.I0_mean, h.i0_ss, (double)b->N, b->ssim_c1, b->ssim_c2);
+}
+static inline void ssim_refresh_mirrors(TargetHost &h, const mtfhip::SsimSys &q, const double *M) {
+	h.It_mean = q.mt; h.it_ss = M[mtfhip::NCC_IT2] - q.N * q.mt * q.mt; h.a = M[mtfhip::NCC_I0IT] - q.N * q.m0 * q.mt; h.f = q.f;
+}
 /* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
 int scv_capture(mtfhip_batch *b);
 int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);

@@ -146,9 +146,14 @@ __device__ __forceinline__ void fin_count_and_stop(const mtfhip_sm_desc &sm, con
  * row), cmptInitJacobian (ICLK) or half the difference (ESM DiffOfJacs, AppearanceModel.h:161-164, NT/ESM.cc:309).  ICLK's Std Hessian
  * is not constant (cmptInitHessian weights J0 J0^T by a function of It, SPSS.cc:160-165) and comes from the row; the curr / init weights
  * change sign, so every non-self system is solved with pivoting. */
-template <bool COH = false, bool ADDITIVE = false, bool LO = false, bool SPSS = false>
+/* SSIM (k_finish_track_ssim / _ssim_lo, kernels_ssim.hip): the reduced row is an NCC pass's -- the same 72 raw moments, the same template
+ * moments -- read as SSIM reads them (ssim_sys / ssim_g / ssim_h, mtfhip_sm_system.h): beside mean(I0), slot 6 of the target's NCC scalars
+ * holds sum (I0 - mean)^2 itself, and c1, c2 arrive as arguments of the kernel (no field of TrackState: the other kernels' argument
+ * segments keep their layout).  cmptInitHessian / cmptCurrHessian are not symmetric: every entry is taken as (r, c), and the elimination
+ * pivots as for NCC. */
+template <bool COH = false, bool ADDITIVE = false, bool LO = false, bool SPSS = false, bool SSIM = false>
 __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
-	const double *partials, int nblk, int t, int *stop_flag = nullptr) {
+	const double *partials, int nblk, int t, int *stop_flag = nullptr, double ssim_c1 = 0.0, double ssim_c2 = 0.0) {
 	auto LD = [](const double *p) -> double { return fin_ld<COH>(p); };
 	auto LDI = [](const int *p) -> int { return fin_ld<COH>(p); };
 	auto ST = [](double *p, double v) { fin_st<COH>(p, v); };
@@ -156,7 +161,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	__shared__ double acc_s[NCC_ACC_COUNT];   /* >= ACC_COUNT */
 	__shared__ double A[8][9];
 	__shared__ double dps[8];
-	__shared__ double h0s[64], Ws[9], crs[8], ics[12], tms[NCC_TM_COUNT], ncs[2], sos[8];
+	__shared__ double h0s[64], Ws[9], crs[8], ics[12], tms[NCC_TM_COUNT], ncs[SSIM ? 8 : 2], sos[8];
 	const int lane = threadIdx.x;
 	const bool wv0 = lane < 64;
 	const int S = bv.S;
@@ -166,7 +171,8 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	const int SS = lo ? ts.SS : S;
 	/* NCC: the reduced row holds raw moments (NCC_* slots, NCC_ACC_COUNT wide); tms = sum J0 | sum I0 J0 | Gram(J0) of the
 	 * template, ncs = mean(I0), |I0 - mean|.  The calling workgroup then has at least 128 threads. */
-	const bool ncc = bv.am == MTFHIP_AM_NCC;
+	const bool ncc = SSIM || bv.am == MTFHIP_AM_NCC;   /* (an SSIM batch's rows are NCC's) */
+	constexpr int NCS = SSIM ? 7 : 2;
 	const int RL = ncc ? (int)NCC_ACC_COUNT : (int)ACC_COUNT;
 	/* every global operand of this target -- the `active` flag included -- is requested up front, in parallel across
 	 * the lanes, and only then is the flag tested: one memory round trip instead of two (flag, then operands); the
@@ -182,7 +188,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		if (lane < 12) v_ic = ts.init_corners_hm[12 * t + lane];
 		if (ncc) {
 			if (lane < NCC_TM_COUNT) v_tm = ts.ncc_tm[(size_t)t * NCC_TM_COUNT + lane];
-			if (lane < 2) v_nc = ts.ncc[(size_t)t * 8 + lane];
+			if (lane < NCS) v_nc = ts.ncc[(size_t)t * 8 + lane];
 		}
 	}
 	__shared__ double part_s[3][80];
@@ -196,7 +202,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		if (lane < 8) { crs[lane] = v_cr; sos[lane] = v_so; }
 		if (lane < 12) ics[lane] = v_ic;
 		if (lane < NCC_TM_COUNT) tms[lane] = v_tm;
-		if (lane < 2) ncs[lane] = v_nc;
+		if (lane < NCS) ncs[lane] = v_nc;
 	}
 	v_acc = fin_sum_combine(nblk, RL, v_acc, part_s);
 	if (lane < RL) { acc_s[lane] = v_acc; ST(ts.acc + (size_t)t * RL + lane, v_acc); }
@@ -205,8 +211,10 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	const int i = (lane >> 3) & 7, j = lane & 7;
 	/* the system of this pass: mtfhip_sm_system.h.  NCC's scalars once, from the reduced row and the template's constants */
 	NccSys nq = NccSys();
-	if (ncc) nq = ncc_sys(acc_s, tms, ncs[0], ncs[1], (double)bv.N);
-	const double f_row = ncc ? nq.f : ssd_f(SPSS, acc_s);
+	SsimSys sq = SsimSys();
+	if constexpr (SSIM) sq = ssim_sys(acc_s, tms, ncs[0], ncs[6], (double)bv.N, ssim_c1, ssim_c2);
+	else if (ncc) nq = ncc_sys(acc_s, tms, ncs[0], ncs[1], (double)bv.N);
+	const double f_row = SSIM ? sq.f : (ncc ? nq.f : ssd_f(SPSS, acc_s));
 	/* ---- Levenberg-Marquardt: the accept / undo test on the similarity of this pass (uniform over the workgroup) ---- */
 	double *lmp = ts.lm ? ts.lm + (size_t)t * kLmStride : nullptr;
 	double lm_delta = 0.0;
@@ -225,6 +233,7 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 	/* entry (r, c) of H and entry s of g as the search method holds them, padded to 8 x 8: thin adapters over mtfhip_sm_system.h */
 	auto h_entry = [&](int r, int c) -> double {
 		if (r >= S || c >= S) return r == c ? -1.0 : 0.0;
+		if constexpr (SSIM) return ssim_h(sm, sq, h0s[c * S + r], r, c);
 		/* sec_ord_hess: + sum_p df_dI[p] d2I_dp2[:, p] (SSDBase.cc:313-415; NCC.cc:391-410); the homography blocks are not symmetric in their
 		 * last two rows / columns (Homography.cc:421,613,796), so the entry is taken as (r, c), not from a triangle */
 		if (ncc) return ncc_h(sm, nq, h0s[(r < c ? c : r) * S + (r < c ? r : c)], ts.h_extra ? ts.h_extra_scale * ts.h_extra[(size_t)t * S * S + c * S + r] : 0.0, r, c);
@@ -232,7 +241,10 @@ __device__ __forceinline__ void finish_track_body(const BatchView &bv, const mtf
 		if (ts.h_extra) v += ts.h_extra_scale * ts.h_extra[(size_t)t * S * S + c * S + r];
 		return v;
 	};
-	auto g_entry = [&](int s) -> double { return (!SPSS && ncc) ? ncc_g(sm, nq, s) : ssd_g(sm, SPSS, acc_s, s); };
+	auto g_entry = [&](int s) -> double {
+		if constexpr (SSIM) return ssim_g(sm, sq, s);
+		return (!SPSS && ncc) ? ncc_g(sm, nq, s) : ssd_g(sm, SPSS, acc_s, s);
+	};
 	/* Symmetric diagonal equilibration by POWERS OF TWO: the products are exact, so the scaled elimination follows the unscaled
 	 * one bit for bit while its pivots stay near one (and a frexp / ldexp pair replaces the square root and the division of
 	 * 1 / sqrt|d|, a microsecond of dependent arithmetic on an idle workgroup). */

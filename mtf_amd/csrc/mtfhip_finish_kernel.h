@@ -1,6 +1,6 @@
 /*
  * mtfhip_finish_kernel.h -- the body of the stand-alone finish kernels of the two-launch loop: k_finish_track and k_finish_track_lo
- * (kernels_fused.hip), k_finish_track_spss (kernels_fused_spss.hip).  finish_track_body / finish_track_fast_body (mtfhip_finish_device.h) plus
+ * (kernels_fused.hip), k_finish_track_spss (kernels_fused_spss.hip), k_finish_track_ssim and k_finish_track_ssim_lo (kernels_ssim.hip).  finish_track_body / finish_track_fast_body (mtfhip_finish_device.h) plus
  * the launch's own business: issue priority, the delivery of a stopped target to the host, the queues' phase stamps.
  */
 #ifndef MTFHIP_FINISH_KERNEL_H
@@ -23,14 +23,16 @@ namespace mtfhip {
  * the host exactly once -- in the pass that stops it, or in the last pass the host enqueues (ts.last_pass) if it is still active then -- with
  * the hand-over of publish_target; the arrivals of all passes and both queues count to pub.B, the last one raises the host's flag.  pub_t0:
  * the launch's first target in the batch (bv and ts are the chunk's views). */
-template <bool LO, bool SPSS = false>
+/* SSIM (k_finish_track_ssim / _ssim_lo, kernels_ssim.hip): finish_track_body's SSIM form over an NCC pass's rows, with the model's constants */
+template <bool LO, bool SPSS = false, bool SSIM = false>
 __device__ __forceinline__ void finish_track_kernel(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts,
-	const double *partials, int nblk, const PhaseCtl &pc, const HostPublish &pub, int pub_t0) {
+	const double *partials, int nblk, const PhaseCtl &pc, const HostPublish &pub, int pub_t0, double ssim_c1 = 0.0, double ssim_c2 = 0.0) {
 	if (ts.finish_prio) __builtin_amdgcn_s_setprio(3);
 	const int t = blockIdx.x;
 	__shared__ int s_stopped;
 	if (pub.host && threadIdx.x == 0) __hip_atomic_store(&s_stopped, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-	if constexpr (SPSS) finish_track_body<false, false, false, true>(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
+	if constexpr (SSIM) finish_track_body<false, false, LO, false, true>(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr, ssim_c1, ssim_c2);
+	else if constexpr (SPSS) finish_track_body<false, false, false, true>(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
 	else if constexpr (LO) finish_track_body<false, false, true>(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
 	else if (ts.fast_finish) finish_track_fast_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);
 	else finish_track_body(bv, sm, ts, partials, nblk, t, pub.host ? &s_stopped : nullptr);

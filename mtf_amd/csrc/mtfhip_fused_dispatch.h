@@ -31,7 +31,7 @@ enum { RSCV_IT_REPLAY = 0, RSCV_IT_FAST_ICLK = 1, RSCV_IT_FAST_CHAINED = 2, RSCV
 /* the template arguments of one instantiation; mc: the multi-channel body (MC = true, kernels_fused_mc.hip); served = false: the route
  * has no kernel for the input, and the other fields say nothing */
 struct FusedKey {
-	int am, ssm, mode;     /* MTFHIP_AM_SSD / _NCC / _RSCV / _LRSCV / _SPSS ; MTFHIP_SSM_* ; 0 FCLK, 1 ESM, 2 ICLK */
+	int am, ssm, mode;     /* MTFHIP_AM_SSD / _NCC (also an SSIM batch's) / _RSCV / _LRSCV / _SPSS ; MTFHIP_SSM_* ; 0 FCLK, 1 ESM, 2 ICLK */
 	bool chained, mat, fast, mc, served;
 };
 constexpr bool operator==(const FusedKey &a, const FusedKey &b) {
@@ -54,6 +54,9 @@ constexpr FusedKey fused_select(int route, int am, int channels, int ssm, int mo
 	case MTFHIP_AM_LRSCV: k.am = mapped ? MTFHIP_AM_LRSCV : MTFHIP_AM_SSD; break;
 	/* SPSS (kernels_fused_spss.hip): single channel, the two-launch loop only (`plain` below keeps it off the one-launch routes) */
 	case MTFHIP_AM_SPSS: if (channels != 1) return k; k.am = MTFHIP_AM_SPSS; break;
+	/* SSIM: every quantity of SSIM.cc is a function of the raw moments an NCC pass reduces (mtfhip_sm_system.h), so its launches ARE NCC's
+	 * kernels; single channel, the two-launch loop only -- the finish that reads the row as SSIM is k_finish_track_ssim (kernels_ssim.hip) */
+	case MTFHIP_AM_SSIM: if (channels != 1) return k; k.am = MTFHIP_AM_NCC; break;
 	default: return k;
 	}
 	/* the mapping kernels take every row as a pixel of one plane; MCSSD / MCNCC are SSD / NCC with the multi-channel body */

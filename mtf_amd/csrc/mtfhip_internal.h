@@ -666,6 +666,17 @@ void launch_track_prologue(const void *src_host, void *dst, size_t bytes, size_t
 void launch_finish_track_spss(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials, int nblk,
 	hipStream_t st, PhaseCtl pc, const HostPublish &pub, int pub_t0, dim3 block);
 
+/* kernels_ssim.hip: the finish over an NCC pass's rows read as SSIM (mtfhip_sm_system.h: ssim_*), c1 and c2 the model's constants -- k_finish_track_ssim,
+ * or k_finish_track_ssim_lo for ts.lo_ssm; the callers of launch_finish_track hand an SSIM batch's passes here instead.  And the kernels of
+ * the per-function entry points (SSIM.cc:98-287): sum It, sum It^2, sum I0 It into ACC_G + 0 .. 2 of the block rows; df_dIt (curr = 1) or
+ * df_dI0 into `out` from the per-target scalars sc ([B][8]: mo, mu, mult_factor, a, f c, grad_scal); the moments of the pixel Jacobian J
+ * and of the current patch as a 72-wide NCC row per block */
+void launch_finish_track_ssim(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials, int nblk,
+	hipStream_t st, PhaseCtl pc, const HostPublish &pub, int pub_t0, double c1, double c2);
+void launch_ssim_similarity(const BatchView &bv, double *partials, int nblk, hipStream_t st);
+void launch_ssim_grad(const BatchView &bv, const double *sc, int curr, double *out, hipStream_t st);
+void launch_ssim_hess(const BatchView &bv, const double *J, double *partials, int nblk, hipStream_t st);
+
 /* ---- the additive search methods nt::FALK / nt::IALK (kernels_alk.hip) ---- */
 struct AlkArgs {
 	int ialk;            /* 0 FALK: gradient at the current points + cmptPixJacobian; 1 IALK: cmptApproxPixJacobian of dI0_dx */

@@ -2,7 +2,7 @@
  * mtfhip_sm_system.h -- the rule that turns one target's reduced accumulator row into a search method's f, g and H (before damping),
  * stated ONCE for the host-side assembly (api_fused.hip: assemble_rows, api_ncc_moments.hip) and the device-side finish
  * (mtfhip_finish_device.h): the accumulator slots, the Hessian source predicates, the SSD-family and SPSS entries, NCC from its raw
- * moments, and the projection of the affine-coordinate system onto a low-order SSM.  Both sides are compiled with -ffp-contract=off, so
+ * moments, SSIM from the same moments, and the projection of the affine-coordinate system onto a low-order SSM.  Both sides are compiled with -ffp-contract=off, so
  * one expression gives one set of bits: `iterate` followed by a host solve and the device loop are the same method because they call
  * the same functions.  Nothing here needs the HIP runtime; a host compiler takes the header as it stands.
  */
@@ -164,6 +164,118 @@ MTFHIP_HD double ncc_h(const mtfhip_sm_desc &sm, const NccSys &q, double h0v, do
 	if (ht == 3) return ncc_hess(q, NCC_H_CURR, NCC_JM, r, c, kk) + ex;   /* Original: cmptCurrHessian(mean) */
 	return 0.5 * (ncc_hess(q, NCC_H_INIT, NCC_J0, r, c, kk) + ncc_hess(q, NCC_H_CURR, NCC_JT, r, c, kk)) + ex;   /* SumOfStd */
 }
+
+/* ---- SSIM on NCC's moments: everything SSIM.cc derives from its centred vectors is a function of the row an NCC pass reduces ----
+ * With N the patch size, m0 / mt the means, x0 = I0 - m0, xt = It - mt, c1 = (255 k1)^2, c2 = (255 k2)^2 (SSIM.cc:36-39, 98-111):
+ *   v0 = x0.x0 / (N - 1)   vt = (sum It^2 - N mt^2) / (N - 1)   cross = (sum I0 It - N m0 mt) / (N - 1)
+ *   a = 2 mt m0 + c1   b = 2 cross + c2   c = mt^2 + m0^2 + c1   d = vt + v0 + c2   f = a b / (c d)
+ * and for a pixel Jacobian X (`which`, as ncc_mom): sX = sum X, p0 = X^T x0 = sum I0 X - m0 sX, pt = X^T xt = sum It X - mt sX, Gram(X).
+ * Gradients (SSIM.cc:113-142), mu = 2 / (N c d): df_dIt = mu (a x0 - f c xt) + gs_t, gs_t = 2 (m0 b - mt f d) / (c d (N - 1)), hence
+ *   X^T df_dIt = mu (a p0 - f c pt) + gs_t sX          and X^T df_dI0 the same with I0 and It exchanged
+ * (the N against N - 1 is the reference's: the vectors are not the derivatives of f, and are kept).  Hessians (SSIM.cc:144-287): every term
+ * is Gram(X), sX sX^T or an outer product (X^T u)(X^T v)^T with u, v in span{x0, xt, 1}; the expressions are ssim_hess's, term by term the
+ * reference's.  Kept as the reference has them:
+ *   - (2 / (patch_size - 1)) at SSIM.cc:169,183,223,237 is an INTEGER quotient (0 for N >= 4): SsimSys::qi; the 2.0 / (patch_size - 1) at
+ *     :177,231 is floating point;
+ *   - cmptInitHessian and cmptCurrHessian are NOT symmetric (p0 sX^T, pt p0^T): every consumer takes entry (r, c), never a triangle;
+ *   - at :168 and :222 the reference multiplies the column X^T gv^T by a COLUMN, which Eigen only evaluates with its assertions compiled out;
+ *     the vector is taken as the row that makes the product conform (the outer product every neighbouring term is).
+ * Not kept, because it is state and not algebra: cmptSelfHessian overwrites the members c and d until the next updateSimilarity
+ * (SSIM.cc:273-274), and initializeSimilarity reads cross_pix_var before it is set (:64, unused before the first update).  Nothing here
+ * carries such members: every Hessian is taken with the c and d of the row's own similarity, and after init_template f = 1. */
+struct SsimSys {
+	const double *row, *tm;
+	double N, m0, mt, c1, c2;
+	double vt, a, b, c, d, cd, f;       /* SSIM.cc:98-111 */
+	double mu, gs_t, gs_0;              /* mult_factor, curr_grad_scal, init_grad_scal (SSIM.cc:113-142) */
+	double qi;                          /* (2 / (patch_size - 1)), the integer quotient */
+};
+/* ss0: sum (I0 - m0)^2 of the template.  row may be NULL for the system AT the template (It = I0: ssim_sys_template) */
+MTFHIP_HD SsimSys ssim_sys_of(const double *row, const double *tm, double m0, double ss0, double N, double c1, double c2, double mt, double tt, double cr) {
+	SsimSys q;
+	q.row = row; q.tm = tm; q.N = N; q.m0 = m0; q.mt = mt; q.c1 = c1; q.c2 = c2;
+	const double v0 = ss0 / (N - 1);
+	q.vt = tt / (N - 1);
+	q.a = 2 * mt * m0 + c1;
+	q.b = 2 * (cr / (N - 1)) + c2;
+	q.c = mt * mt + m0 * m0 + c1;
+	q.d = q.vt + v0 + c2;
+	q.cd = q.c * q.d;
+	q.f = (q.a * q.b) / q.cd;
+	q.mu = 2.0 / (N * q.cd);
+	q.gs_t = 2 * (m0 * q.b - mt * q.f * q.d) / (q.cd * (N - 1));
+	q.gs_0 = 2 * (mt * q.b - m0 * q.f * q.d) / (q.cd * (N - 1));
+	const long long n = (long long)N;
+	q.qi = n > 1 ? (double)(2 / (n - 1)) : 0.0;
+	return q;
+}
+MTFHIP_HD SsimSys ssim_sys(const double *row, const double *tm, double m0, double ss0, double N, double c1, double c2) {
+	const double mt = row[NCC_IT] / N;
+	return ssim_sys_of(row, tm, m0, ss0, N, c1, c2, mt, row[NCC_IT2] - N * mt * mt, row[NCC_I0IT] - N * m0 * mt);
+}
+/* It = I0: the system init_template leaves (f = 1) and the one the constant self Hessian H0 = cmptSelfHessian(J0) is taken at; only NCC_J0 moments */
+MTFHIP_HD SsimSys ssim_sys_template(const double *tm, double m0, double ss0, double N, double c1, double c2) {
+	return ssim_sys_of(nullptr, tm, m0, ss0, N, c1, c2, m0, ss0, ss0);
+}
+/* one moment of J0, Jt or their mean (ncc_mom's scheme over the two arrays themselves) */
+MTFHIP_HD double ssim_mom(const SsimSys &q, int which, int c0, int ct, int s) {
+	if (which == NCC_J0) return c0 >= 0 ? q.tm[c0 + s] : q.row[NCC_ITJ0 + s];
+	const double vt = q.row[ct + s];
+	return which == NCC_JT ? vt : ((c0 >= 0 ? q.tm[c0 + s] : q.row[NCC_ITJ0 + s]) + vt) / 2;
+}
+MTFHIP_HD double ssim_sj(const SsimSys &q, int which, int s) { return ssim_mom(q, which, NCC_TM_SJ0, NCC_SJ, s); }
+MTFHIP_HD double ssim_p0(const SsimSys &q, int which, int s) { return ssim_mom(q, which, NCC_TM_I0J0, NCC_I0J, s) - q.m0 * ssim_sj(q, which, s); }
+MTFHIP_HD double ssim_pt(const SsimSys &q, int which, int s) { return ssim_mom(q, which, -1, NCC_ITJ, s) - q.mt * ssim_sj(q, which, s); }
+/* X^T init_grad_vec^T / X^T curr_grad_vec^T (the gradient without its scalar part) and cmptInitJacobian / cmptCurrJacobian */
+MTFHIP_HD double ssim_gv(const SsimSys &q, bool curr, int which, int s) {
+	const double po = curr ? ssim_p0(q, which, s) : ssim_pt(q, which, s), pu = curr ? ssim_pt(q, which, s) : ssim_p0(q, which, s);
+	return q.mu * (q.a * po - q.f * q.c * pu);
+}
+MTFHIP_HD double ssim_curr_jac(const SsimSys &q, int which, int s) { return ssim_gv(q, true, which, s) + q.gs_t * ssim_sj(q, which, s); }
+MTFHIP_HD double ssim_init_jac(const SsimSys &q, int which, int s) { return ssim_gv(q, false, which, s) + q.gs_0 * ssim_sj(q, which, s); }
+/* entry (r, c) of cmptInitHessian / cmptCurrHessian / cmptSelfHessian (kind: NCC_H_*) over the Jacobian `which` */
+MTFHIP_HD double ssim_hess(const SsimSys &q, int kind, int which, int r, int c) {
+	const int kk = tri8_sym(r, c);
+	const double gram = which == NCC_J0 ? q.tm[NCC_TM_GRAM0 + kk] : q.row[NCC_GRAM + kk];
+	const double N = q.N, sr = ssim_sj(q, which, r), sc = ssim_sj(q, which, c);
+	if (kind == NCC_H_SELF) {   /* SSIM.cc:270-287 */
+		const double cs = 2 * (q.mt * q.mt) + q.c1, ds = 2 * q.vt + q.c2, cds = cs * ds;
+		const double m1 = 2.0 / (N * cds), m2 = 2.0 / ((N - 1) * cds);
+		return cs * m1 * ((1.0 / N) * sr * sc - gram) - (m2 * ds / N) * sr * sc;
+	}
+	/* SSIM.cc:200-238 (curr; :144-185 init is the same with I0 and It exchanged): `o` the other image's, `u` the image's own the Hessian is taken in */
+	const bool curr = kind == NCC_H_CURR;
+	const double mo = curr ? q.m0 : q.mt, mu = curr ? q.mt : q.m0, gs = curr ? q.gs_t : q.gs_0;
+	const double por = curr ? ssim_p0(q, which, r) : ssim_pt(q, which, r);
+	const double pur = curr ? ssim_pt(q, which, r) : ssim_p0(q, which, r), puc = curr ? ssim_pt(q, which, c) : ssim_p0(q, which, c);
+	const double gr = curr ? ssim_curr_jac(q, which, r) : ssim_init_jac(q, which, r), gc = curr ? ssim_curr_jac(q, which, c) : ssim_init_jac(q, which, c);
+	const double a_diff = 2.0 * mo / N, c_diff = 2.0 * mu / N;
+	const double m1 = 2.0 / (N * q.cd), m2 = 2.0 / ((N - 1) * q.cd);
+	const double wr = q.qi * pur / q.d + (c_diff / q.c) * sr, wc = q.qi * puc / q.d + (c_diff / q.c) * sc;
+	const double ur = m2 * ((2 * mo / (N - 1)) * por - (mu * (q.d * gr + (2.0 / (N - 1)) * q.f * pur) + (q.f * q.d / N) * sr)) - gs * wr;
+	return m1 * (a_diff * por * sc - pur * (q.c * gc + q.f * c_diff * sc) - q.f * q.c * (gram - (1.0 / N) * sr * sc))
+		- ssim_gv(q, curr, which, r) * wc + ur * sc;
+}
+/* the search method's Jacobian and Hessian: NCC's wiring (ncc_g, ncc_h; ncc_h_which / ncc_has_gram say which Gram matrix the pass must carry).
+ * ESM calls updateCurrGrad and updateInitGrad in every pass (NT/ESM.cc:247-252), FCLK the first alone, ICLK the second: no method reads a
+ * gradient member another pass left.  h0v: entry (r, c) of the constant self Hessian */
+MTFHIP_HD double ssim_g(const mtfhip_sm_desc &sm, const SsimSys &q, int s) {
+	if (sm.sm == MTFHIP_SM_FCLK) return ssim_curr_jac(q, NCC_JT, s);
+	if (sm.sm == MTFHIP_SM_ICLK) return ssim_init_jac(q, NCC_J0, s);
+	if (sm.jac_type == 0) return ssim_curr_jac(q, NCC_JM, s);
+	return 0.5 * (ssim_curr_jac(q, NCC_JT, s) - ssim_init_jac(q, NCC_J0, s));
+}
+MTFHIP_HD double ssim_h(const mtfhip_sm_desc &sm, const SsimSys &q, double h0v, int r, int c) {
+	const int ht = sm.hess_type;
+	if (ht == 0) return h0v;
+	if (sm.sm == MTFHIP_SM_ICLK) return ssim_hess(q, NCC_H_INIT, NCC_J0, r, c);   /* Std: cmptInitHessian(J0) */
+	if (sm.sm == MTFHIP_SM_FCLK || ht == 1 || ht == 5) return ssim_hess(q, ht == 1 ? NCC_H_SELF : NCC_H_CURR, NCC_JT, r, c);
+	if (ht == 2) return 0.5 * (ssim_hess(q, NCC_H_SELF, NCC_JT, r, c) + h0v);   /* SumOfSelf */
+	if (ht == 3) return ssim_hess(q, NCC_H_CURR, NCC_JM, r, c);   /* Original: cmptCurrHessian(mean) */
+	return 0.5 * (ssim_hess(q, NCC_H_INIT, NCC_J0, r, c) + ssim_hess(q, NCC_H_CURR, NCC_JT, r, c));   /* SumOfStd */
+}
+/* SSIM::getLikelihood, SSIM.cc:45-48 */
+MTFHIP_HD double ssim_likelihood(double f, double alpha) { const double d = (1.0 / f) - 1; return exp(-alpha * d * d); }
 
 /* ---- the low-order SSMs: J_S = J_aff M with M constant, 6 x SS, at most two +-1 entries per column (Translation.h:45-63,
  * Isometry.cc:115-135,162-185, Similitude.cc:163-210) --

@@ -89,6 +89,7 @@ void HipPair::setLRSCV(int sub_regions_x, int sub_regions_y, int spacing_x, int 
 		weighted_mapping ? 1 : 0));
 }
 void HipPair::setSPSS(double k) { check(mtfhip_batch_set_spss(b, k)); }
+void HipPair::setSSIM(double k1, double k2) { check(mtfhip_batch_set_ssim(b, k1, k2)); }
 void HipPair::setRSCV(bool use_bspl, bool weighted_mapping, bool mapped_gradient) {
 	check(mtfhip_batch_set_rscv(b, use_bspl ? 1 : 0, weighted_mapping ? 1 : 0, mapped_gradient ? 1 : 0));
 }
@@ -108,7 +109,7 @@ int HipPair::hessianBuffer(const MatrixXd &D, bool may_register) {
 /* ------------------------------------------------------------------ AM */
 HipAM::HipAM(std::shared_ptr<HipPair> pair) : p(pair) {
 	name = p->am == MTFHIP_AM_SSD ? "ssd" : (p->am == MTFHIP_AM_NCC ? "ncc" : (p->am == MTFHIP_AM_SCV ? "scv" : (p->am == MTFHIP_AM_RSCV ? "rscv" : (p->am == MTFHIP_AM_LSCV ? "lscv" :
-		(p->am == MTFHIP_AM_LRSCV ? "lrscv" : (p->am == MTFHIP_AM_SPSS ? "spss" : "mi"))))));
+		(p->am == MTFHIP_AM_LRSCV ? "lrscv" : (p->am == MTFHIP_AM_SPSS ? "spss" : (p->am == MTFHIP_AM_SSIM ? "ssim" : "mi")))))));
 	I0.resize(p->N); It.resize(p->N);
 	dI0_dx.resize(p->N, 2); dIt_dx.resize(p->N, 2);
 	d2I0_dx2.resize(4, p->N); d2It_dx2.resize(4, p->N);

@@ -53,6 +53,7 @@ struct HipPair {
 	void setLRSCV(int sub_regions_x, int sub_regions_y, int spacing_x, int spacing_y, bool affine_mapping, bool once_per_frame,
 		bool weighted_mapping);                                                /* mtfhip_batch_set_lrscv (am = MTFHIP_AM_LRSCV) */
 	void setSPSS(double k);                                                    /* mtfhip_batch_set_spss (am = MTFHIP_AM_SPSS) */
+	void setSSIM(double k1, double k2);                                        /* mtfhip_batch_set_ssim (am = MTFHIP_AM_SSIM) */
 	int hessianBuffer(const MatrixXd &D, bool may_register);
 };
 
@@ -97,6 +98,11 @@ struct HipLRSCVParams {
 struct HipSPSSParams {
 	double k = 0.01;
 };
+/* SSIMParams (AM/include/mtf/AM/SSIM.h), the reference's field names and class defaults (SSIM.cc:4-5: the shipped ssim_k1, ssim_k2):
+ * c1 = (255 k1)^2, c2 = (255 k2)^2 */
+struct HipSSIMParams {
+	double k1 = 0.01, k2 = 0.03;
+};
 struct HipLink {
 	int am = MTFHIP_AM_SSD, ssm = MTFHIP_SSM_HOMOGRAPHY, resx = 50, resy = 50;   /* AMParams / SSMParams: resx, resy */
 	double grad_eps = 1e-8, likelihood_alpha = 1.0;                           /* AMParams::grad_eps; SSDParams / NCCParams / MIParams::likelihood_alpha */
@@ -106,6 +112,7 @@ struct HipLink {
 	HipLSCVParams lscv;                                                        /* am = MTFHIP_AM_LSCV ("lscv") */
 	HipLRSCVParams lrscv;                                                      /* am = MTFHIP_AM_LRSCV ("lrscv", "lrsc") */
 	HipSPSSParams spss;                                                        /* am = MTFHIP_AM_SPSS ("spss") */
+	HipSSIMParams ssim;                                                        /* am = MTFHIP_AM_SSIM ("ssim") */
 	int device = 0; void *stream = nullptr;
 	std::shared_ptr<HipPair> pair(int n_channels = 1) {
 		if (!p && am == MTFHIP_AM_SCV) {
@@ -131,6 +138,10 @@ struct HipLink {
 		if (!p && am == MTFHIP_AM_SPSS) {
 			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, 0, 0.0, 0, device, stream, n_channels);
 			p->setSPSS(spss.k);
+		}
+		if (!p && am == MTFHIP_AM_SSIM) {
+			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, 0, 0.0, 0, device, stream, n_channels);
+			p->setSSIM(ssim.k1, ssim.k2);
 		}
 		if (!p) p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, device, stream, n_channels);
 		else if (n_channels > 1 && n_channels != p->n_channels)   /* (SearchMethod<AM, SSM> constructs the AM first: it fixes the channel count) */
@@ -269,6 +280,32 @@ private:
 		if (!sp || !sp->link) throw utils::InvalidArgument("SPSS :: the parameter block carries no HipLink (the AM and the SSM of a tracker share one)");
 		sp->link->am = MTFHIP_AM_SPSS;
 		sp->link->spss.k = sp->k;
+		return sp;
+	}
+};
+
+/* The reference's names for the SSIM model (AM/include/mtf/AM/SSIM.h): SSIMParams {k1, k2} -- with the HipLink in place of the AMParams base --
+ * and class SSIM with its ParamType, params and c1 = (k1 (PIX_MAX - PIX_MIN))^2, c2 likewise (SSIM.cc:36-39).  A caller that wrote
+ * `SSIM(&ssim_params)` constructs this one: the HipAM of an MTFHIP_AM_SSIM pair whose constants are the block's. */
+struct SSIMParams : HipAMParams {
+	double k1 = 0.01, k2 = 0.03;
+	SSIMParams() = default;
+	SSIMParams(std::shared_ptr<HipLink> link_, double k1_, double k2_) : k1(k1_), k2(k2_) { link = link_; }
+};
+class SSIM : public HipAM {
+public:
+	typedef SSIMParams ParamType;
+	explicit SSIM(const ParamType *ssim_params, int _n_channels = 1) : HipAM(linked(ssim_params), _n_channels), params(*ssim_params),
+		c1(sq255(params.k1, 0.01)), c2(sq255(params.k2, 0.03)) {}
+	const ParamType params;
+	const double c1, c2;
+private:
+	static double sq255(double k, double dflt) { const double c = (k > 0 ? k : dflt) * 255.0; return c * c; }
+	/* the link's appearance model and constants are the block's, set before the pair is created (a pair that exists keeps what it was created with) */
+	static const HipAMParams *linked(const ParamType *sp) {
+		if (!sp || !sp->link) throw utils::InvalidArgument("SSIM :: the parameter block carries no HipLink (the AM and the SSM of a tracker share one)");
+		sp->link->am = MTFHIP_AM_SSIM;
+		sp->link->ssim.k1 = sp->k1; sp->link->ssim.k2 = sp->k2;
 		return sp;
 	}
 };

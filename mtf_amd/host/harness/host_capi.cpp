@@ -127,6 +127,17 @@ mtfhost_tracker *mtfhost_create_spss(int sm, int ssm, int resx, int resy, int ma
 		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
 	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
+/* the same tracker with HipAM("ssim"): its SSIMParams through the HipLink */
+mtfhost_tracker *mtfhost_create_ssim(int sm, int ssm, int resx, int resy, int max_iters, double epsilon, int jac_type, int hess_type, int chained_warp,
+	int leven_marq, double lm_delta_init, double lm_delta_update, int device, double k1, double k2) {
+	try {
+		auto link = std::make_shared<hip::HipLink>();
+		link->am = MTFHIP_AM_SSIM; link->ssm = ssm; link->resx = resx; link->resy = resy; link->device = device;
+		const hip::SSIMParams ssim_params(link, k1, k2);   /* (the reference's block: SSIM(&ssim_params) is the HipAM create_on builds over this pair) */
+		link->ssim.k1 = ssim_params.k1; link->ssim.k2 = ssim_params.k2;
+		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
+	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
 void mtfhost_destroy(mtfhost_tracker *t) { delete t; }
 /* ESM / FC / IC_ENABLE_LEARNING + the AM's learning_rate: am->updateModel(ssm->getPts()) at the end of every update() */
 int mtfhost_set_learning(mtfhost_tracker *t, int enable, double learning_rate) {

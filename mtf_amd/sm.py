@@ -42,6 +42,13 @@ def _refuse_spss(what, am):
         raise L.FunctionNotImplemented(-2, "%s: the SPSS appearance model is served by LKTracker and NTSearchMethod only" % what)
 
 
+def _refuse_ssim(what, am):
+    """GridTracker, ParticleFilter, NNDataset and NNTracker are not served with the SSIM appearance model (include/mtfhip.h): raised before
+    any device call"""
+    if am == L.AM_SSIM:
+        raise L.FunctionNotImplemented(-2, "%s: the SSIM appearance model is served by LKTracker and NTSearchMethod only" % what)
+
+
 class LKTracker:
     """One or many (B) independent targets tracked with ESM / FCLK / ICLK (or the additive FALK / IALK: SSD and NCC, k_alk_pass +
     k_alk_finish) + SSD, NCC or MI on one GPU through the fused path
@@ -428,6 +435,7 @@ class GridTracker:
                  grid_size_y=None, patch_size_y=None, fb_err_thresh=0.0, fb_reinit=1, n_model_pts=4, est_params=None, est_seed=1, **sm_params):
         _refuse_low_order("GridTracker", ssm, grid_ssm)
         _refuse_spss("GridTracker", am)
+        _refuse_ssim("GridTracker", am)
         self.ctx = ctx
         # est_params (_lib.est_params(...) = SSMEstimatorParams): the device RANSAC / LMedS estimator (Context.estimate_warp_from_pts) takes the
         # place of `estimator`; pix_mask / est_ok / est_result follow every update (GridTracker.cc:269, 332-340); frame f draws from est_seed + f
@@ -821,6 +829,7 @@ class ParticleFilter:
         import ctypes as C
         _refuse_low_order("ParticleFilter", ssm)
         _refuse_spss("ParticleFilter", am)
+        _refuse_ssim("ParticleFilter", am)
         # seed 0 = "draw one" (below) -- but only an unsharded filter may: the ranks of a sharded one must propose identical particles
         # (each scores a block of ITS proposals, the all-gather mixes the weights), so there seed 0 is refused before anything is
         # created (mtfhip_pf_set_comm cross-checks the seeds of all ranks as well)
@@ -1048,6 +1057,7 @@ class NNDataset:
                  ssm_sigma=(0.01, 0.01, 2.0, 0.01, 0.01, 2.0, 1e-5, 1e-5), ssm_mean=None, seed=0, am_params=None, distr_n_samples=None):
         _refuse_low_order("NNDataset", ssm)
         _refuse_spss("NNDataset", am)
+        _refuse_ssim("NNDataset", am)
         self.batch = Batch(ctx, am, ssm, resx, resy, 1, **(am_params or {}))
         self.S = self.batch.S
         self.n = int(n_samples)
@@ -1174,6 +1184,7 @@ class NNTracker:
         self._h = None
         _refuse_low_order("NNTracker", ssm)
         _refuse_spss("NNTracker", am)
+        _refuse_ssim("NNTracker", am)
         if index not in ("exact", "gnn"):
             raise ValueError("NNTracker: index must be 'exact' or 'gnn'")
         self.index, self.gnn_params = index, dict(gnn_params or {})

@@ -25,11 +25,7 @@ int mtfhip_am_initialize_pix_vals(mtfhip_batch *b, const double *pts) {
 		b->init_pix_vals = true;
 		b->it_valid = true;
 	}
-	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_capture(b));   /* SCV::initializePixVals: I0_orig = I0 (SCV.cc:166) */
-	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_capture(b));   /* RSCV::initializePixVals (RSCV.cc:124-168) */
-	if (b->desc.am == MTFHIP_AM_LSCV) TRY(lscv_capture(b));   /* LSCV::initializePixVals: I0_orig = I0 (LSCV.cc:232) */
-	if (b->desc.am == MTFHIP_AM_LRSCV) TRY(lrscv_capture(b));   /* LRSCV::initializePixVals (LRSCV.cc:197-222) */
-	return MTFHIP_OK;
+	return imap_capture(b);   /* the SCV family's initializePixVals (SCV.cc:166, RSCV.cc:124-168, LSCV.cc:232, LRSCV.cc:197-222) */
 }
 /* SSD::updateModel AM/src/SSD.cc:49-75, NCC::updateModel AM/src/NCC.cc:539-566 (the search methods call it at the end of update()
  * when enable_learning is set, NT/ESM.cc:293-295): template <- average with the patch at pts, then AppearanceModel::reinitialize
@@ -37,14 +33,8 @@ int mtfhip_am_initialize_pix_vals(mtfhip_batch *b, const double *pts) {
 int mtfhip_am_update_model(mtfhip_batch *b, const double *pts, double learning_rate) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "update_model: NULL batch");
-	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: MI has no online template update in the reference either");
-	if (b->desc.am == MTFHIP_AM_SCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: SCV is not available on this entry point (the template update would have to refresh I0_orig)");
-	if (b->desc.am == MTFHIP_AM_RSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: RSCV is not available on this entry point (the template update would have to refresh its code plane)");
-	if (b->desc.am == MTFHIP_AM_LSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LSCV is not available on this entry point (the template update would have to refresh I0_orig)");
-	if (b->desc.am == MTFHIP_AM_LRSCV) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: LRSCV is not available on this entry point (the template update would have to refresh its code plane)");
-	TRY(spss_refuse(b, "updateModel", " has no online template update on the device path"));
-	TRY(ssim_refuse(b, "updateModel", " has no online template update (SSIM.cc has none either)"));
-	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "updateModel :: appearance model %d", b->desc.am);
+	/* (served: SSD and NCC) */
+	if (am_traits(b->desc.am).no_update_model) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s", am_traits(b->desc.am).no_update_model);
 	TRY(single_channel(b, "update_model"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "update_model before initializePixVals");
 	TRY(need_image(b));
@@ -71,12 +61,11 @@ static int do_update_pix_vals(mtfhip_batch *b, const double *pts) {
 	TRY(protect_stale(b, false, false));   /* IT is about to change: gradients skipped by a fused launch keep the old IT */
 	const double *dp;
 	TRY(resolve_pts(b, pts, MTFHIP_BUF_CURR_PTS, 2 * (size_t)b->NP, &dp));
-	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_update_pix_vals(b, dp));   /* RSCV::updatePixVals: It = map(It_orig) (RSCV.cc:170-238) */
-	else if (b->desc.am == MTFHIP_AM_LRSCV) TRY(lrscv_update_pix_vals(b, dp));   /* LRSCV::updatePixVals (LRSCV.cc:224-261) */
-	else {
+	const int mapped = imap_update_pix_vals(b, dp);   /* RSCV / LRSCV::updatePixVals: It = map(It_orig) (RSCV.cc:170-238, LRSCV.cc:224-261) */
+	if (mapped == IMAP_NOT_MINE) {
 		TimedScope ts(b->ctx, "sample");
 		launch_sample(b->view(), b->ctx->img, dp, b->buf[MTFHIP_BUF_IT], b->norm_mult, b->norm_add, b->ctx->stream);
-	}
+	} else TRY(mapped);
 	touch(b, MTFHIP_BUF_IT);
 	b->lz.it_epoch = pts ? -1 : b->lz.epoch;
 	b->it_valid = true;
@@ -341,7 +330,7 @@ static int mi_grad(mtfhip_batch *b, int curr) {
 
 /* ------------------------------------------------------------------ AppearanceModel */
 static int am_supported(mtfhip_batch *b, const char *fn) {
-	if (ssd_like(b) || b->desc.am == MTFHIP_AM_NCC || b->desc.am == MTFHIP_AM_MI || spss_am(b) || ssim_am(b)) return MTFHIP_OK;
+	if (b->desc.am >= 0 && b->desc.am < (int)(sizeof(kAmTraits) / sizeof(kAmTraits[0]))) return MTFHIP_OK;   /* (every model with a row of traits) */
 	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s :: appearance model %d is not available on the device path yet", fn, b->desc.am);
 }
 
@@ -431,10 +420,9 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 	}
 	if (spss_am(b)) return spss_update_similarity(b, prereq_only);
 	if (ssim_am(b)) return ssim_update_similarity(b, prereq_only);
-	/* SCV::updateSimilarity (SCV.cc:194-230): the intensity map from It and I0_orig, I0 re-mapped, then SSDBase::updateSimilarity */
-	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 1, b->ctx->stream));
-	/* LSCV::updateSimilarity (LSCV.cc:263-304): unless once_per_frame and not the first iteration, the localized re-map of I0 */
-	if (lscv_due(b)) TRY(lscv_enqueue(b, b->view(), 0, nullptr, 1, b->ctx->stream));
+	/* SCV / LSCV::updateSimilarity (SCV.cc:194-230, LSCV.cc:263-304): the intensity map(s) from It and I0_orig, I0 re-mapped, then
+	 * SSDBase::updateSimilarity */
+	TRY(imap_before_pass(b, nullptr, 0, nullptr, nullptr, 1, b->first_iter != 0, b->ctx->stream, nullptr));
 	int nblk = simple_blocks_per_target(b->N);
 	{
 		TimedScope ts(b->ctx, "ssd_residual");

@@ -19,12 +19,9 @@ static const double *template_hull(const mtfhip_batch *b, double *hull_buf) {
 }
 /* SCV, RSCV, LSCV and LRSCV have no per-candidate form: the refusal of the entry point fn, "<fn>: <model><what> (<why>)" */
 int refuse_intensity_mapped(const mtfhip_batch *b, const char *fn, const char *what) {
-	if (!intensity_mapped(b)) return MTFHIP_OK;
-	static const char *const why[4] = {"SCVDist is a per-candidate intensity map", "RSCVDist is a per-candidate intensity map",
-		"LSCVDist is a per-candidate intensity map", "its maps are per-candidate intensity maps"};
-	const int am = b->desc.am;
-	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s%s (%s)", fn, intensity_mapped_name(b), what,
-		why[am == MTFHIP_AM_SCV ? 0 : (am == MTFHIP_AM_RSCV ? 1 : (am == MTFHIP_AM_LSCV ? 2 : 3))]);
+	const AmTraits &am = am_traits(b->desc.am);
+	if (!am.no_candidates) return MTFHIP_OK;
+	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s%s (%s)", fn, am.name, what, am.no_candidates);
 }
 
 /* ------------------------------------------------------------------ candidate scoring */

@@ -318,27 +318,11 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	if ((double)d->resx * d->resy * 3.0 >= (double)(1u << 26)) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: %dx%d sample points per target exceed the 2^26-row limit", d->resx, d->resy);
 	if (d->grad_eps <= 0 || d->hess_eps < 0) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: grad_eps must be positive (got %g)", d->grad_eps);
 	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_SSIM) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
-	if (d->am == MTFHIP_AM_SSIM && d->n_channels == 3)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "SSIM with n_channels 3 (MCSSIM) is not available on the device path (single channel only)");
-	if (d->am == MTFHIP_AM_SPSS && d->n_channels == 3)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "SPSS with n_channels 3 (MCSPSS) is not available on the device path (single channel only)");
-	if (d->am == MTFHIP_AM_LRSCV && (d->mi_n_bins > kLscvMaxBins || d->mi_n_bins == 1))
-		return fail(MTFHIP_ERR_INVALID_ARG, "LRSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kLscvMaxBins);
-	if (d->am == MTFHIP_AM_LRSCV && d->n_channels == 3)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "LRSCV with n_channels 3 is not available (no multi-channel LRSCV exists in the reference either)");
-	if (d->am == MTFHIP_AM_LSCV && (d->mi_n_bins > kLscvMaxBins || d->mi_n_bins == 1))
-		return fail(MTFHIP_ERR_INVALID_ARG, "LSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kLscvMaxBins);
-	if (d->am == MTFHIP_AM_LSCV && d->n_channels == 3)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "LSCV with n_channels 3 (MCLSCV) is not available on the device path (single channel only)");
-	if (d->am == MTFHIP_AM_RSCV && (d->mi_n_bins > kRscvMaxBins || d->mi_n_bins == 1))
-		return fail(MTFHIP_ERR_INVALID_ARG, "RSCV: n_bins %d outside [2, %d]", d->mi_n_bins, kRscvMaxBins);
-	if (d->am == MTFHIP_AM_RSCV && d->n_channels == 3)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "RSCV with n_channels 3 (MCRSCV) is not available on the device path (single channel only)");
-	if (d->am == MTFHIP_AM_SCV && d->mi_n_bins > kScvMaxBins) return fail(MTFHIP_ERR_INVALID_ARG, "SCV: n_bins %d outside [2, %d]", d->mi_n_bins, kScvMaxBins);
-	if (d->am == MTFHIP_AM_SCV && d->mi_n_bins == 1) return fail(MTFHIP_ERR_INVALID_ARG, "SCV: n_bins 1 outside [2, %d]", kScvMaxBins);
-	if (d->am == MTFHIP_AM_SCV && d->n_channels == 3)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "SCV with n_channels 3 (MCSCV) is not available on the device path (single channel only)");
-	if (d->am == MTFHIP_AM_MI && (d->mi_n_bins < 2 || d->mi_n_bins > MI_NB)) return fail(MTFHIP_ERR_INVALID_ARG, "MI: n_bins %d outside [2, %d]", d->mi_n_bins, (int)MI_NB);
+	const AmTraits &am = am_traits(d->am);
+	/* (n_bins where the model reads it: 2 .. max_bins, and where bins_default a value <= 0 stands for max_bins) */
+	if (am.max_bins && (d->mi_n_bins > am.max_bins || (am.bins_default ? d->mi_n_bins == 1 : d->mi_n_bins < 2)))
+		return fail(MTFHIP_ERR_INVALID_ARG, "%s: n_bins %d outside [2, %d]", am.name, d->mi_n_bins, am.max_bins);
+	if (am.no_3ch && d->n_channels == 3) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s", am.no_3ch);
 	if (d->am == MTFHIP_AM_MI && d->mi_partition_of_unity && d->mi_n_bins < 4) /* MI.cc:83-87 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "MI::Too few bins %d specified to enforce partition of unity constraint", d->mi_n_bins);
 	if (!ssm_known(d->ssm)) return fail(MTFHIP_ERR_INVALID_ARG, "unknown state space model %d", d->ssm);
@@ -366,25 +350,12 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		b->norm_mult = (hi - lo) / (255.0 - 0.0 + 1);
 		b->norm_add = lo;
 	}
-	if (d->am == MTFHIP_AM_SCV) {
+	if (am.intensity_mapped) {
 		/* SCVParams: n_bins <= 0 selects SCV_N_BINS = 256 (SCV.cc:30); SCV ctor SCV.cc:117-131: [0, n_bins - 1] over PIX_MAX - PIX_MIN = 255
-		 * (not MI's 256 levels) -- BSpline with partition of unity, the only other range, is refused */
-		b->scv_nb = d->mi_n_bins <= 0 ? kScvMaxBins : d->mi_n_bins;
-		b->norm_mult = (b->scv_nb - 1.0) / (255.0 - 0.0);
-		b->norm_add = 0;
-	}
-	if (d->am == MTFHIP_AM_RSCV) {
-		/* RSCVParams: n_bins <= 0 selects RSCV_N_BINS = 256 (RSCV.cc:6); RSCV ctor RSCV.cc:81-103 with use_bspl 0: [0, n_bins - 1] over
-		 * PIX_MAX - PIX_MIN = 255, as SCV */
-		b->rscv_nb = d->mi_n_bins <= 0 ? kRscvMaxBins : d->mi_n_bins;
-		b->norm_mult = (b->rscv_nb - 1.0) / (255.0 - 0.0);
-		b->norm_add = 0;
-	}
-	if (d->am == MTFHIP_AM_LSCV || d->am == MTFHIP_AM_LRSCV) {
-		/* LSCVParams: n_bins <= 0 selects LSCV_N_BINS = 256 (LSCV.cc:8, :39-40); LSCV ctor LSCV.cc:120-135: [0, n_bins - 1] over
-		 * PIX_MAX - PIX_MIN = 255, as SCV.  LRSCVParams / LRSCV ctor the same (LRSCV.cc:37-38, :97-110) */
-		b->lscv_nb = d->mi_n_bins <= 0 ? kLscvMaxBins : d->mi_n_bins;
-		b->norm_mult = (b->lscv_nb - 1.0) / (255.0 - 0.0);
+		 * (not MI's 256 levels) -- BSpline with partition of unity, the only other range, is refused.  RSCVParams / RSCV ctor with use_bspl 0
+		 * (RSCV.cc:6, :81-103), LSCV (LSCV.cc:8, :39-40, :120-135) and LRSCV (LRSCV.cc:37-38, :97-110) the same */
+		b->imap.nb = d->mi_n_bins <= 0 ? am.max_bins : d->mi_n_bins;
+		b->norm_mult = (b->imap.nb - 1.0) / (255.0 - 0.0);
 		b->norm_add = 0;
 	}
 	const size_t N = b->N, S = b->S, NP = b->NP;

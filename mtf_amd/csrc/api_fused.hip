@@ -429,24 +429,18 @@ static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, do
 	TRY(need_image(b));
 	if (b->desc.am == MTFHIP_AM_MI) return mi_iterate(b, sm, f, g, H);
 	if (second_order_term(sm) >= 0) TRY(ensure_pts(b));   /* k_second_order_ssd reads the current points */
-	/* SCV::updateSimilarity: the intensity map at the current warp and the re-mapped template, then the SSD iteration on it */
-	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, b->view(), 0, nullptr, 0, b->ctx->stream));
-	/* LSCV::updateSimilarity: unless once_per_frame and not the first iteration, the localized re-map at the current warp */
-	if (lscv_due(b)) TRY(lscv_enqueue(b, b->view(), 0, nullptr, 0, b->ctx->stream));
 	FusedArgs fa;
 	TRY(fused_args(b, sm, fa));
-	/* RSCV::updatePixVals: the intensity map of the current patch at the current warp, applied by the fused pass to every sample */
-	RscvMap rm;
-	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_enqueue(b, b->view(), 0, nullptr, fa, b->ctx->stream, &rm));
-	/* LRSCV::updatePixVals: unless once_per_frame and not the first iteration, the sub-region maps of the current patch, blended into
-	 * every sample by the fused pass; otherwise the SSD pass on the raw patch */
-	LrscvMap lm;
-	if (lrscv_due(b)) TRY(lrscv_enqueue(b, b->view(), 0, nullptr, fa, b->ctx->stream, &lm));
+	/* the SCV family at the current warp: SCV / LSCV::updateSimilarity re-map the template, then the SSD iteration on it; RSCV /
+	 * LRSCV::updatePixVals build the map(s) of the current patch, which the fused pass applies to every sample (an LRSCV pass without
+	 * them is the SSD pass on the raw patch) */
+	FusedMaps maps;
+	TRY(imap_before_pass(b, nullptr, 0, nullptr, &fa, 0, b->first_iter != 0, b->ctx->stream, &maps));
 	int nblk = fused_blocks_per_target(b->N, b->B);
 	{
 		TimedScope ts(b->ctx, "fused_lk");
 		const SpssArgs sp = spss_am(b) ? spss_args(b, sm) : SpssArgs{};
-		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream, &rm, &lm, spss_am(b) ? &sp : nullptr);
+		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, b->ctx->stream, &maps, spss_am(b) ? &sp : nullptr);
 	}
 	b->it_valid = fa.materialize;
 	b->dit_valid = fa.materialize && fa.mode != 2;

@@ -7,8 +7,7 @@
 
 int spss_refuse(const mtfhip_batch *b, const char *fn, const char *what) {
 	if (!b || !spss_am(b)) return MTFHIP_OK;
-	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SPSS%s (served: the first-order per-function AppearanceModel entry points and init_template / set_region / "
-		"iterate / track / track_region with ESM, FCLK and ICLK)", fn, what);
+	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SPSS%s" MTFHIP_FIRST_ORDER_SERVED, fn, what);
 }
 
 /* the weight of the Gram matrix the pass accumulates and the row of its current Jacobian, by search method and Hessian type (NT/FCLK.cc:262-283,

@@ -9,8 +9,7 @@
 
 int ssim_refuse(const mtfhip_batch *b, const char *fn, const char *what) {
 	if (!b || !ssim_am(b)) return MTFHIP_OK;
-	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SSIM%s (served: the first-order per-function AppearanceModel entry points and init_template / set_region / "
-		"iterate / track / track_region with ESM, FCLK and ICLK)", fn, what);
+	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SSIM%s" MTFHIP_FIRST_ORDER_SERVED, fn, what);
 }
 
 /* cmptSelfHessian(J0) at It = I0 (SSIM.cc:270-287; NT/ESM.cc:133-141, NT/FCLK.cc:120-128, NT/ICLK.cc:96-118) from th[].ncc_tm, column-major S x S */

@@ -226,7 +226,7 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 /* LSCV / LRSCV: update() sets first_iter in front of its loop and every completed iteration clears it (NT/ESM.cc:178, :291): the device
  * loop maps in front of its first pass (track_core) and leaves the batch's flag clear */
 static int lscv_after_track(mtfhip_batch *b, int rc) {
-	if (rc == MTFHIP_OK && b && (b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV)) b->lscv_first_iter = 0;
+	if (rc == MTFHIP_OK && b && imap_localized(b)) b->first_iter = 0;
 	return rc;
 }
 int mtfhip_batch_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners) {
@@ -313,7 +313,7 @@ int track_validate(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "track before init_template");
 	/* (a rejected Levenberg-Marquardt step of FCLK repeats a pass within one iteration of its while loop: the passes do not tell which
 	 * iteration is the first) */
-	if ((b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV) && b->lscv_once && sm->leven_marq && sm->sm == MTFHIP_SM_FCLK)
+	if (imap_localized(b) && b->imap.once && sm->leven_marq && sm->sm == MTFHIP_SM_FCLK)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "track: %s once_per_frame with Levenberg-Marquardt FCLK is not available on the device loop (use the per-function entry points)",
 			intensity_mapped_name(b));
 	return need_image(b);
@@ -417,7 +417,7 @@ static void track_materialise_stopped(mtfhip_batch *b, const ChunkRun &r) {
 	FusedArgs fm = r.fc;
 	fm.active = r.tc.need_mat;
 	TimedScope tsc(b->ctx, "fused_lk", r.s);
-	launch_fused_ssd(bm, b->ctx->img, fm, r.part, r.nblk_c, r.s, nullptr, nullptr);
+	launch_fused_ssd(bm, b->ctx->img, fm, r.part, r.nblk_c, r.s);
 }
 /* the extra queues of the loop and the phase stamps that keep two of them apart (PhaseCtl); what cannot be created leaves one queue.
  * MTFHIP_TRACK_PHASE: the fraction of a period the queues are kept apart; 0 = no control */
@@ -470,19 +470,13 @@ static int track_chunk_pass(mtfhip_batch *b, const mtfhip_sm_desc *sm, const Fus
 		launch_track_step(r.bc, b->ctx->img, r.fc, *sm, r.tc, r.part, r.nblk_c, b->d_persist + r.t0, r.s);
 		return MTFHIP_OK;
 	}
-	if (b->desc.am == MTFHIP_AM_SCV) TRY(scv_enqueue(b, r.bc, r.t0, r.fc.active, 0, r.s));   /* (the chunk's template re-map) */
-	/* (LSCV: the chunk's localized re-map -- with once_per_frame in front of the first pass only, LSCV.cc:264-265) */
-	if (b->desc.am == MTFHIP_AM_LSCV && (!b->lscv_once || it == 0)) TRY(lscv_enqueue(b, r.bc, r.t0, r.fc.active, 0, r.s));
-	RscvMap rm;
-	if (b->desc.am == MTFHIP_AM_RSCV) TRY(rscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &rm));   /* (the chunk's current maps) */
-	/* (LRSCV: the chunk's sub-region maps -- with once_per_frame in front of the first pass only, LRSCV.cc:234-235; the later
-	 * passes are SSD passes on the raw patch) */
-	LrscvMap lm;
-	if (b->desc.am == MTFHIP_AM_LRSCV && (!b->lscv_once || it == 0)) TRY(lrscv_enqueue(b, r.bc, r.t0, r.fc.active, r.fc, r.s, &lm));
+	/* (the SCV family: the chunk's template re-map or current maps -- the loop's first pass is the frame's first iteration) */
+	FusedMaps maps;
+	TRY(imap_before_pass(b, &r.bc, r.t0, r.fc.active, &r.fc, 0, it == 0, r.s, &maps));
 	{
 		TimedScope tsc(b->ctx, "fused_lk", r.s);
 		const SpssArgs sp = spss_am(b) ? spss_args(b, sm) : SpssArgs{};
-		launch_fused_ssd(r.bc, b->ctx->img, lean ? r.fl : r.fc, r.part, r.nblk_c, r.s, &rm, &lm, spss_am(b) ? &sp : nullptr);
+		launch_fused_ssd(r.bc, b->ctx->img, lean ? r.fl : r.fc, r.part, r.nblk_c, r.s, &maps, spss_am(b) ? &sp : nullptr);
 	}
 	if (cx.so_term >= 0) {
 		TimedScope tsc(b->ctx, "second_order", r.s);

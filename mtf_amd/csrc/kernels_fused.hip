@@ -68,14 +68,14 @@ __global__ __launch_bounds__(64) void k_finish_track_mi(BatchView bv, mtfhip_sm_
 
 /* the unit's instantiations and the one of a launch: fused_select / fused_visit (mtfhip_fused_dispatch.h) */
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk,
-	hipStream_t st, const RscvMap *rm, const LrscvMap *lm, const SpssArgs *sp) {
+	hipStream_t st, const FusedMaps *maps, const SpssArgs *sp) {
 	/* (the API enqueues pass 1 of RSCV / LRSCV in front and hands its maps over.  RSCV: no map, no launch; LRSCV without one -- a later
 	 * pass of a frame under once_per_frame -- is an SSD pass on the raw patch, LRSCV.cc:234-235) */
-	const bool mapped = bv.am == MTFHIP_AM_RSCV ? (rm && rm->map) : (bv.am == MTFHIP_AM_LRSCV && lm && lm->map);
+	const bool mapped = bv.am == MTFHIP_AM_RSCV ? (maps && maps->rm.map) : (bv.am == MTFHIP_AM_LRSCV && maps && maps->lm.map);
 	const FusedKey k = fused_select(FUSED_ROUTE_LOOP, bv.am, bv.C, bv.ssm, fa.mode, fa.chained, fa.materialize, fa.fast_math, mapped);
 	if (!k.served) return;
-	if (k.am == MTFHIP_AM_RSCV) { launch_fused_rscv(bv, im, fa, partials, nblk, *rm, st); return; }
-	if (k.am == MTFHIP_AM_LRSCV) { launch_fused_lrscv(bv, im, fa, partials, nblk, *lm, st); return; }
+	if (k.am == MTFHIP_AM_RSCV) { launch_fused_rscv(bv, im, fa, partials, nblk, maps->rm, st); return; }
+	if (k.am == MTFHIP_AM_LRSCV) { launch_fused_lrscv(bv, im, fa, partials, nblk, maps->lm, st); return; }
 	if (k.am == MTFHIP_AM_SPSS) {   /* (the API hands its constant and what the search method reads: a launch without them is an error) */
 		if (sp) launch_fused_spss(bv, im, fa, partials, nblk, *sp, st);
 		else note_launch_error(hipErrorInvalidValue, __FILE__, __LINE__);

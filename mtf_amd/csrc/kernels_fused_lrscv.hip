@@ -21,7 +21,7 @@ __global__ __launch_bounds__(kBlock, MTFHIP_FAST_WAVES) void k_fused_lrscv_fast(
 	fused_lk_body<MTFHIP_AM_LRSCV, SSM, CHAINED, MODE, false, true>(bv, im, fa, partials, nblk, RscvMap{}, lm);
 }
 
-/* the maps live in the dynamic LDS: R nb doubles, or 2 R with affine_mapping (api_lrscv.hip keeps them within 64 KB less the kernel's
+/* the maps live in the dynamic LDS: R nb doubles, or 2 R with affine_mapping (api_imap.hip keeps them within 64 KB less the kernel's
  * static arrays) */
 static size_t lrscv_lds(const LrscvMap &lm) { return sizeof(double) * (size_t)(lm.affine ? 2 * lm.R : lm.R * lm.nb); }
 void launch_fused_lrscv(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const LrscvMap &lm,

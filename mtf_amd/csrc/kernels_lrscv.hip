@@ -15,7 +15,7 @@
  *                         Reads 16 B/px (grid point) + 4 texels + 1 B/px (RSCV's code plane) + 2 B/px (the cell plane, one per batch).
  *   k_lrscv_apply         It = lrscv_blend(It_orig) (per-function path)
  *
- * Reproducibility.  Every sum is an integer, exact in any order (u32: lrscv_capture refuses patches where (n_bins - 1) N could overflow
+ * Reproducibility.  Every sum is an integer, exact in any order (u32: imap_capture refuses patches where (n_bins - 1) N could overflow
  * one), and stays exact as a double; the maps are identical run to run.  Bin agreement: as kernels_rscv.hip's.
  */
 #include "mtfhip_rscv_device.h"
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void k_lrscv_apply(int N, LrscvMap lm, cons
 
 template <int SSM>
 static void launch_lrscv_hist_ssm(const BatchView &bv, const ImgView &im, const LrscvArgs &a, hipStream_t st) {
-	const int nblk = lscv_hist_blocks(bv.N);
+	const int nblk = imap_hist_blocks(bv.N, kImapChunksLocal);
 	const dim3 g = grid2(nblk, bv.B);
 	const size_t lds = sizeof(unsigned) * 2 * (size_t)a.ncell * a.nb;
 	switch (a.kind) {

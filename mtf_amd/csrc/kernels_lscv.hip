@@ -18,7 +18,7 @@
  *                         reference's order and rounding.  Nearest reads the code plane (2 B/px), linear and affine I0_orig (8 B/px);
  *                         the weights are one [n_sub][N] table per batch (8 n_sub B/px, shared by the batch's targets); 8 B/px out.
  *
- * Reproducibility.  Every histogram sum is an integer, exact in any order (u32: lscv_capture refuses patches where (n_bins - 1) N could
+ * Reproducibility.  Every histogram sum is an integer, exact in any order (u32: imap_capture refuses patches where (n_bins - 1) N could
  * overflow one), and stays exact as a double, so the maps are identical run to run and equal to the float64 reference's.  The affine
  * fit sums in a fixed order (lane l takes k = l, l + 64, ..., in order; then a xor butterfly, whose every step adds the same two values
  * on both lanes).  Indices are clamped to [0, n_bins - 1], as in kernels_scv.hip.
@@ -125,14 +125,8 @@ __global__ __launch_bounds__(kBlock) void k_lscv_remap(int N, LscvArgs a, double
 	}
 }
 
-int lscv_hist_blocks(int N) {
-	/* sixteen 256-pixel chunks per workgroup (a workgroup zeroes and scans its whole (cell, bin) table), at most 64 per target */
-	const int chunks = (N + kBlock - 1) / kBlock;
-	int nblk = (chunks + 15) / 16;
-	return nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
-}
 void launch_lscv_update(const BatchView &bv, const ImgView &im, const LscvArgs &a, double *I0, hipStream_t st) {
-	const int nblk = lscv_hist_blocks(bv.N);
+	const int nblk = imap_hist_blocks(bv.N, kImapChunksLocal);
 	const size_t lds_hist = sizeof(unsigned) * 2 * (size_t)a.ncell * a.nb;
 	if (bv.ssm == MTFHIP_SSM_HOMOGRAPHY) MTFHIP_LAUNCH(k_lscv_hist<MTFHIP_SSM_HOMOGRAPHY>, grid2(nblk, bv.B), dim3(kBlock), lds_hist, st, bv, im, a, nblk);
 	else MTFHIP_LAUNCH(k_lscv_hist<MTFHIP_SSM_AFFINE>, grid2(nblk, bv.B), dim3(kBlock), lds_hist, st, bv, im, a, nblk);

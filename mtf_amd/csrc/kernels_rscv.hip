@@ -113,18 +113,12 @@ __global__ __launch_bounds__(kBlock) void k_rscv_apply(int N, int nb, int linear
 	for (int i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) out[i] = rscv_map_val(s_map, nb, linear, x[i]);
 }
 
-int rscv_hist_blocks(int N) {
-	/* eight 256-pixel chunks per workgroup, at most 64 workgroups per target (the last-arriving one sums their rows) */
-	const int chunks = (N + kBlock - 1) / kBlock;
-	int nblk = (chunks + 7) / 8;
-	return nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
-}
 void launch_rscv_codes(int N, int B, int nb, const double *i0, unsigned char *code, hipStream_t st) {
 	MTFHIP_LAUNCH(k_rscv_codes, grid2(simple_blocks_per_target(N), B), dim3(kBlock), 0, st, N, nb, i0, code);
 }
 template <int SSM>
 static void launch_rscv_hist_ssm(const BatchView &bv, const ImgView &im, const RscvArgs &a, hipStream_t st) {
-	const int nblk = rscv_hist_blocks(bv.N);
+	const int nblk = imap_hist_blocks(bv.N, kImapChunks);
 	const dim3 g = grid2(nblk, bv.B);
 	switch (a.kind) {
 	case RSCV_IT_REPLAY: MTFHIP_LAUNCH((k_rscv_hist<SSM, RSCV_IT_REPLAY>), g, dim3(kBlock), 0, st, bv, im, a, nblk); break;

@@ -178,17 +178,11 @@ __global__ __launch_bounds__(kBlock) void k_scv_remap(int N, int nb, int linear,
 	}
 }
 
-int scv_hist_blocks(int N) {
-	/* eight 256-pixel chunks per workgroup, at most 64 workgroups per target (the map kernel sums their rows in order) */
-	const int chunks = (N + kBlock - 1) / kBlock;
-	int nblk = (chunks + 7) / 8;
-	return nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
-}
 void launch_scv_codes(int N, int B, int nb, const double *i0o, unsigned short *code, hipStream_t st) {
 	MTFHIP_LAUNCH(k_scv_codes, grid2(simple_blocks_per_target(N), B), dim3(kBlock), 0, st, N, nb, i0o, code);
 }
 void launch_scv_update(const BatchView &bv, const ImgView &im, const ScvArgs &a, double *part, double *map, double *I0, hipStream_t st) {
-	const int nblk = scv_hist_blocks(bv.N);
+	const int nblk = imap_hist_blocks(bv.N, kImapChunks);
 	if (bv.ssm == MTFHIP_SSM_HOMOGRAPHY) MTFHIP_LAUNCH(k_scv_hist<MTFHIP_SSM_HOMOGRAPHY>, grid2(nblk, bv.B), dim3(kBlock), 0, st, bv, im, a, part, nblk);
 	else MTFHIP_LAUNCH(k_scv_hist<MTFHIP_SSM_AFFINE>, grid2(nblk, bv.B), dim3(kBlock), 0, st, bv, im, a, part, nblk);
 	MTFHIP_LAUNCH(k_scv_map, dim3(bv.B), dim3(kBlock), 0, st, a.nb, a.active, (const double *)part, nblk, map);

@@ -233,6 +233,73 @@ struct TargetHost {
 	double ncc_tm[NCC_TM_COUNT];
 };
 
+/* What is decided by the appearance model alone, stated once per model (indexed by MTFHIP_AM_*).  rows: whose partial / reduced rows the
+ * model's fused passes fill.  max_bins: the limit of mtfhip_patch_desc::mi_n_bins where the model reads it (0: it does not), bins_default:
+ * n_bins <= 0 selects max_bins.  The three texts are the model's refusals, NULL where it is served: n_channels 3 at batch_create,
+ * mtfhip_am_update_model, and the reason it has no per-candidate form (candidates, particle filter, NN dataset). */
+#define MTFHIP_FIRST_ORDER_SERVED " (served: the first-order per-function AppearanceModel entry points and init_template / set_region / " \
+	"iterate / track / track_region with ESM, FCLK and ICLK)"
+enum { AM_ROWS_SSD, AM_ROWS_NCC, AM_ROWS_MI, AM_ROWS_SPSS };
+struct AmTraits {
+	const char *name;
+	int rows;
+	bool intensity_mapped;
+	int max_bins;
+	bool bins_default;
+	const char *no_3ch, *no_update_model, *no_candidates;
+};
+constexpr AmTraits kAmTraits[] = {
+	{"SSD", AM_ROWS_SSD, false, 0, false, nullptr, nullptr, nullptr},
+	{"NCC", AM_ROWS_NCC, false, 0, false, nullptr, nullptr, nullptr},
+	{"MI", AM_ROWS_MI, false, MI_NB, false, nullptr, "updateModel :: MI has no online template update in the reference either", nullptr},
+	{"SCV", AM_ROWS_SSD, true, kScvMaxBins, true, "SCV with n_channels 3 (MCSCV) is not available on the device path (single channel only)",
+		"updateModel :: SCV is not available on this entry point (the template update would have to refresh I0_orig)",
+		"SCVDist is a per-candidate intensity map"},
+	{"RSCV", AM_ROWS_SSD, true, kRscvMaxBins, true, "RSCV with n_channels 3 (MCRSCV) is not available on the device path (single channel only)",
+		"updateModel :: RSCV is not available on this entry point (the template update would have to refresh its code plane)",
+		"RSCVDist is a per-candidate intensity map"},
+	{"LSCV", AM_ROWS_SSD, true, kLscvMaxBins, true, "LSCV with n_channels 3 (MCLSCV) is not available on the device path (single channel only)",
+		"updateModel :: LSCV is not available on this entry point (the template update would have to refresh I0_orig)",
+		"LSCVDist is a per-candidate intensity map"},
+	{"LRSCV", AM_ROWS_SSD, true, kLscvMaxBins, true, "LRSCV with n_channels 3 is not available (no multi-channel LRSCV exists in the reference either)",
+		"updateModel :: LRSCV is not available on this entry point (the template update would have to refresh its code plane)",
+		"its maps are per-candidate intensity maps"},
+	{"SPSS", AM_ROWS_SPSS, false, 0, false, "SPSS with n_channels 3 (MCSPSS) is not available on the device path (single channel only)",
+		"updateModel: SPSS has no online template update on the device path" MTFHIP_FIRST_ORDER_SERVED, nullptr},
+	{"SSIM", AM_ROWS_NCC, false, 0, false, "SSIM with n_channels 3 (MCSSIM) is not available on the device path (single channel only)",
+		"updateModel: SSIM has no online template update (SSIM.cc has none either)" MTFHIP_FIRST_ORDER_SERVED, nullptr},
+};
+static_assert(sizeof(kAmTraits) / sizeof(kAmTraits[0]) == MTFHIP_AM_SSIM + 1, "one row of traits per MTFHIP_AM_*");
+static inline const AmTraits &am_traits(int am) { return kAmTraits[am]; }   /* (am: a batch's, checked by mtfhip_batch_create) */
+
+/* The SCV family (SCV, RSCV, LSCV, LRSCV: SSD behind an intensity map) keeps ONE state: a batch has one appearance model for life.  SCV and
+ * LSCV re-map the template (I0 = map(I0_orig)) in front of a similarity update; the reversed models RSCV and LRSCV map the current patch; the
+ * localized models LSCV and LRSCV keep one map per overlapping sub-region and blend them per pixel (api_imap.hip). */
+struct IntensityMapState {
+	/* *Params: n_bins, weighted_mapping, SCV's hist_type and mapped_gradient; the localized models' n_sub_regions_x / _y, spacing_x / _y,
+	 * affine_mapping, once_per_frame; the cell columns and cells their geometry has */
+	int nb = 0, linear = 0, hist = 0, mapped_grad = 0;
+	int nx = 3, ny = 3, sx = 10, sy = 10, affine = 0, once = 0;
+	int ncx = 0, ncell = 0;
+	Dev<double> orig;             /* [B][N] I0_orig (SCV, LSCV); It_orig of the per-function route (RSCV, LRSCV) */
+	/* the template's code plane [B][N], one per kernel family: (int)I0_orig | (int)rint(I0_orig) << 8 (SCV, LSCV), (int)I0 (RSCV, LRSCV).
+	 * It ARRIVES LAST at initializePixVals and is what everything takes for "captured": while it is null a failed call is simply repeated,
+	 * and what belongs to the first call runs once the whole group is there */
+	Dev<unsigned short> code16;
+	Dev<unsigned char> code8;
+	Dev<double> part_f;           /* [B][imap_hist_blocks][2 nb] pass-1 rows (SCV) */
+	Dev<unsigned> part_u;         /* ... (RSCV) */
+	Dev<unsigned> arrive;         /* [B] arrival counters (RSCV, LSCV, LRSCV) */
+	Dev<double> map, aff;         /* [B][R][nb] the intensity maps, [B][R][2] the affine fits (localized; R = nx ny, else 1) */
+	/* the sub-region geometry, one copy per batch: the cell plane [N] -- it arrives last of these and is what set_lscv / set_lrscv take for
+	 * "the geometry is fixed" --, the cells of each sub-region [2 nx + 2 ny], the weights [R][N]; and the per-target sums [B][2][ncell nb] */
+	Dev<unsigned short> cell;
+	Dev<int> crng;
+	Dev<double> w;
+	Dev<unsigned> tot;
+	bool captured() const { return code16 || code8; }
+};
+
 struct mtfhip_batch;
 static int push_warps(mtfhip_batch *b);
 struct mtfhip_batch {
@@ -292,33 +359,12 @@ struct mtfhip_batch {
 	int d0_variant = MTFHIP_JAC_WARPED; /* how the template's pixel Hessian was formed (fused second-order path) */
 	int mi_row_len = 0;
 	double mi_hist_norm = 0;
-	/* SCV (am = MTFHIP_AM_SCV): SCVParams hist_type / weighted_mapping / mapped_gradient, n_bins; the original template (I0_orig, the
-	 * normalised samples of initializePixVals) and its code plane, pass-1 rows and the intensity maps (kernels_scv.hip) */
-	int scv_hist = 0, scv_linear = 0, scv_mapped_grad = 0, scv_nb = 0;
-	Dev<double> d_scv_i0, d_scv_part, d_scv_map;
-	Dev<unsigned short> d_scv_code;
+	IntensityMapState imap;   /* SCV, RSCV, LSCV, LRSCV: the model's own state (api_imap.hip) */
+	int first_iter = 0;       /* AppearanceModel::first_iter (mtfhip_batch_set_first_iter; the localized models' once_per_frame reads it) */
 	/* SPSS (am = MTFHIP_AM_SPSS): SPSSParams k and c = (k (PIX_MAX - PIX_MIN))^2 (SPSS.cc:37-38) */
 	double spss_k = 0.01, spss_c = (0.01 * 255.0) * (0.01 * 255.0);
 	/* SSIM (am = MTFHIP_AM_SSIM): SSIMParams k1, k2 and c1 = (k1 (PIX_MAX - PIX_MIN))^2, c2 likewise (SSIM.cc:36-39) */
 	double ssim_k1 = 0.01, ssim_k2 = 0.03, ssim_c1 = (0.01 * 255.0) * (0.01 * 255.0), ssim_c2 = (0.03 * 255.0) * (0.03 * 255.0);
-	/* RSCV (am = MTFHIP_AM_RSCV): RSCVParams weighted_mapping, n_bins; the template's code plane ((int)I0), pass-1 rows and arrival
-	 * counters, the intensity maps, and It_orig of the per-function route (kernels_rscv.hip) */
-	int rscv_linear = 0, rscv_nb = 0;
-	Dev<unsigned char> d_rscv_code;
-	Dev<unsigned> d_rscv_part, d_rscv_arrive;
-	Dev<double> d_rscv_map, d_rscv_it;
-	/* (LRSCV, am = MTFHIP_AM_LRSCV, uses RSCV's code plane and It_orig buffer, and LSCV's configuration, first-iteration flag, geometry,
-	 * sums, arrival counters, maps and affine parameters: api_lrscv.hip) */
-	/* LSCV (am = MTFHIP_AM_LSCV): LSCVParams n_sub_regions_x / _y, spacing_x / _y, affine_mapping, once_per_frame, weighted_mapping,
-	 * n_bins; AppearanceModel::first_iter (one per batch); I0_orig and its code plane; the sub-region geometry (the cell plane, the cells of
-	 * each sub-region, the weights: one copy per batch); the per-target sums and arrival counters, the maps and the affine parameters
-	 * (kernels_lscv.hip) */
-	int lscv_nx = 3, lscv_ny = 3, lscv_sx = 10, lscv_sy = 10, lscv_affine = 0, lscv_once = 0, lscv_linear = 0, lscv_nb = 0;
-	int lscv_first_iter = 0, lscv_ncx = 0, lscv_ncell = 0;
-	Dev<double> d_lscv_i0, d_lscv_w, d_lscv_map, d_lscv_aff;
-	Dev<unsigned short> d_lscv_code, d_lscv_cell;
-	Dev<int> d_lscv_crng;
-	Dev<unsigned> d_lscv_tot, d_lscv_arrive;
 	Dev<double> d_cand_mi;   /* MI candidate scoring: histogram rows per candidate */
 	int *d_active = nullptr, *d_iters = nullptr;   /* views into d_slab */
 	/* The small per-target state lives in ONE device allocation (warps | states | corners | init_corners_hm | ncc | w0 |
@@ -547,19 +593,15 @@ static int push_warps(mtfhip_batch *b) {
 /* the BatchView of a fused launch: a stale single-target warp goes into the kernel arguments instead of being uploaded */
 /* SCV and LSCV are SSD on a re-mapped template, RSCV and LRSCV SSD on a mapped current patch: every SSD branch of the entry points serves
  * them */
-static inline bool ssd_like(const mtfhip_batch *b) {
-	return b->desc.am == MTFHIP_AM_SSD || b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV ||
-		b->desc.am == MTFHIP_AM_LRSCV;
-}
+static inline bool ssd_like(const mtfhip_batch *b) { return am_traits(b->desc.am).rows == AM_ROWS_SSD; }
 /* SCV, RSCV, LSCV and LRSCV: an intensity map is rebuilt between the fused passes -- the one-launch, persistent and step loops do not take
  * them (fused_select, mtfhip_fused_dispatch.h) */
-static inline bool intensity_mapped(const mtfhip_batch *b) {
-	return b->desc.am == MTFHIP_AM_SCV || b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV;
-}
+static inline bool intensity_mapped(const mtfhip_batch *b) { return am_traits(b->desc.am).intensity_mapped; }
 /* the name of an intensity-mapped model, for the refusals */
-static inline const char *intensity_mapped_name(const mtfhip_batch *b) {
-	return b->desc.am == MTFHIP_AM_SCV ? "SCV" : (b->desc.am == MTFHIP_AM_RSCV ? "RSCV" : (b->desc.am == MTFHIP_AM_LSCV ? "LSCV" : "LRSCV"));
-}
+static inline const char *intensity_mapped_name(const mtfhip_batch *b) { return am_traits(b->desc.am).name; }
+/* ... the localized ones (sub-regions, once_per_frame) and the reversed ones (the map is of the current patch) among them */
+static inline bool imap_localized(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV; }
+static inline bool imap_reversed(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LRSCV; }
 /* SPSS: a model of its own -- no SSD branch serves it, and of the fused routes only the two-launch loop does (fused_select) */
 static inline bool spss_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SPSS; }
 /* api_spss.hip.  spss_refuse: "<fn>: SPSS<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for an SPSS batch, MTFHIP_OK otherwise; spss_args: what a fused
@@ -575,7 +617,7 @@ static inline bool ssim_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_
 /* THE predicate of "this batch's fused passes reduce NCC's rows": the 72-wide partial / reduced row, the template moments th[].ncc_tm and their
  * upload d_ncc_tm, the per-target scalars d_ncc and their refresh.  (What solves NCC's own system -- the one-launch, step and persistent
  * kernels, the fused template initialisation, the second-order pass, the deferred-fusion layer -- asks for MTFHIP_AM_NCC by name.) */
-static inline bool ncc_rows(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_NCC || ssim_am(b); }
+static inline bool ncc_rows(const mtfhip_batch *b) { return am_traits(b->desc.am).rows == AM_ROWS_NCC; }
 /* api_ssim.hip.  ssim_refuse: "<fn>: SSIM<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for an SSIM batch, MTFHIP_OK otherwise; ssim_h0: the constant self
  * Hessian from the template's moments (th[].ncc_tm must be current); the per-function updateSimilarity, update*Grad and Hessians (kind: NCC_H_*) */
 int ssim_refuse(const mtfhip_batch *b, const char *fn, const char *what);
@@ -590,36 +632,20 @@ static inline mtfhip::SsimSys ssim_host_sys(const mtfhip_batch *b, const TargetH
 static inline void ssim_refresh_mirrors(TargetHost &h, const mtfhip::SsimSys &q, const double *M) {
 	h.It_mean = q.mt; h.it_ss = M[mtfhip::NCC_IT2] - q.N * q.mt * q.mt; h.a = M[mtfhip::NCC_I0IT] - q.N * q.m0 * q.mt; h.f = q.f;
 }
-/* api_scv.hip: I0_orig <- I0 (initializePixVals); the re-map of I0 in front of an SSD similarity update, for the targets [t0, t0 + bv.B) */
-int scv_capture(mtfhip_batch *b);
-int scv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
-/* the configurations SCV and RSCV refuse on the device path, for the entry point fn */
+/* api_imap.hip, the SCV family's hooks; each does nothing for a model outside the family.
+ * imap_capture (initializePixVals): the template's code plane, I0_orig / It_orig, the identity maps, the localized models' geometry.
+ * imap_before_pass: what the model runs in front of a pixel pass over the targets [t0, t0 + chunk->B) (chunk NULL: the whole batch) on st -- SCV / LSCV re-map I0 (from_it 1:
+ * from MTFHIP_BUF_IT, the per-function route; 0: sampled at the current warp); with fa, the fused launch that follows, RSCV / LRSCV run pass 1
+ * + the maps and hand what that launch applies to *out (without fa they have nothing to do: their updatePixVals has mapped It).
+ * first_pass: the localized models under once_per_frame map in front of the first pass of a frame only.
+ * imap_update_pix_vals: the per-function updatePixVals of RSCV / LRSCV, IMAP_NOT_MINE for every other model */
+enum { IMAP_NOT_MINE = 1 };
+int imap_capture(mtfhip_batch *b);
+int imap_before_pass(mtfhip_batch *b, const BatchView *chunk, int t0, const int *active, const FusedArgs *fa, int from_it, bool first_pass,
+	hipStream_t st, FusedMaps *out);
+int imap_update_pix_vals(mtfhip_batch *b, const double *dp);
+/* the configurations the family refuses on the device path, for the entry point fn */
 int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess);
-/* api_rscv.hip: the code plane and the identity map (initializePixVals); pass 1 + the map in front of the fused launch fa for the targets
- * [t0, t0 + bv.B), and the map that launch applies (rm); the per-function updatePixVals (It_orig, the map, It = map(It_orig)) */
-int rscv_capture(mtfhip_batch *b);
-int rscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, const FusedArgs &fa, hipStream_t st, RscvMap *rm);
-int rscv_update_pix_vals(mtfhip_batch *b, const double *dp);
-/* the It_orig expression (RSCV_IT_*) of the fused launch fa selects; RSCV_IT_FROM_BUF without one (the per-function route) */
-int rscv_it_kind(const FusedArgs *fa);
-/* api_lscv.hip: I0_orig, its code plane and the sub-region geometry (initializePixVals); the localized re-map of I0 in front of an SSD
- * similarity update, for the targets [t0, t0 + bv.B) */
-int lscv_capture(mtfhip_batch *b);
-int lscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st);
-/* LSCV.cc:264-265: with once_per_frame the re-map runs only on the first iteration of a frame */
-static inline bool lscv_due(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_LSCV && !(b->lscv_once && !b->lscv_first_iter); }
-/* the sub-region geometry shared by LSCV and LRSCV: the reference's size refusal (fn: the entry point), and at initializePixVals the cell
- * plane, the cells of each sub-region, the weights, the sums, the identity maps -- refused when the pass-1 table or the maps
- * (map_lds_budget) exceed their LDS */
-int lscv_check_geometry(const mtfhip_batch *b, int nx, int ny, int sx, int sy, const char *fn);
-int lscv_geometry(mtfhip_batch *b, size_t map_lds_budget);
-/* api_lrscv.hip: the code plane, It_orig and the geometry (initializePixVals); pass 1 + the maps in front of the fused launch fa for the
- * targets [t0, t0 + bv.B), and the blend that launch applies (lm); the per-function updatePixVals (It, or the blend of It_orig) */
-int lrscv_capture(mtfhip_batch *b);
-int lrscv_enqueue(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, const FusedArgs &fa, hipStream_t st, LrscvMap *lm);
-int lrscv_update_pix_vals(mtfhip_batch *b, const double *dp);
-/* LRSCV.cc:234-235: with once_per_frame the current patch is mapped only on the first iteration of a frame */
-static inline bool lrscv_due(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_LRSCV && !(b->lscv_once && !b->lscv_first_iter); }
 static inline BatchView fused_view(mtfhip_batch *b, FusedArgs &fa) {
 	fa.inline_warp = 0;
 	if (b->warps_dirty && b->B == 1) {

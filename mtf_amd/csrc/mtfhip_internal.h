@@ -344,6 +344,11 @@ struct LrscvMap {
 	const double *wts = nullptr;
 	int nb = 0, R = 0, affine = 0, linear = 0;
 };
+/* what the pass in front of a fused launch hands it (imap_before_pass): the maps of the batch's model, or none */
+struct FusedMaps {
+	RscvMap rm;
+	LrscvMap lm;
+};
 
 /* SPSS (am = MTFHIP_AM_SPSS): what the fused pass needs beside FusedArgs, an extra argument behind the fused kernels' own -- c = (255 k)^2
  * (SPSS.cc:37-38); weight: the per-pixel weight of the Gram matrix in ACC_H (SPSS_W_*: cmptSelfHessian SPSS.cc:221-225, cmptCurrHessian
@@ -534,7 +539,7 @@ void launch_publish_host(const void *src, void *dst_host, size_t bytes, int *cou
 /* the fused LK iteration for SSD (and RSCV: bv.am == MTFHIP_AM_RSCV takes the RSCV instantiations, which need rm; LRSCV: with lm and its
  * maps the LRSCV instantiations, without them -- a later pass of a frame under once_per_frame -- the SSD ones on the raw patch) */
 void launch_fused_ssd(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials,
-	int nblk, hipStream_t st, const RscvMap *rm = nullptr, const LrscvMap *lm = nullptr, const SpssArgs *sp = nullptr);
+	int nblk, hipStream_t st, const FusedMaps *maps = nullptr, const SpssArgs *sp = nullptr);
 /* kernels_fused_spss.hip: the SPSS instantiations of the fused body (replay and tolerance mode); and the finish that reads their rows,
  * k_finish_track_spss (launch_finish_track takes it for bv.am == MTFHIP_AM_SPSS) */
 void launch_fused_spss(const BatchView &bv, const ImgView &im, const FusedArgs &fa, double *partials, int nblk, const SpssArgs &sp,
@@ -690,6 +695,14 @@ void launch_alk_pass(const BatchView &bv, const ImgView &im, const AlkArgs &a, d
 /* row sums, g and H by sm.hess_type (sm.sm = MTFHIP_SM_FCLK: the row's type), Levenberg-Marquardt, solve, additiveUpdate, convergence test */
 void launch_alk_finish(const BatchView &bv, const mtfhip_sm_desc &sm, const TrackState &ts, const double *partials, int nblk, hipStream_t st);
 
+/* ---- the SCV family's pass 1: workgroups per target, `chunks` 256-pixel chunks each, at most 64 (their rows are summed in order) ---- */
+constexpr int kImapChunks = 8;         /* SCV, RSCV */
+constexpr int kImapChunksLocal = 16;   /* LSCV, LRSCV: a workgroup zeroes and scans its whole (cell, bin) table */
+inline int imap_hist_blocks(int N, int chunks) {
+	const int nblk = ((N + kBlock - 1) / kBlock + chunks - 1) / chunks;
+	return nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
+}
+
 /* ---- SCV: the template re-map of SCV::updateSimilarity (kernels_scv.hip) ---- */
 constexpr int kScvMaxBins = 256;
 struct ScvArgs {
@@ -700,9 +713,8 @@ struct ScvArgs {
 	const double *i0o;           /* [B][N] I0_orig */
 	const int *active;           /* optional [B] mask (device-side loop) */
 };
-int scv_hist_blocks(int N);
 void launch_scv_codes(int N, int B, int nb, const double *i0o, unsigned short *code, hipStream_t st);
-/* pass 1 + map + re-map; part: [B][scv_hist_blocks(N)][2 nb], map: [B][nb], I0: MTFHIP_BUF_I0 (all offset to bv's first target) */
+/* pass 1 + map + re-map; part: [B][imap_hist_blocks(N, kImapChunks)][2 nb], map: [B][nb], I0: MTFHIP_BUF_I0 (all offset to bv's first target) */
 void launch_scv_update(const BatchView &bv, const ImgView &im, const ScvArgs &a, double *part, double *map, double *I0, hipStream_t st);
 
 /* ---- RSCV: the current patch's intensity map of RSCV::updatePixVals (kernels_rscv.hip) ---- */
@@ -714,11 +726,10 @@ struct RscvArgs {
 	const unsigned char *code;   /* [B][N] (int)I0, clamped to [0, nb - 1] */
 	const double *it_orig;       /* [B][N] (RSCV_IT_FROM_BUF) */
 	const int *active;           /* optional [B] mask (device-side loop) */
-	unsigned *part;              /* [B][rscv_hist_blocks(N)][2 nb] per-workgroup sums */
+	unsigned *part;              /* [B][imap_hist_blocks(N, kImapChunks)][2 nb] per-workgroup sums */
 	unsigned *arrive;            /* [B] arrival counters (0 between launches) */
 	double *map;                 /* [B][nb] */
 };
-int rscv_hist_blocks(int N);
 void launch_rscv_codes(int N, int B, int nb, const double *i0, unsigned char *code, hipStream_t st);
 /* pass 1 and the map (its last-arriving workgroup per target); all pointers of a offset to bv's first target */
 void launch_rscv_hist(const BatchView &bv, const ImgView &im, const RscvArgs &a, hipStream_t st);
@@ -746,7 +757,6 @@ struct LscvArgs {
 	double *map;                 /* [B][nx ny][nb] */
 	double *aff;                 /* [B][nx ny][2] (affine_mapping) */
 };
-int lscv_hist_blocks(int N);
 /* pass 1 and the maps (its last-arriving workgroup per target), then the re-map of I0; all per-target pointers offset to bv's first target */
 void launch_lscv_update(const BatchView &bv, const ImgView &im, const LscvArgs &a, double *I0, hipStream_t st);
 

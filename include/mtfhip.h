@@ -78,7 +78,27 @@ typedef enum mtfhip_status {
  * two-launch loop.  Everything else returns MTFHIP_ERR_NOT_IMPLEMENTED with its reason in mtfhip_last_error(): n_channels 3 (at
  * mtfhip_batch_create), sec_ord_hess and every second-order entry point, MTFHIP_SM_FALK / _IALK, update_model, the grid entry points,
  * score_candidates / sample_candidates / nn_dataset, the particle filter and the NN / GNN entry points. */
-enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6, MTFHIP_AM_SPSS = 7, MTFHIP_AM_SSIM = 8 };
+/* MTFHIP_AM_CCRE: Cross Cumulative Residual Entropy (AM/src/CCRE.cc), MI's sibling over CUMULATIVE histograms: f = sum_ij cum_joint(i, j)
+ * (log cum_joint(i, j) - log cum_hist_t(i) - log hist_0(j)) (CCRE.cc:406-413), cum_joint the cumulative cubic-B-spline weights of the current
+ * patch (1 below a pixel's window, cumBSpl3 inside it, 0 above; histUtils.h:46-159) times the plain B-spline weights of the template
+ * (:319-365).  CCREParams (:13-18) travel in mi_n_bins (2 .. 16; >= 4 with partition of unity, :87-91), mi_pre_seed and
+ * mi_partition_of_unity; n_blocks is the TBB block count and is ignored.  Pixel values are scaled over PIX_MAX - PIX_MIN = 255 (:98), not
+ * MI's 256: a raw 255 lands exactly on the last bin.  First order, symmetrical_grad = 0, true cumulative histograms: initializeSimilarity /
+ * initializeGrad (:159-308), updateSimilarity (:319-414), updateInitGrad (:425-464), updateCurrGrad (:465-476), cmptInitHessian (:521-560),
+ * cmptCurrHessian (:564-602), cmptSelfHessian with cmptCumSelfHist (:604-678); the Jacobians are AppearanceModel's defaults and
+ * getLikelihood is CCRE.h:72-75 with likelihood_beta = 0.  The histogram pass is MI's dense-slab kernel with the cumulative fill, the rest
+ * kernels of its own.  What is state in the reference and not algebra is not kept: updateSimilarity never writes
+ * curr_cum_hist_mat above a pixel's current window, so cmptInitHessian (:552-554) reads there what an earlier iteration left; here the
+ * cumulative weight above the window is 0, as the definition says.  Served: single channel, homography and affine, every first-order
+ * per-function AppearanceModel entry point, and mtfhip_batch_init_template / _set_region / _iterate / _track / _track_region with ESM, FCLK
+ * and ICLK and every first-order hess_type and jac_type they have for MI (SumOfStd included), chained or not, materialize 0 / 1, with or
+ * without Levenberg-Marquardt, both arithmetic modes (the passes are the same in both).  Everything else returns MTFHIP_ERR_NOT_IMPLEMENTED
+ * with its reason in mtfhip_last_error(): n_channels 3 and the three low-order SSMs (at mtfhip_batch_create), sec_ord_hess and every
+ * second-order entry point, MTFHIP_SM_FALK / _IALK, update_model, the grid entry points, score_candidates / sample_candidates /
+ * nn_dataset, the particle filter and the NN / GNN entry points (CCREDist is a per-candidate histogram).  symmetrical_grad = 1 has no
+ * field here; the host layer refuses it (mtf_amd/host/CCREParams.h). */
+enum { MTFHIP_AM_SSD = 0, MTFHIP_AM_NCC = 1, MTFHIP_AM_MI = 2, MTFHIP_AM_SCV = 3, MTFHIP_AM_RSCV = 4, MTFHIP_AM_LSCV = 5, MTFHIP_AM_LRSCV = 6, MTFHIP_AM_SPSS = 7, MTFHIP_AM_SSIM = 8,
+	MTFHIP_AM_CCRE = 9 };
 /* MTFHIP_SSM_SIMILITUDE / _ISOMETRY / _TRANSLATION: the low-order rigid models (SSM/src/Similitude.cc, Isometry.cc, Translation.cc), states
  * [tx, ty, a, b] (warp [[1 + a, -b, tx], [b, 1 + a, ty]]), [tx, ty, theta] (warp [[cos, -sin, tx], [sin, cos, ty]]) and [tx, ty], S = 4 / 3 / 2.
  * Served: the StateSpaceModel entry points below (set_corners with normalized_init = 0, set_state, compositional_update, invert_state,
@@ -139,7 +159,7 @@ typedef struct mtfhip_patch_desc {
 	int resx, resy;         /* ImgParams / SSMParams resx, resy */
 	double grad_eps;        /* ImgParams::grad_eps (1e-8, AM/include/mtf/AM/ImageBase.h:7-8) */
 	double likelihood_alpha;/* AMParams::likelihood_alpha */
-	int mi_n_bins;          /* MIParams::n_bins; with MTFHIP_AM_SCV / _RSCV / _LSCV / _LRSCV: SCVParams / RSCVParams / LSCVParams / LRSCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as they do */
+	int mi_n_bins;          /* MIParams::n_bins (CCREParams::n_bins with MTFHIP_AM_CCRE, as mi_pre_seed and mi_partition_of_unity); with MTFHIP_AM_SCV / _RSCV / _LSCV / _LRSCV: SCVParams / RSCVParams / LSCVParams / LRSCVParams::n_bins, 2 .. 256, and a value <= 0 selects 256 as they do */
 	double mi_pre_seed;     /* MIParams::pre_seed */
 	int mi_partition_of_unity;
 	double hess_eps;        /* ImgParams::hess_eps (1, AM/include/mtf/AM/ImageBase.h:9); <= 0 selects that default */

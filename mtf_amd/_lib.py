@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTFHIP_LIB", os.path.join(_HERE, "libmtfhip.so"))
 CSRC = os.path.join(_HERE, "csrc")
 
-AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV, AM_LRSCV, AM_SPSS, AM_SSIM = 0, 1, 2, 3, 4, 5, 6, 7, 8
+AM_SSD, AM_NCC, AM_MI, AM_SCV, AM_RSCV, AM_LSCV, AM_LRSCV, AM_SPSS, AM_SSIM, AM_CCRE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 SCV_HIST_DIRAC, SCV_HIST_BILINEAR, SCV_HIST_BSPLINE = 0, 1, 2
 SSM_HOMOGRAPHY, SSM_AFFINE, SSM_SIMILITUDE, SSM_ISOMETRY, SSM_TRANSLATION = 0, 1, 2, 3, 4
 # state sizes (StateSpaceModel::getStateSize): Homography.cc:36, Affine.cc:47, Similitude.cc:63, Isometry.cc:52, Translation.cc:48

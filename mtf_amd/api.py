@@ -252,7 +252,11 @@ class Batch:
     """B independent targets (AM + SSM pairs) sharing the context's current image."""
 
     def __init__(self, ctx, am=AM_SSD, ssm=SSM_HOMOGRAPHY, resx=50, resy=50, n_targets=1, grad_eps=1e-8,
-                 likelihood_alpha=1.0, mi_n_bins=8, mi_pre_seed=10.0, mi_pou=0, hess_eps=1.0, n_channels=1, spss_k=None, ssim_k1=None, ssim_k2=None):
+                 likelihood_alpha=1.0, mi_n_bins=8, mi_pre_seed=10.0, mi_pou=0, hess_eps=1.0, n_channels=1, spss_k=None, ssim_k1=None, ssim_k2=None,
+                 mi_partition_of_unity=None):
+        # (mi_partition_of_unity: the descriptor field's own name for mi_pou -- MIParams / CCREParams::partition_of_unity)
+        if mi_partition_of_unity is not None:
+            mi_pou = int(bool(mi_partition_of_unity))
         self.ctx = ctx
         self.desc = PatchDesc(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, hess_eps,
                               n_channels)

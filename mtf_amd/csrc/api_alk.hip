@@ -21,6 +21,7 @@ static int alk_check(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with MI is not available on the device route (use nt::%s over the per-function entry points)", fn, alk_name(sm), alk_name(sm));
 	TRY(spss_refuse(b, fn, " is not available with the additive search methods (FALK / IALK)"));
 	TRY(ssim_refuse(b, fn, " is not available with the additive search methods (FALK / IALK)"));
+	TRY(ccre_refuse(b, fn, " is not available with the additive search methods (FALK / IALK)"));
 	if (intensity_mapped(b))
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with %s is not available on the device route (use nt::%s over the per-function entry points)", fn, alk_name(sm),
 			intensity_mapped_name(b), alk_name(sm));

@@ -340,6 +340,7 @@ int mtfhip_am_initialize_similarity(mtfhip_batch *b) {
 	TRY(am_supported(b, "initializeSimilarity"));
 	/* (SSIM::initializeSimilarity SSIM.cc:50-76 keeps the template's mean and centred sum of squares, as NCC's does, and f = 1) */
 	if (ncc_rows(b)) return ncc_initialize_similarity(b);
+	if (ccre_am(b)) return ccre_initialize_similarity(b);
 	if (b->desc.am == MTFHIP_AM_MI) {
 		/* MI::initializeSimilarity MI.cc:207-287 */
 		const int first = b->init_sim ? 0 : 1;
@@ -363,6 +364,12 @@ int mtfhip_am_initialize_grad(mtfhip_batch *b) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "initialize_grad: NULL batch");
 	TRY(am_supported(b, "initializeGrad"));
+	if (ccre_am(b)) {
+		/* CCRE::initializeGrad CCRE.cc:287-308: df_dI0 from the initial tables, df_dIt = df_dI0 */
+		if (!b->init_grad) TRY(ccre_grad(b, 2));
+		b->init_grad = true;
+		return MTFHIP_OK;
+	}
 	if (b->desc.am == MTFHIP_AM_MI) {
 		/* MI::initializeGrad MI.cc:299-332: df_dI0 from the initial tables, df_dIt = df_dI0 */
 		if (b->init_grad) return MTFHIP_OK;
@@ -418,6 +425,7 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 		if (!prereq_only) TRY(mi_read_f(b));
 		return MTFHIP_OK;
 	}
+	if (ccre_am(b)) return ccre_update_similarity(b, prereq_only);
 	if (spss_am(b)) return spss_update_similarity(b, prereq_only);
 	if (ssim_am(b)) return ssim_update_similarity(b, prereq_only);
 	/* SCV / LSCV::updateSimilarity (SCV.cc:194-230, LSCV.cc:263-304): the intensity map(s) from It and I0_orig, I0 re-mapped, then
@@ -438,6 +446,7 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 static int do_update_curr_grad(mtfhip_batch *b) {
 	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 1); stale_clear(b, false, true); return rc; }
 	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 1);
+	if (ccre_am(b)) return ccre_grad(b, 1);
 	if (spss_am(b)) return spss_update_grad(b, 1);
 	if (ssim_am(b)) return ssim_update_grad(b, 1);
 	if (b->lz.df0_stale) TRY(ensure_one(b, false));
@@ -469,6 +478,7 @@ int mtfhip_am_update_init_grad(mtfhip_batch *b) {
 	FLUSH(b);
 	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 0); stale_clear(b, true, false); return rc; }
 	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 0);
+	if (ccre_am(b)) return ccre_grad(b, 0);
 	if (spss_am(b)) return spss_update_grad(b, 0);
 	if (ssim_am(b)) return ssim_update_grad(b, 0);
 	return MTFHIP_OK;
@@ -484,6 +494,7 @@ int mtfhip_am_get_likelihood(mtfhip_batch *b, double *l) {
 	if (!b || !l) return fail(MTFHIP_ERR_INVALID_ARG, "get_likelihood: NULL argument");
 	TRY(lazy_try_similarity(b));
 	FLUSH_AM(b);
+	if (ccre_am(b)) return ccre_likelihood(b, l);   /* CCRE::getLikelihood CCRE.h:72-75 */
 	for (int t = 0; t < b->B; ++t) {
 		double f = b->th[t].f;
 		if (spss_am(b)) l[t] = std::exp(b->desc.likelihood_alpha * (f - (double)b->N));   /* SPSS::getLikelihood SPSS.cc:46-48 */
@@ -880,6 +891,7 @@ int mtfhip_am_cmpt_init_hessian(mtfhip_batch *b, int j0_buf, double *H) {
 	TRY(j_ready(b, j0_buf, "cmptInitHessian"));
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, j0_buf, 0, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, j0_buf, 0, H);
+	if (ccre_am(b)) return ccre_hessian(b, j0_buf, 0, H);
 	if (spss_am(b)) return spss_hessian(b, j0_buf, SPSS_W_INIT, H);
 	if (ssim_am(b)) return ssim_hessian(b, j0_buf, NCC_H_INIT, H);
 	return gram_to_host(b, j0_buf, H, -1.0, false);
@@ -891,6 +903,7 @@ int mtfhip_am_cmpt_curr_hessian(mtfhip_batch *b, int jt_buf, double *H) {
 	TRY(j_ready(b, jt_buf, "cmptCurrHessian"));
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 1, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 1, H);
+	if (ccre_am(b)) return ccre_hessian(b, jt_buf, 1, H);
 	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_CURR, H);
 	if (ssim_am(b)) return ssim_hessian(b, jt_buf, NCC_H_CURR, H);
 	return gram_to_host(b, jt_buf, H, -1.0, false);
@@ -902,6 +915,7 @@ int mtfhip_am_cmpt_self_hessian(mtfhip_batch *b, int jt_buf, double *H) {
 	TRY(j_ready(b, jt_buf, "cmptSelfHessian"));
 	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 2, H);
 	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 2, H);
+	if (ccre_am(b)) return ccre_hessian(b, jt_buf, 2, H);
 	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_SELF, H);
 	if (ssim_am(b)) return ssim_hessian(b, jt_buf, NCC_H_SELF, H);
 	return gram_to_host(b, jt_buf, H, -1.0, false);
@@ -918,6 +932,7 @@ int mtfhip_am_cmpt_sum_of_hessians(mtfhip_batch *b, int j0_buf, int jt_buf, doub
 		if (b->desc.am == MTFHIP_AM_NCC) { TRY(ncc_hessian(b, j0_buf, 0, H0.data())); TRY(ncc_hessian(b, jt_buf, 1, H)); }
 		else if (spss_am(b)) { TRY(spss_hessian(b, j0_buf, SPSS_W_INIT, H0.data())); TRY(spss_hessian(b, jt_buf, SPSS_W_CURR, H)); }
 		else if (ssim_am(b)) { TRY(ssim_hessian(b, j0_buf, NCC_H_INIT, H0.data())); TRY(ssim_hessian(b, jt_buf, NCC_H_CURR, H)); }
+		else if (ccre_am(b)) { TRY(ccre_hessian(b, j0_buf, 0, H0.data())); TRY(ccre_hessian(b, jt_buf, 1, H)); }
 		else { TRY(mi_hessian(b, j0_buf, 0, H0.data())); TRY(mi_hessian(b, jt_buf, 1, H)); }
 		for (size_t i = 0; i < H0.size(); ++i) H[i] += H0[i];
 		return MTFHIP_OK;
@@ -1068,6 +1083,7 @@ int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double
 	TRY(scv_refuse(b, "cmpt_init_hessian (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(ssim_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ccre_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_init_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_init_hessian(b, j0_buf, H));
@@ -1079,6 +1095,7 @@ int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 	TRY(scv_refuse(b, "cmpt_curr_hessian (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(ssim_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ccre_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_curr_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_curr_hessian(b, jt_buf, H));
@@ -1090,6 +1107,7 @@ int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 	TRY(scv_refuse(b, "cmpt_self_hessian (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(ssim_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ccre_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_self_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_self_hessian (second order): NULL argument");
@@ -1109,6 +1127,7 @@ int mtfhip_am_cmpt_sum_of_hessians2(mtfhip_batch *b, int j0_buf, int jt_buf, int
 	TRY(scv_refuse(b, "cmpt_sum_of_hessians (second order)", 1));
 	TRY(spss_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(ssim_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(ccre_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
 	TRY(lowdof_refuse(b, "cmpt_sum_of_hessians (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_sum_of_hessians (second order): NULL argument");

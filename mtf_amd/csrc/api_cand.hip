@@ -71,6 +71,7 @@ int mtfhip_score_candidates_dev(mtfhip_batch *b, const double *dev_states, int C
 	TRY(lowdof_refuse(b, "score_candidates"));
 	TRY(spss_refuse(b, "score_candidates", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "score_candidates", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "score_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	TRY(refuse_intensity_mapped(b, "score_candidates", " candidates are not available"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "score_candidates before the template was initialised");
@@ -85,6 +86,7 @@ int mtfhip_score_candidates(mtfhip_batch *b, const double *states, int C, double
 	TRY(lowdof_refuse(b, "score_candidates"));
 	TRY(spss_refuse(b, "score_candidates", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "score_candidates", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "score_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	size_t need = (size_t)C * (b->S + 2);
 	HIP_TRY(b->d_cand.reserve(need));
@@ -104,6 +106,7 @@ int mtfhip_sample_candidates_dev(mtfhip_batch *b, const double *dev_states, int 
 	TRY(lowdof_refuse(b, "sample_candidates"));
 	TRY(spss_refuse(b, "sample_candidates", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "sample_candidates", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "sample_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: MI distance features (5 x N B-spline rows) are not available");
 	TRY(refuse_intensity_mapped(b, "sample_candidates", " distance features are not available"));
@@ -120,6 +123,7 @@ int mtfhip_sample_candidates(mtfhip_batch *b, const double *states, int C, doubl
 	TRY(lowdof_refuse(b, "sample_candidates"));
 	TRY(spss_refuse(b, "sample_candidates", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "sample_candidates", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "sample_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	Dev<double> d_states, d_feat;   /* (released on every return; the release waits for what is in flight) */
 	HIP_TRY(d_states.reserve((size_t)C * b->S));
@@ -146,6 +150,7 @@ int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *d
 	TRY(lowdof_refuse(b, "nn_dataset"));
 	TRY(spss_refuse(b, "nn_dataset", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "nn_dataset", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "nn_dataset", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	TRY(refuse_intensity_mapped(b, "nn_dataset", " is not available on the NN dataset"));
 	if (d->n_samples <= 0 || row_lo < 0 || row_count < 0 || row_lo + row_count > d->n_samples)
 		return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: rows [%d, %d) of %d samples", row_lo, row_lo + row_count, d->n_samples);
@@ -187,6 +192,7 @@ int mtfhip_nn_dataset(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *pe
 	TRY(lowdof_refuse(b, "nn_dataset"));
 	TRY(spss_refuse(b, "nn_dataset", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "nn_dataset", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "nn_dataset", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	if (d->n_samples <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: n_samples must be positive");
 	int F = 0;
 	TRY(mtfhip_nn_feature_size(b, &F));

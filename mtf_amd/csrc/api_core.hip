@@ -317,7 +317,7 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	/* the fused kernel addresses a target's arrays with 32-bit byte offsets (ld_off / st_off): 8 columns of N doubles */
 	if ((double)d->resx * d->resy * 3.0 >= (double)(1u << 26)) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: %dx%d sample points per target exceed the 2^26-row limit", d->resx, d->resy);
 	if (d->grad_eps <= 0 || d->hess_eps < 0) return fail(MTFHIP_ERR_INVALID_ARG, "batch_create: grad_eps must be positive (got %g)", d->grad_eps);
-	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_SSIM) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
+	if (d->am < MTFHIP_AM_SSD || d->am > MTFHIP_AM_CCRE) return fail(MTFHIP_ERR_INVALID_ARG, "unknown appearance model %d", d->am);
 	const AmTraits &am = am_traits(d->am);
 	/* (n_bins where the model reads it: 2 .. max_bins, and where bins_default a value <= 0 stands for max_bins) */
 	if (am.max_bins && (d->mi_n_bins > am.max_bins || (am.bins_default ? d->mi_n_bins == 1 : d->mi_n_bins < 2)))
@@ -325,6 +325,8 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	if (am.no_3ch && d->n_channels == 3) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s", am.no_3ch);
 	if (d->am == MTFHIP_AM_MI && d->mi_partition_of_unity && d->mi_n_bins < 4) /* MI.cc:83-87 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "MI::Too few bins %d specified to enforce partition of unity constraint", d->mi_n_bins);
+	if (d->am == MTFHIP_AM_CCRE && d->mi_partition_of_unity && d->mi_n_bins < 4) /* CCRE.cc:87-91 */
+		return fail(MTFHIP_ERR_INVALID_ARG, "CCRE::Too few bins %d specified to enforce partition of unity constraint", d->mi_n_bins);
 	if (!ssm_known(d->ssm)) return fail(MTFHIP_ERR_INVALID_ARG, "unknown state space model %d", d->ssm);
 	if (d->n_channels != 0 && d->n_channels != 1 && d->n_channels != 3) return fail(MTFHIP_ERR_INVALID_ARG, "n_channels %d (1 or 3 expected)", d->n_channels);
 	/* Similitude / Isometry / Translation: SSD, NCC and SSIM (on NCC's affine pass), single channel (mtfhip.h) -- refused here, before any kernel
@@ -348,6 +350,13 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 		double lo = 0, hi = d->mi_n_bins - 1;
 		if (d->mi_partition_of_unity) { lo = 1; hi = d->mi_n_bins - 2; }
 		b->norm_mult = (hi - lo) / (255.0 - 0.0 + 1);
+		b->norm_add = lo;
+	}
+	if (d->am == MTFHIP_AM_CCRE) {
+		/* CCRE ctor AM/src/CCRE.cc:86-102: over PIX_MAX - PIX_MIN = 255, so a raw 255 lands exactly on norm_pix_max */
+		double lo = 0, hi = d->mi_n_bins - 1;
+		if (d->mi_partition_of_unity) { lo = 1; hi = d->mi_n_bins - 2; }
+		b->norm_mult = (hi - lo) / (255.0 - 0.0);
 		b->norm_add = lo;
 	}
 	if (am.intensity_mapped) {
@@ -396,9 +405,11 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	ALLOC(b->d_h0, (size_t)64 * n_targets);
 	ALLOC(b->d_h0inv, (size_t)64 * n_targets);
 	ALLOC(b->d_colmean, (size_t)8 * n_targets);
-	if (d->am == MTFHIP_AM_MI) {
+	if (d->am == MTFHIP_AM_MI || d->am == MTFHIP_AM_CCRE) {
 		const int nb = d->mi_n_bins;
 		b->mi_row_len = std::max(std::max(nb + 2 * nb * nb, 36 + nb * nb * b->S), nb <= 10 ? mi_fast_row_len(nb) : 0);   /* widest of the MI partial rows (fused passes incl.) */
+		/* CCRE: three histogram rows side by side (launch_ccre_tables), or a Hessian row with the init kind's nb x S block behind it */
+		if (d->am == MTFHIP_AM_CCRE) b->mi_row_len = std::max(3 * (nb + nb * nb), 36 + (nb * nb + nb) * b->S);
 		/* hist_norm_mult = 1 / (patch_size + hist_pre_seed * n_bins), hist_pre_seed = n_bins * pre_seed (MI.cc:97,104) */
 		b->mi_hist_norm = 1.0 / ((double)b->N + (nb * d->mi_pre_seed) * nb);
 		ALLOC(b->d_mi_tb, (size_t)MI_SIZE * n_targets);

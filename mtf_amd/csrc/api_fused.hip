@@ -46,6 +46,12 @@ int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn) {
 				"(cmpt_sum_of_hessians serves it)");
 		return MTFHIP_OK;
 	}
+	if (ccre_am(b)) {
+		/* CCRE: every first-order Jacobian / Hessian type MI's materialising iteration serves, SumOfStd as two Hessian passes; its second-order
+		 * forms (CCRE.cc:797-865) weight the pixel Hessian by gradients no pass of this path hands on */
+		if (sm->sec_ord_hess) return ccre_refuse(b, fn, " with second-order Hessians is not available on the device path (first-order only)");
+		return MTFHIP_OK;
+	}
 	if (ssim_am(b)) {
 		/* SSIM: every first-order type NCC has, from the same rows (ssim_h, mtfhip_sm_system.h); its second-order Hessians weight the pixel
 		 * Hessian by df_dI (SSIM.cc:187-198, 256-268), which no pass accumulates for it */
@@ -428,6 +434,7 @@ static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, do
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "iterate before init_template");
 	TRY(need_image(b));
 	if (b->desc.am == MTFHIP_AM_MI) return mi_iterate(b, sm, f, g, H);
+	if (ccre_am(b)) return ccre_iterate(b, sm, f, g, H);
 	if (second_order_term(sm) >= 0) TRY(ensure_pts(b));   /* k_second_order_ssd reads the current points */
 	FusedArgs fa;
 	TRY(fused_args(b, sm, fa));

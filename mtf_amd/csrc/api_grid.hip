@@ -66,6 +66,7 @@ int mtfhip_grid_update(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *
 	TRY(lowdof_refuse(b, "grid_update"));
 	TRY(spss_refuse(b, "grid_update", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "grid_update", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "grid_update", " is not available on this entry point"));
 	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "grid_update: %s is not available on the grid tracker", intensity_mapped_name(b));
 	const size_t B = (size_t)b->B;
 	static thread_local std::vector<double> in, out;
@@ -92,6 +93,7 @@ static int grid_batch_ok(const mtfhip_batch *b, const mtfhip_grid_desc *g, const
 	TRY(lowdof_refuse(b, fn));   /* (the grid tracker's one-launch kernels solve what they accumulate: no projection) */
 	TRY(spss_refuse(b, fn, " is not available on this entry point"));
 	TRY(ssim_refuse(b, fn, " is not available on this entry point"));
+	TRY(ccre_refuse(b, fn, " is not available on this entry point"));
 	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s is not available on the grid tracker", fn, intensity_mapped_name(b));
 	if (g->grid_size_x <= 0 || g->grid_size_y <= 0 || g->grid_size_x * g->grid_size_y != b->B)   /* GridTracker.cc:124-129 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "%s: mismatch between the grid dimensions (%d x %d) and the batch's %d patch trackers", fn, g->grid_size_x, g->grid_size_y, b->B);

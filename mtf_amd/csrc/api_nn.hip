@@ -37,6 +37,7 @@ int mtfhip_nn_create(mtfhip_batch *b, int n_samples, mtfhip_nn **out) {
 	TRY(lowdof_refuse(b, "nn_create"));
 	TRY(spss_refuse(b, "nn_create", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "nn_create", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "nn_create", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	if (n_samples <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "nn_create: n_samples must be positive");
 	if (b->B != 1) return fail(MTFHIP_ERR_INVALID_ARG, "nn_create: one template per batch (the batch has %d targets)", b->B);
 	if (b->desc.am == MTFHIP_AM_MI)

@@ -285,6 +285,7 @@ int mtfhip_pf_create(mtfhip_batch *b, const mtfhip_pf_desc *d, mtfhip_pf **out) 
 	TRY(lowdof_refuse(b, "pf_create"));
 	TRY(spss_refuse(b, "pf_create", " is not available on this entry point"));
 	TRY(ssim_refuse(b, "pf_create", " is not available on this entry point"));
+	TRY(ccre_refuse(b, "pf_create", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
 	TRY(refuse_intensity_mapped(b, "pf_create", " is not available on the particle filter"));
 	if (b->B != 1) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: the particle filter tracks one target (batch of %d)", b->B);
 	if (d->n_particles < 1) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: n_particles must be positive");

@@ -142,7 +142,7 @@ int mtfhip_batch_track_targets_per_launch(mtfhip_batch *b, const mtfhip_sm_desc 
 int mtfhip_batch_track_queues(mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	FLUSH(b);
 	if (check_sm(b, sm, "track_queues") != MTFHIP_OK) return 0;
-	if (b->desc.am == MTFHIP_AM_MI) return 1;
+	if (hist_am(b)) return 1;
 	if (iclk_one_launch(b, sm)) return 1;
 	FusedArgs fa;
 	if (fused_args(b, sm, fa) != MTFHIP_OK) return 0;
@@ -257,7 +257,7 @@ int track_region_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *r
 	 * MTFHIP_GRID_FUSED=0 keeps the ingest + k_init_grid launch in front of the loop (A/B, and the bit-identity test). */
 	const char *e_gf = std::getenv("MTFHIP_GRID_FUSED");   /* (read per call: the A/B test flips it) */
 	const bool fused_ok = !(e_gf && e_gf[0] == '0');
-	const bool region_mode = fused_ok && folded && b->desc.am != MTFHIP_AM_MI && !sm->leven_marq && iclk_one_launch(b, sm) && second_order_term(sm, b->desc.am) < 0 &&
+	const bool region_mode = fused_ok && folded && !hist_am(b) && !sm->leven_marq && iclk_one_launch(b, sm) && second_order_term(sm, b->desc.am) < 0 &&
 		b->h_stage_a_dev && b->h_pub_dev;
 	const auto t0 = std::chrono::steady_clock::now();
 	static thread_local std::vector<double> patches;
@@ -629,7 +629,7 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 	 * and two rejections never follow each other (the pass after an undo skips the test) */
 	TrackCtx cx{second_order_term(sm, b->desc.am), (sm->leven_marq && sm->sm == MTFHIP_SM_FCLK) ? 2 * sm->max_iters : sm->max_iters, 0, resume, region_mode};
 	hipStream_t st = b->ctx->stream;
-	const bool mi = b->desc.am == MTFHIP_AM_MI, ncc = ncc_rows(b);   /* (ncc: the pass reduces NCC's rows -- NCC itself and SSIM) */
+	const bool mi = hist_am(b), ncc = ncc_rows(b);   /* (mi: MI or CCRE, a driver of their own; ncc: the pass reduces NCC's rows -- NCC itself and SSIM) */
 	/* (the one-launch grid kernel has no Levenberg-Marquardt: with it ICLK takes the fused launch + finish per pass) */
 	const bool one_launch = !mi && !sm->leven_marq && iclk_one_launch(b, sm) && cx.so_term < 0;
 	FusedArgs fa;
@@ -697,7 +697,8 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 		if (b->lo_ssm) { ts.fast_finish = 0; ts.keep_last = (fa.materialize && fa.mode != 2) ? 1 : 0; ts.lo_ssm = b->lo_ssm; ts.SS = ssm_state_size(b->lo_ssm); }
 	}
 	unsigned long long pub_seq = 0;   /* non-zero: the loop's own kernel delivers the results to the host */
-	if (mi) TRY(track_loop_mi(b, sm, ts, cx));
+	if (ccre_am(b)) TRY(track_loop_ccre(b, sm, ts, cx));
+	else if (mi) TRY(track_loop_mi(b, sm, ts, cx));
 	else if (one_launch) TRY(track_loop_one_launch(b, sm, ts, cx, pub_seq));
 	else if (persisted) TRY(track_loop_persist(b, sm, fa, ts, cx));
 	else TRY(track_loop_chunked(b, sm, fa, ts, cx, pub_seq));

@@ -10,7 +10,9 @@ namespace mtfhip {
  * :641-649 self).  Block partial rows: [nb hist | nb*nb joint] */
 /* SELF (MFMA only): the joint histogram of A with itself (cmptSelfHist MI.cc:639-659) is accumulated in the same pass and
  * written behind the ordinary row: [nb hist | nb*nb joint | nb*nb self] */
-template <bool MFMA, bool SELF = false>
+/* CUM (CCRE, AM/src/CCRE.cc:337-364): the A operand's fill is the CUMULATIVE window of A -- 1 below it, cumBSpl3 inside, 0 above -- so the
+ * row's first nb entries are the cumulative histogram and the product is the cumulative joint histogram; everything else as it stands */
+template <bool MFMA, bool SELF = false, bool CUM = false>
 __global__ __launch_bounds__(kBlock) void k_mi_hist(int N, int nb, double norm_mult, const double *A_all,
 	const double *B_all, double *partials, int nblk, int row_len) {
 	extern __shared__ __attribute__((aligned(16))) double dyn[];
@@ -45,11 +47,14 @@ __global__ __launch_bounds__(kBlock) void k_mi_hist(int N, int nb, double norm_m
 		}
 		for (int k2 = 0; k2 < nb; ++k2) { wa[k2 * RS + lane] = 0.0; wb[k2 * RS + lane] = 0.0; }
 		if (i < N) {
-			const BsplWin a = bspl_window(a_cur, nb, norm_mult, false);
+			const BsplWin a = CUM ? cum_window(a_cur, nb, norm_mult) : bspl_window(a_cur, nb, norm_mult, false);
 			const BsplWin b = bspl_window(b_cur, nb, norm_mult, false);
 			/* static indices only: a runtime-indexed window array would live in scratch memory */
+			if constexpr (CUM) cum_fill<RS>(wa, lane, a, nb);
+			else {
 #pragma unroll
-			for (int r = 0; r < 4; ++r) if (r < a.n) wa[(a.lo + r) * RS + lane] = a.w[r];
+				for (int r = 0; r < 4; ++r) if (r < a.n) wa[(a.lo + r) * RS + lane] = a.w[r];
+			}
 #pragma unroll
 			for (int c = 0; c < 4; ++c) if (c < b.n) wb[(b.lo + c) * RS + lane] = b.w[c];
 		}
@@ -473,6 +478,13 @@ void launch_mi_hist(const BatchView &bv, int nb, double norm_mult, const double 
 	static const bool use_mfma = !(getenv("MTFHIP_MI_MFMA") && atoi(getenv("MTFHIP_MI_MFMA")) == 0);
 	if (use_mfma) MTFHIP_LAUNCH((k_mi_hist<true, false>), grid2(nblk, bv.B), dim3(kBlock), lds, st, bv.N, nb, norm_mult, A, Bv, partials, nblk, row_len);
 	else MTFHIP_LAUNCH((k_mi_hist<false, false>), grid2(nblk, bv.B), dim3(kBlock), lds, st, bv.N, nb, norm_mult, A, Bv, partials, nblk, row_len);
+}
+/* CCRE: the cumulative weights of A against the plain weights of B; row: [nb cumulative hist | nb*nb cumulative joint] */
+void launch_ccre_hist(const BatchView &bv, int nb, double norm_mult, const double *A, const double *Bv, double *partials,
+	int nblk, int row_len, hipStream_t st) {
+	const size_t lds = sizeof(double) * std::max<size_t>((size_t)4 * kMiRowMfma * 2 * nb, (size_t)4 * (nb + nb * nb));
+	/* (the matrix-core form at every bin count: MTFHIP_MI_MFMA, MI's A/B switch, has no CCRE side) */
+	MTFHIP_LAUNCH((k_mi_hist<true, false, true>), grid2(nblk, bv.B), dim3(kBlock), lds, st, bv.N, nb, norm_mult, A, Bv, partials, nblk, row_len);
 }
 /* A = It against B = I0 and against itself in one pass (fused MI iteration); row: [nb | nb*nb | nb*nb] */
 void launch_mi_hist_self(const BatchView &bv, int nb, double norm_mult, const double *A, const double *Bv, double *partials,

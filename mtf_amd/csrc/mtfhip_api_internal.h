@@ -268,8 +268,10 @@ constexpr AmTraits kAmTraits[] = {
 		"updateModel: SPSS has no online template update on the device path" MTFHIP_FIRST_ORDER_SERVED, nullptr},
 	{"SSIM", AM_ROWS_NCC, false, 0, false, "SSIM with n_channels 3 (MCSSIM) is not available on the device path (single channel only)",
 		"updateModel: SSIM has no online template update (SSIM.cc has none either)" MTFHIP_FIRST_ORDER_SERVED, nullptr},
+	{"CCRE", AM_ROWS_MI, false, MI_NB, false, "CCRE with n_channels 3 (MCCCRE) is not available on the device path (single channel only)",
+		"updateModel: CCRE has no online template update (CCRE.cc has none either)" MTFHIP_FIRST_ORDER_SERVED, nullptr},   /* (candidates: ccre_refuse says why) */
 };
-static_assert(sizeof(kAmTraits) / sizeof(kAmTraits[0]) == MTFHIP_AM_SSIM + 1, "one row of traits per MTFHIP_AM_*");
+static_assert(sizeof(kAmTraits) / sizeof(kAmTraits[0]) == MTFHIP_AM_CCRE + 1, "one row of traits per MTFHIP_AM_*");
 static inline const AmTraits &am_traits(int am) { return kAmTraits[am]; }   /* (am: a batch's, checked by mtfhip_batch_create) */
 
 /* The SCV family (SCV, RSCV, LSCV, LRSCV: SSD behind an intensity map) keeps ONE state: a batch has one appearance model for life.  SCV and
@@ -358,6 +360,7 @@ struct mtfhip_batch {
 	bool j0_recompute_enabled = !(std::getenv("MTFHIP_J0_RECOMPUTE") && std::getenv("MTFHIP_J0_RECOMPUTE")[0] == '0');
 	int d0_variant = MTFHIP_JAC_WARPED; /* how the template's pixel Hessian was formed (fused second-order path) */
 	int mi_row_len = 0;
+	std::vector<double> ccre_f_max;   /* CCRE: max_similarity, f of initializeSimilarity (CCRE.cc:261), per target */
 	double mi_hist_norm = 0;
 	IntensityMapState imap;   /* SCV, RSCV, LSCV, LRSCV: the model's own state (api_imap.hip) */
 	int first_iter = 0;       /* AppearanceModel::first_iter (mtfhip_batch_set_first_iter; the localized models' once_per_frame reads it) */
@@ -625,6 +628,18 @@ int ssim_h0(const mtfhip_batch *b, double *H0);
 int ssim_update_similarity(mtfhip_batch *b, int prereq_only);
 int ssim_update_grad(mtfhip_batch *b, int curr);
 int ssim_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
+/* CCRE (api_ccre.hip): MI's materialising iteration with cumulative weights on the current patch's side, in the buffers an MI batch has.
+ * hist_am: the models whose iteration is a histogram pipeline of its own behind a materialising SSD pass (mi_enqueue / ccre_enqueue) and whose
+ * device loop is their own driver.  ccre_refuse: "<fn>: CCRE<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for a CCRE batch, MTFHIP_OK otherwise;
+ * ccre_grad: 0 updateInitGrad, 1 updateCurrGrad, 2 initializeGrad; ccre_hessian: kind 0 init, 1 curr, 2 self */
+static inline bool ccre_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_CCRE; }
+static inline bool hist_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_MI || b->desc.am == MTFHIP_AM_CCRE; }
+int ccre_refuse(const mtfhip_batch *b, const char *fn, const char *what);
+int ccre_initialize_similarity(mtfhip_batch *b);
+int ccre_update_similarity(mtfhip_batch *b, int prereq_only);
+int ccre_grad(mtfhip_batch *b, int which);
+int ccre_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
+int ccre_likelihood(const mtfhip_batch *b, double *l);   /* [B] */
 /* one target's reduced NCC row and template mirrors as the SSIM system of mtfhip_sm_system.h; and the host mirrors of SSIM.cc's members it leaves */
 static inline mtfhip::SsimSys ssim_host_sys(const mtfhip_batch *b, const TargetHost &h, const double *M) {
 	return mtfhip::ssim_sys(M, h.ncc_tm, h.I0_mean, h.i0_ss, (double)b->N, b->ssim_c1, b->ssim_c2);
@@ -920,6 +935,8 @@ int mi_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, 
  * k_publish_host launch); words_ready: the head has set the loop's words (need_mat, d_phase, the Levenberg-Marquardt state) */
 struct TrackCtx { int so_term, max_passes, nb2; bool resume, region_mode; bool fused_io = false, words_ready = false; };
 int track_loop_mi(mtfhip_batch *b, const mtfhip_sm_desc *sm, mtfhip::TrackState &ts, const TrackCtx &cx);   /* (api_mi_iter.hip) */
+int ccre_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);                  /* (api_ccre.hip) */
+int track_loop_ccre(mtfhip_batch *b, const mtfhip_sm_desc *sm, mtfhip::TrackState &ts, const TrackCtx &cx);
 /* ... and the skeleton every device-side loop shares (track_core, alk_track): the upload of the state slab, the initial Levenberg-Marquardt
  * state, the look at the stop flags every eighth pass, the read-back of the slab, the tail of a loop that ran to its read-back */
 int loop_upload_slab(mtfhip_batch *b, hipStream_t st, bool keep_ncc, const LoopWords *lw = nullptr);

@@ -422,6 +422,19 @@ void launch_mi_hist_self(const BatchView &bv, int nb, double norm_mult, const do
 struct MiJ0Rebuild { const double *dI0, *pts, *z; int hom, init_variant; };
 void launch_mi_grad_gemv(const BatchView &bv, int nb, double norm_mult, const double *It, const double *I0, const double *tb,
 	const double *Jt, const double *J0, const MiJ0Rebuild &rb, double *df_dIt, double *df_dI0, double *partials, int nblk, hipStream_t st);
+/* CCRE pieces (kernels_ccre.hip; the table block and its modes: mtfhip_ccre_tables.h).  launch_ccre_hist is k_mi_hist with the cumulative fill
+ * (kernels_mi.hip): rows [nb cumulative hist of A | nb*nb cumulative joint (A, B)].  launch_ccre_tables sums rows of
+ * [nb + nb*nb (A, I0) | nb + nb*nb (It, It) | nb plain hist ..]; launch_ccre_hess: kind 0 init (J = J0), 1 curr, 2 self, rows
+ * [36 | nb*nb*S | nb*S (init)], which launch_ccre_hess_finish reads summed to one row per target */
+void launch_ccre_hist(const BatchView &bv, int nb, double norm_mult, const double *A, const double *Bv, double *partials,
+	int nblk, int row_len, hipStream_t st);
+void launch_ccre_tables(const BatchView &bv, int nb, double pre_seed, double norm_mult, int mode, int with_self, const double *partials, int nblk,
+	int row_len, double *tb, double *f_out, hipStream_t st);
+void launch_ccre_grad_gemv(const BatchView &bv, int nb, double norm_mult, const double *It, const double *I0, const double *tb,
+	const double *Jt, const double *J0, const MiJ0Rebuild &rb, double *df_dIt, double *df_dI0, double *partials, int nblk, hipStream_t st);
+void launch_ccre_hess(const BatchView &bv, int nb, double norm_mult, int kind, const double *It, const double *I0, const double *tb, const double *J,
+	double *partials, int nblk, int row_len, hipStream_t st);
+void launch_ccre_hess_finish(const BatchView &bv, int nb, int kind, const double *rows, int row_len, const double *tb, double *out, hipStream_t st);
 /* ---- the recompute form of the MI iteration (kernels_mi_fused.hip; tolerance-mode arithmetic, 8 bins) ---- */
 struct MiFastPlan {
 	int nb = 8;           /* the AM's n_bins: 8 -> the NB = 8 kernels, otherwise (<= 10; hk 0 / 1) the NB = 10 ones */

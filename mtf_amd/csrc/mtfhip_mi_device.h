@@ -95,6 +95,48 @@ __device__ __forceinline__ BsplWin bspl_window(double v, int nb, double norm_mul
 	}
 	return s;
 }
+/* utils::cumBSpl3WithGrad and cumBSpl3Hess (histUtils.h:96-119, :145-159; the truncated constants kept, :10-11), with the reference's
+ * branch boundaries: the cumulative cubic B-spline, 1 at x <= -2 and 0 from 2 on, its derivative and its second derivative */
+__device__ __forceinline__ void cum_bspl3(double &val, double &diff, double &hess, double x) {
+	const double k1by3 = 0.33333333333, k2by3 = 0.66666666666;
+	if (x <= -2) { val = 1; diff = 0; hess = 0; }
+	else if (x <= -1) { const double t = 2 + x; diff = -(t * t * t) / 6; val = 1 + (diff * t) / 4; hess = -(t * t) / 2; }
+	else if (x <= 0) { const double x2 = x * x; val = 0.5 + x * (x2 * (k1by3 + x / 8) - k2by3); diff = x2 * (1 + x / 2) - k2by3; hess = x * (3 * x + 4) / 2; }
+	else if (x <= 1) { const double x2 = x * x; val = 0.5 + x * (x2 * (k1by3 - x / 8) - k2by3); diff = x2 * (1 - x / 2) - k2by3; hess = -x * (3 * x - 4) / 2; }
+	else if (x < 2) { const double t = x - 2, u = 2 - x; diff = (t * t * t) / 6; val = (diff * t) / 4; hess = (u * u) / 2; }
+	else { val = 0; diff = 0; hess = 0; }
+}
+/* The cumulative window of a pixel value (CCRE.cc:337-364): the same bins [lo, hi] as bspl_window; w[k] = cumBSpl3 at the tap, d[k] its
+ * derivative * -hist_norm_mult (:356), h[k] its second derivative * hist_norm_mult (:588).  Below the window the cumulative weight is 1
+ * (:340-352) and above it 0 -- the dense form of that is cum_fill. */
+__device__ __forceinline__ BsplWin cum_window(double v, int nb, double norm_mult) {
+	BsplWin s;
+	const int fl = (int)v;
+	s.lo = max(0, fl - 1);
+	const int hi = min(nb - 1, fl + 2);
+	s.n = hi - s.lo + 1;
+	double diff = s.lo - v;
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		s.w[k] = 0; s.d[k] = 0; s.h[k] = 0;
+		if (k < s.n) {
+			cum_bspl3(s.w[k], s.d[k], s.h[k], diff);
+			s.d[k] *= -norm_mult;
+			s.h[k] *= norm_mult;
+			diff += 1;   /* ++curr_diff, CCRE.cc:362 */
+		}
+	}
+	return s;
+}
+/* the dense cumulative weights of one pixel in its lane's column of a zeroed [nb][RS] slab: 1.0 in the rows below the window, the
+ * window's values (static indices only: kernels_mi.hip), 0 above it */
+template <int RS>
+__device__ __forceinline__ void cum_fill(double *slab, int lane, const BsplWin &a, int nb) {
+	const int below = min(a.lo, nb);   /* (a value past the last bin: every row of the slab, none outside it) */
+	for (int k2 = 0; k2 < below; ++k2) slab[k2 * RS + lane] = 1.0;
+#pragma unroll
+	for (int r = 0; r < 4; ++r) if (r < a.n) slab[(a.lo + r) * RS + lane] = a.w[r];
+}
 /* The same window with four piece evaluations instead of seven: tap k of the un-clamped window [fl - 1, fl + 2] lies in
  * piece k; when the window is clamped at bin 0 (fl == 0) the first tap falls on the non-existent bin -1 and the other
  * three move down one slot.  The tap positions are accumulated exactly like MI.cc:232,359 (x += 1 from lo - v), every piece

@@ -52,6 +52,8 @@ def lib():
         H.mtfhost_create_spss.argtypes = [C.c_int] * 5 + [C.c_double] + [C.c_int] * 4 + [C.c_double, C.c_double] + [C.c_int, C.c_double]
         H.mtfhost_create_ssim.restype = C.c_void_p
         H.mtfhost_create_ssim.argtypes = [C.c_int] * 5 + [C.c_double] + [C.c_int] * 4 + [C.c_double, C.c_double] + [C.c_int, C.c_double, C.c_double]
+        H.mtfhost_create_ccre.restype = C.c_void_p
+        H.mtfhost_create_ccre.argtypes = [C.c_int] * 5 + [C.c_double] + [C.c_int] * 4 + [C.c_double, C.c_double] + [C.c_int] * 3 + [C.c_double, C.c_int, C.c_int]
         H.mtfhost_create_lrscv.restype = C.c_void_p
         H.mtfhost_create_lrscv.argtypes = [C.c_int] * 5 + [C.c_double] + [C.c_int] * 4 + [C.c_double, C.c_double] + [C.c_int] * 9
         H.mtfhost_qr_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -219,6 +221,23 @@ class CppTracker:
         self = cls.__new__(cls)
         h = lib().mtfhost_create_ssim(sm + (16 if device_loop else 0), ssm, resx, resy, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq,
                                       lm_delta_init, lm_delta_update, device, k1, k2)
+        self.n_channels = 1
+        if not h:
+            raise HostError(lib().mtfhost_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+        self._img = None
+        self.iters = 0
+        return self
+
+    @classmethod
+    def ccre(cls, sm, ssm=_lib.SSM_HOMOGRAPHY, resx=50, resy=50, max_iters=30, epsilon=1e-4, jac_type=1, hess_type=-1, chained_warp=1,
+             leven_marq=1, lm_delta_init=0.01, lm_delta_update=10.0, device=0, n_bins=8, partition_of_unity=0, pre_seed=10.0, symmetrical_grad=0,
+             n_blocks=0, device_loop=False):
+        """the same search methods over HipAM("ccre"), built from CCREParams (n_bins, partition_of_unity, pre_seed; n_blocks is ignored;
+        symmetrical_grad = 1 is refused)"""
+        self = cls.__new__(cls)
+        h = lib().mtfhost_create_ccre(sm + (16 if device_loop else 0), ssm, resx, resy, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq,
+                                      lm_delta_init, lm_delta_update, device, n_bins, int(partition_of_unity), pre_seed, int(symmetrical_grad), n_blocks)
         self.n_channels = 1
         if not h:
             raise HostError(lib().mtfhost_last_error().decode("utf-8", "replace"))

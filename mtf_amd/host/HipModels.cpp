@@ -109,7 +109,7 @@ int HipPair::hessianBuffer(const MatrixXd &D, bool may_register) {
 /* ------------------------------------------------------------------ AM */
 HipAM::HipAM(std::shared_ptr<HipPair> pair) : p(pair) {
 	name = p->am == MTFHIP_AM_SSD ? "ssd" : (p->am == MTFHIP_AM_NCC ? "ncc" : (p->am == MTFHIP_AM_SCV ? "scv" : (p->am == MTFHIP_AM_RSCV ? "rscv" : (p->am == MTFHIP_AM_LSCV ? "lscv" :
-		(p->am == MTFHIP_AM_LRSCV ? "lrscv" : (p->am == MTFHIP_AM_SPSS ? "spss" : (p->am == MTFHIP_AM_SSIM ? "ssim" : "mi")))))));
+		(p->am == MTFHIP_AM_LRSCV ? "lrscv" : (p->am == MTFHIP_AM_SPSS ? "spss" : (p->am == MTFHIP_AM_SSIM ? "ssim" : (p->am == MTFHIP_AM_CCRE ? "ccre" : "mi"))))))));
 	I0.resize(p->N); It.resize(p->N);
 	dI0_dx.resize(p->N, 2); dIt_dx.resize(p->N, 2);
 	d2I0_dx2.resize(4, p->N); d2It_dx2.resize(4, p->N);

@@ -103,6 +103,11 @@ struct HipSPSSParams {
 struct HipSSIMParams {
 	double k1 = 0.01, k2 = 0.03;
 };
+/* the histogram parameters of CCREParams (CCREParams.h; AM/src/CCRE.cc:13-18) as they travel to mtfhip_patch_desc::mi_n_bins / mi_pre_seed /
+ * mi_partition_of_unity */
+struct HipCCREParams {
+	int n_bins = 8; bool partition_of_unity = false; double pre_seed = 10;
+};
 struct HipLink {
 	int am = MTFHIP_AM_SSD, ssm = MTFHIP_SSM_HOMOGRAPHY, resx = 50, resy = 50;   /* AMParams / SSMParams: resx, resy */
 	double grad_eps = 1e-8, likelihood_alpha = 1.0;                           /* AMParams::grad_eps; SSDParams / NCCParams / MIParams::likelihood_alpha */
@@ -113,6 +118,7 @@ struct HipLink {
 	HipLRSCVParams lrscv;                                                      /* am = MTFHIP_AM_LRSCV ("lrscv", "lrsc") */
 	HipSPSSParams spss;                                                        /* am = MTFHIP_AM_SPSS ("spss") */
 	HipSSIMParams ssim;                                                        /* am = MTFHIP_AM_SSIM ("ssim") */
+	HipCCREParams ccre;                                                        /* am = MTFHIP_AM_CCRE ("ccre") */
 	int device = 0; void *stream = nullptr;
 	std::shared_ptr<HipPair> pair(int n_channels = 1) {
 		if (!p && am == MTFHIP_AM_SCV) {
@@ -143,6 +149,9 @@ struct HipLink {
 			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, 0, 0.0, 0, device, stream, n_channels);
 			p->setSSIM(ssim.k1, ssim.k2);
 		}
+		if (!p && am == MTFHIP_AM_CCRE)
+			p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, ccre.n_bins, ccre.pre_seed, ccre.partition_of_unity ? 1 : 0,
+				device, stream, n_channels);
 		if (!p) p = std::make_shared<HipPair>(am, ssm, resx, resy, grad_eps, likelihood_alpha, mi_n_bins, mi_pre_seed, mi_pou, device, stream, n_channels);
 		else if (n_channels > 1 && n_channels != p->n_channels)   /* (SearchMethod<AM, SSM> constructs the AM first: it fixes the channel count) */
 			throw utils::InvalidArgument("HipLink :: the pair exists with another channel count");

@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../HipModels.h"
+#include "../CCREParams.h"
 #include "../DeviceLK.h"
 #include "../DevicePF.h"
 #include "../DeviceNN.h"
@@ -137,6 +138,19 @@ mtfhost_tracker *mtfhost_create_ssim(int sm, int ssm, int resx, int resy, int ma
 		link->ssim.k1 = ssim_params.k1; link->ssim.k2 = ssim_params.k2;
 		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
 	} catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+/* the same tracker with HipAM("ccre"): its CCREParams through the HipLink (symmetrical_grad = 1: FunctonNotImplemented, before any device call) */
+mtfhost_tracker *mtfhost_create_ccre(int sm, int ssm, int resx, int resy, int max_iters, double epsilon, int jac_type, int hess_type, int chained_warp,
+	int leven_marq, double lm_delta_init, double lm_delta_update, int device, int n_bins, int partition_of_unity, double pre_seed, int symmetrical_grad,
+	int n_blocks) {
+	try {
+		auto link = std::make_shared<hip::HipLink>();
+		link->ssm = ssm; link->resx = resx; link->resy = resy; link->device = device;
+		const hip::CCREParams ccre_params(link, n_bins, partition_of_unity != 0, pre_seed, symmetrical_grad != 0, n_blocks, false);
+		hip::CCRE::linked(&ccre_params);   /* (the reference's block: CCRE(&ccre_params) is the HipAM create_on builds over this pair) */
+		return create_on(link->pair(), sm, max_iters, epsilon, jac_type, hess_type, chained_warp, leven_marq, lm_delta_init, lm_delta_update, 0);
+	} catch (const utils::Exception &e) { g_err = std::string(e.type()) + ": " + e.what(); return nullptr; }
+	catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
 void mtfhost_destroy(mtfhost_tracker *t) { delete t; }
 /* ESM / FC / IC_ENABLE_LEARNING + the AM's learning_rate: am->updateModel(ssm->getPts()) at the end of every update() */

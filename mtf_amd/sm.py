@@ -49,12 +49,19 @@ def _refuse_ssim(what, am):
         raise L.FunctionNotImplemented(-2, "%s: the SSIM appearance model is served by LKTracker and NTSearchMethod only" % what)
 
 
+def _refuse_ccre(what, am):
+    """GridTracker, ParticleFilter, NNDataset and NNTracker are not served with the CCRE appearance model (include/mtfhip.h): raised before
+    any device call"""
+    if am == L.AM_CCRE:
+        raise L.FunctionNotImplemented(-2, "%s: the CCRE appearance model is served by LKTracker and NTSearchMethod only" % what)
+
+
 class LKTracker:
     """One or many (B) independent targets tracked with ESM / FCLK / ICLK (or the additive FALK / IALK: SSD and NCC, k_alk_pass +
     k_alk_finish) + SSD, NCC or MI on one GPU through the fused path
     (mtfhip_batch_iterate: k_fused_ssd / k_fused_ncc, or the fused MI passes): host_solve=True = fused launch(es) per
     iteration + the reference's pivoted QR and Levenberg-Marquardt on the host; False = the whole loop on the device
-    (mtfhip_batch_track)."""
+    (mtfhip_batch_track).  am=AM_CCRE: CCRE, with am_params mi_n_bins / mi_pre_seed / mi_partition_of_unity (CCREParams)."""
 
     def __init__(self, ctx, sm, ssm=L.SSM_HOMOGRAPHY, resx=50, resy=50, n_targets=1, host_solve=True, am=L.AM_SSD,
                  am_params=None, **params):
@@ -436,6 +443,7 @@ class GridTracker:
         _refuse_low_order("GridTracker", ssm, grid_ssm)
         _refuse_spss("GridTracker", am)
         _refuse_ssim("GridTracker", am)
+        _refuse_ccre("GridTracker", am)
         self.ctx = ctx
         # est_params (_lib.est_params(...) = SSMEstimatorParams): the device RANSAC / LMedS estimator (Context.estimate_warp_from_pts) takes the
         # place of `estimator`; pix_mask / est_ok / est_result follow every update (GridTracker.cc:269, 332-340); frame f draws from est_seed + f
@@ -830,6 +838,7 @@ class ParticleFilter:
         _refuse_low_order("ParticleFilter", ssm)
         _refuse_spss("ParticleFilter", am)
         _refuse_ssim("ParticleFilter", am)
+        _refuse_ccre("ParticleFilter", am)
         # seed 0 = "draw one" (below) -- but only an unsharded filter may: the ranks of a sharded one must propose identical particles
         # (each scores a block of ITS proposals, the all-gather mixes the weights), so there seed 0 is refused before anything is
         # created (mtfhip_pf_set_comm cross-checks the seeds of all ranks as well)
@@ -1058,6 +1067,7 @@ class NNDataset:
         _refuse_low_order("NNDataset", ssm)
         _refuse_spss("NNDataset", am)
         _refuse_ssim("NNDataset", am)
+        _refuse_ccre("NNDataset", am)
         self.batch = Batch(ctx, am, ssm, resx, resy, 1, **(am_params or {}))
         self.S = self.batch.S
         self.n = int(n_samples)
@@ -1185,6 +1195,7 @@ class NNTracker:
         _refuse_low_order("NNTracker", ssm)
         _refuse_spss("NNTracker", am)
         _refuse_ssim("NNTracker", am)
+        _refuse_ccre("NNTracker", am)
         if index not in ("exact", "gnn"):
             raise ValueError("NNTracker: index must be 'exact' or 'gnn'")
         self.index, self.gnn_params = index, dict(gnn_params or {})

@@ -19,12 +19,7 @@ static int alk_check(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
 	if (b->desc.am == MTFHIP_AM_MI)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with MI is not available on the device route (use nt::%s over the per-function entry points)", fn, alk_name(sm), alk_name(sm));
-	TRY(spss_refuse(b, fn, " is not available with the additive search methods (FALK / IALK)"));
-	TRY(ssim_refuse(b, fn, " is not available with the additive search methods (FALK / IALK)"));
-	TRY(ccre_refuse(b, fn, " is not available with the additive search methods (FALK / IALK)"));
-	if (intensity_mapped(b))
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with %s is not available on the device route (use nt::%s over the per-function entry points)", fn, alk_name(sm),
-			intensity_mapped_name(b), alk_name(sm));
+	TRY(am_refuse(b, fn, AM_AT_ADDITIVE_SM, alk_name(sm)));
 	if (b->desc.am != MTFHIP_AM_SSD && b->desc.am != MTFHIP_AM_NCC) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: unknown appearance model", fn);
 	if (b->C != 1)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with n_channels %d is not available on the device route (use nt::%s over the per-function entry points)", fn, alk_name(sm),

@@ -33,8 +33,7 @@ int mtfhip_am_initialize_pix_vals(mtfhip_batch *b, const double *pts) {
 int mtfhip_am_update_model(mtfhip_batch *b, const double *pts, double learning_rate) {
 	FLUSH(b);
 	if (!b) return fail(MTFHIP_ERR_INVALID_ARG, "update_model: NULL batch");
-	/* (served: SSD and NCC) */
-	if (am_traits(b->desc.am).no_update_model) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s", am_traits(b->desc.am).no_update_model);
+	TRY(am_refuse(b, "update_model", AM_AT_UPDATE_MODEL));   /* (served: SSD and NCC) */
 	TRY(single_channel(b, "update_model"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "update_model before initializePixVals");
 	TRY(need_image(b));
@@ -329,6 +328,34 @@ static int mi_grad(mtfhip_batch *b, int curr) {
 }
 
 /* ------------------------------------------------------------------ AppearanceModel */
+/* NCC's and MI's rows of kAmOps: the functions above with the lazy-state bookkeeping of the per-function entry points */
+static int ncc_op_update_similarity(mtfhip_batch *b, int) { int rc = ncc_update_similarity(b); b->lz.df0_it_ver = b->lz.ver[MTFHIP_BUF_IT]; return rc; }
+static int ncc_op_grad(mtfhip_batch *b, int which) { int rc = ncc_update_grad(b, which); stale_clear(b, !which, which != 0); return rc; }
+static int mi_op_update_similarity(mtfhip_batch *b, int prereq_only) {   /* MI::updateSimilarity MI.cc:346-382 */
+	TRY(mi_hist_pass(b, 1, 0));
+	b->lz.df0_it_ver = b->lz.ver[MTFHIP_BUF_IT];
+	if (!prereq_only) TRY(mi_read_f(b));
+	return MTFHIP_OK;
+}
+/* What updateSimilarity, updateInitGrad / updateCurrGrad (which 0 / 1) and cmptInitHessian / cmptCurrHessian / cmptSelfHessian (kind 0 / 1 / 2,
+ * into H [B][S x S]) run for each model (indexed by MTFHIP_AM_*).  A null entry: the SSD body of the entry point -- SSD and the SCV family */
+struct AmOps {
+	int (*update_similarity)(mtfhip_batch *b, int prereq_only);
+	int (*grad)(mtfhip_batch *b, int which);
+	int (*hessian)(mtfhip_batch *b, int j_buf, int kind, double *H);
+};
+static const AmOps kAmOps[] = {
+	{nullptr, nullptr, nullptr},
+	{ncc_op_update_similarity, ncc_op_grad, ncc_hessian},
+	{mi_op_update_similarity, mi_grad, mi_hessian},
+	{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr},
+	{spss_update_similarity, spss_update_grad, spss_hessian},
+	{ssim_update_similarity, ssim_update_grad, ssim_hessian},
+	{ccre_update_similarity, ccre_grad, ccre_hessian},
+};
+static_assert(sizeof(kAmOps) / sizeof(kAmOps[0]) == MTFHIP_AM_CCRE + 1, "one row of operations per MTFHIP_AM_*");
+static inline const AmOps &am_ops(const mtfhip_batch *b) { return kAmOps[b->desc.am]; }
+
 static int am_supported(mtfhip_batch *b, const char *fn) {
 	if (b->desc.am >= 0 && b->desc.am < (int)(sizeof(kAmTraits) / sizeof(kAmTraits[0]))) return MTFHIP_OK;   /* (every model with a row of traits) */
 	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s :: appearance model %d is not available on the device path yet", fn, b->desc.am);
@@ -417,17 +444,7 @@ int mtfhip_am_update_similarity(mtfhip_batch *b, int prereq_only) {
 	return do_update_similarity(b, prereq_only);
 }
 static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
-	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_similarity(b); b->lz.df0_it_ver = b->lz.ver[MTFHIP_BUF_IT]; return rc; }
-	if (b->desc.am == MTFHIP_AM_MI) {
-		/* MI::updateSimilarity MI.cc:346-382 */
-		TRY(mi_hist_pass(b, 1, 0));
-		b->lz.df0_it_ver = b->lz.ver[MTFHIP_BUF_IT];
-		if (!prereq_only) TRY(mi_read_f(b));
-		return MTFHIP_OK;
-	}
-	if (ccre_am(b)) return ccre_update_similarity(b, prereq_only);
-	if (spss_am(b)) return spss_update_similarity(b, prereq_only);
-	if (ssim_am(b)) return ssim_update_similarity(b, prereq_only);
+	if (const auto op = am_ops(b).update_similarity) return op(b, prereq_only);
 	/* SCV / LSCV::updateSimilarity (SCV.cc:194-230, LSCV.cc:263-304): the intensity map(s) from It and I0_orig, I0 re-mapped, then
 	 * SSDBase::updateSimilarity */
 	TRY(imap_before_pass(b, nullptr, 0, nullptr, nullptr, 1, b->first_iter != 0, b->ctx->stream, nullptr));
@@ -444,11 +461,7 @@ static int do_update_similarity(mtfhip_batch *b, int prereq_only) {
 	return MTFHIP_OK;
 }
 static int do_update_curr_grad(mtfhip_batch *b) {
-	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 1); stale_clear(b, false, true); return rc; }
-	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 1);
-	if (ccre_am(b)) return ccre_grad(b, 1);
-	if (spss_am(b)) return spss_update_grad(b, 1);
-	if (ssim_am(b)) return ssim_update_grad(b, 1);
+	if (const auto op = am_ops(b).grad) return op(b, 1);
 	if (b->lz.df0_stale) TRY(ensure_one(b, false));
 	TimedScope ts(b->ctx, "negate");
 	launch_negate(b->buf[MTFHIP_BUF_DF_DI0], b->buf[MTFHIP_BUF_DF_DIT], (size_t)b->N * b->B, b->ctx->stream);
@@ -476,11 +489,7 @@ int mtfhip_am_update_init_grad(mtfhip_batch *b) {
 		return MTFHIP_OK;
 	}
 	FLUSH(b);
-	if (b->desc.am == MTFHIP_AM_NCC) { int rc = ncc_update_grad(b, 0); stale_clear(b, true, false); return rc; }
-	if (b->desc.am == MTFHIP_AM_MI) return mi_grad(b, 0);
-	if (ccre_am(b)) return ccre_grad(b, 0);
-	if (spss_am(b)) return spss_update_grad(b, 0);
-	if (ssim_am(b)) return ssim_update_grad(b, 0);
+	if (const auto op = am_ops(b).grad) return op(b, 0);
 	return MTFHIP_OK;
 }
 int mtfhip_am_get_similarity(mtfhip_batch *b, double *f) {
@@ -884,56 +893,29 @@ static int gram_to_host(mtfhip_batch *b, int j_buf, double *H, double scale, boo
 	}
 	return MTFHIP_OK;
 }
-int mtfhip_am_cmpt_init_hessian(mtfhip_batch *b, int j0_buf, double *H) {
+/* cmptInitHessian / cmptCurrHessian / cmptSelfHessian (kind 0 / 1 / 2) of the Jacobian in j_buf; fn, ref: the entry point's and the reference's name */
+static int cmpt_hessian(mtfhip_batch *b, int j_buf, int kind, double *H, const char *fn, const char *ref) {
 	FLUSH_AM(b);
-	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_init_hessian: NULL argument");
-	TRY(am_supported(b, "cmptInitHessian"));
-	TRY(j_ready(b, j0_buf, "cmptInitHessian"));
-	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, j0_buf, 0, H);
-	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, j0_buf, 0, H);
-	if (ccre_am(b)) return ccre_hessian(b, j0_buf, 0, H);
-	if (spss_am(b)) return spss_hessian(b, j0_buf, SPSS_W_INIT, H);
-	if (ssim_am(b)) return ssim_hessian(b, j0_buf, NCC_H_INIT, H);
-	return gram_to_host(b, j0_buf, H, -1.0, false);
+	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
+	TRY(am_supported(b, ref));
+	TRY(j_ready(b, j_buf, ref));
+	if (const auto op = am_ops(b).hessian) return op(b, j_buf, kind, H);
+	return gram_to_host(b, j_buf, H, -1.0, false);
 }
-int mtfhip_am_cmpt_curr_hessian(mtfhip_batch *b, int jt_buf, double *H) {
-	FLUSH_AM(b);
-	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_curr_hessian: NULL argument");
-	TRY(am_supported(b, "cmptCurrHessian"));
-	TRY(j_ready(b, jt_buf, "cmptCurrHessian"));
-	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 1, H);
-	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 1, H);
-	if (ccre_am(b)) return ccre_hessian(b, jt_buf, 1, H);
-	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_CURR, H);
-	if (ssim_am(b)) return ssim_hessian(b, jt_buf, NCC_H_CURR, H);
-	return gram_to_host(b, jt_buf, H, -1.0, false);
-}
-int mtfhip_am_cmpt_self_hessian(mtfhip_batch *b, int jt_buf, double *H) {
-	FLUSH_AM(b);
-	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_self_hessian: NULL argument");
-	TRY(am_supported(b, "cmptSelfHessian"));
-	TRY(j_ready(b, jt_buf, "cmptSelfHessian"));
-	if (b->desc.am == MTFHIP_AM_NCC) return ncc_hessian(b, jt_buf, 2, H);
-	if (b->desc.am == MTFHIP_AM_MI) return mi_hessian(b, jt_buf, 2, H);
-	if (ccre_am(b)) return ccre_hessian(b, jt_buf, 2, H);
-	if (spss_am(b)) return spss_hessian(b, jt_buf, SPSS_W_SELF, H);
-	if (ssim_am(b)) return ssim_hessian(b, jt_buf, NCC_H_SELF, H);
-	return gram_to_host(b, jt_buf, H, -1.0, false);
-}
+int mtfhip_am_cmpt_init_hessian(mtfhip_batch *b, int j0_buf, double *H) { return cmpt_hessian(b, j0_buf, 0, H, "cmpt_init_hessian", "cmptInitHessian"); }
+int mtfhip_am_cmpt_curr_hessian(mtfhip_batch *b, int jt_buf, double *H) { return cmpt_hessian(b, jt_buf, 1, H, "cmpt_curr_hessian", "cmptCurrHessian"); }
+int mtfhip_am_cmpt_self_hessian(mtfhip_batch *b, int jt_buf, double *H) { return cmpt_hessian(b, jt_buf, 2, H, "cmpt_self_hessian", "cmptSelfHessian"); }
 int mtfhip_am_cmpt_sum_of_hessians(mtfhip_batch *b, int j0_buf, int jt_buf, double *H) {
 	FLUSH_AM(b);
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_sum_of_hessians: NULL argument");
 	TRY(am_supported(b, "cmptSumOfHessians"));
 	TRY(j_ready(b, j0_buf, "cmptSumOfHessians"));
 	TRY(j_ready(b, jt_buf, "cmptSumOfHessians"));
-	if (!ssd_like(b)) {
+	if (const auto op = am_ops(b).hessian) {
 		/* generic AppearanceModel::cmptSumOfHessians AppearanceModel.h:196-208 */
 		std::vector<double> H0((size_t)b->B * b->S * b->S);
-		if (b->desc.am == MTFHIP_AM_NCC) { TRY(ncc_hessian(b, j0_buf, 0, H0.data())); TRY(ncc_hessian(b, jt_buf, 1, H)); }
-		else if (spss_am(b)) { TRY(spss_hessian(b, j0_buf, SPSS_W_INIT, H0.data())); TRY(spss_hessian(b, jt_buf, SPSS_W_CURR, H)); }
-		else if (ssim_am(b)) { TRY(ssim_hessian(b, j0_buf, NCC_H_INIT, H0.data())); TRY(ssim_hessian(b, jt_buf, NCC_H_CURR, H)); }
-		else if (ccre_am(b)) { TRY(ccre_hessian(b, j0_buf, 0, H0.data())); TRY(ccre_hessian(b, jt_buf, 1, H)); }
-		else { TRY(mi_hessian(b, j0_buf, 0, H0.data())); TRY(mi_hessian(b, jt_buf, 1, H)); }
+		TRY(op(b, j0_buf, 0, H0.data()));
+		TRY(op(b, jt_buf, 1, H));
 		for (size_t i = 0; i < H0.size(); ++i) H[i] += H0[i];
 		return MTFHIP_OK;
 	}
@@ -1080,10 +1062,7 @@ static int add_second_order(mtfhip_batch *b, int d2a, int d2b, const double *dev
 /* SSDBase.cc:313-343 ; NCC.cc:391-400 ; MI.cc:659-673 */
 int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
-	TRY(scv_refuse(b, "cmpt_init_hessian (second order)", 1));
-	TRY(spss_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ssim_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ccre_refuse(b, "cmpt_init_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(am_refuse(b, "cmpt_init_hessian (second order)", AM_AT_SEC_ORD_HESS));
 	TRY(lowdof_refuse(b, "cmpt_init_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_init_hessian(b, j0_buf, H));
@@ -1092,10 +1071,7 @@ int mtfhip_am_cmpt_init_hessian2(mtfhip_batch *b, int j0_buf, int d2_buf, double
 /* SSDBase.cc:345-375 ; NCC.cc:401-410 ; MI.cc:680-694 */
 int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
-	TRY(scv_refuse(b, "cmpt_curr_hessian (second order)", 1));
-	TRY(spss_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ssim_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ccre_refuse(b, "cmpt_curr_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(am_refuse(b, "cmpt_curr_hessian (second order)", AM_AT_SEC_ORD_HESS));
 	TRY(lowdof_refuse(b, "cmpt_curr_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	TRY(mtfhip_am_cmpt_curr_hessian(b, jt_buf, H));
@@ -1104,10 +1080,7 @@ int mtfhip_am_cmpt_curr_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 /* SSD: first order only (SSDBase.h:95-98) ; NCC: am_func_not_implemeted (AppearanceModel.h:188-191) ; MI.cc:696-733 */
 int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double *H) {
 	FLUSH_AM(b);
-	TRY(scv_refuse(b, "cmpt_self_hessian (second order)", 1));
-	TRY(spss_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ssim_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ccre_refuse(b, "cmpt_self_hessian (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(am_refuse(b, "cmpt_self_hessian (second order)", AM_AT_SEC_ORD_HESS));
 	TRY(lowdof_refuse(b, "cmpt_self_hessian (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_self_hessian (second order): NULL argument");
@@ -1124,10 +1097,7 @@ int mtfhip_am_cmpt_self_hessian2(mtfhip_batch *b, int jt_buf, int d2_buf, double
 /* SSDBase.cc:377-415 (both pixel Hessians weighted by df_dI0) ; NCC / MI: generic AppearanceModel.h:209-219 */
 int mtfhip_am_cmpt_sum_of_hessians2(mtfhip_batch *b, int j0_buf, int jt_buf, int d20_buf, int d2t_buf, double *H) {
 	FLUSH_AM(b);
-	TRY(scv_refuse(b, "cmpt_sum_of_hessians (second order)", 1));
-	TRY(spss_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ssim_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
-	TRY(ccre_refuse(b, "cmpt_sum_of_hessians (second order)", " with second-order Hessians is not available on the device path (first-order only)"));
+	TRY(am_refuse(b, "cmpt_sum_of_hessians (second order)", AM_AT_SEC_ORD_HESS));
 	TRY(lowdof_refuse(b, "cmpt_sum_of_hessians (second order)"));
 	if (b) TRY(ensure_df(b));   /* the second-order terms are weighted by df_dI */
 	if (!b || !H) return fail(MTFHIP_ERR_INVALID_ARG, "cmpt_sum_of_hessians (second order): NULL argument");

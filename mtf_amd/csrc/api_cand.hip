@@ -17,12 +17,6 @@ static const double *template_hull(const mtfhip_batch *b, double *hull_buf) {
 	}
 	return hull_buf;
 }
-/* SCV, RSCV, LSCV and LRSCV have no per-candidate form: the refusal of the entry point fn, "<fn>: <model><what> (<why>)" */
-int refuse_intensity_mapped(const mtfhip_batch *b, const char *fn, const char *what) {
-	const AmTraits &am = am_traits(b->desc.am);
-	if (!am.no_candidates) return MTFHIP_OK;
-	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s%s (%s)", fn, am.name, what, am.no_candidates);
-}
 
 /* ------------------------------------------------------------------ candidate scoring */
 /* candidates [lo, lo + cnt) of dev_states: weight (the AM's likelihood, or PF's Gaussian / reciprocal mapping of the similarity) and
@@ -69,11 +63,8 @@ int mtfhip_score_candidates_dev(mtfhip_batch *b, const double *dev_states, int C
 	FLUSH_AM(b);   /* (every candidate warps the template grid itself: CURR_PTS are not read) */
 	if (!b || !dev_states) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "score_candidates"));
-	TRY(spss_refuse(b, "score_candidates", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "score_candidates", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "score_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
+	TRY(am_refuse(b, "score_candidates", AM_AT_SCORE_CANDIDATES));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
-	TRY(refuse_intensity_mapped(b, "score_candidates", " candidates are not available"));
 	if (!b->init_pix_vals) return fail(MTFHIP_ERR_LOGIC, "score_candidates before the template was initialised");
 	TRY(need_image(b));
 	TimedScope ts(b->ctx, "score_candidates");
@@ -84,9 +75,7 @@ int mtfhip_score_candidates(mtfhip_batch *b, const double *states, int C, double
 	FLUSH(b);
 	if (!b || !states) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "score_candidates"));
-	TRY(spss_refuse(b, "score_candidates", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "score_candidates", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "score_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
+	TRY(am_refuse(b, "score_candidates", AM_AT_SCORE_CANDIDATES));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "score_candidates: n_candidates must be positive");
 	size_t need = (size_t)C * (b->S + 2);
 	HIP_TRY(b->d_cand.reserve(need));
@@ -104,12 +93,9 @@ int mtfhip_sample_candidates_dev(mtfhip_batch *b, const double *dev_states, int 
 	FLUSH(b);
 	if (!b || !dev_states || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "sample_candidates"));
-	TRY(spss_refuse(b, "sample_candidates", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "sample_candidates", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "sample_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
+	TRY(am_refuse(b, "sample_candidates", AM_AT_SAMPLE_CANDIDATES));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	if (b->desc.am == MTFHIP_AM_MI) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "sample_candidates: MI distance features (5 x N B-spline rows) are not available");
-	TRY(refuse_intensity_mapped(b, "sample_candidates", " distance features are not available"));
 	TRY(single_channel(b, "sample_candidates"));
 	if (!b->have_corners) return fail(MTFHIP_ERR_LOGIC, "sample_candidates before set_corners");
 	TRY(need_image(b));
@@ -121,9 +107,7 @@ int mtfhip_sample_candidates(mtfhip_batch *b, const double *states, int C, doubl
 	FLUSH(b);
 	if (!b || !states || !features) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: NULL argument");
 	TRY(lowdof_refuse(b, "sample_candidates"));
-	TRY(spss_refuse(b, "sample_candidates", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "sample_candidates", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "sample_candidates", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
+	TRY(am_refuse(b, "sample_candidates", AM_AT_SAMPLE_CANDIDATES));
 	if (C <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "sample_candidates: n_samples must be positive");
 	Dev<double> d_states, d_feat;   /* (released on every return; the release waits for what is in flight) */
 	HIP_TRY(d_states.reserve((size_t)C * b->S));
@@ -148,10 +132,7 @@ int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *d
 	FLUSH(b);
 	if (!b || !d || !dev_features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
 	TRY(lowdof_refuse(b, "nn_dataset"));
-	TRY(spss_refuse(b, "nn_dataset", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "nn_dataset", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "nn_dataset", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
-	TRY(refuse_intensity_mapped(b, "nn_dataset", " is not available on the NN dataset"));
+	TRY(am_refuse(b, "nn_dataset", AM_AT_NN_DATASET));
 	if (d->n_samples <= 0 || row_lo < 0 || row_count < 0 || row_lo + row_count > d->n_samples)
 		return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: rows [%d, %d) of %d samples", row_lo, row_lo + row_count, d->n_samples);
 	if (d->additive_update) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_dataset: additive_update (NNParams, NT/NN.cc:150-152): the compositional form only");
@@ -190,9 +171,7 @@ int mtfhip_nn_dataset_dev(mtfhip_batch *b, const mtfhip_nn_desc *d, const double
 int mtfhip_nn_dataset(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *perturbations_in, double *perturbations_out, double *features) {
 	if (!b || !d || !features) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: NULL argument");
 	TRY(lowdof_refuse(b, "nn_dataset"));
-	TRY(spss_refuse(b, "nn_dataset", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "nn_dataset", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "nn_dataset", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
+	TRY(am_refuse(b, "nn_dataset", AM_AT_NN_DATASET));
 	if (d->n_samples <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "nn_dataset: n_samples must be positive");
 	int F = 0;
 	TRY(mtfhip_nn_feature_size(b, &F));

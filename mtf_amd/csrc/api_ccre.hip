@@ -10,11 +10,6 @@
 #include "mtfhip_api_internal.h"
 #include "mtfhip_ccre_tables.h"
 
-int ccre_refuse(const mtfhip_batch *b, const char *fn, const char *what) {
-	if (!b || !ccre_am(b)) return MTFHIP_OK;
-	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: CCRE%s" MTFHIP_FIRST_ORDER_SERVED, fn, what);
-}
-
 static int ccre_read_f(mtfhip_batch *b, bool as_max) {
 	std::vector<double> f(b->B);
 	HIP_TRY(hipMemcpyAsync(f.data(), b->d_mi_f, sizeof(double) * b->B, hipMemcpyDeviceToHost, b->ctx->stream));

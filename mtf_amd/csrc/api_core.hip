@@ -322,7 +322,7 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	/* (n_bins where the model reads it: 2 .. max_bins, and where bins_default a value <= 0 stands for max_bins) */
 	if (am.max_bins && (d->mi_n_bins > am.max_bins || (am.bins_default ? d->mi_n_bins == 1 : d->mi_n_bins < 2)))
 		return fail(MTFHIP_ERR_INVALID_ARG, "%s: n_bins %d outside [2, %d]", am.name, d->mi_n_bins, am.max_bins);
-	if (am.no_3ch && d->n_channels == 3) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s", am.no_3ch);
+	if (d->n_channels == 3) TRY(am_refuse(d->am, "batch_create", AM_AT_3_CHANNELS));
 	if (d->am == MTFHIP_AM_MI && d->mi_partition_of_unity && d->mi_n_bins < 4) /* MI.cc:83-87 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "MI::Too few bins %d specified to enforce partition of unity constraint", d->mi_n_bins);
 	if (d->am == MTFHIP_AM_CCRE && d->mi_partition_of_unity && d->mi_n_bins < 4) /* CCRE.cc:87-91 */
@@ -405,7 +405,7 @@ int mtfhip_batch_create(mtfhip_ctx *c, const mtfhip_patch_desc *d, int n_targets
 	ALLOC(b->d_h0, (size_t)64 * n_targets);
 	ALLOC(b->d_h0inv, (size_t)64 * n_targets);
 	ALLOC(b->d_colmean, (size_t)8 * n_targets);
-	if (d->am == MTFHIP_AM_MI || d->am == MTFHIP_AM_CCRE) {
+	if (am.rows == AM_ROWS_MI) {   /* (MI and CCRE) */
 		const int nb = d->mi_n_bins;
 		b->mi_row_len = std::max(std::max(nb + 2 * nb * nb, 36 + nb * nb * b->S), nb <= 10 ? mi_fast_row_len(nb) : 0);   /* widest of the MI partial rows (fused passes incl.) */
 		/* CCRE: three histogram rows side by side (launch_ccre_tables), or a Hessian row with the init kind's nb x S block behind it */

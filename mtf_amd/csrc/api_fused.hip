@@ -37,30 +37,17 @@ int check_sm(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const char *fn) {
 		 * initialize / setRegion).  Eight bins (the weights are read from the 8-bin gradient-factor tables). */
 		return MTFHIP_OK;
 	}
-	if (spss_am(b)) {
-		/* SPSS: first-order Hessians; the pass fills ONE weighted Gram matrix per row (kernels_fused_spss.hip), and ESM's SumOfStd is the mean
-		 * of two with different weights and rows (cmptInitHessian(J0) + cmptCurrHessian(Jt), AppearanceModel.h:194-206) */
-		if (sm->sec_ord_hess) return spss_refuse(b, fn, " with second-order Hessians is not available on the device path (first-order only)");
-		if (sm->sm == MTFHIP_SM_ESM && sm->hess_type == 4)
-			return spss_refuse(b, fn, " with ESM hess_type SumOfStd needs two weighted Gram matrices in one pass and is not available on the fused entry points "
-				"(cmpt_sum_of_hessians serves it)");
-		return MTFHIP_OK;
-	}
-	if (ccre_am(b)) {
-		/* CCRE: every first-order Jacobian / Hessian type MI's materialising iteration serves, SumOfStd as two Hessian passes; its second-order
-		 * forms (CCRE.cc:797-865) weight the pixel Hessian by gradients no pass of this path hands on */
-		if (sm->sec_ord_hess) return ccre_refuse(b, fn, " with second-order Hessians is not available on the device path (first-order only)");
-		return MTFHIP_OK;
-	}
-	if (ssim_am(b)) {
-		/* SSIM: every first-order type NCC has, from the same rows (ssim_h, mtfhip_sm_system.h); its second-order Hessians weight the pixel
-		 * Hessian by df_dI (SSIM.cc:187-198, 256-268), which no pass accumulates for it */
-		if (sm->sec_ord_hess) return ssim_refuse(b, fn, " with second-order Hessians is not available on the device path (first-order only)");
-		return MTFHIP_OK;
-	}
-	TRY(scv_refuse(b, fn, sm->sec_ord_hess));   /* (SCV: SSD on the re-mapped template, first order) */
-	if (!ssd_like(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: unknown appearance model", fn);
-	return MTFHIP_OK;
+	/* Second-order Hessians of SPSS, SSIM, CCRE and the SCV family: CCRE's forms (CCRE.cc:797-865) weight the pixel Hessian by gradients no
+	 * pass of this path hands on, SSIM's by df_dI (SSIM.cc:187-198, 256-268), which no pass accumulates for it; SCV is SSD on the re-mapped
+	 * template, first order.  First order: CCRE has every type MI's materialising iteration serves (SumOfStd as two Hessian passes), SSIM
+	 * every type NCC has, from the same rows (ssim_h, mtfhip_sm_system.h) */
+	if (sm->sec_ord_hess) TRY(am_refuse(b, fn, AM_AT_SEC_ORD_HESS));
+	/* SPSS: the pass fills ONE weighted Gram matrix per row (kernels_fused_spss.hip), and ESM's SumOfStd is the mean of two with different
+	 * weights and rows (cmptInitHessian(J0) + cmptCurrHessian(Jt), AppearanceModel.h:194-206) */
+	if (spss_am(b) && sm->sm == MTFHIP_SM_ESM && sm->hess_type == 4)
+		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SPSS with ESM hess_type SumOfStd needs two weighted Gram matrices in one pass and is not available on the fused entry points "
+			"(cmpt_sum_of_hessians serves it)" MTFHIP_FIRST_ORDER_SERVED, fn);
+	return MTFHIP_OK;   /* (every model mtfhip_batch_create accepts has its row of traits) */
 }
 
 /* inverse of a definite S x S matrix (column-major) by Gauss-Jordan on the diagonally scaled system */
@@ -122,7 +109,7 @@ static int init_self_hessian(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *
 	/* SPSS: the constant Hessian of InitialSelf is cmptSelfHessian at It = I0 (SPSS.cc:91-101, :221-225).  At initialize the It buffer holds I0;
 	 * a setRegion that refreshes H0 comes behind a loop whose last pass may or may not have materialised It, so the weight is taken from I0
 	 * itself: the same H0 whatever the loop wrote */
-	if (spss_am(b)) { FLUSH_AM(b); return spss_hessian(b, MTFHIP_BUF_J0, SPSS_W_SELF0, H0); }
+	if (spss_am(b)) { FLUSH_AM(b); return spss_weighted_hessian(b, MTFHIP_BUF_J0, SPSS_W_SELF0, H0); }
 	/* SSIM: cmptSelfHessian(J0) at It = I0 (SSIM.cc:270-287) is a function of the template's moments (every caller takes them in front: th[].ncc_tm
 	 * is current); no pixel pass of its own, and the same H0 whatever a loop left in the It buffer */
 	if (ssim_am(b)) return ssim_h0(b, H0);

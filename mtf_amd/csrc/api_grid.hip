@@ -64,10 +64,7 @@ static int grid_reinit_fused(mtfhip_batch *b, const mtfhip_sm_desc *sm, const do
 int mtfhip_grid_update(mtfhip_batch *b, const mtfhip_sm_desc *sm, const double *regions_2x4, int *n_iters, double *corners_2x4, double *centroids) {
 	if (!b || !sm || !regions_2x4) return fail(MTFHIP_ERR_INVALID_ARG, "grid_update: NULL argument");
 	TRY(lowdof_refuse(b, "grid_update"));
-	TRY(spss_refuse(b, "grid_update", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "grid_update", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "grid_update", " is not available on this entry point"));
-	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "grid_update: %s is not available on the grid tracker", intensity_mapped_name(b));
+	TRY(am_refuse(b, "grid_update", AM_AT_GRID));
 	const size_t B = (size_t)b->B;
 	static thread_local std::vector<double> in, out;
 	in.resize(8 * B); out.resize(8 * B);
@@ -91,10 +88,7 @@ static inline void centroid_f(float *dst, const double *c) {
 static int grid_batch_ok(const mtfhip_batch *b, const mtfhip_grid_desc *g, const char *fn) {
 	if (!b || !g) return fail(MTFHIP_ERR_INVALID_ARG, "%s: NULL argument", fn);
 	TRY(lowdof_refuse(b, fn));   /* (the grid tracker's one-launch kernels solve what they accumulate: no projection) */
-	TRY(spss_refuse(b, fn, " is not available on this entry point"));
-	TRY(ssim_refuse(b, fn, " is not available on this entry point"));
-	TRY(ccre_refuse(b, fn, " is not available on this entry point"));
-	if (intensity_mapped(b)) return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s is not available on the grid tracker", fn, intensity_mapped_name(b));
+	TRY(am_refuse(b, fn, AM_AT_GRID));
 	if (g->grid_size_x <= 0 || g->grid_size_y <= 0 || g->grid_size_x * g->grid_size_y != b->B)   /* GridTracker.cc:124-129 */
 		return fail(MTFHIP_ERR_INVALID_ARG, "%s: mismatch between the grid dimensions (%d x %d) and the batch's %d patch trackers", fn, g->grid_size_x, g->grid_size_y, b->B);
 	return MTFHIP_OK;

@@ -298,14 +298,6 @@ int imap_update_pix_vals(mtfhip_batch *b, const double *dp) {
 	return MTFHIP_OK;
 }
 
-int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess) {
-	if (!b || !intensity_mapped(b)) return MTFHIP_OK;
-	if (sec_ord_hess)
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: %s with second-order Hessians is not available on the device path (first-order only)", fn,
-			intensity_mapped_name(b));
-	return MTFHIP_OK;
-}
-
 /* mtfhip_batch_set_lscv / _set_lrscv for the model am, named fn in the messages */
 static int set_localized(mtfhip_batch *b, int am, const char *fn, int nx, int ny, int sx, int sy, int affine_mapping, int once_per_frame,
 	int weighted_mapping) {

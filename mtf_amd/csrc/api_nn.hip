@@ -35,15 +35,11 @@ int mtfhip_nn_create(mtfhip_batch *b, int n_samples, mtfhip_nn **out) {
 	if (!b || !out) return fail(MTFHIP_ERR_INVALID_ARG, "nn_create: NULL argument");
 	*out = nullptr;
 	TRY(lowdof_refuse(b, "nn_create"));
-	TRY(spss_refuse(b, "nn_create", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "nn_create", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "nn_create", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
+	TRY(am_refuse(b, "nn_create", AM_AT_NN_CREATE));
 	if (n_samples <= 0) return fail(MTFHIP_ERR_INVALID_ARG, "nn_create: n_samples must be positive");
 	if (b->B != 1) return fail(MTFHIP_ERR_INVALID_ARG, "nn_create: one template per batch (the batch has %d targets)", b->B);
 	if (b->desc.am == MTFHIP_AM_MI)
 		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_create: MI is not available on the NN search (MIDist, MI.cc:749, is a joint histogram per dataset row)");
-	if (intensity_mapped(b))
-		return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "nn_create: %s is not available on the NN search (its distance functor is a per-candidate intensity map)", intensity_mapped_name(b));
 	int F = 0;
 	TRY(mtfhip_nn_feature_size(b, &F));
 	if (F > kNnSearchMaxFeat)

@@ -283,10 +283,7 @@ static size_t pf_round_chunk(size_t n) { const size_t c = (size_t)pf_chunk(); re
 int mtfhip_pf_create(mtfhip_batch *b, const mtfhip_pf_desc *d, mtfhip_pf **out) {
 	if (!b || !d || !out) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: NULL argument");
 	TRY(lowdof_refuse(b, "pf_create"));
-	TRY(spss_refuse(b, "pf_create", " is not available on this entry point"));
-	TRY(ssim_refuse(b, "pf_create", " is not available on this entry point"));
-	TRY(ccre_refuse(b, "pf_create", " is not available on this entry point (CCREDist is a per-candidate histogram)"));
-	TRY(refuse_intensity_mapped(b, "pf_create", " is not available on the particle filter"));
+	TRY(am_refuse(b, "pf_create", AM_AT_PF_CREATE));
 	if (b->B != 1) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: the particle filter tracks one target (batch of %d)", b->B);
 	if (d->n_particles < 1) return fail(MTFHIP_ERR_INVALID_ARG, "pf_create: n_particles must be positive");
 	if (d->dynamic_model < 0 || d->dynamic_model > 1 || d->update_type < 0 || d->update_type > 1 || d->likelihood_func < 0 || d->likelihood_func > 2 ||

@@ -5,11 +5,6 @@
  */
 #include "mtfhip_api_internal.h"
 
-int spss_refuse(const mtfhip_batch *b, const char *fn, const char *what) {
-	if (!b || !spss_am(b)) return MTFHIP_OK;
-	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SPSS%s" MTFHIP_FIRST_ORDER_SERVED, fn, what);
-}
-
 /* the weight of the Gram matrix the pass accumulates and the row of its current Jacobian, by search method and Hessian type (NT/FCLK.cc:262-283,
  * NT/ESM.cc:298-377, NT/ICLK.cc:204-252): the self types weight Jt by cmptSelfHessian's factor, the Std types by cmptCurrHessian's (ESM Original:
  * over the mean row, FusedArgs::hess_mean) or, for ICLK, J0 by cmptInitHessian's; InitialSelf reads the constant H0 and ignores the sum */
@@ -41,7 +36,7 @@ int spss_update_grad(mtfhip_batch *b, int curr) {
 	launch_spss_grad(b->view(), b->spss_c, curr, b->buf[curr ? MTFHIP_BUF_DF_DIT : MTFHIP_BUF_DF_DI0], b->ctx->stream);
 	return MTFHIP_OK;
 }
-int spss_hessian(mtfhip_batch *b, int j_buf, int weight, double *H) {
+int spss_weighted_hessian(mtfhip_batch *b, int j_buf, int weight, double *H) {
 	const int nblk = simple_blocks_per_target(b->N), S = b->S;
 	{
 		TimedScope ts(b->ctx, "spss_hessian");
@@ -59,6 +54,11 @@ int spss_hessian(mtfhip_batch *b, int j_buf, int weight, double *H) {
 			}
 	}
 	return MTFHIP_OK;
+}
+/* SPSS::cmptInitHessian / cmptCurrHessian / cmptSelfHessian: kind 0 init, 1 curr, 2 self */
+int spss_hessian(mtfhip_batch *b, int j_buf, int kind, double *H) {
+	static const int weight[3] = {SPSS_W_INIT, SPSS_W_CURR, SPSS_W_SELF};
+	return spss_weighted_hessian(b, j_buf, weight[kind], H);
 }
 
 extern "C" {

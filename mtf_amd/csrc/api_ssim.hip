@@ -7,11 +7,6 @@
  */
 #include "mtfhip_api_internal.h"
 
-int ssim_refuse(const mtfhip_batch *b, const char *fn, const char *what) {
-	if (!b || !ssim_am(b)) return MTFHIP_OK;
-	return fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s: SSIM%s" MTFHIP_FIRST_ORDER_SERVED, fn, what);
-}
-
 /* cmptSelfHessian(J0) at It = I0 (SSIM.cc:270-287; NT/ESM.cc:133-141, NT/FCLK.cc:120-128, NT/ICLK.cc:96-118) from th[].ncc_tm, column-major S x S */
 int ssim_h0(const mtfhip_batch *b, double *H0) {
 	const int S = b->S;
@@ -67,6 +62,7 @@ int ssim_update_grad(mtfhip_batch *b, int curr) {
 }
 /* SSIM::cmptInitHessian / cmptCurrHessian / cmptSelfHessian SSIM.cc:144-287 over any Jacobian buffer: one reduction of its moments beside the
  * current patch's (k_ssim_hess), then ssim_hess entry by entry -- the row stands where an NCC pass's stands, the buffer where its Jt does */
+static_assert(NCC_H_INIT == 0 && NCC_H_CURR == 1 && NCC_H_SELF == 2, "kind 0 init, 1 curr, 2 self, as every model's Hessian takes it");
 int ssim_hessian(mtfhip_batch *b, int j_buf, int kind, double *H) {
 	const int nblk = simple_blocks_per_target(b->N), S = b->S;
 	{

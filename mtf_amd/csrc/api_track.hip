@@ -92,7 +92,7 @@ bool iclk_one_launch(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	/* (SCV re-maps its template, RSCV rebuilds its map between the passes: they take the fused launch + finish per pass) */
 	/* (a low-order SSM takes the two-launch loop, whose finish projects the affine system: the one-launch kernels solve what they accumulate) */
 	/* (SPSS: the one-launch kernels accumulate SSD's or NCC's sums; SSIM: NCC's sums, but they solve NCC's system) */
-	return b->C == 1 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && !ssim_am(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
+	return b->C == 1 && !b->lo_ssm && !loop_only(b) && sm->sm == MTFHIP_SM_ICLK && (sm->hess_type == 0 || (sm->hess_type == 2 && b->desc.am == MTFHIP_AM_SSD)) &&
 		b->N <= iclk_one_launch_max_pix();
 }
 
@@ -214,9 +214,7 @@ static bool persist_fits(const mtfhip_batch *b, const mtfhip_sm_desc *sm, const 
 	if (!(e && e[0] == '1') || !b->persist_ok || fa.materialize || b->ctx->n_cus <= 0 || b->B > b->ctx->n_cus || !b->h_pub_dev) return false;
 	if (b->C != 1) return false;   /* (no multi-channel instantiation of the persistent kernel) */
 	if (b->lo_ssm) return false;   /* (the low-order SSMs are served by the two-launch loop only) */
-	if (intensity_mapped(b)) return false;   /* (the template re-map / the current map runs between the passes) */
-	if (spss_am(b)) return false;   /* (SPSS is served by the two-launch loop only: fused_select) */
-	if (ssim_am(b)) return false;   /* (SSIM: NCC's pass, but its own finish -- the two-launch loop only) */
+	if (loop_only(b)) return false;   /* (the SCV family: a re-map runs between the passes; SPSS; SSIM: NCC's pass, but its own finish) */
 	if (b->B > 8) return false;   /* a batch is better served by its own decomposition (eight workgroups per target) */
 	if (sm->max_iters < 2) return false;
 	int nblk, rows;
@@ -459,7 +457,7 @@ static bool track_takes_step(const mtfhip_batch *b, const FusedArgs &fa, int so_
 	const char *e_st = std::getenv("MTFHIP_STEP");   /* (read per call: the tests flip it) */
 	const char *e_mx = std::getenv("MTFHIP_STEP_MAX_TARGETS");
 	const int max_t = e_mx ? std::atoi(e_mx) : 8;
-	return (e_st && e_st[0] == '1') && so_term < 0 && !b->lo_ssm && !intensity_mapped(b) && !spss_am(b) && !ssim_am(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
+	return (e_st && e_st[0] == '1') && so_term < 0 && !b->lo_ssm && !loop_only(b) && n_streams == 1 && b->B <= max_t && track_step_available(b->view(), fa);
 }
 /* one pass of one chunk on its queue: the intensity re-maps, the pixel pass (lean: the non-materialising one), the second-order pass, the finish */
 struct FinishCtl { PhaseCtl pc; HostPublish pub; int prio; };
@@ -691,7 +689,7 @@ static int track_core_impl(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_ite
 		/* tolerance mode + a definite first-order system: the register-resident finish (finish_track_fast_body) */
 		const char *e = std::getenv("MTFHIP_FAST_FINISH");   /* (read per call: the tests compare the two bodies in one process) */
 		const bool enabled = !(e && e[0] == '0');
-		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && !ncc && !mi && !spss_am(b) && !ssim_am(b) && cx.so_term < 0) ? 1 : 0;   /* (SPSS: k_finish_track_spss; SSIM: k_finish_track_ssim) */
+		ts.fast_finish = (enabled && b->math_mode == MTFHIP_MATH_FAST && ssd_like(b) && cx.so_term < 0) ? 1 : 0;   /* (SSD's rows: NCC, MI and CCRE, SPSS and SSIM each have a finish of their own) */
 		/* a low-order SSM: the projection lives in finish_track_body alone (the register-resident body would index its rows at run time);
 		 * its materialising loop keeps every target's last warp for the Jacobian written behind the loop (track_core) */
 		if (b->lo_ssm) { ts.fast_finish = 0; ts.keep_last = (fa.materialize && fa.mode != 2) ? 1 : 0; ts.lo_ssm = b->lo_ssm; ts.SS = ssm_state_size(b->lo_ssm); }

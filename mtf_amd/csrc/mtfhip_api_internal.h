@@ -7,6 +7,7 @@
 #ifndef MTFHIP_API_INTERNAL_H
 #define MTFHIP_API_INTERNAL_H
 #include "mtfhip_internal.h"
+#include "mtfhip_am_served.h"
 
 #include <algorithm>
 #include <chrono>
@@ -29,8 +30,9 @@ void launch_init_grid(const BatchView &bv, const double *dev_w0, int resx, int r
 
 /* ------------------------------------------------------------------ errors */
 extern thread_local std::string g_last_error;   /* one per thread for the whole library; defined in api_core.hip */
+constexpr size_t kErrMsgCap = 512;
 static int fail(int code, const char *fmt, ...) {
-	char buf[512];
+	char buf[kErrMsgCap];
 	va_list ap;
 	va_start(ap, fmt);
 	vsnprintf(buf, sizeof(buf), fmt, ap);
@@ -233,46 +235,10 @@ struct TargetHost {
 	double ncc_tm[NCC_TM_COUNT];
 };
 
-/* What is decided by the appearance model alone, stated once per model (indexed by MTFHIP_AM_*).  rows: whose partial / reduced rows the
- * model's fused passes fill.  max_bins: the limit of mtfhip_patch_desc::mi_n_bins where the model reads it (0: it does not), bins_default:
- * n_bins <= 0 selects max_bins.  The three texts are the model's refusals, NULL where it is served: n_channels 3 at batch_create,
- * mtfhip_am_update_model, and the reason it has no per-candidate form (candidates, particle filter, NN dataset). */
-#define MTFHIP_FIRST_ORDER_SERVED " (served: the first-order per-function AppearanceModel entry points and init_template / set_region / " \
-	"iterate / track / track_region with ESM, FCLK and ICLK)"
-enum { AM_ROWS_SSD, AM_ROWS_NCC, AM_ROWS_MI, AM_ROWS_SPSS };
-struct AmTraits {
-	const char *name;
-	int rows;
-	bool intensity_mapped;
-	int max_bins;
-	bool bins_default;
-	const char *no_3ch, *no_update_model, *no_candidates;
-};
-constexpr AmTraits kAmTraits[] = {
-	{"SSD", AM_ROWS_SSD, false, 0, false, nullptr, nullptr, nullptr},
-	{"NCC", AM_ROWS_NCC, false, 0, false, nullptr, nullptr, nullptr},
-	{"MI", AM_ROWS_MI, false, MI_NB, false, nullptr, "updateModel :: MI has no online template update in the reference either", nullptr},
-	{"SCV", AM_ROWS_SSD, true, kScvMaxBins, true, "SCV with n_channels 3 (MCSCV) is not available on the device path (single channel only)",
-		"updateModel :: SCV is not available on this entry point (the template update would have to refresh I0_orig)",
-		"SCVDist is a per-candidate intensity map"},
-	{"RSCV", AM_ROWS_SSD, true, kRscvMaxBins, true, "RSCV with n_channels 3 (MCRSCV) is not available on the device path (single channel only)",
-		"updateModel :: RSCV is not available on this entry point (the template update would have to refresh its code plane)",
-		"RSCVDist is a per-candidate intensity map"},
-	{"LSCV", AM_ROWS_SSD, true, kLscvMaxBins, true, "LSCV with n_channels 3 (MCLSCV) is not available on the device path (single channel only)",
-		"updateModel :: LSCV is not available on this entry point (the template update would have to refresh I0_orig)",
-		"LSCVDist is a per-candidate intensity map"},
-	{"LRSCV", AM_ROWS_SSD, true, kLscvMaxBins, true, "LRSCV with n_channels 3 is not available (no multi-channel LRSCV exists in the reference either)",
-		"updateModel :: LRSCV is not available on this entry point (the template update would have to refresh its code plane)",
-		"its maps are per-candidate intensity maps"},
-	{"SPSS", AM_ROWS_SPSS, false, 0, false, "SPSS with n_channels 3 (MCSPSS) is not available on the device path (single channel only)",
-		"updateModel: SPSS has no online template update on the device path" MTFHIP_FIRST_ORDER_SERVED, nullptr},
-	{"SSIM", AM_ROWS_NCC, false, 0, false, "SSIM with n_channels 3 (MCSSIM) is not available on the device path (single channel only)",
-		"updateModel: SSIM has no online template update (SSIM.cc has none either)" MTFHIP_FIRST_ORDER_SERVED, nullptr},
-	{"CCRE", AM_ROWS_MI, false, MI_NB, false, "CCRE with n_channels 3 (MCCCRE) is not available on the device path (single channel only)",
-		"updateModel: CCRE has no online template update (CCRE.cc has none either)" MTFHIP_FIRST_ORDER_SERVED, nullptr},   /* (candidates: ccre_refuse says why) */
-};
-static_assert(sizeof(kAmTraits) / sizeof(kAmTraits[0]) == MTFHIP_AM_CCRE + 1, "one row of traits per MTFHIP_AM_*");
-static inline const AmTraits &am_traits(int am) { return kAmTraits[am]; }   /* (am: a batch's, checked by mtfhip_batch_create) */
+/* (the bin limits of kAmTraits, mtfhip_am_served.h, are the kernels' own) */
+static_assert(kAmTraits[MTFHIP_AM_MI].max_bins == MI_NB && kAmTraits[MTFHIP_AM_CCRE].max_bins == MI_NB && kAmTraits[MTFHIP_AM_SCV].max_bins == kScvMaxBins &&
+	kAmTraits[MTFHIP_AM_RSCV].max_bins == kRscvMaxBins && kAmTraits[MTFHIP_AM_LSCV].max_bins == kLscvMaxBins && kAmTraits[MTFHIP_AM_LRSCV].max_bins == kLscvMaxBins,
+	"kAmTraits::max_bins");
 
 /* The SCV family (SCV, RSCV, LSCV, LRSCV: SSD behind an intensity map) keeps ONE state: a batch has one appearance model for life.  SCV and
  * LSCV re-map the template (I0 = map(I0_orig)) in front of a similarity update; the reversed models RSCV and LRSCV map the current patch; the
@@ -600,20 +566,32 @@ static inline bool ssd_like(const mtfhip_batch *b) { return am_traits(b->desc.am
 /* SCV, RSCV, LSCV and LRSCV: an intensity map is rebuilt between the fused passes -- the one-launch, persistent and step loops do not take
  * them (fused_select, mtfhip_fused_dispatch.h) */
 static inline bool intensity_mapped(const mtfhip_batch *b) { return am_traits(b->desc.am).intensity_mapped; }
-/* the name of an intensity-mapped model, for the refusals */
+/* the name of an intensity-mapped model, for the messages */
 static inline const char *intensity_mapped_name(const mtfhip_batch *b) { return am_traits(b->desc.am).name; }
 /* ... the localized ones (sub-regions, once_per_frame) and the reversed ones (the map is of the current patch) among them */
-static inline bool imap_localized(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_LSCV || b->desc.am == MTFHIP_AM_LRSCV; }
-static inline bool imap_reversed(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_RSCV || b->desc.am == MTFHIP_AM_LRSCV; }
+static inline bool imap_localized(const mtfhip_batch *b) { return am_traits(b->desc.am).localized; }
+static inline bool imap_reversed(const mtfhip_batch *b) { return am_traits(b->desc.am).reversed; }
+/* of the fused routes only the two-launch loop serves the model: the intensity-mapped ones (the template re-map / the current map runs
+ * between the passes), SPSS (the one-launch kernels accumulate SSD's or NCC's sums) and SSIM (NCC's sums, but they solve NCC's system) */
+static inline bool loop_only(const mtfhip_batch *b) { return am_traits(b->desc.am).loop_only; }
+/* THE refusal of what depends on the model and the place (AM_AT_*) alone: the text of mtfhip_am_served.h for the entry point fn as
+ * MTFHIP_ERR_NOT_IMPLEMENTED, MTFHIP_OK where the model is served (and for a NULL batch: the entry point's own check reports it) */
+static inline int am_refuse(int am, const char *fn, int place, const char *extra = nullptr) {
+	char text[kErrMsgCap];
+	return am_refused(am, place, fn, extra, text, sizeof(text)) ? fail(MTFHIP_ERR_NOT_IMPLEMENTED, "%s", text) : MTFHIP_OK;
+}
+static inline int am_refuse(const mtfhip_batch *b, const char *fn, int place, const char *extra = nullptr) {
+	return b ? am_refuse(b->desc.am, fn, place, extra) : MTFHIP_OK;
+}
 /* SPSS: a model of its own -- no SSD branch serves it, and of the fused routes only the two-launch loop does (fused_select) */
 static inline bool spss_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SPSS; }
-/* api_spss.hip.  spss_refuse: "<fn>: SPSS<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for an SPSS batch, MTFHIP_OK otherwise; spss_args: what a fused
- * launch for the search method sm reads beside FusedArgs; the per-function updateSimilarity, update*Grad and Hessians (weight: SPSS_W_*) */
-int spss_refuse(const mtfhip_batch *b, const char *fn, const char *what);
+/* api_spss.hip.  spss_args: what a fused launch for the search method sm reads beside FusedArgs; the per-function updateSimilarity, update*Grad
+ * and Hessians (spss_weighted_hessian: weight SPSS_W_*; spss_hessian: kind 0 init, 1 curr, 2 self) */
 mtfhip::SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int spss_update_similarity(mtfhip_batch *b, int prereq_only);
 int spss_update_grad(mtfhip_batch *b, int curr);
-int spss_hessian(mtfhip_batch *b, int j_buf, int weight, double *H);
+int spss_weighted_hessian(mtfhip_batch *b, int j_buf, int weight, double *H);
+int spss_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
 /* SSIM: every quantity of SSIM.cc is a function of the raw moments an NCC pass reduces (mtfhip_sm_system.h), so an SSIM batch launches NCC's
  * pass kernels (fused_select) on the two-launch loop, and its own finish (kernels_ssim.hip) */
 static inline bool ssim_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SSIM; }
@@ -621,20 +599,18 @@ static inline bool ssim_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_
  * upload d_ncc_tm, the per-target scalars d_ncc and their refresh.  (What solves NCC's own system -- the one-launch, step and persistent
  * kernels, the fused template initialisation, the second-order pass, the deferred-fusion layer -- asks for MTFHIP_AM_NCC by name.) */
 static inline bool ncc_rows(const mtfhip_batch *b) { return am_traits(b->desc.am).rows == AM_ROWS_NCC; }
-/* api_ssim.hip.  ssim_refuse: "<fn>: SSIM<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for an SSIM batch, MTFHIP_OK otherwise; ssim_h0: the constant self
- * Hessian from the template's moments (th[].ncc_tm must be current); the per-function updateSimilarity, update*Grad and Hessians (kind: NCC_H_*) */
-int ssim_refuse(const mtfhip_batch *b, const char *fn, const char *what);
+/* api_ssim.hip.  ssim_h0: the constant self Hessian from the template's moments (th[].ncc_tm must be current); the per-function
+ * updateSimilarity, update*Grad and Hessians (kind 0 init, 1 curr, 2 self: NCC_H_*) */
 int ssim_h0(const mtfhip_batch *b, double *H0);
 int ssim_update_similarity(mtfhip_batch *b, int prereq_only);
 int ssim_update_grad(mtfhip_batch *b, int curr);
 int ssim_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
 /* CCRE (api_ccre.hip): MI's materialising iteration with cumulative weights on the current patch's side, in the buffers an MI batch has.
  * hist_am: the models whose iteration is a histogram pipeline of its own behind a materialising SSD pass (mi_enqueue / ccre_enqueue) and whose
- * device loop is their own driver.  ccre_refuse: "<fn>: CCRE<what>" as MTFHIP_ERR_NOT_IMPLEMENTED for a CCRE batch, MTFHIP_OK otherwise;
- * ccre_grad: 0 updateInitGrad, 1 updateCurrGrad, 2 initializeGrad; ccre_hessian: kind 0 init, 1 curr, 2 self */
+ * device loop is their own driver (MI and CCRE).  ccre_grad: 0 updateInitGrad, 1 updateCurrGrad, 2 initializeGrad; ccre_hessian: kind 0 init,
+ * 1 curr, 2 self */
 static inline bool ccre_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_CCRE; }
-static inline bool hist_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_MI || b->desc.am == MTFHIP_AM_CCRE; }
-int ccre_refuse(const mtfhip_batch *b, const char *fn, const char *what);
+static inline bool hist_am(const mtfhip_batch *b) { return am_traits(b->desc.am).hist_driver; }
 int ccre_initialize_similarity(mtfhip_batch *b);
 int ccre_update_similarity(mtfhip_batch *b, int prereq_only);
 int ccre_grad(mtfhip_batch *b, int which);
@@ -659,8 +635,6 @@ int imap_capture(mtfhip_batch *b);
 int imap_before_pass(mtfhip_batch *b, const BatchView *chunk, int t0, const int *active, const FusedArgs *fa, int from_it, bool first_pass,
 	hipStream_t st, FusedMaps *out);
 int imap_update_pix_vals(mtfhip_batch *b, const double *dp);
-/* the configurations the family refuses on the device path, for the entry point fn */
-int scv_refuse(const mtfhip_batch *b, const char *fn, int sec_ord_hess);
 static inline BatchView fused_view(mtfhip_batch *b, FusedArgs &fa) {
 	fa.inline_warp = 0;
 	if (b->warps_dirty && b->B == 1) {
@@ -963,11 +937,10 @@ static inline int lowdof_sm_refuse(const mtfhip_batch *b, const mtfhip_sm_desc *
 int alk_init_template(mtfhip_batch *b, const mtfhip_sm_desc *sm);
 int alk_iterate(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, double *g, double *H);
 int alk_track(mtfhip_batch *b, const mtfhip_sm_desc *sm, int *n_iters, double *corners);
-/* api_cand.hip (peer: also store the weights to the other ranks' mailboxes; refuse_intensity_mapped: "<fn>: <model><what> (<why>)") */
+/* api_cand.hip (peer: also store the weights to the other ranks' mailboxes) */
 int nn_dataset_enqueue(mtfhip_batch *b, const mtfhip_nn_desc *d, const double *dev_perturbations_in, double *dev_perturbations_out, double *dev_features,
 	int row_lo, int row_count, const double *base_dev, const int *done);
 int score_block_dev(mtfhip_batch *b, const double *dev_states, int lo, int cnt, double *wts, double *sim, int likelihood_func,
 	double measurement_sigma, double max_similarity, const mtfhip::PfPeerPush *peer = nullptr);
-int refuse_intensity_mapped(const mtfhip_batch *b, const char *fn, const char *what);
 } /* extern "C" */
 #endif

@@ -35,25 +35,15 @@ def _refuse_low_order(what, *ssms):
                                                "NTSearchMethod only (got ssm %d)" % (what, ssm))
 
 
-def _refuse_spss(what, am):
-    """GridTracker, ParticleFilter, NNDataset and NNTracker are not served with the SPSS appearance model (include/mtfhip.h): raised before
-    any device call"""
-    if am == L.AM_SPSS:
-        raise L.FunctionNotImplemented(-2, "%s: the SPSS appearance model is served by LKTracker and NTSearchMethod only" % what)
+# the appearance models that LKTracker and NTSearchMethod alone serve
+_LK_ONLY_AM = {L.AM_SPSS: "SPSS", L.AM_SSIM: "SSIM", L.AM_CCRE: "CCRE"}
 
 
-def _refuse_ssim(what, am):
-    """GridTracker, ParticleFilter, NNDataset and NNTracker are not served with the SSIM appearance model (include/mtfhip.h): raised before
-    any device call"""
-    if am == L.AM_SSIM:
-        raise L.FunctionNotImplemented(-2, "%s: the SSIM appearance model is served by LKTracker and NTSearchMethod only" % what)
-
-
-def _refuse_ccre(what, am):
-    """GridTracker, ParticleFilter, NNDataset and NNTracker are not served with the CCRE appearance model (include/mtfhip.h): raised before
-    any device call"""
-    if am == L.AM_CCRE:
-        raise L.FunctionNotImplemented(-2, "%s: the CCRE appearance model is served by LKTracker and NTSearchMethod only" % what)
+def _refuse_am(what, am):
+    """GridTracker, ParticleFilter, NNDataset and NNTracker are not served with the SPSS, SSIM and CCRE appearance models
+    (include/mtfhip.h): raised before any device call"""
+    if am in _LK_ONLY_AM:
+        raise L.FunctionNotImplemented(-2, "%s: the %s appearance model is served by LKTracker and NTSearchMethod only" % (what, _LK_ONLY_AM[am]))
 
 
 class LKTracker:
@@ -441,9 +431,7 @@ class GridTracker:
                  reset_at_each_frame=1, dyn_patch_size=0, patch_centroid_inside=1, grid_ssm=L.SSM_HOMOGRAPHY, estimator=None,
                  grid_size_y=None, patch_size_y=None, fb_err_thresh=0.0, fb_reinit=1, n_model_pts=4, est_params=None, est_seed=1, **sm_params):
         _refuse_low_order("GridTracker", ssm, grid_ssm)
-        _refuse_spss("GridTracker", am)
-        _refuse_ssim("GridTracker", am)
-        _refuse_ccre("GridTracker", am)
+        _refuse_am("GridTracker", am)
         self.ctx = ctx
         # est_params (_lib.est_params(...) = SSMEstimatorParams): the device RANSAC / LMedS estimator (Context.estimate_warp_from_pts) takes the
         # place of `estimator`; pix_mask / est_ok / est_result follow every update (GridTracker.cc:269, 332-340); frame f draws from est_seed + f
@@ -836,9 +824,7 @@ class ParticleFilter:
         156-165, 214-227)"""
         import ctypes as C
         _refuse_low_order("ParticleFilter", ssm)
-        _refuse_spss("ParticleFilter", am)
-        _refuse_ssim("ParticleFilter", am)
-        _refuse_ccre("ParticleFilter", am)
+        _refuse_am("ParticleFilter", am)
         # seed 0 = "draw one" (below) -- but only an unsharded filter may: the ranks of a sharded one must propose identical particles
         # (each scores a block of ITS proposals, the all-gather mixes the weights), so there seed 0 is refused before anything is
         # created (mtfhip_pf_set_comm cross-checks the seeds of all ranks as well)
@@ -1065,9 +1051,7 @@ class NNDataset:
     def __init__(self, ctx, am=L.AM_SSD, ssm=L.SSM_HOMOGRAPHY, resx=50, resy=50, n_samples=1000,
                  ssm_sigma=(0.01, 0.01, 2.0, 0.01, 0.01, 2.0, 1e-5, 1e-5), ssm_mean=None, seed=0, am_params=None, distr_n_samples=None):
         _refuse_low_order("NNDataset", ssm)
-        _refuse_spss("NNDataset", am)
-        _refuse_ssim("NNDataset", am)
-        _refuse_ccre("NNDataset", am)
+        _refuse_am("NNDataset", am)
         self.batch = Batch(ctx, am, ssm, resx, resy, 1, **(am_params or {}))
         self.S = self.batch.S
         self.n = int(n_samples)
@@ -1193,9 +1177,7 @@ class NNTracker:
                  seed=0, am_params=None, index="exact", gnn_params=None):
         self._h = None
         _refuse_low_order("NNTracker", ssm)
-        _refuse_spss("NNTracker", am)
-        _refuse_ssim("NNTracker", am)
-        _refuse_ccre("NNTracker", am)
+        _refuse_am("NNTracker", am)
         if index not in ("exact", "gnn"):
             raise ValueError("NNTracker: index must be 'exact' or 'gnn'")
         self.index, self.gnn_params = index, dict(gnn_params or {})

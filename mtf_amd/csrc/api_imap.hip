@@ -1,7 +1,7 @@
 /*
  * api_imap.hip -- the SCV family's own state and hooks: SCV, RSCV, LSCV and LRSCV (AM/src/SCV.cc, RSCV.cc, LSCV.cc, LRSCV.cc), SSD behind an
- * intensity map (C-ABI implementation, include/mtfhip.h; the kernels: kernels_scv.hip, kernels_rscv.hip, kernels_lscv.hip, kernels_lrscv.hip,
- * kernels_fused_rscv.hip, kernels_fused_lrscv.hip; the state: IntensityMapState, mtfhip_api_internal.h)
+ * intensity map (C-ABI implementation, include/mtfhip.h; the kernels: kernels_imap.hip, kernels_fused_rscv.hip, kernels_fused_lrscv.hip;
+ * the state: IntensityMapState, mtfhip_api_internal.h)
  *
  * SCV and LSCV are SSDBase models whose updateSimilarity first re-maps the template through the conditional expectation E[It | I0_orig]
  * (SCV.cc:194-230; LSCV.cc:263-304: one per sub-region, blended with per-pixel weights).  The device path keeps that split: imap_before_pass
@@ -168,36 +168,38 @@ int imap_capture(mtfhip_batch *b) {
 	return MTFHIP_OK;
 }
 
-/* SCV / LSCV: I0 = map(I0_orig) for the targets [t0, t0 + bv.B) */
-static void remap_template(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st) {
+/* the argument block of the model's pass 1 and what follows it, for the targets [t0, t0 + bv.B); kind: how pass 1 obtains It (RSCV_IT_*) */
+static ImapArgs imap_args(const mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int kind) {
 	const IntensityMapState &m = b->imap;
 	const size_t N = (size_t)b->N, nb = (size_t)m.nb, R = imap_regions(b), E = (size_t)m.ncell * nb;
-	if (imap_localized(b)) {
-		LscvArgs a;
-		a.nb = m.nb; a.nx = m.nx; a.ny = m.ny; a.ncx = m.ncx; a.ncell = m.ncell;
-		a.from_it = from_it; a.affine = m.affine; a.linear = m.linear;
-		a.norm_mult = b->norm_mult; a.norm_add = b->norm_add;
-		a.code = m.code16 + (size_t)t0 * N;
-		a.i0o = m.orig + (size_t)t0 * N;
-		a.cell = m.cell; a.crng = m.crng; a.wts = m.w;
-		a.active = active;
-		a.tot = m.tot + (size_t)t0 * 2 * E;
-		a.arrive = m.arrive + t0;
-		a.map = m.map + (size_t)t0 * R * nb;
-		a.aff = m.aff + (size_t)t0 * 2 * R;
-		TimedScope ts(b->ctx, "lscv_remap", st);
-		launch_lscv_update(bv, b->ctx->img, a, bv.buf[MTFHIP_BUF_I0], st);
-	} else {
-		ScvArgs a;
-		a.nb = m.nb; a.hist = m.hist; a.linear = m.linear; a.from_it = from_it;
-		a.norm_mult = b->norm_mult; a.norm_add = b->norm_add;
-		a.code = m.code16 + (size_t)t0 * N;
-		a.i0o = m.orig + (size_t)t0 * N;
-		a.active = active;
-		TimedScope ts(b->ctx, "scv_remap", st);
-		launch_scv_update(bv, b->ctx->img, a, m.part_f + (size_t)t0 * imap_hist_blocks(b->N, kImapChunks) * 2 * nb, m.map + (size_t)t0 * nb,
-			bv.buf[MTFHIP_BUF_I0], st);
-	}
+	const size_t rows = (size_t)imap_hist_blocks(b->N, kImapChunks) * 2 * nb;
+	ImapArgs a;
+	a.nb = m.nb; a.kind = kind;
+	a.hist = m.hist; a.linear = m.linear; a.affine = m.affine;
+	a.nx = m.nx; a.ny = m.ny; a.ncx = m.ncx; a.ncell = m.ncell;
+	a.norm_mult = b->norm_mult; a.norm_add = b->norm_add; a.grad_eps = b->desc.grad_eps;
+	/* (the buffers a model does not have are null, and stay so) */
+	a.src = kind != RSCV_IT_FROM_BUF ? nullptr : (imap_reversed(b) ? m.orig + (size_t)t0 * N : bv.buf[MTFHIP_BUF_IT]);
+	a.code16 = m.code16 ? m.code16 + (size_t)t0 * N : nullptr;
+	a.code8 = m.code8 ? m.code8 + (size_t)t0 * N : nullptr;
+	a.i0o = m.orig + (size_t)t0 * N;
+	a.cell = m.cell; a.crng = m.crng; a.wts = m.w;
+	a.active = active;
+	a.part_f = m.part_f ? m.part_f + (size_t)t0 * rows : nullptr;
+	a.part_u = m.part_u ? m.part_u + (size_t)t0 * rows : nullptr;
+	a.tot = m.tot ? m.tot + (size_t)t0 * 2 * E : nullptr;
+	a.arrive = m.arrive ? m.arrive + t0 : nullptr;
+	a.map = m.map + (size_t)t0 * R * nb;
+	a.aff = m.aff ? m.aff + (size_t)t0 * 2 * R : nullptr;
+	return a;
+}
+
+/* SCV / LSCV: I0 = map(I0_orig) for the targets [t0, t0 + bv.B) */
+static void remap_template(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, int from_it, hipStream_t st) {
+	const ImapArgs a = imap_args(b, bv, t0, active, from_it ? RSCV_IT_FROM_BUF : RSCV_IT_REPLAY);
+	TimedScope ts(b->ctx, imap_localized(b) ? "lscv_remap" : "scv_remap", st);
+	if (imap_localized(b)) launch_lscv_update(bv, b->ctx->img, a, bv.buf[MTFHIP_BUF_I0], st);
+	else launch_scv_update(bv, b->ctx->img, a, bv.buf[MTFHIP_BUF_I0], st);
 	touch(b, MTFHIP_BUF_I0);
 }
 
@@ -210,35 +212,9 @@ static int rscv_it_kind(const FusedArgs *fa) {
 
 /* RSCV / LRSCV: pass 1 and the maps of the current patch for the targets [t0, t0 + bv.B) */
 static void map_current(mtfhip_batch *b, const BatchView &bv, int t0, const int *active, const FusedArgs *fa, hipStream_t st) {
-	const IntensityMapState &m = b->imap;
-	const size_t N = (size_t)b->N, nb = (size_t)m.nb, R = imap_regions(b), E = (size_t)m.ncell * nb;
-	if (imap_localized(b)) {
-		LrscvArgs a;
-		a.nb = m.nb; a.kind = rscv_it_kind(fa);
-		a.nx = m.nx; a.ny = m.ny; a.ncx = m.ncx; a.ncell = m.ncell;
-		a.affine = m.affine;
-		a.norm_mult = b->norm_mult; a.norm_add = b->norm_add; a.grad_eps = b->desc.grad_eps;
-		a.code = m.code8 + (size_t)t0 * N;
-		a.it_orig = fa ? nullptr : m.orig + (size_t)t0 * N;
-		a.cell = m.cell; a.crng = m.crng;
-		a.active = active;
-		a.tot = m.tot + (size_t)t0 * 2 * E;
-		a.arrive = m.arrive + t0;
-		a.map = m.map + (size_t)t0 * R * nb;
-		a.aff = m.aff + (size_t)t0 * 2 * R;
-		launch_lrscv_hist(bv, b->ctx->img, a, st);
-	} else {
-		RscvArgs a;
-		a.nb = m.nb; a.kind = rscv_it_kind(fa);
-		a.norm_mult = b->norm_mult; a.norm_add = b->norm_add; a.grad_eps = b->desc.grad_eps;
-		a.code = m.code8 + (size_t)t0 * N;
-		a.it_orig = fa ? nullptr : m.orig + (size_t)t0 * N;
-		a.active = active;
-		a.part = m.part_u + (size_t)t0 * imap_hist_blocks(b->N, kImapChunks) * 2 * nb;
-		a.arrive = m.arrive + t0;
-		a.map = m.map + (size_t)t0 * nb;
-		launch_rscv_hist(bv, b->ctx->img, a, st);
-	}
+	const ImapArgs a = imap_args(b, bv, t0, active, rscv_it_kind(fa));
+	if (imap_localized(b)) launch_lrscv_hist(bv, b->ctx->img, a, st);
+	else launch_rscv_hist(bv, b->ctx->img, a, st);
 }
 
 /* ... and what applies them from the target t0 on: the map (RSCV), the blend (LRSCV) */

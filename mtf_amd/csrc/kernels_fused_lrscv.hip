@@ -2,7 +2,7 @@
  * kernels_fused_lrscv.hip -- the fused Lucas-Kanade iteration for the Localized Reversed SCV appearance model (AM/src/LRSCV.cc):
  * fused_lk_body (mtfhip_fused_device.h) instantiated with AM = MTFHIP_AM_LRSCV, i.e. SSD on the current patch whose every sample is
  * replaced, right after it is taken, by the per-pixel blend of its images through the target's sub-region maps.  The maps come from
- * pass 1 (kernels_lrscv.hip), enqueued in front of every launch that maps.  A translation unit of its own, so that the instantiations of
+ * pass 1 (kernels_imap.hip), enqueued in front of every launch that maps.  A translation unit of its own, so that the instantiations of
  * kernels_fused.hip and kernels_fused_rscv.hip stay exactly what they were.
  */
 #include "mtfhip_fused_device.h"

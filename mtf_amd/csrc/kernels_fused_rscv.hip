@@ -1,7 +1,7 @@
 /*
  * kernels_fused_rscv.hip -- the fused Lucas-Kanade iteration for the Reversed SCV appearance model (AM/src/RSCV.cc): fused_lk_body
  * (mtfhip_fused_device.h) instantiated with AM = MTFHIP_AM_RSCV, i.e. SSD on the current patch mapped through the target's intensity
- * map right after it is sampled.  The maps come from pass 1 (kernels_rscv.hip), enqueued in front of every launch.  A translation unit
+ * map right after it is sampled.  The maps come from pass 1 (kernels_imap.hip), enqueued in front of every launch.  A translation unit
  * of its own, so that the SSD / NCC instantiations of kernels_fused.hip stay exactly what they were.
  */
 #include "mtfhip_fused_device.h"

@@ -236,8 +236,8 @@ struct TargetHost {
 };
 
 /* (the bin limits of kAmTraits, mtfhip_am_served.h, are the kernels' own) */
-static_assert(kAmTraits[MTFHIP_AM_MI].max_bins == MI_NB && kAmTraits[MTFHIP_AM_CCRE].max_bins == MI_NB && kAmTraits[MTFHIP_AM_SCV].max_bins == kScvMaxBins &&
-	kAmTraits[MTFHIP_AM_RSCV].max_bins == kRscvMaxBins && kAmTraits[MTFHIP_AM_LSCV].max_bins == kLscvMaxBins && kAmTraits[MTFHIP_AM_LRSCV].max_bins == kLscvMaxBins,
+static_assert(kAmTraits[MTFHIP_AM_MI].max_bins == MI_NB && kAmTraits[MTFHIP_AM_CCRE].max_bins == MI_NB && kAmTraits[MTFHIP_AM_SCV].max_bins == kImapMaxBins &&
+	kAmTraits[MTFHIP_AM_RSCV].max_bins == kImapMaxBins && kAmTraits[MTFHIP_AM_LSCV].max_bins == kImapMaxBins && kAmTraits[MTFHIP_AM_LRSCV].max_bins == kImapMaxBins,
 	"kAmTraits::max_bins");
 
 /* The SCV family (SCV, RSCV, LSCV, LRSCV: SSD behind an intensity map) keeps ONE state: a batch has one appearance model for life.  SCV and

@@ -330,13 +330,13 @@ struct FusedArgs {
 	const double *w0;
 };
 
-/* RSCV (am = MTFHIP_AM_RSCV): the intensity maps the fused pass applies to every sample (kernels_rscv.hip builds them), an extra
+/* RSCV (am = MTFHIP_AM_RSCV): the intensity maps the fused pass applies to every sample (kernels_imap.hip builds them), an extra
  * argument behind the fused kernels' own -- map: [bv.B][nb], offset to bv's first target; linear: RSCVParams::weighted_mapping */
 struct RscvMap {
 	const double *map = nullptr;
 	int nb = 0, linear = 0;
 };
-/* LRSCV (am = MTFHIP_AM_LRSCV): what the fused pass needs to blend every sample (kernels_lrscv.hip builds the maps) -- map: [bv.B][R][nb]
+/* LRSCV (am = MTFHIP_AM_LRSCV): what the fused pass needs to blend every sample (kernels_imap.hip builds the maps) -- map: [bv.B][R][nb]
  * (affine_mapping: [bv.B][R][2], a_r and c_r), offset to bv's first target; wts: [R][N] sub_region_wts, one per batch, sub-region
  * idy nx + idx; R = nx ny; linear: weighted_mapping */
 struct LrscvMap {
@@ -716,84 +716,47 @@ inline int imap_hist_blocks(int N, int chunks) {
 	return nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
 }
 
-/* ---- SCV: the template re-map of SCV::updateSimilarity (kernels_scv.hip) ---- */
-constexpr int kScvMaxBins = 256;
-struct ScvArgs {
-	int nb, hist, linear;        /* n_bins, hist_type (0 Dirac, 1 Bilinear), weighted_mapping */
-	int from_it;                 /* 1: It from MTFHIP_BUF_IT (per-function path); 0: sampled at the current warp */
-	double norm_mult, norm_add;
-	const unsigned short *code;  /* [B][N] (int)I0_orig | (int)rint(I0_orig) << 8 */
-	const double *i0o;           /* [B][N] I0_orig */
-	const int *active;           /* optional [B] mask (device-side loop) */
-};
-void launch_scv_codes(int N, int B, int nb, const double *i0o, unsigned short *code, hipStream_t st);
-/* pass 1 + map + re-map; part: [B][imap_hist_blocks(N, kImapChunks)][2 nb], map: [B][nb], I0: MTFHIP_BUF_I0 (all offset to bv's first target) */
-void launch_scv_update(const BatchView &bv, const ImgView &im, const ScvArgs &a, double *part, double *map, double *I0, hipStream_t st);
-
-/* ---- RSCV: the current patch's intensity map of RSCV::updatePixVals (kernels_rscv.hip) ---- */
-constexpr int kRscvMaxBins = 256;
-/* (how pass 1 obtains It_orig: RSCV_IT_*, mtfhip_fused_dispatch.h) */
-struct RscvArgs {
-	int nb, kind;                /* n_bins, RSCV_IT_* */
-	double norm_mult, norm_add, grad_eps;
-	const unsigned char *code;   /* [B][N] (int)I0, clamped to [0, nb - 1] */
-	const double *it_orig;       /* [B][N] (RSCV_IT_FROM_BUF) */
-	const int *active;           /* optional [B] mask (device-side loop) */
-	unsigned *part;              /* [B][imap_hist_blocks(N, kImapChunks)][2 nb] per-workgroup sums */
-	unsigned *arrive;            /* [B] arrival counters (0 between launches) */
-	double *map;                 /* [B][nb] */
-};
-void launch_rscv_codes(int N, int B, int nb, const double *i0, unsigned char *code, hipStream_t st);
-/* pass 1 and the map (its last-arriving workgroup per target); all pointers of a offset to bv's first target */
-void launch_rscv_hist(const BatchView &bv, const ImgView &im, const RscvArgs &a, hipStream_t st);
-/* It = map(It_orig) (the per-function route's updatePixVals) */
-void launch_rscv_apply(int N, int B, int nb, int linear, const double *map, const double *it_orig, double *It, hipStream_t st);
-
-/* ---- LSCV: the localized template re-map of LSCV::updateSimilarity (kernels_lscv.hip) ---- */
-constexpr int kLscvMaxBins = 256;
-/* LDS of a pass-1 workgroup: two u32 sums per (cell, template bin); the re-map's maps, n_sub x n_bins doubles, stay within it too.  The
+/* ---- the SCV family: SSD behind an intensity map (kernels_imap.hip) ---- */
+constexpr int kImapMaxBins = 256;
+/* LDS of a localized pass-1 workgroup: two u32 sums per (cell, bin); the re-map's maps, n_sub x n_bins doubles, stay within it too.  The
  * default dynamic-LDS limit: no kernel attribute raises it. */
 constexpr int kLscvLdsBudget = 64 * 1024;
-struct LscvArgs {
-	int nb, nx, ny, ncx, ncell;  /* n_bins, n_sub_regions_x / _y, cell columns, cells */
-	int from_it;                 /* 1: It from MTFHIP_BUF_IT (per-function path); 0: sampled at the current warp */
-	int affine, linear;          /* affine_mapping, weighted_mapping */
-	double norm_mult, norm_add;
-	const unsigned short *code;  /* [B][N] (int)I0_orig | (int)rint(I0_orig) << 8, clamped to [0, nb - 1] */
+/* room left in the fused LRSCV pass's 64 KB of LDS for its own static arrays: the maps get the rest */
+constexpr int kLrscvFusedStaticLds = 8 * 1024;
+/* one argument block for the four models; every per-target pointer is offset to bv's first target.  SCV and LSCV key their sums by the
+ * template's bin and re-map I0 (code16, i0o, wts); RSCV and LRSCV key them by the current patch's bin (code8).  The localized models add
+ * the sub-region geometry (nx .. ncell, cell, crng) and sum per target (tot); SCV and RSCV sum per workgroup (part_f, part_u). */
+struct ImapArgs {
+	int nb, kind;                /* n_bins; how pass 1 obtains It: RSCV_IT_* (mtfhip_fused_dispatch.h) */
+	int hist, linear, affine;    /* SCV's hist_type (0 Dirac, 1 Bilinear), weighted_mapping, affine_mapping */
+	int nx, ny, ncx, ncell;      /* n_sub_regions_x / _y, cell columns, cells */
+	double norm_mult, norm_add, grad_eps;
+	const double *src;           /* [B][N] RSCV_IT_FROM_BUF (per-function path): MTFHIP_BUF_IT (SCV, LSCV), It_orig (RSCV, LRSCV) */
+	const unsigned short *code16; /* [B][N] (int)I0_orig | (int)rint(I0_orig) << 8, clamped to [0, nb - 1] */
+	const unsigned char *code8;  /* [B][N] (int)I0, clamped to [0, nb - 1] */
 	const double *i0o;           /* [B][N] I0_orig */
 	const unsigned short *cell;  /* [N] (one per batch) the pixel's cell, 0xffff outside every sub-region */
 	const int *crng;             /* [2 nx + 2 ny] (one per batch) sub-region idx: cells cx in [crng[2 idx], crng[2 idx + 1]]; then idy: cy */
 	const double *wts;           /* [nx ny][N] (one per batch) sub_region_wts, sub-region idy nx + idx */
-	const int *active;           /* optional [B] mask (device-side loop) */
+	const int *active;           /* optional [B] mask: targets with 0 are skipped (device-side loop) */
+	double *part_f;              /* [B][imap_hist_blocks(N, kImapChunks)][2 nb] per-workgroup sums (SCV) */
+	unsigned *part_u;            /* ... (RSCV) */
 	unsigned *tot;               /* [B][2][ncell nb] per-target sums, zero between launches */
 	unsigned *arrive;            /* [B] arrival counters (0 between launches) */
-	double *map;                 /* [B][nx ny][nb] */
+	double *map;                 /* [B][nx ny][nb] (SCV, RSCV: [B][nb]) */
 	double *aff;                 /* [B][nx ny][2] (affine_mapping) */
 };
-/* pass 1 and the maps (its last-arriving workgroup per target), then the re-map of I0; all per-target pointers offset to bv's first target */
-void launch_lscv_update(const BatchView &bv, const ImgView &im, const LscvArgs &a, double *I0, hipStream_t st);
-
-/* ---- LRSCV: the localized current-patch maps of LRSCV::updatePixVals (kernels_lrscv.hip) ---- */
-/* room left in the fused LRSCV pass's 64 KB of LDS for its own static arrays: the maps get the rest */
-constexpr int kLrscvFusedStaticLds = 8 * 1024;
-struct LrscvArgs {
-	int nb, kind;                /* n_bins, RSCV_IT_* (how It_orig is obtained: rscv_it_orig, mtfhip_rscv_device.h) */
-	int nx, ny, ncx, ncell;      /* n_sub_regions_x / _y, cell columns, cells */
-	int affine;                  /* affine_mapping */
-	double norm_mult, norm_add, grad_eps;
-	const unsigned char *code;   /* [B][N] (int)I0, clamped to [0, nb - 1] (RSCV's code plane) */
-	const double *it_orig;       /* [B][N] (RSCV_IT_FROM_BUF) */
-	const unsigned short *cell;  /* [N] (one per batch) the pixel's cell, 0xffff outside every sub-region (LSCV's cell plane) */
-	const int *crng;             /* [2 nx + 2 ny] (one per batch) the cells of each sub-region, as LscvArgs::crng */
-	const int *active;           /* optional [B] mask (device-side loop) */
-	unsigned *tot;               /* [B][2][ncell nb] per-target sums keyed by (cell, current bin), zero between launches */
-	unsigned *arrive;            /* [B] arrival counters (0 between launches) */
-	double *map;                 /* [B][nx ny][nb] */
-	double *aff;                 /* [B][nx ny][2] (affine_mapping) */
-};
-/* pass 1 and the maps (its last-arriving workgroup per target); all per-target pointers of a offset to bv's first target */
-void launch_lrscv_hist(const BatchView &bv, const ImgView &im, const LrscvArgs &a, hipStream_t st);
-/* It = the blend of the mapped It_orig (the per-function route's updatePixVals); lm as the fused pass's, offset to target 0 */
+/* the template's bins, fixed until the template changes: ImapArgs::code16 of I0_orig, ::code8 of I0 */
+void launch_scv_codes(int N, int B, int nb, const double *i0o, unsigned short *code, hipStream_t st);
+void launch_rscv_codes(int N, int B, int nb, const double *i0, unsigned char *code, hipStream_t st);
+/* SCV, LSCV: pass 1, the maps, then the re-map of I0 (MTFHIP_BUF_I0, offset to bv's first target) */
+void launch_scv_update(const BatchView &bv, const ImgView &im, const ImapArgs &a, double *I0, hipStream_t st);
+void launch_lscv_update(const BatchView &bv, const ImgView &im, const ImapArgs &a, double *I0, hipStream_t st);
+/* RSCV, LRSCV: pass 1 and the maps (its last-arriving workgroup per target) */
+void launch_rscv_hist(const BatchView &bv, const ImgView &im, const ImapArgs &a, hipStream_t st);
+void launch_lrscv_hist(const BatchView &bv, const ImgView &im, const ImapArgs &a, hipStream_t st);
+/* It = map(It_orig), or the blend of the mapped It_orig (the per-function route's updatePixVals); lm as the fused pass's, offset to target 0 */
+void launch_rscv_apply(int N, int B, int nb, int linear, const double *map, const double *it_orig, double *It, hipStream_t st);
 void launch_lrscv_apply(int N, int B, const LrscvMap &lm, const double *it_orig, double *It, hipStream_t st);
 
 } // namespace mtfhip

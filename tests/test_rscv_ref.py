@@ -1,7 +1,7 @@
 """RSCV (the Reversed Sum of Conditional Variance appearance model) on CPU: the fixture tests/golden/lk_golden7.npz and its float64
 definitions (tests/golden/make_golden7.py) held to themselves, and the C ABI the device path adds for it.
 
-- the two-integer-sums-per-current-bin map (what kernels_rscv.hip computes) equals the literal n_bins^2 joint-histogram map bit for bit,
+- the two-integer-sums-per-current-bin map (what k_rscv_hist of kernels_imap.hip computes) equals the literal n_bins^2 joint-histogram map bit for bit,
   and both equal the fixture's map;
 - with the map frozen, g = df/dIt . Jt is the derivative of f over the state (a central difference through the compositional update);
 - the new symbols and MTFHIP_AM_RSCV are exported and mtfhip_patch_desc keeps its layout."""

@@ -1,7 +1,7 @@
 """SCV (the Sum of Conditional Variance appearance model) on CPU: the fixture tests/golden/lk_golden6.npz and its float64 definitions
 (tests/golden/make_golden6.py) held to themselves, and the C ABI the device path adds for it.
 
-- the two-sums-per-template-bin map (what kernels_scv.hip computes) equals the literal n_bins^2 joint-histogram map: bit for bit with
+- the two-sums-per-template-bin map (what k_scv_hist of kernels_imap.hip computes) equals the literal n_bins^2 joint-histogram map: bit for bit with
   Dirac histograms, within 1e-13 relative with Bilinear ones, and both equal the fixture's map;
 - with the map frozen, g = df/dIt . Jt is the derivative of f over the state (a central difference through the compositional update);
 - the new symbols and MTFHIP_AM_SCV are exported and mtfhip_patch_desc keeps its layout."""

@@ -38,7 +38,7 @@ from mtf_amd import synth  # noqa: E402
 IMG = G7.make_image()
 IMG64 = IMG.astype(np.float64)
 MODELS = ("scv_d", "scv_b", "rscv", "lscv", "lrscv")
-# kLscvLdsBudget - 64 (mtf_amd/csrc/mtfhip_internal.h; lscv_geometry in api_lscv.hip refuses 2 * sizeof(unsigned) * cells * n_bins above it).  A
+# kLscvLdsBudget - 64 (mtf_amd/csrc/mtfhip_internal.h; imap_geometry in api_imap.hip refuses 2 * sizeof(unsigned) * cells * n_bins above it).  A
 # copy: if the constant changes, the GPU test's accepted / refused pair stops matching the device and fails
 LDS_HIST_BUDGET = 64 * 1024 - 64
 

@@ -1,0 +1,513 @@
+"""GPU: the histogram appearance models -- MI (the materialising passes and the recompute passes k_mi_pass_hist / k_mi_pass_grad_hess) and CCRE
+(k_ccre_hess, k_ccre_grad_gemv, k_ccre_tables, k_mi_hist<.., CUM>) -- at the seams of their decompositions and of the frame, against their
+references.  The cases are tests/helpers/hist_seam_cases.py's; tests/test_hist_seams_cpu.py holds the references alone to the conditions that
+make these comparisons meaningful.
+
+Part A  one Batch.iterate from the identity on the second frame: the table (pixel counts, bin counts, frame edges, wholly outside, the exact-zero
+        block), batches at the `1024 / B` cap of mi_blocks and where pass 1's workgroup count differs from pass 2's, the candidate axis,
+        three channels;
+Part B  the device loop (Batch.track) against the reference's loop: single targets and a batch of three that stop after different passes.
+
+Bounds.  MI: tests/test_gpu_parity.py::_fused_follow's (FOLLOW_BOUNDS: the oracle's grid, replay arithmetic f 1e-12, H 1e-9, g 1e-10 of
+max(|g|, g_scale) and It, dIt_dx bit for bit; the device's grid f 1e-8, H 1e-5, g 1e-5; tolerance arithmetic, lean, 2e-6; the update DP_TOL or
+DP_CORNER_PX at the corners, from 35 pixels on, in-frame regions only), the loop's LOOP_CORNER_PX.  CCRE: tests/test_gpu_ccre.py's (B_F, B_G,
+B_H, B_DP, LOOP_PX), tolerance arithmetic held to replay's bits.  Where a bound misses, the case is held to max(bound, 16 x the reference's own
+floor) -- MI: the oracle under the seeded +-1e-12 px corner jitter; CCRE: float64 against long double -- and both figures go to the parity
+record; at most one case in ten may need that (test_at_most_one_case_in_ten_runs_on_a_widened_bound).
+
+Wholly outside the frame and inside the exact-zero block every image gradient is a difference of equal samples: f is the reference's finite
+value and g and H are exactly zero, in both arithmetic modes -- measured so on one MI355X: no rounding-size remainder in any case.
+
+Measured on one MI355X (profiles/hist_seams_parity.md has the table per group): no case needed a widened bound (0 of 233), so there is no
+widened case to list here.  MI on the oracle's grid f <= 7.8e-13 (the 4-pixel and the 2- and 3-bin cases, where f is what the logs leave of
+terms of order one), H <= 1.9e-13, g <= 4.2e-15, It and dIt_dx bit for bit; on the device's grid H <= 3.0e-7, g <= 4.7e-9, in tolerance
+arithmetic f <= 8.1e-10, H <= 3.0e-7; CCRE against its generator on the device's samples f, g, H <= 5.1e-13, tolerance arithmetic equal to
+replay's bits in every case; every loop with the reference's n_iters, corners within 5.8e-7 px."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import mtf_amd
+from mtf_amd import _lib as L
+from mtf_amd import synth
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import hist_seam_cases as K   # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+TP, TC = K.TP, K.TC
+REPLAY, FAST = mtf_amd.MATH_REPLAY, mtf_amd.MATH_FAST
+RAN, WIDENED = set(), {}
+
+
+def _hold(err, base, floor_of, what, case, quantity, record):
+    """err < base; where that misses, err < max(base, 16 x the reference's own floor), recorded"""
+    RAN.add(case)
+    if err < base:
+        return
+    floor = float(floor_of())
+    tol = K.widened(base, floor)
+    WIDENED.setdefault(case, []).append(dict(quantity=quantity, what=what, error=err, bound=base, reference_floor=floor, held_to=tol))
+    record.append(dict(test="hist_seams_widened_bound", case=case, what=what, quantity=quantity, error=err, bound=base, reference_floor=floor, held_to=tol))
+    print("%s %s: %.3e misses %.1e; the reference's own floor %.3e, held to %.3e" % (what, quantity, err, base, floor, tol))
+    assert err < tol, (what, quantity, err, base, floor)
+
+
+# ================================================================================================ MI
+def _mi_batch(gpu_ctx, frame, ssm, resx, resy, corners, nb, pou, math, grid_from=None, channels=1):
+    gpu_ctx.set_image(frame)
+    b = mtf_amd.Batch(gpu_ctx, L.AM_MI, ssm, resx, resy, corners.shape[0], mi_n_bins=nb, mi_pou=pou, n_channels=channels)
+    b.set_math_mode(math)
+    b.set_corners(corners)
+    if grid_from is not None:
+        hm = grid_from["init_pts_hm"].reshape(-1, 3)
+        b.write(L.BUF_INIT_PTS, grid_from["init_pts"].reshape(1, -1, 2).transpose(0, 2, 1))
+        b.write(L.BUF_INIT_HXY, hm[:, :2].T[None])
+        b.write(L.BUF_INIT_Z, hm[:, 2][None])
+        b.set_state(np.zeros((1, b.S)))
+    return b
+
+
+def _sm(sm, extra, materialize, **kw):
+    params = dict(leven_marq=0)
+    params.update(extra)
+    params.update(kw)
+    return mtf_amd.sm_desc(sm, materialize=materialize, **params)
+
+
+def _mi_check(oracle, b, f, g, H, rec, bounds, floor_of, what, case, record, flat, dp_corners=None):
+    """f, g, H of one target against the oracle's record; dp_corners: the region, where the update is compared too"""
+    tol_f, tol_H, tol_g = bounds
+    ef = K.rel(f, rec["f"])
+    if flat:
+        print("%s: f %.3e (flat)" % (what, ef))
+        assert ef < tol_f, (what, ef)
+        assert np.all(g == 0.0) and np.all(H == 0.0), (what, np.abs(g).max(), np.abs(H).max())
+        RAN.add(case)
+        return dict(f=ef, H=0.0, g=0.0)
+    eH, eg = K.rel(H, rec["H"]), K.g_err(g, rec)
+    print("%s: f %.3e H %.3e g %.3e" % (what, ef, eH, eg))
+    _hold(ef, tol_f, lambda: floor_of()["f"], what, case, "f", record)
+    _hold(eH, tol_H, lambda: floor_of()["H"], what, case, "H", record)
+    _hold(eg, tol_g, lambda: floor_of()["g"], what, case, "g", record)
+    e = dict(f=ef, H=eH, g=eg)
+    if dp_corners is not None:
+        dp = -oracle.colpiv_qr_solve(H, g)
+        e["dp"] = K.rel(dp, rec["dp"])
+        c_gpu = b.apply_warp_to_corners(dp_corners[None], dp[None])[0]
+        c_ref = b.apply_warp_to_corners(dp_corners[None], rec["dp"][None])[0]
+        if not np.abs(c_gpu - c_ref).max() < TP.DP_CORNER_PX:
+            _hold(e["dp"], TP.DP_TOL, lambda: floor_of()["dp"], what, case, "dp", record)
+    return e
+
+
+def _mi_part_a(oracle, gpu_ctx, sm, ssm, extra, resx, resy, corners, nb, pou, flat, in_frame, case, record, channels=1, tight=True):
+    """one target: the oracle's grid (replay, materialised and lean), the device's grid (replay, materialised and lean; tolerance arithmetic,
+    lean).  The worst errors per (grid, arithmetic)."""
+    frame, frame2 = K.frames() if channels == 1 else K.frames_mc()
+    ref = K.mi_reference(oracle, sm, ssm, extra, resx, resy, corners, nb, pou, channels)
+    rec = ref["rec"]
+
+    def floor_of():
+        return K.mi_floor(oracle, sm, ssm, extra, resx, resy, corners, nb, pou, channels)
+    dp_corners = corners if (in_frame and resx * resy >= 35) else None
+    worst = {}
+    for grid in (("oracle_grid", "device_grid") if tight else ("device_grid",)):
+        for materialize in (1, 0):
+            b = _mi_batch(gpu_ctx, frame, ssm, resx, resy, corners[None], nb, pou, REPLAY, ref if grid == "oracle_grid" else None, channels)
+            try:
+                smd = _sm(sm, extra, materialize)
+                b.init_template(smd)
+                gpu_ctx.set_image(frame2)
+                f, g, H = b.iterate(smd)
+                what = "%s %s materialize=%d" % (case, grid, materialize)
+                e = _mi_check(oracle, b, f[0], g[0], H[0], rec, TP.FOLLOW_BOUNDS[grid], floor_of, what, case, record, flat,
+                              dp_corners if grid == "device_grid" else None)
+                if grid == "oracle_grid" and materialize and channels == 1:
+                    assert np.array_equal(b.read(L.BUF_IT)[0], ref["It"]), what
+                    if sm != K.ICLK:
+                        assert np.array_equal(b.read(L.BUF_DIT_DX)[0], ref["dIt_dx"].reshape(2, -1).T), what
+                worst[grid] = {q: max(v, worst.get(grid, {}).get(q, 0.0)) for q, v in e.items()}
+                if grid == "device_grid" and not materialize:
+                    b.set_math_mode(FAST)
+                    ff, gf, Hf = b.iterate(smd)
+                    worst["fast"] = _mi_check(oracle, b, ff[0], gf[0], Hf[0], rec, TP.FOLLOW_BOUNDS["fast"], floor_of, what + " MATH_FAST", case, record,
+                                              flat, dp_corners)
+            finally:
+                b.close()
+    return worst
+
+
+@pytest.mark.parametrize("cid", K.MI_IDS)
+def test_mi_fused_iteration_at_the_seams(oracle, gpu_ctx, cid, parity_record):
+    """Part A, MI: one Batch.iterate per (grid, materialize, arithmetic) against the oracle's first iteration.  The cap case (65 792 px, past
+    the 64 block rows of k_mi_grad_gemv) runs the device's grid only."""
+    c = K.BY_ID[cid]
+    worst = _mi_part_a(oracle, gpu_ctx, c.sm, c.ssm, c.extra, c.resx, c.resy, K.REGIONS[c.region], c.nb, c.pou, c.region in K.FLAT,
+                       c.region in ("inside", "h50a"), cid, parity_record, tight=c.group != "cap")
+    parity_record.append(dict(test="hist_seams_mi", case=cid, group=c.group, **worst))
+
+
+@pytest.mark.parametrize("math", [REPLAY, FAST], ids=["replay", "fast"])
+@pytest.mark.parametrize("shape", K.MC_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_mi_three_channels(oracle, gpu_ctx, shape, math, parity_record):
+    """6.  n_channels = 3, 8 bins, FCLK default: 63, 66, 255 and 258 (pixel, channel) rows -- a 64-row chunk ends inside a pixel
+    (k_mi_pass_hist<.., MC>) -- on the device's grid in either arithmetic, lean and materialised"""
+    resx, resy = shape
+    case = "mc-%dx%d-%s" % (resx, resy, "fast" if math == FAST else "replay")
+    frame, frame2 = K.frames_mc()
+    corners = K.REGIONS["inside"]
+    rec = K.mi_reference(oracle, K.FCLK, K.HOM, {}, resx, resy, corners, 8, 0, 3)["rec"]
+    assert np.abs(rec["H"]).max() > 0
+
+    def floor_of():
+        return K.mi_floor(oracle, K.FCLK, K.HOM, {}, resx, resy, corners, 8, 0, 3)
+    worst = {}
+    for materialize in ((1, 0) if math == REPLAY else (0,)):
+        b = _mi_batch(gpu_ctx, frame, K.HOM, resx, resy, corners[None], 8, 0, math, channels=3)
+        try:
+            smd = _sm(K.FCLK, {}, materialize)
+            b.init_template(smd)
+            gpu_ctx.set_image(frame2)
+            f, g, H = b.iterate(smd)
+            worst[materialize] = _mi_check(oracle, b, f[0], g[0], H[0], rec, TP.FOLLOW_BOUNDS["fast" if math == FAST else "device_grid"], floor_of,
+                                           "%s materialize=%d" % (case, materialize), case, parity_record, False)
+        finally:
+            b.close()
+    parity_record.append(dict(test="hist_seams_mi_channels", case=case, **{"materialize=%d" % k: v for k, v in worst.items()}))
+
+
+# ------------------------------------------------------------------------------------------------ batches
+def _expected_blocks(N, B):
+    """mi_blocks and mi_enqueue_fast's pass-1 count (api_am.hip, api_mi_iter.hip) for this device"""
+    import torch
+    nblk = min(max(1024 // B, 1), -(-N // 1024))
+    slots = 3 * max(torch.cuda.get_device_properties(0).multi_processor_count, 1)
+    nblk1 = min(nblk, slots // B) if (nblk * B > slots and slots // B >= 1) else nblk
+    return nblk, nblk1
+
+
+def _mi_batch_of_cycled_regions(oracle, gpu_ctx, sm, extra, shape, B, nb, pou, math, case, record):
+    resx, resy = shape
+    frame, frame2 = K.frames()
+    corners = np.stack([K.CYCLE[t % 4] for t in range(B)])
+    recs = [K.mi_reference(oracle, sm, K.HOM, extra, resx, resy, K.CYCLE[k], nb, pou)["rec"] for k in range(4)]
+    b = _mi_batch(gpu_ctx, frame, K.HOM, resx, resy, corners, nb, pou, math)
+    try:
+        smd = _sm(sm, extra, 0)
+        b.init_template(smd)
+        gpu_ctx.set_image(frame2)
+        f, g, H = b.iterate(smd)
+    finally:
+        b.close()
+    bounds = TP.FOLLOW_BOUNDS["fast" if math == FAST else "device_grid"]
+    worst = dict(f=0.0, H=0.0, g=0.0)
+    for t in range(B):
+        k = t % 4
+        e = dict(f=K.rel(f[t], recs[k]["f"]), H=K.rel(H[t], recs[k]["H"]), g=K.g_err(g[t], recs[k]))
+        for q, tol in zip(("f", "H", "g"), bounds):
+            _hold(e[q], tol, lambda k=k, q=q: K.mi_floor(oracle, sm, K.HOM, extra, resx, resy, K.CYCLE[k], nb, pou)[q],
+                  "%s target %d" % (case, t), case, q, record)
+            worst[q] = max(worst[q], e[q])
+        if t >= 4:       # the same region gives the same bits wherever it sits in the batch
+            assert f[t] == f[k] and np.array_equal(g[t], g[k]) and np.array_equal(H[t], H[k]), (case, t)
+    print("%s: worst %s" % (case, worst))
+    record.append(dict(test="hist_seams_mi_batch", case=case, targets=B, **worst))
+
+
+@pytest.mark.parametrize("math", [REPLAY, FAST], ids=["replay", "fast"])
+@pytest.mark.parametrize("B", [512, 600])
+def test_mi_batch_at_the_block_cap(oracle, gpu_ctx, B, math, parity_record):
+    """4 (a).  1025 pixels need two workgroups; with B = 512 mi_blocks' `1024 / B` is exactly that, with B = 600 it caps them to one.  The
+    replay arithmetic runs the Std Hessian (k_mi_hist, k_mi_hess over mi_blocks rows), the tolerance arithmetic the recompute passes."""
+    nblk, _ = _expected_blocks(1025, B)
+    assert nblk == (2 if B == 512 else 1)
+    sm, extra = (K.FCLK, dict(hess_type=2)) if math == REPLAY else (K.FCLK, dict())
+    _mi_batch_of_cycled_regions(oracle, gpu_ctx, sm, extra, (25, 41), B, 8, 0, math, "batch-25x41-B%d-%s" % (B, "fast" if math == FAST else "replay"),
+                                parity_record)
+
+
+@pytest.mark.parametrize("nb,pou", [(8, 0), (10, 1)])
+def test_mi_pass1_block_count_differs_from_pass2(oracle, gpu_ctx, nb, pou, parity_record):
+    """4 (b).  4900 pixels, B = 200, tolerance arithmetic: mi_blocks gives five rows per target; once nblk B exceeds three workgroups per CU
+    pass 1 writes fewer rows (three on 256 CUs) and the tables kernel must read that many, pass 2 still five"""
+    nblk, nblk1 = _expected_blocks(4900, 200)
+    assert nblk == 5
+    assert nblk1 != nblk, "this device (%d rows in pass 1) no longer makes pass 1's workgroup count differ from pass 2's: the case needs another B" % nblk1
+    _mi_batch_of_cycled_regions(oracle, gpu_ctx, K.FCLK, dict(), (70, 70), 200, nb, pou, FAST, "batch-70x70-B200-mi%d%s" % (nb, "p" if pou else ""),
+                                parity_record)
+
+
+# ------------------------------------------------------------------------------------------------ candidates
+@pytest.mark.parametrize("nb,pou", [(8, 0), (10, 1)])
+@pytest.mark.parametrize("shape", K.CAND_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_mi_candidate_scores(oracle, gpu_ctx, shape, nb, pou):
+    """5.  Batch.score_candidates(.., want_similarity=True) (k_mi_pass_hist<.., CAND> and k_mi_cand_score): 37 candidates on the second frame,
+    the identity and one known state among them, against the oracle's f candidate by candidate at tests/test_gpu_parity.py::
+    test_pf_candidate_scores's 1e-9, in both arithmetic modes"""
+    resx, resy = shape
+    frame, frame2 = K.frames()
+    corners = K.REGIONS["inside"]
+    o_ssm = oracle.SSM(K.HOM, resx, resy)
+    o_am = oracle.AM(K.MI, resx, resy, n_bins=nb, pou=pou)
+    o_am.set_curr_img(frame)
+    o_ssm.set_corners(corners)
+    o_am.initialize_pix_vals(o_ssm.get("curr_pts")); o_am.initialize_similarity()
+    o_am.set_curr_img(frame2)
+    states = synth.pf_candidate_states(np.random.default_rng(37), K.N_CAND)
+    known = np.array([0.004, -0.003, 0.8, 0.002, 0.005, -0.6, 2e-6, -3e-6])
+    states[0], states[17] = 0.0, known
+    lik_o, sim_o = oracle.pf_score(o_am, o_ssm, states)
+    assert np.all(np.isfinite(sim_o)) and len(set(np.round(sim_o, 9))) == K.N_CAND
+    b = _mi_batch(gpu_ctx, frame, K.HOM, resx, resy, corners[None], nb, pou, REPLAY)
+    try:
+        b.initialize_pix_vals(); b.initialize_similarity()
+        gpu_ctx.set_image(frame2)
+        for mode in (FAST, REPLAY):
+            b.set_math_mode(mode)
+            lik, sim = b.score_candidates(states, want_similarity=True)
+            print("candidates %dx%d mi%d mode %d: worst f %.3e" % (resx, resy, nb, mode, np.abs(sim / sim_o - 1).max()))
+            np.testing.assert_allclose(sim, sim_o, rtol=1e-9, err_msg="mode %d" % mode)
+            np.testing.assert_allclose(lik, lik_o, rtol=1e-7)
+    finally:
+        b.close()
+
+
+# ================================================================================================ CCRE
+def _ccre_batch(gpu_ctx, c_ssm, resx, resy, B, nb, pou, math):
+    b = mtf_amd.Batch(gpu_ctx, L.AM_CCRE, c_ssm, resx, resy, B, mi_n_bins=nb, mi_pre_seed=K.PRE_SEED, mi_partition_of_unity=pou)
+    b.set_math_mode(math)
+    return b
+
+
+def _ccre_pass(gpu_ctx, b, corners, sm_id, jac, ht, chained, mat):
+    frame, frame2 = K.frames()
+    sm = mtf_amd.sm_desc(sm_id, jac_type=jac, hess_type=ht, chained_warp=chained, materialize=mat, leven_marq=0)
+    gpu_ctx.set_image(frame)
+    b.set_corners(corners)
+    b.init_template(sm)
+    gpu_ctx.set_image(frame2)
+    return b.iterate(sm)
+
+
+def _ccre_dp_floor(a, nb, method):
+    q, q0 = K.ccre_quantities(a, nb)
+    ql, q0l = K.ccre_quantities(a, nb, np.longdouble)
+    g, H = TC.ref_g_H(q, q0["H_self"], *method)
+    gl, Hl = TC.ref_g_H(ql, q0l["H_self"], *method)
+    return K.G10.rel_floor(-np.linalg.solve(H, g), -np.linalg.solve(np.asarray(Hl, dtype=np.float64), np.asarray(gl, dtype=np.float64)))
+
+
+@pytest.mark.parametrize("cid", K.CCRE_IDS)
+def test_ccre_fused_pass_at_the_seams(gpu_ctx, cid, parity_record):
+    """Part A, CCRE: every served (search method, jac_type, hess_type) against make_golden12's quantities on the arrays the device sampled
+    (I0 and It required to be numpy_ref.bilinear's bits); the pass that materialises nothing gives the materialising pass's bits, in either
+    arithmetic mode"""
+    c = K.BY_ID[cid]
+    chained = c.extra["chained_warp"]
+    corners = K.REGIONS[c.region][None]
+    flat = c.region in K.FLAT
+    b = _ccre_batch(gpu_ctx, c.ssm, c.resx, c.resy, 1, c.nb, c.pou, REPLAY)
+    bf = _ccre_batch(gpu_ctx, c.ssm, c.resx, c.resy, 1, c.nb, c.pou, FAST)
+    try:
+        _ccre_pass(gpu_ctx, b, corners, L.SM_ESM, 1, 2, chained, 1)                 # (an ESM pass materialises Jt: the reference reads it)
+        a = dict(I0=b.read(L.BUF_I0)[0].copy(), It=b.read(L.BUF_IT)[0].copy(), J0=b.read(L.BUF_J0)[0].copy(), Jt=b.read(L.BUF_JT)[0].copy())
+        if c.group != "cap":
+            want = K.ccre_arrays(c.resx, c.resy, c.ssm == K.AFF, K.REGIONS[c.region], c.nb, c.pou)
+            assert np.array_equal(a["I0"], want["I0"]) and np.array_equal(a["It"], want["It"]), cid
+        q, q0 = K.ccre_quantities(a, c.nb)
+        floors = {}
+
+        def floor_of(method, quantity):
+            if not floors:
+                floors.update(K.ccre_floors(a, c.nb))
+            return floors[method][quantity]
+        worst = dict(f=0.0, g=0.0, H=0.0, dp=0.0)
+        fixture = {m[1:] for m in TC.FIXTURE_METHODS}
+        for method in K.CCRE_METHODS:
+            sm_id, jac, ht = method
+            f, g, H = _ccre_pass(gpu_ctx, b, corners, sm_id, jac, ht, chained, 1)
+            gr, Hr = TC.ref_g_H(q, q0["H_self"], sm_id, jac, ht)
+            what = "%s %s" % (cid, method)
+            ef = TC.rel(f[0], q["f"])
+            if flat:
+                assert ef < TC.B_F, (what, ef)
+                assert not np.any(g[0]) and not np.any(H[0]), (what, np.abs(g[0]).max(), np.abs(H[0]).max())
+                RAN.add(cid)
+                worst["f"] = max(worst["f"], ef)
+            else:
+                e = dict(f=ef, g=TC.rel(g[0], gr), H=TC.rel(H[0], Hr))
+                for quantity, base in (("f", TC.B_F), ("g", TC.B_G), ("H", TC.B_H)):
+                    _hold(e[quantity], base, lambda: floor_of(method, quantity), what, cid, quantity, parity_record)
+                if method in fixture and c.region in ("inside", "h50a") and K.n_pix(c) >= 35:
+                    e["dp"] = TC.rel(-np.linalg.solve(H[0], g[0]), -np.linalg.solve(Hr, gr))
+                    _hold(e["dp"], TC.B_DP, lambda: _ccre_dp_floor(a, c.nb, method), what, cid, "dp", parity_record)
+                for n in e:
+                    worst[n] = max(worst[n], e[n])
+            fl, gl, Hl = _ccre_pass(gpu_ctx, b, corners, sm_id, jac, ht, chained, 0)
+            assert np.array_equal(fl, f) and np.array_equal(gl, g) and np.array_equal(Hl, H), what
+            ft, gt, Ht = _ccre_pass(gpu_ctx, bf, corners, sm_id, jac, ht, chained, 0)
+            assert np.array_equal(ft, f) and np.array_equal(gt, g) and np.array_equal(Ht, H), what
+        print("%s worst: %s" % (cid, worst))
+        parity_record.append(dict(test="hist_seams_ccre", case=cid, group=c.group, **worst))
+    finally:
+        b.close(); bf.close()
+
+
+@pytest.mark.parametrize("B", [512, 600])
+def test_ccre_batch_at_the_block_cap(gpu_ctx, B, parity_record):
+    """4 (a) for CCRE: 1025 pixels with mi_blocks at exactly the two workgroups N needs (B = 512) and capped to one (B = 600); the targets cycle
+    through four regions, the reference is evaluated on the device's samples of the first four"""
+    resx, resy = 25, 41
+    case = "batch-25x41-B%d-ccre8" % B
+    corners = np.stack([K.CYCLE[t % 4] for t in range(B)])
+    b = _ccre_batch(gpu_ctx, K.HOM, resx, resy, B, 8, 0, REPLAY)
+    try:
+        f, g, H = _ccre_pass(gpu_ctx, b, corners, L.SM_ESM, 1, 2, 1, 1)
+        arrays = [dict(I0=b.read(L.BUF_I0)[k].copy(), It=b.read(L.BUF_IT)[k].copy(), J0=b.read(L.BUF_J0)[k].copy(), Jt=b.read(L.BUF_JT)[k].copy())
+                  for k in range(4)]
+        fl, gl, Hl = _ccre_pass(gpu_ctx, b, corners, L.SM_ESM, 1, 2, 1, 0)
+        assert np.array_equal(fl, f) and np.array_equal(gl, g) and np.array_equal(Hl, H)
+    finally:
+        b.close()
+    refs = []
+    for a in arrays:
+        q, q0 = K.ccre_quantities(a, 8)
+        refs.append((q["f"],) + TC.ref_g_H(q, q0["H_self"], L.SM_ESM, 1, 2))
+    worst = dict(f=0.0, g=0.0, H=0.0)
+    for t in range(B):
+        fr, gr, Hr = refs[t % 4]
+        e = dict(f=TC.rel(f[t], fr), g=TC.rel(g[t], gr), H=TC.rel(H[t], Hr))
+        for quantity, base in (("f", TC.B_F), ("g", TC.B_G), ("H", TC.B_H)):
+            _hold(e[quantity], base, lambda: K.ccre_floors(arrays[t % 4], 8)[(L.SM_ESM, 1, 2)][quantity], "%s target %d" % (case, t), case, quantity,
+                  parity_record)
+            worst[quantity] = max(worst[quantity], e[quantity])
+        if t >= 4:
+            assert f[t] == f[t % 4] and np.array_equal(g[t], g[t % 4]) and np.array_equal(H[t], H[t % 4]), t
+    print("%s: worst %s" % (case, worst))
+    parity_record.append(dict(test="hist_seams_ccre_batch", case=case, targets=B, **worst))
+
+
+# ================================================================================================ Part B
+def _mi_track(gpu_ctx, sm, extra, shape, regions, nb, pou, math, eps):
+    frame, frame2 = K.frames()
+    corners = np.stack([K.REGIONS[r] for r in regions])
+    b = _mi_batch(gpu_ctx, frame, K.HOM, shape[0], shape[1], corners, nb, pou, math)
+    try:
+        smd = _sm(sm, extra, 0, max_iters=K.MAX_ITERS, epsilon=eps)
+        b.init_template(smd)
+        gpu_ctx.set_image(frame2)
+        n, final = b.track(smd)
+        return n, final
+    finally:
+        b.close()
+
+
+def _mi_loop_reference(oracle, sm, extra, shape, regions, nb, pou):
+    runs = [K.mi_trace(oracle, sm, K.HOM, extra, shape[0], shape[1], K.REGIONS[r], nb, pou) for r in regions]
+    eps, margin = K.pick_eps(runs)
+    assert margin > 1.5, (regions, eps, margin)          # (held on the CPU: tests/test_hist_seams_cpu.py)
+    n = [K.stop_at(r["changes"], eps) for r in runs]
+    return eps, n, [r["corners"][k - 1] for r, k in zip(runs, n)]
+
+
+@pytest.mark.parametrize("math", [REPLAY, FAST], ids=["replay", "fast"])
+@pytest.mark.parametrize("model", range(len(K.MI_LOOP_MODELS)), ids=lambda k: K.sm_name(K.MI_LOOP_MODELS[k][0]) + "-mi%d" % K.MI_LOOP_MODELS[k][2])
+@pytest.mark.parametrize("region", K.LOOP_REGIONS)
+@pytest.mark.parametrize("shape", K.LOOP_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_mi_device_loop(oracle, gpu_ctx, shape, region, model, math, parity_record):
+    """Part B, MI: Batch.track against the oracle's loop -- n_iters equal, corners within test_device_side_loop_mi's bound"""
+    sm, extra, nb, pou = K.MI_LOOP_MODELS[model]
+    eps, n_ref, c_ref = _mi_loop_reference(oracle, sm, extra, shape, (region,), nb, pou)
+    n, final = _mi_track(gpu_ctx, sm, extra, shape, (region,), nb, pou, math, eps)
+    err = float(np.abs(final[0] - c_ref[0]).max())
+    print("loop %dx%d %s %s mi%d math %d: n %d (reference %d), corners %.3e px" % (shape[0], shape[1], region, K.sm_name(sm), nb, math, n[0], n_ref[0], err))
+    parity_record.append(dict(test="hist_seams_mi_loop", case="%dx%d-%s-%s-mi%d-%d" % (shape[0], shape[1], region, K.sm_name(sm), nb, math), n=int(n[0]),
+                              corners_px=err))
+    assert n[0] == n_ref[0]
+    assert err < TP.LOOP_CORNER_PX
+
+
+@pytest.mark.parametrize("math", [REPLAY, FAST], ids=["replay", "fast"])
+@pytest.mark.parametrize("model", range(len(K.MI_LOOP_MODELS)), ids=lambda k: K.sm_name(K.MI_LOOP_MODELS[k][0]) + "-mi%d" % K.MI_LOOP_MODELS[k][2])
+def test_mi_device_loop_batch_of_three(oracle, gpu_ctx, model, math, parity_record):
+    """4 (c), MI: three targets, one past the right edge, that stop after different passes (`if (pa.active && !pa.active[t]) return;`): each
+    against its own reference loop, and the bits of the same target tracked alone"""
+    sm, extra, nb, pou = K.MI_LOOP_MODELS[model]
+    shape = K.BATCH3_SHAPE
+    eps, n_ref, c_ref = _mi_loop_reference(oracle, sm, extra, shape, K.BATCH3, nb, pou)
+    assert len(set(n_ref)) > 1
+    n, final = _mi_track(gpu_ctx, sm, extra, shape, K.BATCH3, nb, pou, math, eps)
+    err = [float(np.abs(final[t] - c_ref[t]).max()) for t in range(3)]
+    print("loop batch of three %s mi%d math %d: n %s (reference %s), corners %s px" % (K.sm_name(sm), nb, math, n.tolist(), n_ref, err))
+    parity_record.append(dict(test="hist_seams_mi_loop_batch3", case="%s-mi%d-%d" % (K.sm_name(sm), nb, math), n=n.tolist(), corners_px=max(err)))
+    assert n.tolist() == n_ref
+    assert max(err) < TP.LOOP_CORNER_PX
+    for t, region in enumerate(K.BATCH3):
+        n1, c1 = _mi_track(gpu_ctx, sm, extra, shape, (region,), nb, pou, math, eps)
+        assert n1[0] == n[t] and np.array_equal(c1[0], final[t]), region
+
+
+def _ccre_track(gpu_ctx, shape, regions, key, math, max_iters, eps):
+    frame, frame2 = K.frames()
+    sm_id, jac, ht = TC.LOOP_KEYS[key]
+    sm = mtf_amd.sm_desc(sm_id, jac_type=jac, hess_type=ht, chained_warp=1, materialize=1 if math == REPLAY else 0, max_iters=max_iters, epsilon=eps,
+                         leven_marq=0)
+    b = _ccre_batch(gpu_ctx, K.HOM, shape[0], shape[1], len(regions), K.CCRE_LOOP_BINS, 0, math)
+    try:
+        gpu_ctx.set_image(frame)
+        b.set_corners(np.stack([K.REGIONS[r] for r in regions]))
+        b.init_template(sm)
+        gpu_ctx.set_image(frame2)
+        n, final = b.track(sm)
+        return n, final, b.get_similarity().copy()
+    finally:
+        b.close()
+
+
+@pytest.mark.parametrize("math", [REPLAY, FAST], ids=["replay", "fast"])
+@pytest.mark.parametrize("key", K.CCRE_LOOP_KEYS)
+@pytest.mark.parametrize("region", K.LOOP_REGIONS)
+@pytest.mark.parametrize("shape", K.LOOP_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_ccre_device_loop(gpu_ctx, shape, region, key, math, parity_record):
+    """Part B, CCRE: Batch.track against make_golden12's loop, as far as that loop pins a second implementation (hist_seam_cases.ccre_loop:
+    without a convergence test, up to the iteration its own 1e-11-shifted run follows) -- n_iters equal, corners within LOOP_PX"""
+    ref = K.ccre_loop(shape[0], shape[1], region, K.CCRE_LOOP_BINS, key)
+    assert ref["iters"] >= 1
+    n, final, _ = _ccre_track(gpu_ctx, shape, (region,), key, math, ref["iters"], 0.0)
+    err = float(np.abs(final[0] - ref["corners"][-1]).max())
+    print("ccre loop %dx%d %s %s math %d: n %d (reference %d), corners %.3e px" % (shape[0], shape[1], region, key, math, n[0], ref["iters"], err))
+    parity_record.append(dict(test="hist_seams_ccre_loop", case="%dx%d-%s-%s-%d" % (shape[0], shape[1], region, key, math), n=int(n[0]), corners_px=err))
+    assert n[0] == ref["iters"]
+    assert err < TC.LOOP_PX
+
+
+@pytest.mark.parametrize("math", [REPLAY, FAST], ids=["replay", "fast"])
+@pytest.mark.parametrize("key", [K.CCRE_BATCH_KEY])
+def test_ccre_device_loop_batch_of_three(gpu_ctx, key, math, parity_record):
+    """4 (c), CCRE: the flat target's update is zero, so it stops after its first pass while its neighbours go on -- an inactive target keeps its
+    tables: its similarity after the loop is that of the same target tracked alone, and every target has the bits of its own single run"""
+    shape = K.BATCH3_SHAPE
+    refs = [K.ccre_loop(shape[0], shape[1], r, K.CCRE_LOOP_BINS, key) for r in K.BATCH3]
+    iters = min(r["iters"] for r in refs)
+    n_ref = [iters, iters, 1]
+    assert iters >= 2
+    n, final, sim = _ccre_track(gpu_ctx, shape, K.BATCH3, key, math, iters, K.CCRE_BATCH_EPS)
+    err = [float(np.abs(final[t] - refs[t]["corners"][n_ref[t] - 1]).max()) for t in range(3)]
+    print("ccre loop batch of three %s math %d: n %s (reference %s), corners %s px" % (key, math, n.tolist(), n_ref, err))
+    parity_record.append(dict(test="hist_seams_ccre_loop_batch3", case="%s-%d" % (key, math), n=n.tolist(), corners_px=max(err)))
+    assert n.tolist() == n_ref
+    assert max(err) < TC.LOOP_PX
+    for t, region in enumerate(K.BATCH3):
+        n1, c1, s1 = _ccre_track(gpu_ctx, shape, (region,), key, math, iters, K.CCRE_BATCH_EPS)
+        assert n1[0] == n[t] and np.array_equal(c1[0], final[t]) and s1[0] == sim[t], region
+
+
+# ================================================================================================ the widened bounds
+def test_at_most_one_case_in_ten_runs_on_a_widened_bound():
+    """(runs last in this file.)  Of the cases this session ran, those held to max(bound, 16 x the reference's floor) instead of the bound"""
+    print("widened: %d of %d cases: %s" % (len(WIDENED), len(RAN), sorted(WIDENED)))
+    assert len(WIDENED) * 10 <= max(len(RAN), 1), sorted(WIDENED)

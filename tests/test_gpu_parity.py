@@ -283,7 +283,13 @@ def test_fused_iterations_follow_oracle(oracle, gpu_ctx, frame, case, materializ
     _fused_follow(oracle, gpu_ctx, frame, L.AM_SSD, case, materialize, grid)
 
 
-def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=None, dp_tol=1e-5):
+# _fused_follow's bounds on (f, H, g), by grid and arithmetic (the seam suites take them from here); the update: DP_TOL relative, or
+# DP_CORNER_PX at the corners; LOOP_CORNER_PX: the corners after a device-side loop (_device_loop)
+FOLLOW_BOUNDS = dict(oracle_grid=(1e-12, 1e-9, 1e-10), device_grid=(1e-8, 1e-5, 1e-5), fast=(1e-8, 2e-6, 2e-6))
+DP_TOL, DP_CORNER_PX, LOOP_CORNER_PX = 1e-5, 1e-6, 2e-4
+
+
+def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=None, dp_tol=DP_TOL):
     """Drive the SM loop on the host exactly as the reference does (solve + compositional update on the
     CPU), with the device producing f, g, H per iteration; compare every iteration with the oracle's
     trace of nt::ESM / nt::FCLK / nt::ICLK::update.
@@ -365,13 +371,14 @@ def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=Non
                     assert rel(gf[0], r6["g"]) < 2e-5 and rel(dpf, r6["dp"]) < 2e-5, it
                 assert rel(gf[0], rec["g"]) < 1e-5 and rel(dpf, rec["dp"]) < dp_tol, it
             # (ii) against the reference's own arithmetic: one set of bounds for SSD, NCC and MI
-            assert rel(ff[0], rec["f"]) < 1e-8, it
-            assert rel(Hf[0], rec["H"]) < 2e-6, it
-            assert np.linalg.norm(gf[0] - rec["g"]) < 2e-6 * max(np.linalg.norm(rec["g"]), gs), it
+            tol_f, tol_H, tol_g = FOLLOW_BOUNDS["fast"]
+            assert rel(ff[0], rec["f"]) < tol_f, it
+            assert rel(Hf[0], rec["H"]) < tol_H, it
+            assert np.linalg.norm(gf[0] - rec["g"]) < tol_g * max(np.linalg.norm(rec["g"]), gs), it
             cf = b.apply_warp_to_corners(corners[None], dpf[None])[0]
             cr = b.apply_warp_to_corners(corners[None], rec["dp"][None])[0]
             # (later passes: dp itself goes to zero, so either its relative error or what it does to the corners)
-            assert rel(dpf, rec["dp"]) < dp_tol or np.abs(cf - cr).max() < 1e-6, it
+            assert rel(dpf, rec["dp"]) < dp_tol or np.abs(cf - cr).max() < DP_CORNER_PX, it
         f, g, H = b.iterate(sm)
         dp = -oracle.colpiv_qr_solve(H[0], g[0])
         if it <= 1 and not tight:    # plain relative errors while g and dp are far from zero (north_star's literal wording)
@@ -379,18 +386,19 @@ def _fused_follow(oracle, gpu_ctx, frame, am, case, materialize, grid, am_kw=Non
             assert rel(dp, rec["dp"]) < dp_tol, it
         # scale of g: Cauchy-Schwarz ||J|| ||r|| for SSD; for NCC the gradient vectors have norm <= 2 / b, so ||Jc|| ~ sqrt(|tr H|)
         g_scale = np.sqrt(abs(np.trace(rec["H"]))) * (np.sqrt(abs(2 * rec["f"])) if am == L.AM_SSD else 1.0)
+        tol_f, tol_H, tol_g = FOLLOW_BOUNDS[grid]
         if tight:
-            assert rel(f[0], rec["f"]) < 1e-12, it
-            assert rel(H[0], rec["H"]) < 1e-9, it
-            assert np.linalg.norm(g[0] - rec["g"]) < 1e-10 * max(np.linalg.norm(rec["g"]), g_scale), it
+            assert rel(f[0], rec["f"]) < tol_f, it
+            assert rel(H[0], rec["H"]) < tol_H, it
+            assert np.linalg.norm(g[0] - rec["g"]) < tol_g * max(np.linalg.norm(rec["g"]), g_scale), it
             assert rel(dp, rec["dp"]) < 1e-6 or np.abs(dp - rec["dp"]).max() < 1e-12, it
         else:
-            assert rel(f[0], rec["f"]) < 1e-8, it
-            assert rel(H[0], rec["H"]) < 1e-5, it
-            assert np.linalg.norm(g[0] - rec["g"]) < 1e-5 * max(np.linalg.norm(rec["g"]), g_scale), it
+            assert rel(f[0], rec["f"]) < tol_f, it
+            assert rel(H[0], rec["H"]) < tol_H, it
+            assert np.linalg.norm(g[0] - rec["g"]) < tol_g * max(np.linalg.norm(rec["g"]), g_scale), it
             c_gpu = b.apply_warp_to_corners(corners[None], dp[None])[0]
             c_ref = b.apply_warp_to_corners(corners[None], rec["dp"][None])[0]
-            assert rel(dp, rec["dp"]) < dp_tol or np.abs(c_gpu - c_ref).max() < 1e-6, it
+            assert rel(dp, rec["dp"]) < dp_tol or np.abs(c_gpu - c_ref).max() < DP_CORNER_PX, it
         # follow the oracle's trajectory so that every iteration is compared on identical inputs
         dp = rec["dp"]
         if sm_kind == L.SM_ICLK:
@@ -596,7 +604,7 @@ def _device_loop(oracle, gpu_ctx, frame, sm_kind, ssm, am, res, extra, record=No
         trk.initialize(corners[t])
         o_am.set_curr_img(frame2)
         iters = trk.update()
-        np.testing.assert_allclose(final[t], trk.get_region(), rtol=0, atol=2e-4)
+        np.testing.assert_allclose(final[t], trk.get_region(), rtol=0, atol=LOOP_CORNER_PX)
         assert abs(int(n_it[t]) - iters) <= 1
     # target chunking (all iterations of 2 targets, then the next 2, ...) changes the schedule, not the result
     import os

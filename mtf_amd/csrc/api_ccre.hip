@@ -40,7 +40,6 @@ int ccre_initialize_similarity(mtfhip_batch *b) {
 	const bool first = !b->init_sim;
 	ccre_hist_tables(b, first ? mtfhip::CCRE_TB_INIT : mtfhip::CCRE_TB_HIST0, 0);
 	if (first) TRY(ccre_read_f(b, true));
-	b->init_sim = true;
 	return MTFHIP_OK;
 }
 /* CCRE::updateSimilarity CCRE.cc:319-414 */
@@ -88,12 +87,10 @@ int ccre_hessian(mtfhip_batch *b, int j_buf, int kind, double *H) {
 }
 /* CCRE::getLikelihood CCRE.h:72-75 with likelihood_beta = 0 (the descriptor carries alpha alone): d = max_similarity / f - 1.
  * max_similarity is initializeSimilarity's f: without one there is nothing to compare with */
-int ccre_likelihood(const mtfhip_batch *b, double *l) {
+int ccre_likelihood(const mtfhip_batch *b, int t, double *l) {
 	if ((int)b->ccre_f_max.size() != b->B) return fail(MTFHIP_ERR_LOGIC, "getLikelihood: CCRE before initializeSimilarity (max_similarity is its f)");
-	for (int t = 0; t < b->B; ++t) {
-		const double d = (b->ccre_f_max[t] / b->th[t].f) - 1;
-		l[t] = std::exp(-b->desc.likelihood_alpha * d * d);
-	}
+	const double d = (b->ccre_f_max[t] / b->th[t].f) - 1;
+	*l = std::exp(-b->desc.likelihood_alpha * d * d);
 	return MTFHIP_OK;
 }
 

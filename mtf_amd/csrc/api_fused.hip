@@ -461,73 +461,6 @@ static int iterate_core(mtfhip_batch *b, const mtfhip_sm_desc *sm, double *f, do
 	return assemble_rows(b, sm, fa.hess_mean != 0, nblk, term >= 0 ? so.data() : nullptr, term == 1 ? 0.5 : 1.0, f, g, H);
 }
 
-/* getSimilarity() right after updatePixVals + updateSimilarity -- Levenberg-Marquardt's test in the middle of every
- * iteration (NT/ESM.cc:186-204, FCLK.cc:205-223, ICLK.cc:181-199): one launch of the lean (ICLK-type) fused kernel
- * writes IT and accumulates what f needs, instead of sample + residual (SSD) or sample + two reduction passes with
- * two host round trips (NCC).  Anything else pending, or nothing pending: not taken, the caller flushes. */
-int lazy_try_similarity(mtfhip_batch *b) {
-	mtfhip_batch::Lazy &L = b->lz;
-	if (!L.enabled || !L.pv || !L.sim || L.pv > L.sim || L.gp || L.pg || L.pj || L.cg || L.ig || L.jm) return MTFHIP_OK;
-	if (!b->init_pix_vals || !b->init_sim || !b->have_corners || !b->ctx->img.data || b->ctx->img.channels != 1) return MTFHIP_OK;
-	const bool ncc = b->desc.am == MTFHIP_AM_NCC;
-	mtfhip_sm_desc sm;
-	std::memset(&sm, 0, sizeof(sm));
-	sm.sm = MTFHIP_SM_ICLK; sm.hess_type = 0; sm.materialize = 1; sm.max_iters = 1; sm.chained_warp = 1;
-	FusedArgs fa;
-	TRY(fused_args(b, &sm, fa));
-	const bool mi = b->desc.am == MTFHIP_AM_MI;
-	if (!mi) TRY(protect_stale(b, !ncc, false));   /* SSD's updateSimilarity re-produces df_dI0 */
-	const int nblk = fused_blocks_per_target(b->N, b->B);
-	hipStream_t st = b->ctx->stream;
-	{
-		TimedScope ts(b->ctx, "fused_lk");
-		launch_fused_ssd(fused_view(b, fa), b->ctx->img, fa, b->d_partials, nblk, st);
-	}
-	touch(b, MTFHIP_BUF_IT);
-	b->it_valid = true;
-	L.it_epoch = L.epoch;
-	L.df0_it_ver = L.ver[MTFHIP_BUF_IT];
-	if (!ncc && !mi) { L.df0_stale = true; L.df0_sh = false; if (!L.dft_sh) L.shadow_valid = false; }
-	L.pv = L.sim = 0;
-	if (mi) {
-		/* MI: the lean launch wrote It (its SSD sums are ignored); now the histogram pass and the table kernel */
-		const int nb = b->desc.mi_n_bins, nblk_mi = mi_blocks(b);
-		const bool self = L.mi_want_self && !L.no_cache;
-		{
-			TimedScope ts(b->ctx, "mi_hist");
-			const double *It = b->buf[MTFHIP_BUF_IT], *I0 = b->buf[MTFHIP_BUF_I0];
-			if (self) launch_mi_hist_self(b->view(), nb, b->mi_hist_norm, It, I0, b->d_mi_part, nblk_mi, b->mi_row_len, st);
-			else launch_mi_hist(b->view(), nb, b->mi_hist_norm, It, I0, b->d_mi_part, nblk_mi, b->mi_row_len, st);
-			launch_mi_tables_iter(b->view(), nb, b->desc.mi_pre_seed, b->mi_hist_norm, self ? 1 : 0, b->d_mi_part, nblk_mi, b->mi_row_len, b->d_mi_tb,
-				b->d_mi_f, st);
-		}
-		L.mi_self_it = self ? L.ver[MTFHIP_BUF_IT] : -1;
-		std::vector<double> fv(b->B);
-		HIP_TRY(hipMemcpyAsync(fv.data(), b->d_mi_f, sizeof(double) * b->B, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		for (int t = 0; t < b->B; ++t) b->th[t].f = fv[t];
-		return MTFHIP_OK;
-	}
-	if (ncc) {
-		TRY(read_rows(b, nblk, NCC_ACC_COUNT));
-		for (int t = 0; t < b->B; ++t) ncc_refresh_mirrors(b, b->th[t], b->h_acc + (size_t)t * NCC_ACC_COUNT);
-		b->ncc_host_newer = true;
-		if (!L.no_cache) {   /* sum It J0 and the scalars: enough for cmptInitJacobian / cmptInitHessian of this IT */
-			L.ncc_M.assign(b->h_acc.get(), b->h_acc + (size_t)NCC_ACC_COUNT * b->B);
-			L.ncc_M_mean = false; L.ncc_M_it = L.ver[MTFHIP_BUF_IT]; L.ncc_M_jt = L.ncc_M_jm = -1;
-		}
-		return MTFHIP_OK;
-	}
-	TRY(read_acc(b, nblk));
-	for (int t = 0; t < b->B; ++t) b->th[t].f = -b->h_acc[(size_t)t * ACC_COUNT + ACC_RR] / 2;
-	if (!L.no_cache) {
-		L.sim_g.resize((size_t)8 * b->B);
-		for (int t = 0; t < b->B; ++t) std::memcpy(&L.sim_g[(size_t)8 * t], b->h_acc + (size_t)t * ACC_COUNT + ACC_G, sizeof(double) * 8);
-		L.sim_g_it = L.ver[MTFHIP_BUF_IT]; L.sim_g_j0 = L.ver[MTFHIP_BUF_J0];
-	}
-	return MTFHIP_OK;
-}
-
 } /* extern "C" */
 
 #ifdef MTFHIP_FIN_TRACE

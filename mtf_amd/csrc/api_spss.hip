@@ -19,6 +19,13 @@ SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm) {
 	return sp;
 }
 
+/* SPSS::initializeSimilarity SPSS.cc:94-100: It = I0, f_vec = 1, f = patch_size */
+int spss_initialize_similarity(mtfhip_batch *b) {
+	if (b->init_sim) return MTFHIP_OK;
+	HIP_TRY(hipMemsetAsync(b->buf[MTFHIP_BUF_DF_DI0], 0, sizeof(double) * b->N * b->B, b->ctx->stream));
+	for (auto &h : b->th) h.f = (double)b->N;
+	return MTFHIP_OK;
+}
 int spss_update_similarity(mtfhip_batch *b, int prereq_only) {
 	/* (f_vec, f_vec_den and It_sqr are functions of I0 and It: every kernel that needs them recomputes them, so prereq_only has nothing to store) */
 	if (prereq_only) return MTFHIP_OK;
@@ -31,9 +38,11 @@ int spss_update_similarity(mtfhip_batch *b, int prereq_only) {
 	for (int t = 0; t < b->B; ++t) b->th[t].f = b->h_acc[(size_t)t * ACC_COUNT + ACC_RR];
 	return MTFHIP_OK;
 }
-int spss_update_grad(mtfhip_batch *b, int curr) {
+/* which 0: updateInitGrad, 1: updateCurrGrad, 2: initializeGrad (SPSS.cc:104-114) */
+int spss_update_grad(mtfhip_batch *b, int which) {
+	if (which == 2) return zero_grad_vectors(b);
 	TimedScope ts(b->ctx, "spss_grad");
-	launch_spss_grad(b->view(), b->spss_c, curr, b->buf[curr ? MTFHIP_BUF_DF_DIT : MTFHIP_BUF_DF_DI0], b->ctx->stream);
+	launch_spss_grad(b->view(), b->spss_c, which, b->buf[which ? MTFHIP_BUF_DF_DIT : MTFHIP_BUF_DF_DI0], b->ctx->stream);
 	return MTFHIP_OK;
 }
 int spss_weighted_hessian(mtfhip_batch *b, int j_buf, int weight, double *H) {
@@ -59,6 +68,11 @@ int spss_weighted_hessian(mtfhip_batch *b, int j_buf, int weight, double *H) {
 int spss_hessian(mtfhip_batch *b, int j_buf, int kind, double *H) {
 	static const int weight[3] = {SPSS_W_INIT, SPSS_W_CURR, SPSS_W_SELF};
 	return spss_weighted_hessian(b, j_buf, weight[kind], H);
+}
+/* SPSS::getLikelihood SPSS.cc:46-48 */
+int spss_likelihood(const mtfhip_batch *b, int t, double *l) {
+	*l = std::exp(b->desc.likelihood_alpha * (b->th[t].f - (double)b->N));
+	return MTFHIP_OK;
 }
 
 extern "C" {

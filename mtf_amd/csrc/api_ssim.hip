@@ -46,8 +46,9 @@ int ssim_update_similarity(mtfhip_batch *b, int prereq_only) {
 	b->ncc_host_newer = true;
 	return MTFHIP_OK;
 }
-/* SSIM::updateCurrGrad / updateInitGrad SSIM.cc:113-142 into DF_DIT / DF_DI0 */
+/* which 1 / 0: SSIM::updateCurrGrad / updateInitGrad SSIM.cc:113-142 into DF_DIT / DF_DI0; 2: initializeGrad (SSIM.cc:78-96) */
 int ssim_update_grad(mtfhip_batch *b, int curr) {
+	if (curr == 2) return zero_grad_vectors(b);
 	std::vector<double> sc(8 * (size_t)b->B, 0.0);
 	for (int t = 0; t < b->B; ++t) {
 		const SsimSys q = ssim_mirror_sys(b, b->th[t]);

@@ -1,8 +1,9 @@
 /*
  * mtfhip_api_internal.h -- what the translation units of the C-ABI implementation share: error plumbing, the small
  * host-side math (3x3 warps, 4-corner DLT), the context / batch handles and their helpers, and the declarations of
- * the functions that cross unit boundaries (the deferred-fusion layer lives in api_am.hip, the NCC moment forms in
- * api_ncc_moments.hip, the skeleton of the device-side loops in api_track.hip).  Not installed: include/mtfhip.h is the public contract.
+ * the functions that cross unit boundaries (the per-function entry points and kAmOps live in api_am.hip, each appearance model's own code in
+ * a unit of its name, the deferred-fusion layer in api_lazy.hip, the skeleton of the device-side loops in api_track.hip).  Not installed:
+ * include/mtfhip.h is the public contract.
  */
 #ifndef MTFHIP_API_INTERNAL_H
 #define MTFHIP_API_INTERNAL_H
@@ -585,13 +586,15 @@ static inline int am_refuse(const mtfhip_batch *b, const char *fn, int place, co
 }
 /* SPSS: a model of its own -- no SSD branch serves it, and of the fused routes only the two-launch loop does (fused_select) */
 static inline bool spss_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SPSS; }
-/* api_spss.hip.  spss_args: what a fused launch for the search method sm reads beside FusedArgs; the per-function updateSimilarity, update*Grad
- * and Hessians (spss_weighted_hessian: weight SPSS_W_*; spss_hessian: kind 0 init, 1 curr, 2 self) */
+/* api_spss.hip.  spss_args: what a fused launch for the search method sm reads beside FusedArgs; SPSS's row of kAmOps (and
+ * spss_weighted_hessian: weight SPSS_W_*) */
 mtfhip::SpssArgs spss_args(const mtfhip_batch *b, const mtfhip_sm_desc *sm);
+int spss_initialize_similarity(mtfhip_batch *b);
 int spss_update_similarity(mtfhip_batch *b, int prereq_only);
-int spss_update_grad(mtfhip_batch *b, int curr);
+int spss_update_grad(mtfhip_batch *b, int which);
 int spss_weighted_hessian(mtfhip_batch *b, int j_buf, int weight, double *H);
 int spss_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
+int spss_likelihood(const mtfhip_batch *b, int t, double *l);
 /* SSIM: every quantity of SSIM.cc is a function of the raw moments an NCC pass reduces (mtfhip_sm_system.h), so an SSIM batch launches NCC's
  * pass kernels (fused_select) on the two-launch loop, and its own finish (kernels_ssim.hip) */
 static inline bool ssim_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_SSIM; }
@@ -599,23 +602,35 @@ static inline bool ssim_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_
  * upload d_ncc_tm, the per-target scalars d_ncc and their refresh.  (What solves NCC's own system -- the one-launch, step and persistent
  * kernels, the fused template initialisation, the second-order pass, the deferred-fusion layer -- asks for MTFHIP_AM_NCC by name.) */
 static inline bool ncc_rows(const mtfhip_batch *b) { return am_traits(b->desc.am).rows == AM_ROWS_NCC; }
-/* api_ssim.hip.  ssim_h0: the constant self Hessian from the template's moments (th[].ncc_tm must be current); the per-function
- * updateSimilarity, update*Grad and Hessians (kind 0 init, 1 curr, 2 self: NCC_H_*) */
+/* api_ssim.hip.  ssim_h0: the constant self Hessian from the template's moments (th[].ncc_tm must be current); SSIM's row of kAmOps
+ * (its initializeSimilarity is NCC's, its likelihood NCC's form) */
 int ssim_h0(const mtfhip_batch *b, double *H0);
 int ssim_update_similarity(mtfhip_batch *b, int prereq_only);
-int ssim_update_grad(mtfhip_batch *b, int curr);
+int ssim_update_grad(mtfhip_batch *b, int which);
 int ssim_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
 /* CCRE (api_ccre.hip): MI's materialising iteration with cumulative weights on the current patch's side, in the buffers an MI batch has.
  * hist_am: the models whose iteration is a histogram pipeline of its own behind a materialising SSD pass (mi_enqueue / ccre_enqueue) and whose
- * device loop is their own driver (MI and CCRE).  ccre_grad: 0 updateInitGrad, 1 updateCurrGrad, 2 initializeGrad; ccre_hessian: kind 0 init,
- * 1 curr, 2 self */
+ * device loop is their own driver (MI and CCRE).  CCRE's row of kAmOps follows */
 static inline bool ccre_am(const mtfhip_batch *b) { return b->desc.am == MTFHIP_AM_CCRE; }
 static inline bool hist_am(const mtfhip_batch *b) { return am_traits(b->desc.am).hist_driver; }
 int ccre_initialize_similarity(mtfhip_batch *b);
 int ccre_update_similarity(mtfhip_batch *b, int prereq_only);
 int ccre_grad(mtfhip_batch *b, int which);
 int ccre_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
-int ccre_likelihood(const mtfhip_batch *b, double *l);   /* [B] */
+int ccre_likelihood(const mtfhip_batch *b, int t, double *l);
+/* What differs by model at the per-function AppearanceModel entry points (api_am.hip: kAmOps, one row per MTFHIP_AM_*):
+ * initializeSimilarity (the model's own reads init_sim; the entry point sets it); updateSimilarity; grad, which 0 updateInitGrad into DF_DI0,
+ * 1 updateCurrGrad into DF_DIT, 2 initializeGrad into both (the entry point asks once per batch); cmptInitHessian / cmptCurrHessian /
+ * cmptSelfHessian, kind 0 / 1 / 2, into H [B][S x S]; getLikelihood of target t from th[t].f, no launch.  A null entry: the SSD body of
+ * the entry point -- SSD and the SCV family */
+struct AmOps {
+	int (*initialize_similarity)(mtfhip_batch *b);
+	int (*update_similarity)(mtfhip_batch *b, int prereq_only);
+	int (*grad)(mtfhip_batch *b, int which);
+	int (*hessian)(mtfhip_batch *b, int j_buf, int kind, double *H);
+	int (*likelihood)(const mtfhip_batch *b, int t, double *l);
+};
+const AmOps &am_ops(const mtfhip_batch *b);
 /* one target's reduced NCC row and template mirrors as the SSIM system of mtfhip_sm_system.h; and the host mirrors of SSIM.cc's members it leaves */
 static inline mtfhip::SsimSys ssim_host_sys(const mtfhip_batch *b, const TargetHost &h, const double *M) {
 	return mtfhip::ssim_sys(M, h.ncc_tm, h.I0_mean, h.i0_ss, (double)b->N, b->ssim_c1, b->ssim_c2);
@@ -797,12 +812,7 @@ static inline int begin_entry(mtfhip_batch *b) {
 	if (b) { touch_all(b); b->lz.it_epoch = -1; TRY(ensure_df(b)); }
 	return MTFHIP_OK;
 }
-static int ensure_one(mtfhip_batch *b, bool curr);
-void stale_clear(mtfhip_batch *b, bool df0, bool dft);
-int protect_stale(mtfhip_batch *b, bool w0, bool wt);
-int lazy_try_similarity(mtfhip_batch *b);
 int do_cmpt_pix_jacobian(mtfhip_batch *b, int variant, int grad_buf, int dst_buf);
-static int do_mean_jacobian(mtfhip_batch *b);
 static int lazy_flush_ctx(mtfhip_ctx *c) {   /* called by everything that replaces the current image */
 	for (mtfhip_batch *b : c->batches) {
 		/* the record of a fused template initialisation does not depend on the image any more (d_h0 / d_ncc / d_ncc_tm are written): with no
@@ -864,11 +874,39 @@ const float *pair_image_if_it_pays(mtfhip_ctx *c, int n_candidates);
 int set_corners_core(mtfhip_batch *b, const double *corners, bool for_track, bool defer_grid = false, bool layout_later = false);   /* api_core.hip */
 void set_corners_finish_deferred(mtfhip_batch *b);
 int do_update_grad_pts(mtfhip_batch *b, double grad_eps);
+/* api_am.hip: the executors of the per-function calls the deferred layer records and replays (do_*, pix_grad_common), the gradient vectors'
+ * common start, the Jacobian product */
+int do_update_pix_vals(mtfhip_batch *b, const double *pts);
+int pix_grad_common(mtfhip_batch *b, const double *pts, bool warped, bool init);
+int do_update_similarity(mtfhip_batch *b, int prereq_only);
+int do_update_curr_grad(mtfhip_batch *b);
+int do_mean_jacobian(mtfhip_batch *b);
+int zero_grad_vectors(mtfhip_batch *b);
 int gemv_to_host(mtfhip_batch *b, const double *v1, int j1, const double *v2, int j2, int sum_mode, double *g, int diff);
+/* api_lazy.hip (stale_clear: df_dI0 / df_dIt have just been written for the current IT; ensure_one: df_dI0 (curr 0) / df_dIt (1) derived if a
+ * fused launch skipped it; protect_stale: see there; lazy_try_fused: trig LAZY_*, *done = 1 when one fused launch served the request) */
+void stale_clear(mtfhip_batch *b, bool df0, bool dft);
+int ensure_one(mtfhip_batch *b, bool curr);
+int protect_stale(mtfhip_batch *b, bool w0, bool wt);
+int lazy_try_fused(mtfhip_batch *b, int trig, int j_a, int j_b, double *g, int *done);
+int lazy_try_similarity(mtfhip_batch *b);
+/* api_mi.hip: MI's row of kAmOps, the pixel weights of its second-order self Hessian (into d_d2_w), its half of the deferred layer */
 int mi_blocks(const mtfhip_batch *b);
-int push_ncc(mtfhip_batch *b);
-/* api_ncc_moments.hip (ncc_host_sys: one target's reduced row and template mirrors as the NCC system of mtfhip_sm_system.h; ncc_refresh_mirrors: its
+int mi_initialize_similarity(mtfhip_batch *b);
+int mi_update_similarity(mtfhip_batch *b, int prereq_only);
+int mi_grad(mtfhip_batch *b, int which);
+int mi_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
+int mi_self_weight(mtfhip_batch *b);
+int mi_lazy_similarity(mtfhip_batch *b);
+int mi_lazy_fused(mtfhip_batch *b, int trig, int j_a, const mtfhip_sm_desc &sm, bool replay, double *g, int *done);
+/* api_ncc.hip: NCC's row of kAmOps (ncc_initialize_similarity is SSIM's too); push_ncc: the host scalars -> d_ncc; the moment forms of the
+ * fused path (ncc_host_sys: one target's reduced row and template mirrors as the NCC system of mtfhip_sm_system.h; ncc_refresh_mirrors: its
  * scalars -> It_mean / b / a / f) */
+int push_ncc(mtfhip_batch *b);
+int ncc_initialize_similarity(mtfhip_batch *b);
+int ncc_update_similarity(mtfhip_batch *b, int prereq_only);
+int ncc_grad(mtfhip_batch *b, int which);
+int ncc_hessian(mtfhip_batch *b, int j_buf, int kind, double *H);
 int ncc_template_moments(mtfhip_batch *b);
 int ncc_lazy_outputs(mtfhip_batch *b, int trig, int j_a, bool hess_mean, double *g);
 int ncc_hessian_from_cache(mtfhip_batch *b, int j_buf, int kind, double *H);

@@ -1,6 +1,6 @@
 /*
  * mtfhip_sm_system.h -- the rule that turns one target's reduced accumulator row into a search method's f, g and H (before damping),
- * stated ONCE for the host-side assembly (api_fused.hip: assemble_rows, api_ncc_moments.hip) and the device-side finish
+ * stated ONCE for the host-side assembly (api_fused.hip: assemble_rows, api_ncc.hip) and the device-side finish
  * (mtfhip_finish_device.h): the accumulator slots, the Hessian source predicates, the SSD-family and SPSS entries, NCC from its raw
  * moments, SSIM from the same moments, and the projection of the affine-coordinate system onto a low-order SSM.  Both sides are compiled with -ffp-contract=off, so
  * one expression gives one set of bits: `iterate` followed by a host solve and the device loop are the same method because they call

@@ -182,7 +182,7 @@ def test_mi_three_channels(oracle, gpu_ctx, shape, math, parity_record):
 
 # ------------------------------------------------------------------------------------------------ batches
 def _expected_blocks(N, B):
-    """mi_blocks and mi_enqueue_fast's pass-1 count (api_am.hip, api_mi_iter.hip) for this device"""
+    """mi_blocks and mi_enqueue_fast's pass-1 count (api_mi.hip, api_mi_iter.hip) for this device"""
     import torch
     nblk = min(max(1024 // B, 1), -(-N // 1024))
     slots = 3 * max(torch.cuda.get_device_properties(0).multi_processor_count, 1)

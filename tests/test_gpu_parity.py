@@ -917,13 +917,15 @@ def _lazy_batch(gpu_ctx, frame, ssm, res, corners, lazy, monkeypatch, am=L.AM_SS
 
 @pytest.mark.parametrize("am", [L.AM_SSD, L.AM_NCC, L.AM_MI])
 @pytest.mark.parametrize("ssm", [L.SSM_HOMOGRAPHY, L.SSM_AFFINE])
-@pytest.mark.parametrize("flow", ["esm", "esm_original", "fclk", "fclk_unchained", "iclk", "lm", "odd_order"])
+@pytest.mark.parametrize("flow", ["esm", "esm_original", "fclk", "fclk_unchained", "iclk", "lm", "odd_order", "flush_only"])
 def test_deferred_fusion_equals_call_by_call(gpu_ctx, frame, frame2, ssm, flow, am, monkeypatch):
     """The per-function entry points only record the pixel-level calls of an iteration and serve the ESM / FCLK / ICLK
     sequences with one fused launch (mtfhip_batch::Lazy).  Whatever the call pattern, buffers and results must be those
     of the call-by-call execution (MTFHIP_LAZY=0): per-pixel arrays bit for bit, the N-wide sums to summation order.
     NCC: the fused launch derives the scalars from raw moments instead of two passes, so everything that depends on them
-    (f, g, H, and the gradient vectors df_dI re-derived afterwards) agrees to rounding, not to the bit."""
+    (f, g, H, and the gradient vectors df_dI re-derived afterwards) agrees to rounding, not to the bit.
+    flush_only: no Jacobian is asked for, so nothing fuses and the flush replays every recorded call -- updateInitGrad
+    included -- through the un-fused kernels in the recorded order: every array bit for bit, no tolerance."""
     rng = np.random.default_rng(11)
     corners = synth.square_corners(250, 260, 70) + rng.uniform(-3, 3, size=(2, 4))
     p = (synth.random_small_homography(rng) if ssm == L.SSM_HOMOGRAPHY else rng.uniform(-1, 1, 6) * [2, 2, .02, .02, .02, .02])
@@ -941,6 +943,11 @@ def test_deferred_fusion_equals_call_by_call(gpu_ctx, frame, frame2, ssm, flow, 
             b.update_similarity(False)
             if flow == "lm":
                 res.append(b.get_similarity().copy())       # Levenberg-Marquardt reads f in the middle of the iteration
+            if flow == "flush_only":
+                b.update_init_grad(); b.update_curr_grad()
+                res += [b.read(buf).copy() for buf in (L.BUF_IT, L.BUF_DF_DI0, L.BUF_DF_DIT)] + [b.get_similarity().copy()]
+                state = state + 0.02 * (it + 1) * p
+                continue
             if flow in ("esm", "esm_original", "lm"):
                 b.update_pix_grad(); b.cmpt_pix_jacobian(L.JAC_WARPED, L.BUF_DIT_DX, L.BUF_JT)
                 if flow == "esm_original": b.mean_jacobian()
@@ -979,10 +986,14 @@ def test_deferred_fusion_equals_call_by_call(gpu_ctx, frame, frame2, ssm, flow, 
     assert out[0][1] == 0
     # one fused launch per iteration; with the LM pattern a lean one behind getSimilarity() and the full one afterwards
     # (MI: the fused LK kernel is its materialising pass; df_dIt . Jm of the Original Jacobian is not accumulated there)
-    expect = {"odd_order": 0, "lm": 6}.get(flow, 3)
+    expect = {"odd_order": 0, "flush_only": 0, "lm": 6}.get(flow, 3)
     if am == L.AM_MI and flow == "esm_original": expect = 0
     assert out[1][1] == expect, "the deferred path did not take the fused launch"
     assert len(direct) == len(fused)
+    if flow == "flush_only":
+        for k, (a, c) in enumerate(zip(direct, fused)):
+            assert np.array_equal(a, c), k
+        return
     ncc = am != L.AM_SSD    # NCC and MI: values that pass through the scalars / tables agree to rounding
     for k, (a, c) in enumerate(zip(direct, fused)):
         if a.size <= 64:                       # g, H, f: sums over the pixels

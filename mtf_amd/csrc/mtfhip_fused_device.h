@@ -49,7 +49,7 @@ struct PixIn {
 	double j0[MODE == 0 ? 1 : S];
 	int ch;   /* MC: the row's channel */
 };
-/* warped position of a grid point and the four texels of its bilinear cell, fetched one row ahead */
+/* warped position of a grid point and the four texels of its bilinear cell (TEX_AHEAD: taken one row ahead) */
 struct Tex {
 	double wx, wy, cx, cy, D;
 	double inv;        /* FAST: 1 / D */
@@ -60,12 +60,16 @@ struct Tex {
 };
 
 /*
- * Software pipeline (per thread, rows are 256 pixels apart):
- *   iteration i:  [texel loads of row i+1] -> [streaming loads of row i+2: grid point, I0, J0 columns]
+ * Software pipeline (per thread, rows are 256 pixels apart).  Every kernel but the TEX_AHEAD ones:
+ *   iteration i:  position + [texel loads of row i] -> [streaming loads of row i+1: grid point, I0, J0 columns]
  *                 -> arithmetic of row i -> [stores of row i]
- * vmcnt retires in order, so the texels of a row are requested before the younger streaming loads and
- * are consumed one iteration later, when everything older has long completed; each wave keeps two rows
- * of HBM reads plus one row of writes in flight.
+ * vmcnt retires in order, so the texels of a row are requested before the younger streaming loads and the row waits for them
+ * alone -- but it does wait: they were requested some thirty instructions earlier, and only the SIMD's other waves cover the
+ * round trip.  The TEX_AHEAD kernels (lean_tex_ahead_kernel below: the lean replay SSD passes that fit the registers):
+ *   iteration i:  position + [texel loads of row i+1] -> [position operands of row i+2, other streaming operands of row i+1]
+ *                 -> arithmetic of row i, on texels requested one iteration earlier
+ * What crosses a row is wx, wy, D, the cell (two integers), four float texels and the `ok` mask; each pixel's operations and each
+ * thread's order of accumulation are the same in both forms.
  */
 
 /* AM = MTFHIP_AM_SSD: the residual-weighted sums above.  AM = MTFHIP_AM_NCC: the same pass accumulates the raw moments
@@ -166,6 +170,20 @@ __device__ __forceinline__ void spss_gram(double *acc, double w, const double *r
  * kernels_step.hip whose last-arriving workgroup reads every row in the same launch) */
 /* X: the arguments of a model beyond the maps -- one SpssArgs for AM = MTFHIP_AM_SPSS (deduced from the call), none otherwise: the other
  * models' instantiations keep the signature they had */
+/* TEX_AHEAD: the instantiations whose full-row loop requests a row's texels one row ahead (run_rows) -- the lean replay SSD passes of
+ * kernels_fused.hip, FCLK and ESM, that stay clear of scratch and keep their waves per SIMD with it (`fits`).  The others request and use
+ * a row's texels in the same iteration: NCC sits at 226-235 VGPRs, the materialising kernels are bound by their byte stream, the
+ * tolerance-mode kernels would lose their third wave.  -DMTFHIP_LEAN_TEX_AHEAD=0 builds every kernel with the one loop. */
+#ifndef MTFHIP_LEAN_TEX_AHEAD
+#define MTFHIP_LEAN_TEX_AHEAD 1
+#endif
+constexpr bool lean_tex_ahead_kernel(int am, int ssm, bool chained, int mode, bool mat, bool fast, bool persist, bool mc, bool cohrow) {
+	/* (homography with the non-chained gradient keeps cx, cy and eight more quotients alive: 36 to 204 B of scratch per lane with the row
+	 * ahead; affine chained FCLK has three waves per SIMD at 166 VGPRs and would drop to two at 182) */
+	const bool fits = !(ssm == MTFHIP_SSM_HOMOGRAPHY && !chained) && !(ssm == MTFHIP_SSM_AFFINE && chained && mode == 0);
+	return MTFHIP_LEAN_TEX_AHEAD != 0 && !MTFHIP_NT_LOAD && fits && am == MTFHIP_AM_SSD && (mode == 0 || mode == 1) && !mat && !fast && !persist &&
+		!mc && !cohrow;
+}
 __device__ __forceinline__ const SpssArgs *spss_args_ptr() { return nullptr; }
 __device__ __forceinline__ const SpssArgs *spss_args_ptr(const SpssArgs &a) { return &a; }
 template <int AM, int SSM, bool CHAINED, int MODE, bool MAT, bool FAST = false, bool PERSIST = false, bool MC = false, bool COHROW = PERSIST,
@@ -275,6 +293,8 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 	 * row alone are tabulated once per workgroup in LDS (launch_fused_ssd sizes it: (resx + resy) double2): a row costs two LDS reads
 	 * and four additions, and the loop keeps two scalars of the map (W0[2] 1.0, W0[5] 1.0) instead of the map and the lattice. */
 	constexpr bool GR_OK = grid_regen_kernel(AM, SSM, CHAINED, MODE, MAT) && !FAST && !PERSIST && !MC && !COHROW;
+	constexpr bool TEX_AHEAD = lean_tex_ahead_kernel(AM, SSM, CHAINED, MODE, MAT, FAST, PERSIST, MC, COHROW);
+	static_assert(!(TEX_AHEAD && GR_OK), "no kernel both rebuilds the grid and fetches texels ahead");
 	extern __shared__ double2 grid_tab[];   /* [resx] (W0[0] nx, W0[3] nx) | [resy] (W0[1] ny, W0[4] ny) -- RSCV: its map, [rm.nb] double */
 	constexpr bool RSCV = AM == MTFHIP_AM_RSCV;
 	static_assert(!(RSCV && (GR_OK || NCC || PERSIST || MC || COHROW)), "RSCV: single channel, one launch per pass, no grid rebuild");
@@ -338,9 +358,36 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 		else { in.hp = ld_off<double2>(ih, o16); in.z = ld_off<double>(iz, oz); }
 		return in;
 	};
+	/* TEX_AHEAD: load_in in two parts.  What a row's position is computed from -- the grid point, or (hx, hy, z) when the corners are no
+	 * parallelogram -- is requested two rows ahead, everything else one row ahead as in load_in: the second row in flight then costs 4 to
+	 * 10 VGPRs, not the whole operand set (with the J0 columns read back that alone is 22 more, and the kernel no longer fits 256). */
+	auto load_pos_part = [&](unsigned i, auto uz) {
+		PixIn<S, MODE> in{};
+		in.z = 1.0;
+		if constexpr (decltype(uz)::value) in.p = ld_off<double2>(ip, i * 16u);
+		else { in.hp = ld_off<double2>(ih, i * 16u); in.z = ld_off<double>(iz, i * 8u); }
+		return in;
+	};
+	auto load_rest_part = [&](unsigned i, const PixIn<S, MODE> &pos, auto uz, auto jr) {
+		PixIn<S, MODE> in = pos;
+		const unsigned o8 = i * 8u;
+		if constexpr (!decltype(uz)::value) in.p = ld_off<double2>(ip, i * 16u);
+		in.i0 = ld_off<double>(I0, o8);
+		if constexpr (MODE != 0 && decltype(jr)::value) {
+			in.j0[0] = ld_off<double>(dI0, o8); in.j0[1] = ld_off<double>(dI0 + N, o8);
+		} else if constexpr (MODE != 0) {
+#pragma unroll
+			for (int s = 0; s < S; ++s) in.j0[s] = ld_off<double>(J0 + (size_t)s * N, o8);
+		} else {
+			in.j0[0] = 0;
+		}
+		return in;
+	};
 	/* curr_pts_hm = curr_warp * init_pts_hm and its dehomogenisation (Homography.cc:86-90, Affine.cc:104),
 	 * then the texel fetch of the bilinear cell */
-	auto issue_tex = [&](const PixIn<S, MODE> &in, auto uz) {
+	/* The position part -- warp, the two divisions, the cell, the `ok` test, the texel address and its four loads: everything a row needs
+	 * before its texels can be requested (and, TEX_AHEAD, everything that crosses a row: wx, wy, D, lx, ly, the texels and `ok`). */
+	auto issue_pos = [&](const PixIn<S, MODE> &in, auto uz) {
 		Tex tx;
 		constexpr bool UZ = decltype(uz)::value;
 		const double z = UZ ? 1.0 : in.z, hx = UZ ? in.p.x : in.hp.x, hy = UZ ? in.p.y : in.hp.y;
@@ -380,6 +427,14 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 #endif
 		return tx;
 	};
+	/* The part that is only needed at use.  A position that was taken a row ahead carries the cell as two integers and converts them
+	 * here (one conversion each, the same value the `ok` test compared against) instead of keeping two more doubles across the row;
+	 * cx / cy are dead behind the division in the CHAINED instantiations and cross the row only where updateGradPts reads them. */
+	auto tex_at_use = [&](Tex tx) {
+		tx.lxd = (double)tx.lx; tx.lyd = (double)tx.ly;
+		return tx;
+	};
+	/* (where a row's position is taken and used in the same iteration, issue_pos's own lxd / lyd are the ones row_compute reads) */
 
 	const int n_rows = fa.rows_per_block;
 	const unsigned base = blockIdx.x * (unsigned)(kBlock * n_rows) + threadIdx.x;
@@ -824,10 +879,35 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 			fill_map();   /* (behind the first row's loads) */
 			setup_target();
 			if (!live) return;
+			if constexpr (TEX_AHEAD) {
+				/* iteration i: position + texel request of row i+1 (from `pnxt`, loaded during iteration i-1) -> loads of row i+2's
+				 * position operands and of row i+1's other operands -> arithmetic of row i on the texels requested during iteration
+				 * i-1.  Indices past the target are clamped to N - 1 as below (a position and four texels nobody uses, no address
+				 * beyond the target); behind the workgroup's last full row nothing more is requested. */
+				static_assert(!decltype(grg)::value, "the split loaders read the stored grid point");
+				Tex tcur = issue_pos(cur, uz);
+				asm volatile("" ::: "memory");
+				const unsigned i1 = base + kBlock;
+				PixIn<S, MODE> pnxt = load_pos_part(i1 < N ? i1 : N - 1, uz);
+				asm volatile("" ::: "memory");
+#pragma unroll 1
+				for (int kk = 0; kk + 1 < full; ++kk) {
+					const unsigned i = base + (unsigned)kk * kBlock;
+					const Tex tnxt = issue_pos(pnxt, uz);
+					asm volatile("" ::: "memory");      /* texel fetch first, then the streaming operands: keeps the order */
+					const unsigned in1 = i + kBlock, in2 = i + 2 * kBlock;   /* (in1 < N: row i+1 is one of the workgroup's full rows) */
+					const PixIn<S, MODE> pnn = load_pos_part(in2 < N ? in2 : N - 1, uz);
+					const PixIn<S, MODE> nxt = load_rest_part(in1, pnxt, uz, jr);
+					asm volatile("" ::: "memory");
+					row_compute(i, cur, tex_at_use(tcur), jr);
+					cur = nxt; pnxt = pnn; tcur = tnxt;
+				}
+				row_compute(base + (unsigned)(full - 1) * kBlock, cur, tex_at_use(tcur), jr);
+			} else {
 #pragma unroll 1
 			for (int kk = 0; kk < full; ++kk) {
 				const unsigned i = base + (unsigned)kk * kBlock;
-				const Tex tcur = issue_tex(cur, uz);
+				const Tex tcur = issue_pos(cur, uz);
 				asm volatile("" ::: "memory");      /* texel fetch first, then the next row's operands: keeps the order */
 				const unsigned inext = i + kBlock;
 				next_pos();   /* (past the end of the target on the last row: a point nobody uses, no memory touched) */
@@ -835,6 +915,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 				asm volatile("" ::: "memory");
 				row_compute(i, cur, tcur, jr);
 				cur = nxt;
+			}
 			}
 		}
 		/* the partial last row of a target (only the workgroup that owns the end of the patch gets here; the lattice position is
@@ -844,7 +925,7 @@ __device__ __forceinline__ void fused_lk_body(const BatchView &bv, const ImgView
 			if (full == 0) { fill_map(); setup_target(); if (!live) return; }
 			if (i < N) {
 				const PixIn<S, MODE> c = load_in(i, uz, jr, grg, gc, gr);
-				const Tex tc = issue_tex(c, uz);
+				const Tex tc = issue_pos(c, uz);
 				row_compute(i, c, tc, jr);
 			}
 		}
